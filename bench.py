@@ -15,10 +15,16 @@ Inputs are resident in HBM when the clock starts.
 
 **Which arithmetic is the headline (VERDICT r03 "next" #2).**  ``value`` / ``dtype`` / ``roofline`` are the run with EXACT fp32
 products (``v_mfma_f32_32x32x2_f32``, the reference's arithmetic; roofline against the 157.3 TFLOP/s fp32-MFMA peak).  The
-package's default precision (``f16f6``: error-compensated fp16 split with fp6 correction terms) is measured in the same
-process with the same --steps / --warmup, the same barriers and the same max-over-ranks, and reported as
+package's default precision (``f16f6``: error-compensated fp16 split with fp6 correction terms) is measured with ``--full`` in
+the same process with the same --steps / --warmup, the same barriers and the same max-over-ranks, and reported as
 ``value_default_precision`` with its own roofline block against the 2.5 PFLOP/s f16 peak -- it is an accelerated mode inside
 the parity bounds, not fp32 arithmetic, so it is not in the headline slot.  ``--precision`` moves another mode there.
+
+**Plain run and ``--full``.**  A plain run sets up, warms up, times exactly --steps steps of the headline precision, writes the
+outputs of the last timed step when ``--dump-outputs DIR`` is given, and prints the line (``metric``, ``value``, ``unit``,
+``ms_per_step``, ``higher_is_better``, ``dtype``, configuration, rank evidence).  ``--full`` adds everything else, as before:
+per-launch HIP-event kernel timings in the timed loop and the roofline blocks, the frame digest of one more untimed step, every
+other precision, the CPU baseline and the parity check of the timed frame against the CPU oracle.
 
 **Launch (VERDICT r03 "next" #1).**  ``python bench.py --gpus N`` started as a plain process spawns its N ranks itself
 (``neural_jacobian_field_amd.launch``: ``python -m torch.distributed.run``, one rank per GPU, rendezvous on 127.0.0.1);
@@ -32,7 +38,7 @@ shards (``parallel.shard_bounds``), weights and feature map are replicated, each
 ``Model.forward``, ONE collective per step.  value = rays of the frame / max-over-ranks time.  ``--scaling weak``: every
 rank renders its own full frame.
 
-Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling strong|weak]
+Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling strong|weak] [--full] [--dump-outputs DIR]
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -143,6 +149,15 @@ def parse():
                     help="launcher self-test WITHOUT a GPU (tests/test_host_cpu.py): the same launch / world check / barriers / "
                          "rank evidence / one JSON line, over the gloo backend, with parallel.ShardedFrameStep driven by the "
                          "stand-in kernels the given python file provides.  The line says dry_launch: true and has no value")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: the other precisions, per-launch kernel timings and the roofline "
+                         "blocks, the frame digest, the CPU baseline and the parity check of the timed frame against the CPU "
+                         "oracle (--no-other-precisions / --no-cpu-baseline drop parts of it).  Without it a run sets up, warms "
+                         "up, times --steps steps of the headline precision and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (assembled frame, frame scalars, the "
+                         "model output of this rank's rays) as DIR/<name>.npy in float32; at most 64 MB in all (a larger output "
+                         "is written as a fixed, seeded sample of its rays)")
     return ap.parse_args()
 
 
@@ -189,6 +204,50 @@ def emit(line: dict, gpus: int) -> None:
     ctypes.CDLL(None).fflush(None)  # anything native libraries buffered goes out first (to stderr once stdout is reserved)
     sys.stdout.flush()
     launch.print_line(line)         # the process's ORIGINAL stdout: nothing else is ever written there (launch.reserve_stdout)
+
+
+DUMP_LIMIT_BYTES = 64 * 2**20
+
+
+def step_arrays(result) -> dict:
+    """What one step handed its caller, as {name: tensor}: the step function's (model output, frame scalars / losses, frame)."""
+    out, scalars, frame = result
+    arrays = {}
+    if frame is not None:
+        arrays["frame"] = frame                       # [B,R,6] rgb | clipped depth | flow of the whole frame
+    if isinstance(scalars, dict):                     # round-2 step: {"loss/rgb": [], "loss/flow_loss": []}
+        for k, v in scalars.items():
+            arrays[k.replace("/", "_")] = v.reshape(1)
+    elif scalars is not None:
+        arrays["frame_scalars"] = scalars             # [6] depth-clip min, max, sum sq rgb, sum sq flow, rgb loss, flow loss
+    std = getattr(out, "standard_output", out)        # this rank's rays (depth before the frame's clip)
+    if std is not None:
+        arrays.update(rgb=std.rgb, depth=std.depth, optical_flow=std.optical_flow)
+    # copied off the device now: the step's buffers are refilled by every later step
+    return {k: v.detach().to("cpu", torch.float64 if v.dtype == torch.float64 else torch.float32, copy=True)
+            for k, v in arrays.items()}
+
+
+def write_outputs(path: str, arrays: dict) -> None:
+    """DIR/<name>.npy per array.  Above DUMP_LIMIT_BYTES in all, every array of more than 4,096 rows (rays: all dimensions but
+    the last flattened) keeps the same fixed, seeded sample of its rows, so two runs with the same arguments stay comparable."""
+    import numpy as np
+    total = sum(a.numel() * a.element_size() for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        keep_frac = 0.95 * DUMP_LIMIT_BYTES / total
+        sampled = {}
+        for k, a in arrays.items():
+            rows = a.reshape(-1, a.shape[-1] if a.dim() > 1 else 1)
+            n = rows.shape[0]
+            if n > 4096:   # (the same permutation for every array of n rows: rgb, depth and flow keep the same rays)
+                idx = torch.randperm(n, generator=torch.Generator().manual_seed(0))[: int(n * keep_frac)].sort().values
+                a = rows[idx]
+                print(f"[bench] --dump-outputs: {k} written as a seeded sample of {a.shape[0]} of its {n} rows", file=sys.stderr)
+            sampled[k] = a
+        arrays = sampled
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, f"{k}.npy"), a.numpy())
 
 
 def cpu_baseline(case, ray_index, passes: int):
@@ -384,7 +443,8 @@ def main():
                                "action_decoder": {"name": DEC}})
     precision = args.precision or HEADLINE_PRECISION
     default_precision = hip.DEFAULT_PRECISION
-    wanted = [precision] + ([] if args.no_other_precisions else [p for p in (default_precision, "f16f6", "f16x2", "f32", "f16", "f16+f16x2")])
+    others = args.full and not args.no_other_precisions
+    wanted = [precision] + ([p for p in (default_precision, "f16f6", "f16x2", "f32", "f16", "f16+f16x2")] if others else [])
     models = {}
     for prec in dict.fromkeys(wanted):
         m = Model(cfg).to(device).eval().requires_grad_(False)
@@ -440,10 +500,11 @@ def main():
                 acc[key] += e0.elapsed_time(e1)
         return {k: v / steps for k, v in acc.items()}
 
-    def measure(prec: str, steps: int, warmup: int) -> dict:
+    def measure(prec: str, steps: int, warmup: int, keep_outputs: bool = False) -> dict:
         """`warmup` untimed steps, then EXACTLY `steps` steps between barrier + synchronize on both sides, max over ranks.
-        Per-launch HIP events on the launch stream give the kernel durations: inside the timed steps when they run eagerly,
-        in an eager pass right after the timed loop when the rank-local compute is replayed as a HIP graph."""
+        With --full, per-launch HIP events on the launch stream give the kernel durations: inside the timed steps when they run
+        eagerly, in an eager pass right after the timed loop when the rank-local compute is replayed as a HIP graph; and one
+        more untimed step gives the frame digest.  `keep_outputs`: a host copy of what the last timed step returned."""
         model = models[prec]
         for _ in range(warmup):
             step(model)
@@ -465,10 +526,20 @@ def main():
             for _ in range(2):
                 step(model)
         launches = []
-        if not graphed:
+        if args.full and not graphed:
             hip.set_profile_sink(launches)   # per-launch HIP events on the launch stream (roofline.achieved)
-        elapsed, local = timed_loop(lambda: step(model), steps, dist, sync)
+        last = [None]
+
+        def timed_step():
+            last[0] = step(model)
+
+        elapsed, local = timed_loop(timed_step, steps, dist, sync)
         hip.set_profile_sink(None)
+        outputs = step_arrays(last[0]) if keep_outputs else None
+        result = {"elapsed": max_over_ranks(dist, elapsed, device), "local_ms": 1e3 * local / steps, "steps": steps,
+                  "warmup": warmup, "graphed": graphed, "outputs": outputs}
+        if not args.full:
+            return result
         digest_hex = None
         if use_frame_step:   # one more UNTIMED step through the same (possibly graph-replayed) step function, on every rank
             import hashlib
@@ -487,18 +558,18 @@ def main():
             hip.set_profile_sink(None)
             timing_note = ("mean njf_render_forward launch duration over an EAGER pass of the same steps right after the timed "
                            "(graph-replayed) loop, HIP events on the launch stream")
-        return {"elapsed": max_over_ranks(dist, elapsed, device), "local_ms": 1e3 * local / steps, "steps": steps, "warmup": warmup,
-                "kernel_ms": kernel_ms(launches, steps), "launches_per_step": len(launches) / max(steps, 1), "graphed": graphed,
-                "timing_note": timing_note, "digest": digest_hex}
+        result.update(kernel_ms=kernel_ms(launches, steps), launches_per_step=len(launches) / max(steps, 1), timing_note=timing_note,
+                      digest=digest_hex)
+        return result
 
-    # headline first; the package's default precision with the SAME steps / warm-up / barriers; every other mode likewise
-    runs = {precision: measure(precision, args.steps, args.warmup)}
+    # headline first; with --full the package's default precision with the SAME steps / warm-up / barriers, every other mode likewise
+    runs = {precision: measure(precision, args.steps, args.warmup, keep_outputs=args.dump_outputs is not None and rank == 0)}
     for prec in models:
         if prec not in runs:
             # every mode with the SAME --steps / --warmup as the headline (a 60-step run of the slowest extra mode is 0.7 s)
             runs[prec] = measure(prec, args.steps, args.warmup)
     head = runs[precision]
-    evidence = launch.rank_evidence(dist, device, head["local_ms"], graph=head["graphed"], kernel_ms=head["kernel_ms"])
+    evidence = launch.rank_evidence(dist, device, head["local_ms"], graph=head["graphed"], kernel_ms=head.get("kernel_ms"))
     # One more UNTIMED step of the headline mode on every rank: the digest of what it produced (assembled frame + the six clip /
     # loss scalars).  The kernels are bit-reproducible, so a one-rank run WITH the collective (--force-dist, eager or --graph)
     # must print the digest of the plain run (tests/test_rccl_gpu.py).
@@ -561,89 +632,95 @@ def main():
             "config": {"workload": workload, "precision": precision, "rays_per_gpu": local_rays, "decoder": DEC, "action_dim": AD,
                        "parallelism": f"dp{world} ({'one frame, rays sharded' if strong else 'one frame per rank'}, replicated weights "
                                       "and feature map)"},
-            "kernel_ms": {k: round(v, 3) for k, v in head["kernel_ms"].items()},
+            **({"kernel_ms": {k: round(v, 3) for k, v in head["kernel_ms"].items()}} if args.full else {}),
             "step": {"form": ("ShardedFrameStep: Model.forward (one per-image projection for all networks, njf_proposal_forward, njf_render_forward "
                               "with the frame reductions in its epilogue) + njf_reduce_frame_partials + "
                               + ("ONE all_gather of [pixels | 4 scalars] + " if world > 1 else "")
                               + "njf_assemble_frame (global depth clip, rgb / flow loss)") if use_frame_step else
                              "round-2 step: Model.forward + ATen depth clip, loss sums, concatenation (three collectives at N > 1)",
-                     "c_abi_launches_per_step": round(head["launches_per_step"], 2), "hip_graph": head["graphed"]},
-            "roofline": roofline(precision, head),
+                     **({"c_abi_launches_per_step": round(head["launches_per_step"], 2)} if args.full else {}),
+                     "hip_graph": head["graphed"]},
+            **({"roofline": roofline(precision, head)} if args.full else {}),
             **({"reduced_precision": True,
                 "reduced_precision_note": "--precision put a REDUCED-precision mode in the headline slot: `value` is NOT fp32-parity arithmetic; "
                                           "its tolerance is other_precisions' `tolerance` text (oracle/parity_harness.py: operand-rounding model)"}
                if precision in REDUCED_PRECISIONS else {}),
             "rccl": evidence,
-            "frame_digest": digest,
+            **({"frame_digest": digest} if args.full else {}),
+            "full": bool(args.full),
         }
         if sim_world:
             out["simulated"] = f"rank 0's shard of a {sim_world}-way strong split rendered on ONE GPU, no collectives: value counts only these rays"
-        out["other_precisions"] = {}
-        for prec, run in runs.items():
-            if prec == precision:
-                continue
-            ms = 1e3 * run["elapsed"] / run["steps"]
-            rf = roofline(prec, run)
-            out["other_precisions"][prec] = {
-                "ms_per_step": round(ms, 3), "steps": run["steps"], "warmup": run["warmup"],
-                "rays_per_s": round(total_rays / (ms * 1e-3), 1), "kernel_ms": {k: round(v, 3) for k, v in run["kernel_ms"].items()},
-                "roofline_achieved_tflops": rf["achieved"], "roofline_peak_tflops": rf["peak"], "roofline_frac": rf["frac"],
-                "hip_graph": run["graphed"]}
-            if prec in REDUCED_PRECISIONS:   # its own roofline block and its own stated tolerance (VERDICT r04 "next" #1)
-                out["other_precisions"][prec].update(
-                    dtype=DTYPE_TEXT[prec], roofline=rf, reduced_precision=True,
-                    tolerance="norm-wise err <= max(2e-3, f x the operand-rounding model of plain fp16 on the CPU oracle) per quantity, f = 2 for "
-                              "tensors of >= 1,024 elements, 4 for smaller ones and for the placement-dominated pixels rgb / depth / optical_flow "
-                              "of the all-fp16 mode; AND element-wise against float64 on tensors of >= 1,024 elements: rms <= 1.5 x, max <= 2 x "
-                              "the model's error (pixels of the all-fp16 mode: median <= 1.5 x, rms <= 2.5 x, max <= 4 x) -- "
-                              "parity_on_bench_frame; tests/test_hip_parity.py::test_plain_f16_mode_within_stated_tolerance, "
-                              "::test_f16_shading_with_compensated_placement_at_full_size")
-            if prec == default_precision:   # the mode a user gets without asking: same protocol as the headline, NOT fp32 arithmetic
-                out["value_default_precision"] = {
-                    "value": round(total_rays / (ms * 1e-3), 1), "unit": "rays/s", "ms_per_step": round(ms, 3), "steps": run["steps"],
-                    "warmup": run["warmup"], "dtype": DTYPE_TEXT[prec],
-                    "timing": "same step function and process as the headline, its own warm-up, barrier + synchronize on both sides "
-                              "of exactly `steps` steps, max over ranks",
-                    "kernel_ms": {k: round(v, 3) for k, v in run["kernel_ms"].items()}, "roofline": rf,
-                    "note": "an accelerated mode held to the same parity bounds (parity_on_bench_frame, profiles/r04_parity_margins.json); "
-                            "its products are not fp32 products, so it is not the headline"}
-        out["parity_note"] = ("every PARITY precision (f32, f16x2, f16f6) is held to the SAME bound against the CPU oracle / the reference's goldens "
-                              "(the reduced-precision mode f16 has its own stated rule: other_precisions.f16.tolerance): "
-                              "max(1e-4, 2 x the reference's own fp32-vs-fp64 difference of that quantity), and is reported "
-                              "element-wise against the float64 truth next to the reference's own fp32 error (truth columns).  rgb, "
-                              "depth and the per-sample fields meet north_star's 1e-4; END-TO-END optical_flow is bounded by the "
-                              "reference's own fp32 floor (5e-4 ... 3e-3: sample placement feeds a 2*pi*512-gain encoding), not by "
-                              "1e-4, in EVERY precision including exact fp32 arithmetic")
-        if world == 1 and not sim_world and not args.no_cpu_baseline and (BB, HH, WW, SS) == (1, 256, 256, 64):
-            case = {"params": params, "feats": feats_cpu, "cams": cams, "origins": origins.cpu(), "directions": directions.cpu(),
-                    "k_pix": k_pix.cpu(), "action": action_cpu, "decoder_kind": DEC}
-            stride = max(1, (HH * WW) // args.cpu_sample_rays)
-            ray_index = torch.arange(0, HH * WW, stride)[: args.cpu_sample_rays]
-            out["cpu_baseline"], ref, ref64, sub_case = cpu_baseline(case, ray_index, args.cpu_passes)
-            # full-size parity of the frame that was just timed, in every precision
-            out["parity_on_bench_frame"] = {
-                "rays": f"{ray_index.numel()} rays of the timed C2 frame (every {stride}th), 128x128x512 feature map, 64+64 samples",
-                "rule": "err <= max(1e-4, 2 x floor); err, floor norm-wise (max|a-b| / max|b|); floor = CPU oracle fp32 vs the same "
-                        "oracle in float64 on these rays.  truth: element-wise |hip - fp64| against |fp32 oracle - fp64|, relative "
-                        "to max|fp64|; truth_ok = max and 99.9th percentile within 1.5 x the oracle's own (or 4 fp32 ulps of scale) -- "
-                        "truth_ok_strict -- OR both within 2.0 x with the rms within 1.5 x (rows then marked tail_outlier)",
-                "rule_reduced_precision": "modes in REDUCED_PRECISIONS ('f16': plain fp16 products; 'f16+f16x2': plain-fp16 final pass, compensated "
-                                          "proposal pass -- its pixels are held to the model's FINAL STAGE at the fp32 sample locations with f = 2, "
-                                          "its proposal rows to the fp32 rule): err <= max(2e-3, f x model), f = 2 "
-                                          "(4 for tensors below 1,024 elements and for rgb / depth / optical_flow, whose error is "
-                                          "sample placement through the inverse CDF), model = "
-                                          "the CPU oracle with every matrix operand rounded to fp16 (oracle/njf_oracle.py::operand_rounding) "
-                                          "against the fp32 oracle on these rays; truth columns then take e_ref = |model - fp64| and are ASSERTED "
-                                          "(rms <= 1.5 x, max <= 2 x; all-fp16 pixels: median <= 1.5 x, rms <= 2.5 x, max <= 4 x): `ok` includes them",
-                **parity_on_bench_frame(models, cam, rob, z_near, z_far, origins, directions, ray_index, ref, ref64, sub_case)}
-            out["parity_on_bench_frame"]["all_ok"] = all(r["ok"] for k, v in out["parity_on_bench_frame"].items()
-                                                         if isinstance(v, dict) for r in v.values())
-            out["parity_on_bench_frame"]["headline_truth_ok"] = all(
-                r["truth"]["truth_ok"] for r in out["parity_on_bench_frame"][precision].values())
-            out["parity_on_bench_frame"]["headline_truth_ok_strict"] = all(
-                r["truth"]["truth_ok_strict"] for r in out["parity_on_bench_frame"][precision].values())
-            out["parity_on_bench_frame"]["headline_tail_outlier_rows"] = sum(
-                bool(r["truth"].get("tail_outlier")) for r in out["parity_on_bench_frame"][precision].values())
+        if args.full:   # everything the headline does not need: other precisions, CPU baseline, parity of the timed frame
+            out["other_precisions"] = {}
+            for prec, run in runs.items():
+                if prec == precision:
+                    continue
+                ms = 1e3 * run["elapsed"] / run["steps"]
+                rf = roofline(prec, run)
+                out["other_precisions"][prec] = {
+                    "ms_per_step": round(ms, 3), "steps": run["steps"], "warmup": run["warmup"],
+                    "rays_per_s": round(total_rays / (ms * 1e-3), 1), "kernel_ms": {k: round(v, 3) for k, v in run["kernel_ms"].items()},
+                    "roofline_achieved_tflops": rf["achieved"], "roofline_peak_tflops": rf["peak"], "roofline_frac": rf["frac"],
+                    "hip_graph": run["graphed"]}
+                if prec in REDUCED_PRECISIONS:   # its own roofline block and its own stated tolerance (VERDICT r04 "next" #1)
+                    out["other_precisions"][prec].update(
+                        dtype=DTYPE_TEXT[prec], roofline=rf, reduced_precision=True,
+                        tolerance="norm-wise err <= max(2e-3, f x the operand-rounding model of plain fp16 on the CPU oracle) per quantity, f = 2 for "
+                                  "tensors of >= 1,024 elements, 4 for smaller ones and for the placement-dominated pixels rgb / depth / optical_flow "
+                                  "of the all-fp16 mode; AND element-wise against float64 on tensors of >= 1,024 elements: rms <= 1.5 x, max <= 2 x "
+                                  "the model's error (pixels of the all-fp16 mode: median <= 1.5 x, rms <= 2.5 x, max <= 4 x) -- "
+                                  "parity_on_bench_frame; tests/test_hip_parity.py::test_plain_f16_mode_within_stated_tolerance, "
+                                  "::test_f16_shading_with_compensated_placement_at_full_size")
+                if prec == default_precision:   # the mode a user gets without asking: same protocol as the headline, NOT fp32 arithmetic
+                    out["value_default_precision"] = {
+                        "value": round(total_rays / (ms * 1e-3), 1), "unit": "rays/s", "ms_per_step": round(ms, 3), "steps": run["steps"],
+                        "warmup": run["warmup"], "dtype": DTYPE_TEXT[prec],
+                        "timing": "same step function and process as the headline, its own warm-up, barrier + synchronize on both sides "
+                                  "of exactly `steps` steps, max over ranks",
+                        "kernel_ms": {k: round(v, 3) for k, v in run["kernel_ms"].items()}, "roofline": rf,
+                        "note": "an accelerated mode held to the same parity bounds (parity_on_bench_frame, profiles/r04_parity_margins.json); "
+                                "its products are not fp32 products, so it is not the headline"}
+            out["parity_note"] = ("every PARITY precision (f32, f16x2, f16f6) is held to the SAME bound against the CPU oracle / the reference's goldens "
+                                  "(the reduced-precision mode f16 has its own stated rule: other_precisions.f16.tolerance): "
+                                  "max(1e-4, 2 x the reference's own fp32-vs-fp64 difference of that quantity), and is reported "
+                                  "element-wise against the float64 truth next to the reference's own fp32 error (truth columns).  rgb, "
+                                  "depth and the per-sample fields meet north_star's 1e-4; END-TO-END optical_flow is bounded by the "
+                                  "reference's own fp32 floor (5e-4 ... 3e-3: sample placement feeds a 2*pi*512-gain encoding), not by "
+                                  "1e-4, in EVERY precision including exact fp32 arithmetic")
+            if world == 1 and not sim_world and not args.no_cpu_baseline and (BB, HH, WW, SS) == (1, 256, 256, 64):
+                case = {"params": params, "feats": feats_cpu, "cams": cams, "origins": origins.cpu(), "directions": directions.cpu(),
+                        "k_pix": k_pix.cpu(), "action": action_cpu, "decoder_kind": DEC}
+                stride = max(1, (HH * WW) // args.cpu_sample_rays)
+                ray_index = torch.arange(0, HH * WW, stride)[: args.cpu_sample_rays]
+                out["cpu_baseline"], ref, ref64, sub_case = cpu_baseline(case, ray_index, args.cpu_passes)
+                # full-size parity of the frame that was just timed, in every precision
+                out["parity_on_bench_frame"] = {
+                    "rays": f"{ray_index.numel()} rays of the timed C2 frame (every {stride}th), 128x128x512 feature map, 64+64 samples",
+                    "rule": "err <= max(1e-4, 2 x floor); err, floor norm-wise (max|a-b| / max|b|); floor = CPU oracle fp32 vs the same "
+                            "oracle in float64 on these rays.  truth: element-wise |hip - fp64| against |fp32 oracle - fp64|, relative "
+                            "to max|fp64|; truth_ok = max and 99.9th percentile within 1.5 x the oracle's own (or 4 fp32 ulps of scale) -- "
+                            "truth_ok_strict -- OR both within 2.0 x with the rms within 1.5 x (rows then marked tail_outlier)",
+                    "rule_reduced_precision": "modes in REDUCED_PRECISIONS ('f16': plain fp16 products; 'f16+f16x2': plain-fp16 final pass, compensated "
+                                              "proposal pass -- its pixels are held to the model's FINAL STAGE at the fp32 sample locations with f = 2, "
+                                              "its proposal rows to the fp32 rule): err <= max(2e-3, f x model), f = 2 "
+                                              "(4 for tensors below 1,024 elements and for rgb / depth / optical_flow, whose error is "
+                                              "sample placement through the inverse CDF), model = "
+                                              "the CPU oracle with every matrix operand rounded to fp16 (oracle/njf_oracle.py::operand_rounding) "
+                                              "against the fp32 oracle on these rays; truth columns then take e_ref = |model - fp64| and are ASSERTED "
+                                              "(rms <= 1.5 x, max <= 2 x; all-fp16 pixels: median <= 1.5 x, rms <= 2.5 x, max <= 4 x): `ok` includes them",
+                    **parity_on_bench_frame(models, cam, rob, z_near, z_far, origins, directions, ray_index, ref, ref64, sub_case)}
+                out["parity_on_bench_frame"]["all_ok"] = all(r["ok"] for k, v in out["parity_on_bench_frame"].items()
+                                                             if isinstance(v, dict) for r in v.values())
+                out["parity_on_bench_frame"]["headline_truth_ok"] = all(
+                    r["truth"]["truth_ok"] for r in out["parity_on_bench_frame"][precision].values())
+                out["parity_on_bench_frame"]["headline_truth_ok_strict"] = all(
+                    r["truth"]["truth_ok_strict"] for r in out["parity_on_bench_frame"][precision].values())
+                out["parity_on_bench_frame"]["headline_tail_outlier_rows"] = sum(
+                    bool(r["truth"].get("tail_outlier")) for r in out["parity_on_bench_frame"][precision].values())
+        if args.dump_outputs is not None:
+            write_outputs(args.dump_outputs, head["outputs"])
+            out["outputs_dumped"] = sorted(head["outputs"])
         emit(out, args.gpus)
     if dist is not None:
         dist.barrier()

@@ -952,6 +952,29 @@ def test_bench_roofline_work_counts_follow_survey_8d():
     assert t6["reference_formulation"] == 575 * 64 + 3 * (64 * 512 + 2 * 512 * 6 + 512 * 64 + 2 * 64 * 64) + 64 * 18
 
 
+def test_bench_output_dump_is_bounded_and_seeded(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: one float32 .npy per array; above the size limit every array of many rows keeps the SAME fixed,
+    seeded sample of its rows (rgb still matches the frame's rgb ray for ray, two runs write identical files), small ones whole."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import importlib
+    bench = importlib.import_module("bench")
+    frame = torch.rand(1, 50_000, 6, generator=torch.Generator().manual_seed(3))
+    arrays = {"frame": frame, "rgb": frame[..., :3].clone(), "frame_scalars": torch.arange(6.0)}
+    bench.write_outputs(str(tmp_path / "whole"), arrays)
+    got = {n: np.load(tmp_path / "whole" / f"{n}.npy") for n in arrays}
+    assert all(np.array_equal(got[n], arrays[n].numpy()) and got[n].dtype == np.float32 for n in arrays)
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 1 << 20)             # 1.8 MB of arrays -> a sample
+    for run in ("a", "b"):
+        bench.write_outputs(str(tmp_path / run), arrays)
+    a = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in arrays}
+    b = {n: np.load(tmp_path / "b" / f"{n}.npy") for n in arrays}
+    assert sum(x.nbytes for x in a.values()) <= 1 << 20
+    assert all(np.array_equal(a[n], b[n]) for n in arrays)
+    assert a["frame"].shape[1] == 6 and 4096 < a["frame"].shape[0] < 50_000
+    assert np.array_equal(a["frame"][:, :3], a["rgb"]) and np.array_equal(a["frame_scalars"], np.arange(6.0, dtype=np.float32))
+
+
 def test_unifdef_lite_resolves_only_the_named_macros():
     """tools/unifdef_lite.py (what moved the retired experiment macros into tools/probes/*.patch): conditionals on the named macros are
     resolved as undefined -- #ifdef / #ifndef / #if defined() with &&, ||, !, #elif, #else, nested -- everything else stays verbatim."""

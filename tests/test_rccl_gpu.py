@@ -36,7 +36,8 @@ def check_rccl(line):
     assert dev["rank"] == 0 and dev.get("pci_bus_id") and dev.get("uuid") and dev["device"] == "cuda:0", dev
 
 
-BENCH = ("--gpus", "1", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-other-precisions")
+# --full: the frame digest (one more untimed step after the timed loop) is part of the full report only
+BENCH = ("--gpus", "1", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-other-precisions")
 
 
 @pytest.fixture(scope="module")
@@ -54,6 +55,29 @@ def test_bench_one_rank_with_the_collective_equals_the_plain_step(plain_bench, g
     assert line["metric"] == plain_bench["metric"] and line["config"]["workload"] == plain_bench["config"]["workload"]
     # all_gather_into_tensor of [pixels | 4 scalars] with one rank + the assemble launch: bit for bit the plain step's frame
     assert line["frame_digest"]["sha256"] == plain_bench["frame_digest"]["sha256"]
+
+
+def test_plain_bench_run_dumps_the_outputs_of_its_last_timed_step(plain_bench, tmp_path):
+    """A plain run (no --full) times exactly --steps steps of the headline precision and reports nothing it did not measure
+    there; --dump-outputs writes what the last timed step returned.  The kernels are bit-reproducible, so the dumped frame and
+    scalars hash to the digest the full report takes of one more step."""
+    import hashlib
+
+    import numpy as np
+    line = run_line("bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path))
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["value"] > 0 and line["full"] is False
+    assert line["metric"] == plain_bench["metric"] and line["dtype"] == plain_bench["dtype"] and line["unit"] == plain_bench["unit"]
+    for key in ("other_precisions", "cpu_baseline", "parity_on_bench_frame", "roofline", "kernel_ms", "frame_digest"):
+        assert key not in line, key
+    names = sorted(f[:-4] for f in os.listdir(tmp_path) if f.endswith(".npy"))
+    assert names == sorted(line["outputs_dumped"]) == ["depth", "frame", "frame_scalars", "optical_flow", "rgb"], names
+    arrays = {n: np.load(os.path.join(tmp_path, n + ".npy")) for n in names}
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrays.values())
+    rays = plain_bench["config"]["rays_per_gpu"]
+    assert arrays["frame"].shape == (1, rays, 6) and arrays["rgb"].shape == (1, rays, 3) and arrays["frame_scalars"].shape == (6,)
+    assert np.array_equal(arrays["frame"][..., :3], arrays["rgb"]) and np.array_equal(arrays["frame"][..., 4:], arrays["optical_flow"])
+    digest = hashlib.sha256(np.ascontiguousarray(arrays["frame"]).tobytes() + arrays["frame_scalars"].tobytes()).hexdigest()
+    assert digest == plain_bench["frame_digest"]["sha256"]
 
 
 def test_bench_train_one_rank_with_the_gradient_all_reduce():

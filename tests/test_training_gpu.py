@@ -914,6 +914,11 @@ def test_transformer_backward_chain_equals_the_library_recomputation(setup):
         for n, p in model.named_parameters():
             if "decoder" not in n:
                 p.requires_grad = False
+        # the frozen trunk's library convolutions (MIOpen) are not bit-reproducible from one call to the next, and at A = 8 the
+        # samples they place move the comparisons below by as much as their 1e-4 bound: the trunk runs ONCE and every route
+        # differentiates the forward pass on those same latents
+        latents = [t.detach() for t in model.encoder._latents(s["cam"].input_image)]
+        model.encoder._latents = lambda rgb, kept=latents: [t.clone() for t in kept]
         action = torch.randn(case["action"].shape[0], A, generator=torch.Generator().manual_seed(8)) * 0.3
         grads = {}
         for route in ("torch", "hip"):

@@ -6,6 +6,6 @@ cd "$(dirname "$0")/.."
 for v in "$@"; do
   if [ "$v" = shipped ]; then unset NJF_HIP_LIB; else export NJF_HIP_LIB=$PWD/build/libnjf_$v.so; fi
   sums=$(python tools/ab_checksum.py 2>/dev/null | tr '\n' ' ')
-  line=$(python bench.py --steps 10 --warmup 3 --no-cpu-baseline 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['ms_per_step'], d['kernel_ms'], 'f32:', d['other_precision']['ms_per_step'], d['other_precision']['render_kernel_ms'])")
+  line=$(python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['ms_per_step'], d['kernel_ms'], 'f32:', d['other_precision']['ms_per_step'], d['other_precision']['render_kernel_ms'])")
   echo "$v | $sums| $line"
 done

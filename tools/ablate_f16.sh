@@ -10,6 +10,6 @@ if [ "$1" = "--args" ]; then ARGS="$2"; shift 2; fi
 for v in "$@"; do
   export NJF_HIP_LIB=$PWD/build/libnjf_$v.so
   [ -f "$NJF_HIP_LIB" ] || { echo "$v: missing"; continue; }
-  timeout 200 python bench.py --precision f16 --steps 8 --warmup 2 --no-cpu-baseline --no-other-precisions $ARGS 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$v', d['ms_per_step'], d['kernel_ms'])"
+  timeout 200 python bench.py --full --precision f16 --steps 8 --warmup 2 --no-cpu-baseline --no-other-precisions $ARGS 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$v', d['ms_per_step'], d['kernel_ms'])"
 done
 unset NJF_HIP_LIB NJF_AUTO_RANGE_CHECK

@@ -2,9 +2,9 @@
 # Round-1 measurement sweep behind profiles/r01_{bench,configs,heads,control_loop,training_step}.json (GPU box, one gpurun call).
 cd "$(dirname "$0")/.."
 O=gpurun_out/measure_r01; mkdir -p $O
-python bench.py > $O/bench.json 2> $O/bench.err
+python bench.py --full > $O/bench.json 2> $O/bench.err
 for a in "--batch 4 --samples 128" "--height 512 --width 512" "--samples 256" "--samples 32"; do
-  echo "ARGS $a"; python bench.py --steps 5 --warmup 2 --no-cpu-baseline $a 2>/dev/null | tail -1
+  echo "ARGS $a"; python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline $a 2>/dev/null | tail -1
 done > $O/configs.txt
 python tools/bench_heads.py > $O/heads.txt 2>&1
 python tools/bench_control.py > $O/control.txt 2>&1

@@ -10,7 +10,7 @@ if [ "$STEP" = all ] || [ "$STEP" = tests ]; then
   timeout 1500 python -m pytest tests -m gpu -x -q > $O/pytest_gpu.txt 2>&1; echo "pytest rc=$?"; tail -5 $O/pytest_gpu.txt
 fi
 if [ "$STEP" = all ] || [ "$STEP" = bench ]; then
-  timeout 600 python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; tail -c 1500 $O/bench.json
+  timeout 600 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; tail -c 1500 $O/bench.json
 fi
 if [ "$STEP" = all ] || [ "$STEP" = stream ]; then
   timeout 300 python tools/stream_kernels.py --json $O/stream_hip_events.json > $O/stream_hip_events.txt 2>&1; cat $O/stream_hip_events.txt | tail -9
@@ -20,19 +20,19 @@ if [ "$STEP" = all ] || [ "$STEP" = stream ]; then
 fi
 if [ "$STEP" = all ] || [ "$STEP" = configs ]; then
   for a in "--batch 4 --samples 128" "--height 512 --width 512" "--samples 256" "--samples 32"; do
-    echo "ARGS $a"; python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-other-precisions $a 2>/dev/null | tail -1
+    echo "ARGS $a"; python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-other-precisions $a 2>/dev/null | tail -1
   done > $O/configs.txt
-  python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-other-precisions --force-dist 2>/dev/null | tail -1 > $O/force_dist.json
+  python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-other-precisions --force-dist 2>/dev/null | tail -1 > $O/force_dist.json
   for n in 2 4 8; do
-    python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-other-precisions --simulate-world $n 2>/dev/null | tail -1
+    python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-other-precisions --simulate-world $n 2>/dev/null | tail -1
   done > $O/simulate_world.txt
   tail -c 400 $O/simulate_world.txt
 fi
 if [ "$STEP" = scaling ]; then   # the N > 1 code on one GPU: RCCL with one rank, and rank 0's shard of an 8-way split, eager / graph / round-2 step
   for extra in "" "--graph" "--legacy-step"; do
-    echo "FORCE-DIST $extra"; python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-other-precisions --force-dist $extra 2>$O/fd.err | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['ms_per_step'], d['kernel_ms'], d.get('step',{}).get('c_abi_launches_per_step'))"
+    echo "FORCE-DIST $extra"; python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-other-precisions --force-dist $extra 2>$O/fd.err | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['ms_per_step'], d['kernel_ms'], d.get('step',{}).get('c_abi_launches_per_step'))"
     for n in 2 4 8; do
-      echo "SIM $n $extra"; python bench.py --steps 40 --warmup 10 --no-cpu-baseline --no-other-precisions --simulate-world $n $extra 2>>$O/fd.err | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['ms_per_step'], d['value'], d['kernel_ms'])"
+      echo "SIM $n $extra"; python bench.py --full --steps 40 --warmup 10 --no-cpu-baseline --no-other-precisions --simulate-world $n $extra 2>>$O/fd.err | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['ms_per_step'], d['value'], d['kernel_ms'])"
     done
   done > $O/scaling_dry.txt 2>&1
   cat $O/scaling_dry.txt

@@ -12,14 +12,14 @@ tests)
   NJF_MARGINS_OUT=$PWD/$O/r04_parity_margins.json timeout 1500 python -m pytest tests -m gpu -q > $O/pytest_gpu.txt 2>&1
   echo "pytest rc=$?"; tail -5 $O/pytest_gpu.txt ;;
 bench)
-  timeout 600 python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; tail -c 2500 $O/bench.json ;;
+  timeout 600 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; tail -c 2500 $O/bench.json ;;
 dist)      # the N > 1 code on ONE GPU: RCCL initialised with a single rank (collective for real), eager and graph
   for extra in "" "--graph"; do
-    timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --force-dist $extra 2>>$O/dist.err | tail -1 > $O/force_dist${extra:+_graph}.json
+    timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --force-dist $extra 2>>$O/dist.err | tail -1 > $O/force_dist${extra:+_graph}.json
     python -c "import sys,json; d=json.load(open('$O/force_dist${extra:+_graph}.json')); print('force-dist $extra', d['ms_per_step'], d['value_default_precision']['ms_per_step'], d['rccl']['backend'], d['rccl']['devices'][0].get('pci_bus_id'), d['rccl']['rank_step_ms'])"
   done
   for n in 2 4 8; do
-    timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --simulate-world $n --graph 2>>$O/dist.err | tail -1
+    timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --simulate-world $n --graph 2>>$O/dist.err | tail -1
   done > $O/simulate_world.txt
   python - <<PY
 import json
@@ -34,7 +34,7 @@ train)
   done ;;
 configs)
   for a in "--batch 4 --samples 128" "--height 512 --width 512" "--samples 256" "--samples 32"; do
-    echo "ARGS $a"; python bench.py --steps 5 --warmup 2 --no-cpu-baseline $a 2>/dev/null | tail -1
+    echo "ARGS $a"; python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline $a 2>/dev/null | tail -1
   done > $O/configs.txt ;;
 stream)    # HBM table of the streaming kernels: HIP events with warm and with COLD inputs, and rocprofv3 per-dispatch durations by shape
   timeout 300 python tools/stream_kernels.py --json $O/stream_hip_events_warm.json > $O/stream_hip_events_warm.txt 2>&1; tail -13 $O/stream_hip_events_warm.txt
@@ -52,7 +52,7 @@ ablate)    # experiment builds (build/libnjf_ablate_<v>.so, -DNJF_ABLATE_<V>): k
     for v in "" gather barrier dma dmabarrier pe afrag; do
       if [ -z "$v" ]; then unset NJF_HIP_LIB; name=baseline; else export NJF_HIP_LIB=$PWD/build/libnjf_ablate_$v.so; name=$v; fi
       [ -n "$v" ] && [ ! -f "$NJF_HIP_LIB" ] && continue
-      timeout 200 python bench.py --precision $prec --steps 8 --warmup 2 --no-cpu-baseline --no-other-precisions 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$prec', '$name', d['ms_per_step'], d['kernel_ms'])"
+      timeout 200 python bench.py --full --precision $prec --steps 8 --warmup 2 --no-cpu-baseline --no-other-precisions 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$prec', '$name', d['ms_per_step'], d['kernel_ms'])"
     done
   done | tee $O/ablate.txt
   unset NJF_HIP_LIB ;;
@@ -61,7 +61,7 @@ mix)       # VERDICT r03 "next" #5: the first n wide layers of the (f16x2) propo
            #  the experiment is reproducible from commit b0f5543, its result is profiles/r04_proposal_layer_mix_gpu.txt)
   for n in 0 2 3 5; do
     if [ $n = 0 ]; then unset NJF_HIP_LIB NJF_PROPOSAL_MIX; else export NJF_HIP_LIB=$PWD/build/libnjf_mix$n.so NJF_PROPOSAL_MIX=$n; fi
-    timeout 300 python bench.py --precision f16f6 --no-other-precisions --steps 10 --warmup 3 2>/dev/null | tail -1 > $O/mix$n.json
+    timeout 300 python bench.py --full --precision f16f6 --no-other-precisions --steps 10 --warmup 3 2>/dev/null | tail -1 > $O/mix$n.json
     python - <<PY
 import json
 d = json.load(open('$O/mix$n.json')); p = d['parity_on_bench_frame']['f16f6']

@@ -13,18 +13,18 @@ newtests)  # round 5's new test files only
   timeout 1800 python -m pytest tests/test_training_fixed_bins_gpu.py tests/test_rccl_gpu.py -m gpu -q -x > $O/pytest_new.txt 2>&1
   echo "pytest rc=$?"; tail -30 $O/pytest_new.txt ;;
 bench)
-  timeout 900 python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; tail -c 3000 $O/bench.json ;;
+  timeout 900 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; tail -c 3000 $O/bench.json ;;
 smoke)
   timeout 300 python __graft_entry__.py smoke > $O/smoke.txt 2>&1; echo "smoke rc=$?"; tail -c 1500 $O/smoke.txt ;;
 c5)        # BASELINE config 5 (512 x 512, A = 8 bench weights): frame times of every precision, headline protocol
-  timeout 600 python bench.py --height 512 --width 512 --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_c5.json 2> $O/bench_c5.err
+  timeout 600 python bench.py --full --height 512 --width 512 --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_c5.json 2> $O/bench_c5.err
   echo "c5 rc=$?"; python -c "
 import json; d=json.loads(open('$O/bench_c5.json').read().strip().splitlines()[-1])
 print('f32', d['ms_per_step'], d['kernel_ms'], d['roofline']['frac'])
 for k,v in d['other_precisions'].items(): print(k, v['ms_per_step'], v['kernel_ms'], v['roofline_frac'])" ;;
 configs)
   for a in "--batch 4 --samples 128" "--samples 256" "--samples 32"; do
-    echo "ARGS $a"; python bench.py --steps 5 --warmup 2 --no-cpu-baseline $a 2>/dev/null | tail -1
+    echo "ARGS $a"; python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline $a 2>/dev/null | tail -1
   done > $O/configs.txt ;;
 profile_c5)   # the "rocprof roofline report" BASELINE config 5 names: kernel stats + PMC of the 512 x 512 frame, three precisions
   bash tools/profile_r05.sh f16 r05_c5 full "--height 512 --width 512" > $O/profile_c5_f16.log 2>&1
