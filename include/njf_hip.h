@@ -449,6 +449,25 @@ int njf_solve_action(const float* mean_position, const float* jacobian, const fl
                      const float* visible_mask, const float* init_action, int batch, int rays, int action_dim,
                      int iterations, float damping, float* action, void* stream);
 
+/* The notebook's own objective (2_inverse_dynamics.ipynb: smooth_l1_loss(pred_flow, target_flow) + reg * a.pow(2).mean(),
+ * Adam; inference/action.py::optimize_actions: the same with mse_loss), with joint limits and several cameras per
+ * command.  B = G * views linearisations, each run of `views` consecutive batch elements sharing one command (G commands;
+ * batch % views == 0).  mean_position, jacobian, projection, target_flow and visible_mask keep njf_solve_action's layout;
+ * init_action, lower and upper are [G,A] (each may be NULL: zero start / unbounded).  Per command
+ *   L(a) = (1/N) sum_i m_i rho(r_i(a)) + (reg/A) sum_k a_k^2,  N = 2 sum_r m_r  (mask weights m_r >= 0),
+ * r_i the two flow components of every ray of every view of the command, rho = r^2 (loss NJF_LOSS_MSE) or torch's
+ * smooth-L1 with `beta` (NJF_LOSS_SMOOTH_L1), minimised over lower <= a <= upper by `iterations` projected IRLS
+ * Levenberg-Marquardt steps in ONE launch (one workgroup per command, deterministic reductions, capture-safe); a step
+ * is kept only if L drops.  The start is clamped into the box; a command with no observed ray returns it.  A <= 16;
+ * beta <= 0, reg < 0 or damping < 0 return NJF_E_VALUE (lower <= upper is the caller's to check: it lives on the
+ * device).  Writes action [G,A]. */
+#define NJF_LOSS_MSE 0
+#define NJF_LOSS_SMOOTH_L1 1
+int njf_solve_action_robust(const float* mean_position, const float* jacobian, const float* projection,
+                            const float* target_flow, const float* visible_mask, const float* init_action,
+                            const float* lower, const float* upper, int batch, int views, int rays, int action_dim,
+                            int loss, float beta, float reg, int iterations, float damping, float* action, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

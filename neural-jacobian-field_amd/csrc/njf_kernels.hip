@@ -24,6 +24,7 @@ enum {
   NJF_E_DOUT = -5,
   NJF_E_MODE = -6,
   NJF_E_GMAP = -7,
+  NJF_E_VALUE = -8,
 };
 
 extern "C" int njf_abi_version(void) { return NJF_ABI_VERSION; }
@@ -39,6 +40,7 @@ extern "C" const char* njf_error_string(int code) {
     case NJF_E_DOUT: return "ResnetFC d_out must be in [1, 32]";
     case NJF_E_MODE: return "unknown mode";
     case NJF_E_GMAP: return "feature map stride/offset does not cover NJF_ZDIM channels or is not 16-byte aligned";
+    case NJF_E_VALUE: return "invalid solver option (beta must be > 0, reg and damping >= 0)";
     default: return code > 0 ? "HIP runtime error (hipError_t)" : "unknown njf error";
   }
 }
@@ -2197,6 +2199,253 @@ extern "C" int njf_solve_action(const float* mean_position, const float* jacobia
   if (action_dim < 1 || action_dim > NJF_SOLVE_MAX_A) return NJF_E_ACTION_DIM;
   SolveArgs a{mean_position, jacobian, projection, target_flow, visible_mask, init_action, rays, action_dim, iterations, damping, action};
   solve_action_kernel<<<batch, 256, 0, (hipStream_t)stream>>>(a);
+  return launch_status();
+}
+
+// =============================================================================================
+// robust inverse dynamics: projected IRLS Levenberg-Marquardt, one workgroup per command
+// =============================================================================================
+// The objective notebooks/real_world/2_inverse_dynamics.ipynb minimises with Adam, per command (group of V views):
+//   L(a) = (1/N) sum_i m_i rho(r_i(a)) + (reg/A) |a|^2,  N = 2 sum_r m_r,  rho = r^2 (mse) or torch's smooth-L1,
+// with a box lower <= a <= upper.  Every iteration linearises each ray as in solve_action_kernel, but scales its two
+// Jacobian rows and residuals by sqrt(m omega / N), rho'(r) = omega(r) r (iteratively reweighted least squares), so the
+// same fixed-order [H | g] contraction yields the IRLS normal equations; the regulariser adds (2 reg / A)(I | a).
+// Coordinates on a bound whose gradient points outward are frozen (identity row and column, zero right-hand side), the
+// damped system is solved by a Gauss-Jordan sweep over all A * (A + 1) entries in parallel, the candidate is clamped into
+// the box, and it is kept only if the TRUE objective drops.
+struct RobustSolveArgs {
+  const float* pos;     // [B,R,3], B = G * V (view-major within a group)
+  const float* jac;     // [B,R,3,A]
+  const float* proj;    // [B,3,4]  K . inv(E)[:3] of each view
+  const float* target;  // [B,R,2]
+  const float* mask;    // [B,R] or null
+  const float* init;    // [G,A] or null
+  const float* lower;   // [G,A] or null
+  const float* upper;   // [G,A] or null
+  int R, A, V, iters, loss;
+  float beta, reg, damping;
+  float* action;        // [G,A]
+};
+
+__global__ void __launch_bounds__(256) robust_solve_kernel(RobustSolveArgs a) {
+  __shared__ float rows[256][2 * NJF_SOLVE_MAX_A + 2];  // per ray: 2 weighted Jacobian rows (A each) + 2 residuals
+  __shared__ float hmat[NJF_SOLVE_MAX_A][NJF_SOLVE_MAX_A + 1];
+  __shared__ float act[NJF_SOLVE_MAX_A], cand[NJF_SOLVE_MAX_A], lo[NJF_SOLVE_MAX_A], hi[NJF_SOLVE_MAX_A];
+  __shared__ float grad[NJF_SOLVE_MAX_A], red[256];
+  __shared__ int active[NJF_SOLVE_MAX_A];
+  __shared__ float lam, cost;
+  const int grp = blockIdx.x, tid = threadIdx.x, A = a.A, R = a.R, VR = a.V * a.R;
+  const size_t ray0 = (size_t)grp * VR;  // first ray of the group in [B,R] order
+  const float reg_a = a.reg / (float)A, two_reg_a = 2.0f * reg_a;
+  if (tid < A) {
+    lo[tid] = a.lower ? a.lower[grp * A + tid] : -INFINITY;
+    hi[tid] = a.upper ? a.upper[grp * A + tid] : INFINITY;
+    act[tid] = fminf(fmaxf(a.init ? a.init[grp * A + tid] : 0.f, lo[tid]), hi[tid]);
+  }
+  if (tid == 0) lam = a.damping;
+
+  auto block_sum = [&](float v) -> float {
+    red[tid] = v;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+      if (tid < o) red[tid] += red[tid + o];
+      __syncthreads();
+    }
+    const float out = red[0];
+    __syncthreads();
+    return out;
+  };
+  auto rho = [&](float e, float& omega) -> float {  // loss of one residual component and its IRLS weight
+    if (a.loss == NJF_LOSS_MSE) {
+      omega = 2.0f;
+      return e * e;
+    }
+    const float ae = fabsf(e);
+    if (ae < a.beta) {
+      omega = 1.0f / a.beta;
+      return 0.5f * e * e / a.beta;
+    }
+    omega = 1.0f / ae;
+    return ae - 0.5f * a.beta;
+  };
+
+  float msum = 0.f;
+  for (int q = tid; q < VR; q += 256) msum += a.mask ? a.mask[ray0 + q] : 1.f;
+  msum = block_sum(msum);
+  if (!(msum > 0.f)) {  // nothing observed: the clamped start is the answer
+    if (tid < A) a.action[grp * A + tid] = act[tid];
+    return;
+  }
+  const float inv_n = 1.0f / (2.0f * msum);
+
+  // m * (rho(r_u) + rho(r_v)) of ray q of the group at command `cmd`, and optionally its weighted rows into LDS `slot`
+  auto eval_ray = [&](int q, const float* cmd, bool want_rows, int slot) -> float {
+    const size_t ri = ray0 + q;
+    const float m = a.mask ? a.mask[ri] : 1.f;
+    if (m == 0.f) {
+      if (want_rows)
+        for (int k = 0; k < 2 * A + 2; ++k) rows[slot][k] = 0.f;
+      return 0.f;
+    }
+    const float* P = a.proj + (size_t)(grp * a.V + q / R) * 12;
+    float x[3], x0[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      x0[c] = a.pos[ri * 3 + c];
+      float v = x0[c];
+      for (int k = 0; k < A; ++k) v = fmaf(a.jac[(ri * 3 + c) * A + k], cmd[k], v);
+      x[c] = v;
+    }
+    auto project = [&](const float* p, float& u, float& v, float& d) {
+      const float hx = fmaf(P[2], p[2], fmaf(P[1], p[1], P[0] * p[0])) + P[3];
+      const float hy = fmaf(P[6], p[2], fmaf(P[5], p[1], P[4] * p[0])) + P[7];
+      d = fmaf(P[10], p[2], fmaf(P[9], p[1], P[8] * p[0])) + P[11] + 1e-9f;
+      u = hx / d;
+      v = hy / d;
+    };
+    float u0, v0, d0, u, v, d;
+    project(x0, u0, v0, d0);
+    project(x, u, v, d);
+    const float e0 = (u - u0) - a.target[ri * 2], e1 = (v - v0) - a.target[ri * 2 + 1];
+    float om0, om1;
+    const float l = rho(e0, om0) + rho(e1, om1);
+    if (want_rows) {
+      const float s0 = sqrtf(m * om0 * inv_n), s1 = sqrtf(m * om1 * inv_n);
+      float gu[3], gv[3];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        gu[c] = (P[c] - u * P[8 + c]) / d;
+        gv[c] = (P[4 + c] - v * P[8 + c]) / d;
+      }
+      for (int k = 0; k < A; ++k) {
+        float ju = 0.f, jv = 0.f;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          const float mk = a.jac[(ri * 3 + c) * A + k];
+          ju = fmaf(gu[c], mk, ju);
+          jv = fmaf(gv[c], mk, jv);
+        }
+        rows[slot][k] = ju * s0;
+        rows[slot][A + k] = jv * s1;
+      }
+      rows[slot][2 * A] = e0 * s0;
+      rows[slot][2 * A + 1] = e1 * s1;
+    }
+    return m * l;
+  };
+
+  // entry e = hi * (A + 1) + hj of [H | g]; A * (A + 1) <= 272, so a thread owns entry tid and, for A = 16, tid + 256
+  const int entries = A * (A + 1);
+  for (int it = 0; it < a.iters; ++it) {
+    float hacc[2] = {0.f, 0.f}, csum = 0.f;
+    for (int q0 = 0; q0 < VR; q0 += 256) {
+      const int q = q0 + tid;
+      if (q < VR) csum += eval_ray(q, act, true, tid);
+      __syncthreads();
+      const int n = min(256, VR - q0);
+#pragma unroll
+      for (int k = 0; k < 2; ++k) {
+        const int e = tid + 256 * k;
+        if (e < entries) {
+          const int i = e / (A + 1), j = e % (A + 1);
+          float acc = hacc[k];
+          for (int q = 0; q < n; ++q) {
+            const float bu = j < A ? rows[q][j] : rows[q][2 * A], bv = j < A ? rows[q][A + j] : rows[q][2 * A + 1];
+            acc = fmaf(rows[q][i], bu, acc);
+            acc = fmaf(rows[q][A + i], bv, acc);
+          }
+          hacc[k] = acc;
+        }
+      }
+      __syncthreads();
+    }
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const int e = tid + 256 * k;
+      if (e < entries) hmat[e / (A + 1)][e % (A + 1)] = hacc[k];
+    }
+    const float c_now = block_sum(csum);  // its barriers publish hmat
+    // gradient with the regulariser; a coordinate on a bound whose gradient points out of the box is frozen
+    if (tid < A) {
+      const float gi = fmaf(two_reg_a, act[tid], hmat[tid][A]);
+      grad[tid] = gi;
+      active[tid] = (act[tid] <= lo[tid] && gi > 0.f) || (act[tid] >= hi[tid] && gi < 0.f);
+    }
+    if (tid == 0) {
+      float sq = 0.f;
+      for (int k = 0; k < A; ++k) sq = fmaf(act[k], act[k], sq);
+      cost = fmaf(c_now, inv_n, reg_a * sq);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {  // (H + (2 reg / A) I) with frozen rows / columns, then + lam diag
+      const int e = tid + 256 * k;
+      if (e < entries) {
+        const int i = e / (A + 1), j = e % (A + 1);
+        float v = hmat[i][j];
+        if (j == A)
+          v = active[i] ? 0.f : grad[i];
+        else if (active[i] || active[j])
+          v = i == j ? 1.f : 0.f;
+        else if (i == j)
+          v += two_reg_a;
+        if (i == j) v += lam * fmaxf(v, 1e-12f);
+        hmat[i][j] = v;
+      }
+    }
+    __syncthreads();
+    // un-pivoted Gauss-Jordan (symmetric positive definite after damping), one pivot per step over all entries
+    for (int p = 0; p < A; ++p) {
+      float nv[2];
+#pragma unroll
+      for (int k = 0; k < 2; ++k) {
+        const int e = tid + 256 * k;
+        if (e < entries) {
+          const int i = e / (A + 1), j = e % (A + 1);
+          const float pj = hmat[p][j] * (1.0f / hmat[p][p]);
+          nv[k] = i == p ? pj : fmaf(-hmat[i][p], pj, hmat[i][j]);
+        }
+      }
+      __syncthreads();
+#pragma unroll
+      for (int k = 0; k < 2; ++k) {
+        const int e = tid + 256 * k;
+        if (e < entries) hmat[e / (A + 1)][e % (A + 1)] = nv[k];
+      }
+      __syncthreads();
+    }
+    if (tid < A) cand[tid] = fminf(fmaxf(act[tid] - hmat[tid][A], lo[tid]), hi[tid]);
+    __syncthreads();
+    float cs = 0.f;
+    for (int q = tid; q < VR; q += 256) cs += eval_ray(q, cand, false, 0);
+    const float c_new = block_sum(cs);
+    if (tid == 0) {
+      float sq = 0.f;
+      for (int k = 0; k < A; ++k) sq = fmaf(cand[k], cand[k], sq);
+      const bool better = fmaf(c_new, inv_n, reg_a * sq) < cost;  // NaN (a point behind the camera): rejected
+      if (better)
+        for (int i = 0; i < A; ++i) act[i] = cand[i];
+      lam = fminf(fmaxf(better ? lam / 3.0f : lam * 4.0f, 1e-9f), 1e9f);
+    }
+    __syncthreads();
+  }
+  if (tid < A) a.action[grp * A + tid] = act[tid];
+}
+
+extern "C" int njf_solve_action_robust(const float* mean_position, const float* jacobian, const float* projection,
+                                       const float* target_flow, const float* visible_mask, const float* init_action,
+                                       const float* lower, const float* upper, int batch, int views, int rays,
+                                       int action_dim, int loss, float beta, float reg, int iterations, float damping,
+                                       float* action, void* stream) {
+  if (!mean_position || !jacobian || !projection || !target_flow || !action) return NJF_E_NULL;
+  if (batch < 1 || rays < 1 || iterations < 0 || views < 1 || batch % views != 0) return NJF_E_SHAPE;
+  if ((long long)views * rays > 0x7fffffffLL) return NJF_E_SHAPE;
+  if (action_dim < 1 || action_dim > NJF_SOLVE_MAX_A) return NJF_E_ACTION_DIM;
+  if (loss != NJF_LOSS_MSE && loss != NJF_LOSS_SMOOTH_L1) return NJF_E_MODE;
+  if (!(beta > 0.f) || !(reg >= 0.f) || !(damping >= 0.f)) return NJF_E_VALUE;
+  RobustSolveArgs a{mean_position, jacobian, projection, target_flow, visible_mask, init_action, lower, upper,
+                    rays, action_dim, views, iterations, loss, beta, reg, damping, action};
+  robust_solve_kernel<<<batch / views, 256, 0, (hipStream_t)stream>>>(a);
   return launch_status();
 }
 

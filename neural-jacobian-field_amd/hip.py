@@ -127,6 +127,8 @@ _SIGNATURES = {
     "njf_upsample_concat": ([C.POINTER(PyramidLevel), C.c_int, C.c_int, _vp, _vp], C.c_int),
     "njf_upsample_concat_backward": ([_vp, C.POINTER(PyramidLevel), C.c_int, C.c_int, _vp], C.c_int),
     "njf_solve_action": ([_vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _vp, _vp], C.c_int),
+    "njf_solve_action_robust": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                 C.c_float, C.c_float, C.c_int, C.c_float, _vp, _vp], C.c_int),
     "njf_invert_4x4": ([_vp, C.c_int, _vp, _vp], C.c_int),
     "njf_generate_rays": ([_vp, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp], C.c_int),
     "njf_proposal_forward": ([_vp, _vp, C.c_int, C.POINTER(Cameras), C.POINTER(FeatureMap), C.c_int, _vp, _vp,
@@ -583,6 +585,39 @@ def solve_action(mean_position, jacobian, projection, target_flow, visible_mask,
     _launch("njf_solve_action", load_library().njf_solve_action, _ptr(mean_position), _ptr(jacobian), _ptr(projection), _ptr(target_flow),
                                            _ptr(visible_mask), _ptr(init_action), b, r, jacobian.shape[-1], int(iterations),
                                            float(damping), _ptr(action))
+
+
+SOLVE_MAX_ACTION_DIM = 16
+SOLVE_LOSSES = {"mse": 0, "smooth_l1": 1}   # include/njf_hip.h: NJF_LOSS_*
+
+
+def solve_action_robust(mean_position, jacobian, projection, target_flow, visible_mask, init_action, lower, upper,
+                        views: int, loss: str, beta: float, reg: float, iterations: int, damping: float, action) -> None:
+    """njf_solve_action_robust: mean_position [B,R,3], jacobian [B,R,3,A], projection [B,3,4], target_flow [B,R,2],
+    visible_mask [B,R] | None, init_action / lower / upper [G,A] | None with B = G * views -> action [G,A]."""
+    if loss not in SOLVE_LOSSES:
+        raise ValueError(f"njf_hip: unknown loss {loss!r}; choose from {sorted(SOLVE_LOSSES)}")
+    if target_flow.dim() != 3 or target_flow.shape[-1] != 2:
+        raise ValueError(f"njf_hip: target_flow must be [B,R,2] (got {tuple(target_flow.shape)})")
+    b, r = target_flow.shape[:2]
+    a = jacobian.shape[-1]
+    if views < 1 or b % views:
+        raise ValueError(f"njf_hip: views_per_command={views} must be >= 1 and divide the batch of {b} linearisations")
+    if not 1 <= a <= SOLVE_MAX_ACTION_DIM:
+        raise ValueError(f"njf_hip: the solve supports 1 <= A <= {SOLVE_MAX_ACTION_DIM} (got {a})")
+    g = b // views
+    shapes = {"mean_position": (mean_position, (b, r, 3)), "jacobian": (jacobian, (b, r, 3, a)),
+              "projection": (projection, (b, 3, 4)), "visible_mask": (visible_mask, (b, r)),
+              "init_action": (init_action, (g, a)), "lower": (lower, (g, a)), "upper": (upper, (g, a)),
+              "action": (action, (g, a))}
+    for name, (t, shape) in shapes.items():
+        if t is not None and tuple(t.shape) != shape:
+            raise ValueError(f"njf_hip: {name} must be {list(shape)} (got {list(t.shape)})")
+    _launch("njf_solve_action_robust", load_library().njf_solve_action_robust, _ptr(mean_position, "mean_position"),
+            _ptr(jacobian, "jacobian"), _ptr(projection, "projection"), _ptr(target_flow, "target_flow"),
+            _ptr(visible_mask, "visible_mask"), _ptr(init_action, "init_action"), _ptr(lower, "lower"),
+            _ptr(upper, "upper"), b, int(views), r, a, SOLVE_LOSSES[loss], float(beta), float(reg), int(iterations),
+            float(damping), _ptr(action, "action"))
 
 
 def scatter_footprint(grad, foot_idx, foot_w, out, run_length: int = 1) -> None:

@@ -57,23 +57,103 @@ def _projection_matrix(lin: FlowLinearization) -> torch.Tensor:
     return lin.trgt_intrinsics @ hip.inverse(lin.trgt_extrinsics)[:, :3, :]
 
 
+LOSSES = ("mse", "smooth_l1")
+
+
+def _check_options(loss: str, beta: float, reg: float, views_per_command: int, batch: int) -> None:
+    if loss not in LOSSES:
+        raise ValueError(f"solve_action: unknown loss {loss!r}; choose from {LOSSES}")
+    if not beta > 0:
+        raise ValueError(f"solve_action: beta must be > 0 (got {beta})")
+    if not reg >= 0:
+        raise ValueError(f"solve_action: reg must be >= 0 (got {reg})")
+    if views_per_command < 1 or batch % views_per_command:
+        raise ValueError(f"solve_action: views_per_command={views_per_command} must be >= 1 and divide the batch of "
+                         f"{batch} linearisations")
+
+
+def _box(bounds, groups: int, action_dim: int, device) -> tuple:
+    """(lower, upper), each None, a number, [A] or [G,A] -> contiguous fp32 [G,A] tensors (or None) on `device`."""
+    if bounds is None:
+        return None, None
+    if len(bounds) != 2:
+        raise ValueError("solve_action: bounds must be a pair (lower, upper)")
+    out = []
+    for name, b in zip(("lower", "upper"), bounds):
+        if b is None:
+            out.append(None)
+            continue
+        t = torch.as_tensor(b, dtype=torch.float32, device=device)
+        if t.dim() > 2 or (t.dim() == 2 and t.shape[0] not in (1, groups)) or (t.dim() >= 1 and t.shape[-1] not in (1, action_dim)):
+            raise ValueError(f"solve_action: {name} bound must be [A] or [G,A] = [{groups},{action_dim}] (got {list(t.shape)})")
+        out.append(t.expand(groups, action_dim).contiguous())
+    lo, hi = out
+    # lower <= upper lives on the device: checked here, in eager calls (a capture cannot synchronise; the graphed
+    # controller runs this check in its eager warm-up)
+    if lo is not None and hi is not None and not (lo.is_cuda and torch.cuda.is_current_stream_capturing()):
+        if bool((lo > hi).any()):
+            raise ValueError("solve_action: lower bound exceeds upper bound")
+    return lo, hi
+
+
 @torch.no_grad()
 def solve_action(lin: FlowLinearization, target_flow: torch.Tensor, init_action: Optional[torch.Tensor] = None,
-                 iterations: int = 20, damping: float = 1e-3, visible_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+                 iterations: int = 20, damping: float = 1e-3, visible_mask: Optional[torch.Tensor] = None, *,
+                 loss: str = "mse", beta: float = 1.0, reg: float = 0.0, bounds=None,
+                 views_per_command: int = 1) -> torch.Tensor:
     """Levenberg-Marquardt on ``|| optical_flow(a) - target_flow ||^2`` (pixels): all iterations in ONE HIP launch
     (``njf_solve_action``: one workgroup per batch element, deterministic reductions, no host synchronisation).
 
     target_flow [B,R,2], visible_mask [B,R] (the notebook masks the loss with the tracker's visibility) -> [B,A].
     The only non-linearity is the perspective divide, so for the few-pixel flows of a control step a handful of
     iterations reach the minimum; a step is kept only where it lowers the cost, which keeps large-flow problems
-    stable.  GPU tensors only (no CPU path); the tensor-op restatement used by the tests lives in oracle/."""
+    stable.  GPU tensors only (no CPU path); the tensor-op restatement used by the tests lives in oracle/.
+
+    The keyword options select the notebook's own objective (``njf_solve_action_robust``, see ``action_objective``):
+    ``loss`` "mse" | "smooth_l1" (torch's, with ``beta``) on the masked mean of the flow residuals, plus
+    ``reg * a.pow(2).mean()``; ``bounds = (lower, upper)``, each a number, [A] or [G,A] (either may be None), a box on
+    the command; ``views_per_command = V``: each run of V consecutive linearisations (cameras) constrains one command,
+    so init_action is [G,A] and the result [G,A] with G = B / V.  With every option at its default the call is the
+    plain least-squares solve above, unchanged."""
     from . import hip
     b = target_flow.shape[0]
-    out = torch.empty(b, lin.jacobian.shape[-1], dtype=torch.float32, device=target_flow.device)
+    a = lin.jacobian.shape[-1]
+    _check_options(loss, beta, reg, views_per_command, b)
     f = lambda t: None if t is None else t.float().contiguous()
-    hip.solve_action(f(lin.mean_position), f(lin.jacobian), f(_projection_matrix(lin)), f(target_flow), f(visible_mask),
-                     f(init_action), iterations, damping, out)
+    if loss == "mse" and reg == 0 and bounds is None and views_per_command == 1:
+        out = torch.empty(b, a, dtype=torch.float32, device=target_flow.device)
+        hip.solve_action(f(lin.mean_position), f(lin.jacobian), f(_projection_matrix(lin)), f(target_flow),
+                         f(visible_mask), f(init_action), iterations, damping, out)
+        return out
+    g = b // views_per_command
+    lower, upper = _box(bounds, g, a, target_flow.device)
+    out = torch.empty(g, a, dtype=torch.float32, device=target_flow.device)
+    hip.solve_action_robust(f(lin.mean_position), f(lin.jacobian), f(_projection_matrix(lin)), f(target_flow),
+                            f(visible_mask), f(init_action), lower, upper, views_per_command, loss, beta, reg,
+                            iterations, damping, out)
     return out
+
+
+def action_objective(lin: FlowLinearization, target_flow: torch.Tensor, action: torch.Tensor,
+                     visible_mask: Optional[torch.Tensor] = None, *, loss: str = "mse", beta: float = 1.0,
+                     reg: float = 0.0, views_per_command: int = 1) -> torch.Tensor:
+    """The objective ``solve_action``'s options select, per command, in torch ops (any device, differentiable):
+    ``L(a) = (1/N) sum_i m_i rho(r_i(a)) + (reg/A) |a|^2`` over the two flow components r_i of every ray of the
+    command's views, N = 2 sum_r m_r, rho = r^2 ("mse") or torch's smooth-L1 with ``beta``.  With a binary mask and
+    one view this is the notebook's ``F.smooth_l1_loss(pred[m], target[m], beta=beta) + reg * a.pow(2).mean()`` (or
+    ``mse_loss``).  action [G,A] -> [G]; a command without observed rays scores its regulariser alone."""
+    _check_options(loss, beta, reg, views_per_command, target_flow.shape[0])
+    g = action.shape[0]
+    res = lin.optical_flow(action.repeat_interleave(views_per_command, dim=0)) - target_flow
+    if loss == "mse":
+        rho = res.square()
+    else:
+        rho = torch.where(res.abs() < beta, 0.5 * res.square() / beta, res.abs() - 0.5 * beta)
+    m = torch.ones_like(res[..., 0]) if visible_mask is None else visible_mask.to(res.dtype)
+    rho = torch.where(m[..., None] != 0, rho * m[..., None], torch.zeros_like(rho))   # unobserved rays: no term at all
+    n = 2 * m.reshape(g, -1).sum(1)
+    data = torch.where(n > 0, rho.reshape(g, -1).sum(1) / n.clamp_min(1e-30), torch.zeros_like(n))
+    return data + reg * action.square().mean(-1)
 
 
 class GraphedLinearizer:
@@ -108,23 +188,34 @@ class GraphedInverseDynamics:
     """The whole control step -- encoder, lin_z hoist, proposal pass, final pass, ``iterations`` Levenberg-Marquardt
     steps -- as ONE replayed HIP graph: ``action = controller(image, target_flow[, init_action, visible_mask])``.
     Camera rig, tracked rays and iteration count are fixed at capture time; nothing in the step synchronises with the
-    host, so the per-frame host cost is three small copies and one graph launch."""
+    host, so the per-frame host cost is three small copies and one graph launch.
+
+    ``loss``, ``beta``, ``reg``, ``bounds`` and ``views_per_command`` are ``solve_action``'s options, fixed at capture
+    time as well.  With ``views_per_command = V`` the rig's B = G * V cameras constrain G commands: one call takes the B
+    images [B,3,H,W] and target flows [B,R,2] (init_action [G,A]) and returns [G,A].  ``linearization`` holds the
+    graph's static linearisation of the last call."""
 
     def __init__(self, model: Model, camera_input: CameraInput, rendering_input: RenderingInput, iterations: int = 8,
-                 damping: float = 1e-3, action_dim: Optional[int] = None, warmup: int = 2):
+                 damping: float = 1e-3, action_dim: Optional[int] = None, warmup: int = 2, *, loss: str = "mse",
+                 beta: float = 1.0, reg: float = 0.0, bounds=None, views_per_command: int = 1):
         a = action_dim or model.cfg.action_dim
         b, r = rendering_input.origins.shape[:2]
         dev = rendering_input.origins.device
+        _check_options(loss, beta, reg, views_per_command, b)
+        g = b if views_per_command == 1 else b // views_per_command
         self._image = camera_input.input_image.clone()
         self._target = torch.zeros(b, r, 2, device=dev)
-        self._init = torch.zeros(b, a, device=dev)
+        self._init = torch.zeros(g, a, device=dev)
         self._mask = torch.ones(b, r, device=dev)
+        if bounds is not None:   # static copies, kept alive with the graph: the captured launch reads these buffers
+            bounds = self._bounds = tuple(None if t is None else t.clone() for t in _box(bounds, g, a, dev))
+        options = dict(loss=loss, beta=beta, reg=reg, bounds=bounds, views_per_command=views_per_command)
         cam = CameraInput(self._image, camera_input.ctxt_extrinsics, camera_input.ctxt_intrinsics,
                           camera_input.trgt_extrinsics, camera_input.trgt_intrinsics)
 
         def step():
-            lin = linearize_flow(model, cam, rendering_input, a)
-            return solve_action(lin, self._target, self._init, iterations, damping, self._mask)
+            self.linearization = linearize_flow(model, cam, rendering_input, a)
+            return solve_action(self.linearization, self._target, self._init, iterations, damping, self._mask, **options)
 
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())

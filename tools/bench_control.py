@@ -2,7 +2,9 @@
 """Control-loop latency (not the headline metric): one context image, R tracked rays, 64+64 samples.
 Times (a) the encoder, (b) linearize_flow = one fused render of the tracked rays, eager and as a replayed HIP graph,
 (c) the Levenberg-Marquardt solve, next to (d) the notebook's route: encode_image once + 100 Adam steps through
-infer_optical_flow (notebooks/real_world/2_inverse_dynamics.ipynb cells 26-29)."""
+infer_optical_flow (notebooks/real_world/2_inverse_dynamics.ipynb cells 26-29); then the notebook's real objective
+(smooth-L1 + reg, Adam at lr 0.1) against the robust solve of it (njf_solve_action_robust: eager on the same
+linearisation, on synthetic linearisations with A = 8 / 16 and 1 / 4 views per command, and as the graphed control step)."""
 import json, os, sys, time
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -75,4 +77,50 @@ def adam_100():
 
 t_adam, _ = timed(adam_100, n=2, warm=1)
 res["notebook_route_100_adam_steps_ms"] = round(t_adam, 1)
+
+# the notebook's real objective (smooth-L1 + reg * a.pow(2).mean(), lr 0.1) and the robust solve of it
+REG = 1e-4
+act_s = torch.zeros(B, A, device=dev, requires_grad=True)
+opt_s = torch.optim.Adam([act_s], lr=0.1)
+
+
+def adam_100_smooth_l1():
+    for _ in range(100):
+        opt_s.zero_grad()
+        flow = model.infer_optical_flow(enc, cam, RobotInput(act_s))
+        loss = torch.nn.functional.smooth_l1_loss(flow, target) + REG * act_s.pow(2).mean()
+        loss.backward()
+        opt_s.step()
+
+
+t_adam_s, _ = timed(adam_100_smooth_l1, n=2, warm=1)
+res["notebook_route_100_adam_steps_smooth_l1_ms"] = round(t_adam_s, 1)
+with torch.no_grad():
+    robust = dict(loss="smooth_l1", reg=REG)
+    t_rob, got_r = timed(lambda: idyn.solve_action(lin, target, iterations=8, **robust))
+    res["robust_solve_ms_8_iters"] = round(t_rob, 3)   # same linearisation and rays as lm_solve_ms_8_iters
+    res["robust_objective_vs_adam"] = [idyn.action_objective(lin, target, got_r, **robust).item(),
+                                       idyn.action_objective(lin, target, act_s.detach(), **robust).item()]
+    gen = torch.Generator().manual_seed(1)
+    for a_dim, views in ((8, 1), (8, 4), (16, 1), (16, 4)):   # synthetic linearisations: R rays per view, 8 iterations
+        b = 1 * views
+        pos = torch.rand(b, R, 3, generator=gen) * torch.tensor([1.0, 1.0, 0.5]) + torch.tensor([-0.5, -0.5, 1.5])
+        ext = torch.eye(4).repeat(b, 1, 1)
+        ext[:, :3, 3] = torch.randn(b, 3, generator=gen) * 0.05
+        k = torch.tensor([[200.0, 0, 128], [0, 210.0, 120], [0, 0, 1]]).repeat(b, 1, 1)
+        syn = idyn.FlowLinearization(pos.to(dev), (torch.randn(b, R, 3, a_dim, generator=gen) * 0.05).to(dev),
+                                     ext.to(dev), k.to(dev))
+        tgt = syn.optical_flow((torch.randn(b, a_dim, generator=gen) * 0.5).to(dev))
+        if views == 1:
+            t_l2, _ = timed(lambda: idyn.solve_action(syn, tgt, iterations=8))
+            res[f"lm_solve_ms_8_iters_synthetic_a{a_dim}"] = round(t_l2, 3)
+        t_r, _ = timed(lambda: idyn.solve_action(syn, tgt, iterations=8, views_per_command=views,
+                                                 bounds=(-1.0, 1.0), **robust))
+        res[f"robust_solve_ms_8_iters_synthetic_a{a_dim}_v{views}"] = round(t_r, 3)
+try:
+    ctrl_s = idyn.GraphedInverseDynamics(model, cam, rin, iterations=8, **robust)
+    t_ctrl_s, _ = timed(lambda: ctrl_s(cam.input_image, target))
+    res["control_step_graph_smooth_l1_ms"] = round(t_ctrl_s, 3)
+except Exception as e:  # noqa: BLE001
+    res["graph_smooth_l1_error"] = repr(e)[:300]
 print(json.dumps(res))
