@@ -332,6 +332,61 @@ int njf_points_forward(const float* xyz, const float* dirs, int points_per_batch
                        float* density, float* color, float* flow, float* jacobian, float* geo, float* features, int precision,
                        void* stream);
 
+/* ---- voxel-grid field extraction (additive within ABI v20): the 3-D Jacobian-field point cloud --------------------- */
+/* The reference colours point clouds of per-point Jacobians (inference/jacobian_color_map.py:113-160) that it obtains by
+ * hand: a dense grid through Model.compute_density (model.py:416-456), then threshold / nonzero / gather.  These entry
+ * points generate the grid on the device, cull it in stages and evaluate the decoder on the survivors only.
+ *
+ * A grid is shared by the B context images of a call.  Node (ix, iy, iz) has the linear index n = (ix*ny + iy)*nz + iz,
+ * the coordinate fmaf((float)i_c, step[c], origin[c]) per component c, and -- for batch element b -- the GLOBAL index
+ * b*N + n with N = nx*ny*nz; B*N must stay below 2^31 (NJF_E_SHAPE otherwise, as for any dims[c] < 1).
+ *
+ * A LIST names nodes: `indices` (device int32 global indices; NULL = the identity 0, 1, 2, ...), `count` (device int32,
+ * the number of entries; NULL = `capacity`) and `capacity` (host int >= 0: the extent the launch covers and the most
+ * entries ever read; with indices == NULL it may not exceed B*N).  The entries used are the first min(*count, capacity);
+ * the count is read ON THE DEVICE, so a caller that may not synchronise (graph capture) launches for a capacity and the
+ * surplus workgroups leave at once.  Indices outside [0, B*N) are clamped into it.  Every per-entry array below is
+ * COMPACT: row i belongs to list entry i. */
+typedef struct NjfFieldGrid {
+  float origin[3];  /* coordinate of node (0, 0, 0) */
+  float step[3];    /* spacing per axis */
+  int dims[3];      /* (nx, ny, nz), each >= 1 */
+} NjfFieldGrid;
+
+/* xyz [capacity, 3] <- the coordinates of the list's nodes (rows past the entry count are left untouched). */
+int njf_field_points(const NjfFieldGrid* grid, int batch, const int* indices, const int* count, int capacity, float* xyz,
+                     void* stream);
+
+/* Ordered selection.  Entry i of the list is kept when
+ *   (values == NULL || values[i] >= threshold)  and
+ *   (cams == NULL   || its node projects inside the context image of its batch element with positive camera depth:
+ *                      the camera-space point and the normalised image coordinates (u, v) of the fused kernels' feature
+ *                      gather; kept iff z_cam > 0 and 0 <= u <= 1 and 0 <= v <= 1; only ctxt_w2c / ctxt_k are read and
+ *                      cams->batch must equal `batch`).
+ * At least one of `values` (device fp32 [capacity], compact) and `cams` must be given (NJF_E_NULL).  Writes the GLOBAL
+ * indices of the kept entries to out_indices IN INPUT ORDER -- the first out_capacity of them -- and the TRUE number of
+ * kept entries to *out_count (device int32; it may exceed out_capacity; out_indices may be NULL when out_capacity == 0).
+ * out_indices must not alias indices.  `workspace`: device int32 [ceil(capacity / NJF_FIELD_SELECT_BLOCK)] (at least one
+ * element), caller-owned.  Three launches -- per-workgroup counts by ballot + popcount, a one-workgroup exclusive scan, a
+ * scatter -- in integer arithmetic without atomics: the output bytes are reproducible. */
+#define NJF_FIELD_SELECT_BLOCK 1024
+int njf_field_select(const NjfFieldGrid* grid, const NjfCameras* cams, int batch, const float* values, float threshold,
+                     const int* indices, const int* count, int capacity, int* out_indices, int* out_count, int out_capacity,
+                     int* workspace, void* stream);
+
+/* njf_points_forward on the nodes of a list (the batch is cams->batch): same networks, same weight / bias / map / precision
+ * arguments and the same per-point arithmetic -- a node's outputs equal what njf_points_forward returns for its coordinate.
+ * mode 0: proposal net -> density [capacity] (required).  mode 1: decoder -> density [capacity], color [capacity, 3],
+ * jacobian [capacity, 3A]; with jacobian_kind == NJF_JACOBIAN_NONE and color == NULL only the density network runs (and only
+ * its blob is read: w_color / b_color may be NULL); otherwise density / color may be NULL, `jacobian` is required when a head
+ * is selected.  view_dir: HOST pointer to the 3 floats of the colour head's constant view direction, used as given (NULL =
+ * (0, 0, 1), what Model.compute_density feeds).  cams->action is not read.  Rows past the entry count are left untouched. */
+int njf_field_forward(const NjfFieldGrid* grid, const int* indices, const int* count, int capacity, const float* view_dir,
+                      const NjfCameras* cams, const NjfFeatureMap* gmap, int gmap_offset_density, int gmap_offset_jacobian,
+                      int mode, int jacobian_kind /* NJF_JACOBIAN_* */, const float* w_density, const float* b_density,
+                      const float* w_color, const float* b_color, const float* w_jacobian, const float* b_jacobian,
+                      float* density, float* color, float* jacobian, int precision, void* stream);
+
 /* ---- stand-alone sampler / compositing ops (API parity with the un-fused reference calls) -- */
 /* RaySamples.get_weights (ray_samplers.py:77-101): deltas, densities [N,S] -> weights [N,S]. */
 int njf_alpha_weights(const float* deltas, const float* densities, int rays, int samples, float* weights, void* stream);

@@ -2037,6 +2037,266 @@ __global__ void __launch_bounds__(NJF_THREADS, 2) points_kernel(PointsArgs a) {
 }
 
 // =============================================================================================
+// voxel-grid field extraction: grid-driven point evaluator, ordered selection, coordinates
+// =============================================================================================
+// Node (ix, iy, iz) of a grid (NjfFieldGrid) has linear index n = (ix*ny + iy)*nz + iz and the coordinate
+// fmaf(i_c, step[c], origin[c]); node n of batch element b has the GLOBAL index b*N + n (N = nx*ny*nz, B*N < 2^31).
+// A "list" is `indices` (global indices, NULL = the identity) with its entry count min(*count, capacity) read from device
+// memory (count NULL = capacity): a capture-safe caller launches for the capacity, surplus workgroups leave at once.
+struct FieldList {
+  NjfFieldGrid grid;
+  int nodes;           // N
+  int total;           // B*N
+  const int* indices;  // or null
+  const int* count;    // or null
+  int capacity;
+};
+
+__device__ __forceinline__ int field_entries(const FieldList& l) {
+  return l.count ? min(max(*l.count, 0), l.capacity) : l.capacity;
+}
+
+// global index of list entry i, clamped into the grid (an index list is caller data: nothing may address outside the
+// cameras / the hoisted map because of it)
+__device__ __forceinline__ int field_global_index(const FieldList& l, int i) {
+  const int gi = l.indices ? l.indices[i] : i;
+  return min(max(gi, 0), l.total - 1);
+}
+
+__device__ __forceinline__ void field_node(const FieldList& l, int gi, int& b, float& px, float& py, float& pz) {
+  b = gi / l.nodes;
+  const int n = gi - b * l.nodes;
+  const int yz = l.grid.dims[1] * l.grid.dims[2];
+  const int ix = n / yz, r = n - ix * yz;
+  const int iy = r / l.grid.dims[2], iz = r - iy * l.grid.dims[2];
+  px = fmaf((float)ix, l.grid.step[0], l.grid.origin[0]);
+  py = fmaf((float)iy, l.grid.step[1], l.grid.origin[1]);
+  pz = fmaf((float)iz, l.grid.step[2], l.grid.origin[2]);
+}
+
+struct FieldArgs {
+  FieldList list;
+  float dirx, diry, dirz;  // constant view direction of the colour head
+  NjfCameras cams;
+  NjfFeatureMap gmap;
+  int goff_d, goff_j;
+  const float* w_all;
+  const float* b_d;
+  const float* b_c;
+  const float* b_j;
+  float* density;   // [entries]
+  float* color;     // [entries, 3]
+  float* jacobian;  // [entries, 3A]
+};
+
+// The point-list evaluator (points_kernel) fed from a grid descriptor + list: row i of every output is list entry i.
+// MODE 0: proposal net; 1: decoder density only (the density net alone is streamed); 2: density + colour; 3: density +
+// colour + ResnetFC Jacobian head; 4: density + colour + transformer Jacobian head.  Same stages, same weight stream and
+// the same per-point arithmetic as points_kernel: a node's outputs equal those of njf_points_forward on its coordinate.
+template <int MODE, int PREC, int PRECJ = PREC>
+__global__ void __launch_bounds__(NJF_THREADS, 2) field_points_kernel(FieldArgs a) {
+  const int entries = field_entries(a.list);
+  const int tid = threadIdx.x;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int lane = tid & 63, j = lane & 31, hh = lane >> 5;
+  const int wg = xcd_remap(blockIdx.x, gridDim.x);
+  if (wg * (NJF_WAVES * 32) >= entries) return;  // the whole workgroup (it shares the weight stream), before any barrier
+  const int tile = wg * NJF_WAVES + wave;
+  const int p = tile * 32 + j;
+  const bool ok = p < entries;
+  const int pc = min(p, entries - 1);
+
+  load_bias_block(a.b_d, NJF_RESNET_B_FLOATS, 0);
+  if (MODE >= 2) load_bias_block(a.b_c, NJF_COLOR_B_FLOATS, NJF_RESNET_B_FLOATS);
+  if (MODE == 3) load_bias_block(a.b_j, NJF_RESNET_B_FLOATS, NJF_RESNET_B_FLOATS + NJF_COLOR_B_FLOATS);
+  if (MODE == 4) load_bias_block(a.b_j, NJF_TRANSFORMER_B_FLOATS, NJF_RESNET_B_FLOATS + NJF_COLOR_B_FLOATS);
+  WeightStreamT<resnet_gap_at<PREC>(), resnet_gap<PREC>()> st;
+  stream_begin(st, a.w_all,
+               MODE <= 1 ? resnet_chunks<PREC>()
+                         : resnet_chunks<PREC>() + 1 + (MODE == 3 ? resnet_chunks<PRECJ>() : (MODE == 4 ? NJF_TRANSFORMER_CHUNKS : 0)),
+               1, wave, lane);
+  int b;
+  float px, py, pz;
+  field_node(a.list, field_global_index(a.list, pc), b, px, py, pz);
+  CamCtx cam;
+  load_ctx(a.cams.ctxt_w2c, a.cams.ctxt_k, b, cam);
+  PointGeom g;
+  const unsigned gbase = (unsigned)b * (unsigned)(a.gmap.height * a.gmap.width) * (unsigned)a.gmap.stride;
+  point_geometry(cam, px, py, pz, a.gmap.height, a.gmap.width, a.gmap.stride, gbase, g);
+  const float* bias = njf_lds + LDS_BIAS;
+  if (MODE == 0) {
+    f32x16 pe[2], out[1];
+    positional_encoding(g.xc, g.yc, g.zc, hh, pe);
+    resnet_tile<PREC>(st, bias, map_at<PREC>(a.gmap.data, a.goff_d), g, pe, wave, lane, out);
+    if (ok && hh == 0) a.density[p] = expf(out[0][0] - 1.0f);
+  } else {
+    const int A = a.cams.action_dim;
+    constexpr int JK = MODE >= 3 ? MODE - 2 : 0;
+    const ActDump nodump{nullptr, nullptr, 0};
+    f32x16 geo[1];
+    const float sigma = density_stage<PREC, 0>(st, map_at<PREC>(a.gmap.data, a.goff_d), g, wave, lane, geo, nodump);
+    if (ok && hh == 0 && a.density) a.density[p] = sigma;
+    if (MODE >= 2) {
+      float rgb[3];
+      color_stage<PREC, 0>(st, geo, a.dirx, a.diry, a.dirz, wave, lane, rgb, ColorDump{nullptr, nullptr, 0});
+      if (ok && hh == 0 && a.color) {
+        a.color[3 * (size_t)p] = rgb[0];
+        a.color[3 * (size_t)p + 1] = rgb[1];
+        a.color[3 * (size_t)p + 2] = rgb[2];
+      }
+    }
+    if (JK != 0) {
+      f32x16 jac[1];
+      float flow[3];
+      jacobian_stage<JK, PRECJ, 0>(st, map_at<PRECJ>(a.gmap.data, a.goff_j), g, nullptr, A, wave, lane, jac, flow, nodump);
+      if (ok && a.jacobian) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int d = 16 * hh + r;
+          if (d < 3 * A) a.jacobian[(size_t)p * (3 * A) + d] = jac[0][r];
+        }
+      }
+    }
+  }
+}
+
+// xyz [entries, 3]: the coordinates of a list's nodes (the very floats field_points_kernel evaluates)
+__global__ void __launch_bounds__(256) field_xyz_kernel(FieldList l, float* __restrict__ xyz) {
+  const int entries = field_entries(l);
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= entries) return;
+  int b;
+  float px, py, pz;
+  field_node(l, field_global_index(l, i), b, px, py, pz);
+  xyz[3 * (size_t)i] = px;
+  xyz[3 * (size_t)i + 1] = py;
+  xyz[3 * (size_t)i + 2] = pz;
+}
+
+// ---- ordered selection --------------------------------------------------------------------
+// keep(entry i) = (values == null || values[i] >= threshold) && (no cameras || the node projects inside the context image
+// with positive camera depth).  Three launches: per-workgroup counts (ballot + popcount), a one-workgroup exclusive scan of
+// the counts, a scatter that re-evaluates the predicate and writes the survivors' global indices in input order.  Integer
+// arithmetic only, no atomics: the output bytes do not depend on scheduling.
+#define NJF_SELECT_THREADS 256
+#define NJF_SELECT_ITEMS (NJF_FIELD_SELECT_BLOCK / NJF_SELECT_THREADS)
+static_assert(NJF_SELECT_ITEMS * NJF_SELECT_THREADS == NJF_FIELD_SELECT_BLOCK && NJF_SELECT_ITEMS <= 8, "selection block");
+struct SelectArgs {
+  FieldList list;
+  const float* values;  // [entries] or null
+  float threshold;
+  const float* w2c;     // [B,4,4] or null (no frustum test)
+  const float* k;       // [B,3,3]
+  int* out_indices;
+  int* out_count;
+  int out_capacity;
+  int* block_counts;    // [blocks]: counts, then (after the scan) exclusive offsets
+  int blocks;
+};
+
+// the projection of point_geometry + point_footprint (u, v: normalised image coordinates of the feature gather)
+__device__ __forceinline__ bool field_in_view(const SelectArgs& a, int gi) {
+  int b;
+  float px, py, pz;
+  field_node(a.list, gi, b, px, py, pz);
+  CamCtx cam;
+  load_ctx(a.w2c, a.k, b, cam);
+  const float xc = dot4_h(cam.m + 0, px, py, pz), yc = dot4_h(cam.m + 4, px, py, pz), zc = dot4_h(cam.m + 8, px, py, pz);
+  const float u0 = dot3(cam.k + 0, xc, yc, zc), u1 = dot3(cam.k + 3, xc, yc, zc), u2 = dot3(cam.k + 6, xc, yc, zc);
+  const float inv = __builtin_amdgcn_rcpf(u2 + 1e-9f);
+  const float u = u0 * inv, v = u1 * inv;
+  return zc > 0.0f && u >= 0.0f && u <= 1.0f && v >= 0.0f && v <= 1.0f;  // (NaN compares false)
+}
+
+// bit `it` of the result: keep entry block*NJF_FIELD_SELECT_BLOCK + it*NJF_SELECT_THREADS + tid
+__device__ __forceinline__ unsigned select_flags(const SelectArgs& a, int entries) {
+  unsigned flags = 0;
+#pragma unroll
+  for (int it = 0; it < NJF_SELECT_ITEMS; ++it) {
+    const long long i = (long long)blockIdx.x * NJF_FIELD_SELECT_BLOCK + it * NJF_SELECT_THREADS + threadIdx.x;
+    bool keep = i < entries;
+    if (keep && a.values) keep = a.values[i] >= a.threshold;
+    if (keep && a.w2c) keep = field_in_view(a, field_global_index(a.list, (int)i));
+    flags |= keep ? 1u << it : 0u;
+  }
+  return flags;
+}
+
+__global__ void __launch_bounds__(NJF_SELECT_THREADS) select_count_kernel(SelectArgs a) {
+  __shared__ int wave_count[NJF_SELECT_THREADS / 64];
+  const unsigned flags = select_flags(a, field_entries(a.list));
+  int n = 0;
+#pragma unroll
+  for (int it = 0; it < NJF_SELECT_ITEMS; ++it) n += __popcll(__ballot((flags >> it) & 1u));  // wave-uniform
+  if ((threadIdx.x & 63) == 0) wave_count[threadIdx.x >> 6] = n;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int s = 0;
+    for (int w = 0; w < NJF_SELECT_THREADS / 64; ++w) s += wave_count[w];
+    a.block_counts[blockIdx.x] = s;
+  }
+}
+
+// one workgroup: block_counts -> exclusive prefix sums in place, the total to out_count
+__global__ void __launch_bounds__(NJF_SELECT_THREADS) select_scan_kernel(int* __restrict__ block_counts, int blocks,
+                                                                         int* __restrict__ out_count) {
+  __shared__ int part[NJF_SELECT_THREADS];
+  const int t = threadIdx.x;
+  const int per = (blocks + NJF_SELECT_THREADS - 1) / NJF_SELECT_THREADS;  // a contiguous run per thread
+  const int lo = min(t * per, blocks), hi = min(lo + per, blocks);
+  int s = 0;
+  for (int i = lo; i < hi; ++i) s += block_counts[i];
+  part[t] = s;
+  __syncthreads();
+  if (t == 0) {
+    int run = 0;
+    for (int i = 0; i < NJF_SELECT_THREADS; ++i) {
+      const int c = part[i];
+      part[i] = run;
+      run += c;
+    }
+    *out_count = run;
+  }
+  __syncthreads();
+  int run = part[t];
+  for (int i = lo; i < hi; ++i) {
+    const int c = block_counts[i];
+    block_counts[i] = run;
+    run += c;
+  }
+}
+
+__global__ void __launch_bounds__(NJF_SELECT_THREADS) select_scatter_kernel(SelectArgs a) {
+  constexpr int WAVES = NJF_SELECT_THREADS / 64;
+  __shared__ int wave_count[NJF_SELECT_ITEMS][WAVES];
+  const unsigned flags = select_flags(a, field_entries(a.list));
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int before[NJF_SELECT_ITEMS];  // kept entries of this wave in front of this lane, per item
+#pragma unroll
+  for (int it = 0; it < NJF_SELECT_ITEMS; ++it) {
+    const unsigned long long m = __ballot((flags >> it) & 1u);
+    before[it] = __popcll(m & ((1ull << lane) - 1ull));
+    if (lane == 0) wave_count[it][wave] = __popcll(m);
+  }
+  __syncthreads();
+  int base = a.block_counts[blockIdx.x];  // exclusive offset of this workgroup
+#pragma unroll
+  for (int it = 0; it < NJF_SELECT_ITEMS; ++it) {
+    // input order inside a workgroup: item-major, then wave, then lane
+    int rank = base;
+    for (int w = 0; w < wave; ++w) rank += wave_count[it][w];
+    if ((flags >> it) & 1u) {
+      rank += before[it];
+      if (rank < a.out_capacity) {
+        const int i = blockIdx.x * NJF_FIELD_SELECT_BLOCK + it * NJF_SELECT_THREADS + threadIdx.x;
+        a.out_indices[rank] = field_global_index(a.list, i);
+      }
+    }
+    for (int w = 0; w < WAVES; ++w) base += wave_count[it][w];
+  }
+}
+
+// =============================================================================================
 // inverse dynamics: Levenberg-Marquardt on the linearised flow, one workgroup per batch element
 // =============================================================================================
 // optical_flow(a) = proj(x + M a) - proj(x) with x = sum_s w x_s and M = sum_s w J_s (the composited outputs of the
@@ -3565,6 +3825,127 @@ extern "C" int njf_points_forward(const float* xyz, const float* dirs, int point
     }
     if (jacobian_kind == NJF_JACOBIAN_MLP) return launch_fused(points_kernel<2, NJF_P, NJF_PJ>, a, tiles, s);
     return launch_fused(points_kernel<3, NJF_P, NJF_PJ>, a, tiles, s);
+  });
+}
+
+// ---- voxel-grid field extraction ---------------------------------------------------------------------------------
+static int make_field_list(const NjfFieldGrid* grid, int batch, const int* indices, const int* count, int capacity,
+                           FieldList& l) {
+  if (!grid) return NJF_E_NULL;
+  if (batch < 1 || capacity < 0) return NJF_E_SHAPE;
+  long long total = batch;
+  for (int c = 0; c < 3; ++c) {
+    if (grid->dims[c] < 1) return NJF_E_SHAPE;
+    total *= grid->dims[c];
+    if (total > 0x7fffffffLL) return NJF_E_SHAPE;  // global indices are int32: B*N < 2^31
+  }
+  if (!indices && capacity > total) return NJF_E_SHAPE;  // the identity list has B*N entries
+  l.grid = *grid;
+  l.total = (int)total;
+  l.nodes = l.total / batch;
+  l.indices = indices;
+  l.count = count;
+  l.capacity = capacity;
+  return NJF_OK;
+}
+
+extern "C" int njf_field_points(const NjfFieldGrid* grid, int batch, const int* indices, const int* count, int capacity,
+                                float* xyz, void* stream) {
+  FieldList l;
+  int rc = make_field_list(grid, batch, indices, count, capacity, l);
+  if (rc) return rc;
+  if (!xyz) return NJF_E_NULL;
+  if (capacity == 0) return NJF_OK;
+  field_xyz_kernel<<<(capacity + 255) / 256, 256, 0, (hipStream_t)stream>>>(l, xyz);
+  return launch_status();
+}
+
+extern "C" int njf_field_select(const NjfFieldGrid* grid, const NjfCameras* cams, int batch, const float* values,
+                                float threshold, const int* indices, const int* count, int capacity, int* out_indices,
+                                int* out_count, int out_capacity, int* workspace, void* stream) {
+  SelectArgs a;
+  int rc = make_field_list(grid, batch, indices, count, capacity, a.list);
+  if (rc) return rc;
+  if (!out_count || !workspace || (!values && !cams)) return NJF_E_NULL;  // (no predicate: nothing to select)
+  if (out_capacity < 0 || (out_capacity > 0 && !out_indices)) return out_capacity < 0 ? NJF_E_SHAPE : NJF_E_NULL;
+  if (cams && (!cams->ctxt_w2c || !cams->ctxt_k)) return NJF_E_NULL;
+  if (cams && cams->batch != batch) return NJF_E_SHAPE;
+  a.values = values;
+  a.threshold = threshold;
+  a.w2c = cams ? cams->ctxt_w2c : nullptr;
+  a.k = cams ? cams->ctxt_k : nullptr;
+  a.out_indices = out_indices;
+  a.out_count = out_count;
+  a.out_capacity = out_capacity;
+  a.block_counts = workspace;
+  a.blocks = (int)(((long long)capacity + NJF_FIELD_SELECT_BLOCK - 1) / NJF_FIELD_SELECT_BLOCK);
+  hipStream_t s = (hipStream_t)stream;
+  if (a.blocks > 0) {
+    select_count_kernel<<<a.blocks, NJF_SELECT_THREADS, 0, s>>>(a);
+    if ((rc = launch_status())) return rc;
+  }
+  select_scan_kernel<<<1, NJF_SELECT_THREADS, 0, s>>>(workspace, a.blocks, out_count);
+  if ((rc = launch_status())) return rc;
+  if (a.blocks > 0 && out_capacity > 0) {
+    select_scatter_kernel<<<a.blocks, NJF_SELECT_THREADS, 0, s>>>(a);
+    if ((rc = launch_status())) return rc;
+  }
+  return NJF_OK;
+}
+
+extern "C" int njf_field_forward(const NjfFieldGrid* grid, const int* indices, const int* count, int capacity,
+                                 const float* view_dir, const NjfCameras* cams, const NjfFeatureMap* gmap,
+                                 int gmap_offset_density, int gmap_offset_jacobian, int mode, int jacobian_kind,
+                                 const float* w_density, const float* b_density, const float* w_color, const float* b_color,
+                                 const float* w_jacobian, const float* b_jacobian, float* density, float* color,
+                                 float* jacobian, int precision, void* stream) {
+  if (!grid || !cams || !gmap || !w_density || !b_density) return NJF_E_NULL;
+  if (!cams->ctxt_w2c || !cams->ctxt_k || !gmap->data) return NJF_E_NULL;
+  FieldArgs a;
+  int rc = make_field_list(grid, cams->batch, indices, count, capacity, a.list);
+  if (rc) return rc;
+  if (mode != 0 && mode != 1) return NJF_E_MODE;
+  if (!valid_precision(precision)) return NJF_E_MODE;
+  if (gmap->height < 1 || gmap->width < 1) return NJF_E_SHAPE;
+  if ((rc = check_gmap(gmap, gmap_offset_density, NJF_ZDIM, density_precision(precision)))) return rc;
+  if ((long long)cams->batch * gmap->height * gmap->width * gmap->stride > 0xffffffffLL) return NJF_E_SHAPE;  // PointGeom::gofs
+  if (mode == 0 && !density) return NJF_E_NULL;
+  a.dirx = view_dir ? view_dir[0] : 0.f;
+  a.diry = view_dir ? view_dir[1] : 0.f;
+  a.dirz = view_dir ? view_dir[2] : 1.f;
+  a.cams = *cams;
+  a.gmap = *gmap;
+  a.goff_d = gmap_offset_density;
+  a.goff_j = gmap_offset_jacobian;
+  a.w_all = w_density;
+  a.b_d = b_density;
+  a.b_c = b_color;
+  a.b_j = b_jacobian;
+  a.density = density;
+  a.color = color;
+  a.jacobian = jacobian;
+  const int tiles = (capacity + 31) / 32;
+  hipStream_t s = (hipStream_t)stream;
+  if (mode == 0) {
+    if (capacity == 0) return NJF_OK;
+    return with_precision(density_precision(precision), [&](auto P) { return launch_fused(field_points_kernel<0, NJF_P>, a, tiles, s); });
+  }
+  if ((rc = check_jacobian(jacobian_kind, cams, gmap, gmap_offset_jacobian, w_jacobian, b_jacobian, precision))) return rc;
+  const bool with_j = jacobian_kind != NJF_JACOBIAN_NONE;
+  if (with_j && !jacobian) return NJF_E_NULL;
+  if (!with_j && !color) {  // density only: the density net's blob is all that is streamed
+    if (!density) return NJF_E_NULL;
+    if (capacity == 0) return NJF_OK;
+    return with_precision(density_precision(precision), [&](auto P) { return launch_fused(field_points_kernel<1, NJF_P>, a, tiles, s); });
+  }
+  if (!w_color || !b_color) return NJF_E_NULL;
+  if ((rc = check_contiguous(w_density, w_color, w_jacobian, with_j))) return rc;
+  if (capacity == 0) return NJF_OK;
+  if (!with_j)
+    return with_precision(density_precision(precision), [&](auto P) { return launch_fused(field_points_kernel<2, NJF_P>, a, tiles, s); });
+  return with_precisions(precision, [&](auto P, auto PJ) {
+    if (jacobian_kind == NJF_JACOBIAN_MLP) return launch_fused(field_points_kernel<3, NJF_P, NJF_PJ>, a, tiles, s);
+    return launch_fused(field_points_kernel<4, NJF_P, NJF_PJ>, a, tiles, s);
   });
 }
 

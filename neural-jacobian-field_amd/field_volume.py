@@ -1,0 +1,285 @@
+"""3-D Jacobian-field point clouds from a voxel grid, extracted on the device.
+
+The reference colours point clouds of per-point Jacobians (``inference/jacobian_color_map.py:113-160``) but obtains them by
+hand: a dense ``[B, N, 3]`` grid through ``Model.compute_density`` (model.py:416-456), then threshold / ``nonzero`` / gather.
+Here the grid coordinates are generated inside the kernels, empty space is culled in stages -- context-view frustum, proposal
+density, decoder density -- by an ORDERED stream compaction, and colour + Jacobian head run on the survivors only
+(include/njf_hip.h: ``njf_field_points`` / ``njf_field_select`` / ``njf_field_forward``).
+
+Definitions (fixed, so the result is checkable against the dense route):
+
+* node ``(ix, iy, iz)`` of a grid has the linear index ``n = (ix*ny + iy)*nz + iz`` and the coordinate
+  ``fma(i_c, step[c], origin[c])`` per component (one rounding, fp32);
+* node ``n`` of batch element ``b`` has the global index ``b*N + n``, ``N = nx*ny*nz``, ``B*N < 2**31``;
+* the extracted set is every node that passes the enabled predicates; it is returned in ASCENDING GLOBAL INDEX.
+"""
+
+from __future__ import annotations
+
+import math
+from dataclasses import dataclass
+from typing import Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import hip
+from .decoder import ActionDecoderFlowMlp, ActionDecoderJacobian, PixelEncoding, _cameras, _map_of
+from .inference import jacobian_color_map as _cm
+
+
+def _fma32(i: np.ndarray, step: np.float32, origin: np.float32) -> np.ndarray:
+    """fp32 fma(i, step, origin): the product of an integer below 2**24 and an fp32 is exact in float64, so is its sum with an
+    fp32 up to one float64 rounding far below half an fp32 ulp -- rounding that to fp32 is the fused result."""
+    return (i.astype(np.float64) * np.float64(step) + np.float64(origin)).astype(np.float32)
+
+
+@dataclass(frozen=True)
+class FieldGrid:
+    """A regular grid of ``dims = (nx, ny, nz)`` nodes: node ``(ix, iy, iz)`` sits at ``fma(i_c, step[c], origin[c])``."""
+
+    origin: Tuple[float, float, float]
+    step: Tuple[float, float, float]
+    dims: Tuple[int, int, int]
+
+    def __post_init__(self):
+        if len(self.origin) != 3 or len(self.step) != 3 or len(self.dims) != 3:
+            raise ValueError("FieldGrid: origin, step and dims have three components")
+        if any(int(d) != d or d < 1 for d in self.dims):
+            raise ValueError(f"FieldGrid: dims must be positive integers (got {self.dims})")
+        object.__setattr__(self, "origin", tuple(float(np.float32(v)) for v in self.origin))
+        object.__setattr__(self, "step", tuple(float(np.float32(v)) for v in self.step))
+        object.__setattr__(self, "dims", tuple(int(d) for d in self.dims))
+        if self.num_nodes >= 2 ** 31:
+            raise ValueError("FieldGrid: nx*ny*nz must stay below 2**31")
+
+    @classmethod
+    def from_bounds(cls, lower: Sequence[float], upper: Sequence[float], resolution) -> "FieldGrid":
+        """Nodes from ``lower`` to ``upper`` inclusive, ``resolution`` (an int or one per axis) per axis; an axis of one
+        node sits at ``lower``."""
+        res = (resolution,) * 3 if isinstance(resolution, int) else tuple(int(r) for r in resolution)
+        if len(res) != 3 or any(r < 1 for r in res):
+            raise ValueError(f"FieldGrid.from_bounds: resolution must be >= 1 per axis (got {resolution})")
+        step = tuple((float(u) - float(l)) / (r - 1) if r > 1 else 0.0 for l, u, r in zip(lower, upper, res))
+        return cls(tuple(float(l) for l in lower), step, res)
+
+    @property
+    def num_nodes(self) -> int:
+        return self.dims[0] * self.dims[1] * self.dims[2]
+
+    def linear_index(self, ix, iy, iz):
+        return (ix * self.dims[1] + iy) * self.dims[2] + iz
+
+    def unravel(self, n):
+        """linear (or, modulo ``num_nodes``, global) index -> (ix, iy, iz); ints, numpy arrays or tensors."""
+        n = n % self.num_nodes
+        yz = self.dims[1] * self.dims[2]
+        return n // yz, (n % yz) // self.dims[2], n % self.dims[2]
+
+    def points(self, indices: Optional[torch.Tensor] = None, device=None) -> torch.Tensor:
+        """Node coordinates ``[count, 3]`` fp32: of all ``num_nodes`` nodes in linear order, or of ``indices`` (linear or global
+        indices, any integer tensor).  On a GPU ``njf_field_points`` writes them (the very floats the extraction kernels
+        evaluate); on the CPU the same fused multiply-add is evaluated with numpy."""
+        if indices is not None and device is None:
+            device = indices.device
+        dev = torch.device("cpu" if device is None else device)
+        if dev.type == "cuda":
+            cg = self.c_grid()
+            if indices is None:
+                out = torch.empty(self.num_nodes, 3, dtype=torch.float32, device=dev)
+                hip.field_points(cg, 1, None, None, self.num_nodes, out)
+                return out
+            idx = (indices.reshape(-1) % self.num_nodes).to(torch.int32).contiguous()
+            out = torch.empty(idx.numel(), 3, dtype=torch.float32, device=dev)
+            if idx.numel():
+                hip.field_points(cg, 1, idx, None, idx.numel(), out)
+            return out
+        n = np.arange(self.num_nodes, dtype=np.int64) if indices is None else indices.reshape(-1).cpu().numpy().astype(np.int64)
+        comps = self.unravel(n)
+        xyz = np.stack([_fma32(i, np.float32(s), np.float32(o)) for i, s, o in zip(comps, self.step, self.origin)], axis=-1)
+        return torch.from_numpy(xyz)
+
+    def c_grid(self) -> "hip.FieldGrid":
+        return hip.make_field_grid(self.origin, self.step, self.dims)
+
+
+@dataclass
+class FieldPointCloud:
+    """The extracted nodes in ascending global index.  Exactly sized (``count`` = number of rows) from an eager extraction;
+    padded to ``max_points`` rows from a capture-safe one, where ``count`` (int32 device tensor ``[1]``) holds the TRUE number
+    of survivors -- it may exceed the rows stored -- and rows from ``min(count, max_points)`` on are unspecified."""
+
+    grid: FieldGrid
+    index: torch.Tensor                 # [n] int32 global index b*N + n
+    xyz: torch.Tensor                   # [n, 3]
+    density: torch.Tensor               # [n]
+    color: Optional[torch.Tensor]       # [n, 3]
+    jacobian: Optional[torch.Tensor]    # [n, A, 3] action-major: compute_jacobian_at's rows reshaped
+    count: torch.Tensor                 # [1] int32
+    stage_counts: Tuple[torch.Tensor, ...] = ()   # survivors after each enabled selection stage, in pipeline order
+    stage_names: Tuple[str, ...] = ()
+
+    @property
+    def batch_index(self) -> torch.Tensor:
+        return torch.div(self.index, self.grid.num_nodes, rounding_mode="floor")
+
+    def valid(self) -> int:
+        """Rows that hold survivors (reads ``count``: a host synchronisation)."""
+        return min(int(self.count.item()), self.index.shape[0])
+
+    def colors(self, color_map, mode: int = 0) -> torch.Tensor:
+        """``[n, 3]`` display colours in [0, 1]: ``compute_joint_sensitivity_point_cloud`` chained with
+        ``visualize_joint_sensitivity_point_cloud`` (inference/jacobian_color_map.py) on the valid rows.  ``color_map``: a
+        ``[3, A]`` tensor or the name of a table in ``JACOBIAN_COLORMAP`` (stored ``[A, 3]``)."""
+        if self.jacobian is None:
+            raise ValueError("FieldPointCloud.colors needs the Jacobians (extract with want_jacobian=True)")
+        jac = self.jacobian[:self.valid()]
+        if isinstance(color_map, str):
+            color_map = torch.tensor(_cm.JACOBIAN_COLORMAP[color_map], dtype=torch.float32).t()
+        color_map = torch.as_tensor(color_map, dtype=torch.float32)
+        if tuple(color_map.shape) != (3, jac.shape[1]):
+            raise ValueError(f"FieldPointCloud.colors: color_map must be [3, {jac.shape[1]}] (got {tuple(color_map.shape)})")
+        sens = _cm.compute_joint_sensitivity_point_cloud(jac)
+        return _cm.visualize_joint_sensitivity_point_cloud(sens, color_map.to(jac.device), mode)
+
+    def save_ply(self, path, colors: Optional[torch.Tensor] = None) -> int:
+        """Binary little-endian PLY of the valid rows: ``x y z`` float32, ``red green blue`` uint8, ``density`` float32.
+        ``colors`` ``[n, 3]`` in [0, 1] (default: the colour head's output, white without one).  Returns the vertex count."""
+        n = self.valid()
+        rgb = self.color[:n] if colors is None and self.color is not None else colors
+        rgb = np.ones((n, 3), dtype=np.float32) if rgb is None else rgb[:n].detach().float().cpu().numpy()
+        if rgb.shape != (n, 3):
+            raise ValueError(f"save_ply: colors must be [{n}, 3] (got {rgb.shape})")
+        vertex = np.empty(n, dtype=[("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1"),
+                                    ("density", "<f4")])
+        xyz = self.xyz[:n].detach().cpu().numpy()
+        vertex["x"], vertex["y"], vertex["z"] = xyz[:, 0], xyz[:, 1], xyz[:, 2]
+        rgb8 = np.rint(np.clip(rgb, 0.0, 1.0) * 255.0).astype(np.uint8)
+        vertex["red"], vertex["green"], vertex["blue"] = rgb8[:, 0], rgb8[:, 1], rgb8[:, 2]
+        vertex["density"] = self.density[:n].detach().cpu().numpy()
+        header = ("ply\nformat binary_little_endian 1.0\ncomment Jacobian-field point cloud\n"
+                  f"element vertex {n}\nproperty float x\nproperty float y\nproperty float z\n"
+                  "property uchar red\nproperty uchar green\nproperty uchar blue\nproperty float density\nend_header\n")
+        with open(path, "wb") as f:
+            f.write(header.encode("ascii"))
+            f.write(vertex.tobytes())
+        return n
+
+
+class _Stage:
+    """The running list of the pipeline: (indices, device count, launch extent).  Eager extraction reads the count after each
+    selection to size the next launch exactly; a capture-safe one keeps every intermediate list at B*N entries (4 bytes per
+    node) and lets the kernels read the count on the device."""
+
+    def __init__(self, total: int):
+        self.indices: Optional[torch.Tensor] = None
+        self.count: Optional[torch.Tensor] = None
+        self.extent = total
+
+
+@torch.no_grad()
+def extract_field(model, pixel_encoding: PixelEncoding, grid: FieldGrid, density_threshold: float, *,
+                  cull: Optional[float] = None, proposal_level: int = -1, in_frustum: bool = True,
+                  view_direction: Optional[Sequence[float]] = None, want_color: bool = True, want_jacobian: bool = True,
+                  max_points: Optional[int] = None) -> FieldPointCloud:
+    """Every node of ``grid`` -- per context image of ``pixel_encoding`` -- that
+
+    1. (``in_frustum``) projects inside the context image with positive camera depth,
+    2. (``cull`` is not None) has ``proposal_density >= cull`` for ``model.proposal_networks[proposal_level]``,
+    3. has ``decoder_density >= density_threshold`` (the density ``Model.compute_density`` returns),
+
+    with its density, colour (view direction (0, 0, 1) as ``compute_density`` uses, or ``view_direction``) and Jacobian
+    ``[A, 3]``, in ascending global index.  ``max_points=None``: exactly sized tensors, one host read of a device count per
+    selection stage.  ``max_points=M``: no host synchronisation (safe inside ``torch.cuda.graph``), tensors padded to M rows
+    and ``count`` = the true number of survivors (the rows stored are the first M of them)."""
+    dec = model.decoder
+    if not isinstance(dec, ActionDecoderJacobian):
+        raise TypeError("extract_field needs one of the fused action decoders")
+    is_flow = isinstance(dec, ActionDecoderFlowMlp)
+    if want_jacobian and is_flow:
+        raise NotImplementedError("flow_mlp predicts the scene flow directly; it has no Jacobian")
+    if not math.isfinite(float(density_threshold)) or (cull is not None and not math.isfinite(float(cull))):
+        raise ValueError("extract_field: thresholds must be finite")
+    if max_points is not None and max_points < 1:
+        raise ValueError("extract_field: max_points must be >= 1")
+    if view_direction is not None and len(view_direction) != 3:
+        raise ValueError("extract_field: view_direction has three components")
+    feats = pixel_encoding.features
+    dev = feats.device
+    b = pixel_encoding.extrinsics.shape[0]
+    total = b * grid.num_nodes
+    if total >= 2 ** 31:
+        raise ValueError("extract_field: batch * nx*ny*nz must stay below 2**31")
+    cg = grid.c_grid()
+    eager = max_points is None
+    if dev.type == "cuda" and torch.cuda.is_current_stream_capturing():
+        # the hoisted maps are cached per feature tensor: a capture must CONTAIN the projection, or a replay on refilled
+        # features would read the map of the image that was there when it was recorded
+        model.reset_image_cache()
+    i32 = dict(dtype=torch.int32, device=dev)
+    f32 = dict(dtype=torch.float32, device=dev)
+    cams = _cameras(pixel_encoding, False, action_dim=dec.kernel_action_dim if want_jacobian else None)
+    stage = _Stage(total)
+    counts, names = [], []
+
+    def select(name, values, threshold, frustum, final):
+        # survivors kept: all of them when the host knows the input's length; else B*N for a list that feeds another stage
+        # (4 bytes per node) and max_points for the result
+        capacity = stage.extent if eager else (max_points if final else total)
+        out_idx = torch.empty(max(capacity, 1), **i32)
+        out_count = torch.empty(1, **i32)
+        hip.field_select(cg, b, stage.extent, out_idx, out_count, values=values, threshold=float(threshold),
+                         cams=cams if frustum else None, indices=stage.indices, count=stage.count)
+        counts.append(out_count)
+        names.append(name)
+        stage.indices, stage.count = out_idx, out_count
+        if eager:
+            stage.extent, stage.count = int(out_count.item()), None
+        else:
+            stage.extent = capacity
+
+    if in_frustum:
+        select("frustum", None, 0.0, True, False)
+    if cull is not None and stage.extent > 0:
+        net = model.proposal_networks[proposal_level]
+        w, bias = net.packed()
+        gmap, base = _map_of(net, feats)
+        values = torch.empty(stage.extent, **f32)
+        hip.field_forward(cg, stage.indices, stage.count, stage.extent, cams, hip.make_feature_map(gmap), base, base, 0, w, bias,
+                          density=values, precision=net.precision)
+        select("proposal", values, cull, False, False)
+    w, bd, bc, bj = dec.packed()
+    if is_flow:   # (its own hoisted_map adds the per-image action bias of the flow head, which is not evaluated here)
+        gmap, base = ActionDecoderJacobian.hoisted_map(dec, feats), 0
+    else:
+        gmap, base = _map_of(dec, feats)
+    fmap = hip.make_feature_map(gmap)
+    common = dict(goff_density=base + dec.GOFF_DENSITY, goff_jacobian=base + dec.GOFF_JACOBIAN, mode=1, w_all=w, b_density=bd,
+                  precision=dec.precision)
+    if stage.extent > 0:
+        values = torch.empty(stage.extent, **f32)
+        hip.field_forward(cg, stage.indices, stage.count, stage.extent, cams, fmap, density=values, **common)
+        select("density", values, density_threshold, False, True)
+    else:
+        stage.indices, stage.count = torch.empty(0, **i32), None
+        counts.append(torch.zeros(1, **i32))
+        names.append("density")
+    n = stage.extent
+    a_dim = dec.kernel_action_dim
+    index = stage.indices[:n]
+    cloud = FieldPointCloud(grid=grid, index=index, xyz=torch.empty(n, 3, **f32), density=torch.empty(n, **f32),
+                            color=torch.empty(n, 3, **f32) if want_color else None,
+                            jacobian=torch.empty(n, a_dim, 3, **f32) if want_jacobian else None,
+                            count=counts[-1], stage_counts=tuple(counts), stage_names=tuple(names))
+    if n > 0:
+        hip.field_points(cg, b, index, stage.count, n, cloud.xyz)
+        if want_color or want_jacobian:
+            # the density network runs again on the survivors: cheaper than the Jacobian head on what the selection rejects
+            hip.field_forward(cg, index, stage.count, n, cams, fmap, b_color=bc, b_jacobian=bj if want_jacobian else None,
+                              jacobian_kind=dec.JACOBIAN_KIND if want_jacobian else hip.JACOBIAN_NONE, density=cloud.density,
+                              color=cloud.color,
+                              jacobian=cloud.jacobian, view_direction=view_direction,
+                              jacobian_precision=dec.j_precision if want_jacobian else None, **common)
+        else:
+            hip.field_forward(cg, index, stage.count, n, cams, fmap, density=cloud.density, **common)
+    return cloud

@@ -109,6 +109,11 @@ class ActivationDump(C.Structure):
     _fields_ = [("act", _vp), ("pe", _vp), ("foot_idx", _vp), ("foot_w", _vp), ("mask", _vp), ("act_f16", C.c_int)]
 
 
+class FieldGrid(C.Structure):
+    """NjfFieldGrid: node (ix, iy, iz) sits at fmaf(i_c, step[c], origin[c]); linear index (ix*ny + iy)*nz + iz."""
+    _fields_ = [("origin", C.c_float * 3), ("step", C.c_float * 3), ("dims", C.c_int * 3)]
+
+
 _lib = None
 
 _SIGNATURES = {
@@ -138,6 +143,12 @@ _SIGNATURES = {
                             _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.POINTER(RenderOutputs), C.c_int, _vp], C.c_int),
     "njf_points_forward": ([_vp, _vp, C.c_int, C.POINTER(Cameras), C.POINTER(FeatureMap), C.c_int, C.c_int, C.c_int,
                             C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp], C.c_int),
+    "njf_field_points": ([C.POINTER(FieldGrid), C.c_int, _vp, _vp, C.c_int, _vp, _vp], C.c_int),
+    "njf_field_select": ([C.POINTER(FieldGrid), C.POINTER(Cameras), C.c_int, _vp, C.c_float, _vp, _vp, C.c_int, _vp, _vp, C.c_int,
+                          _vp, _vp], C.c_int),
+    "njf_field_forward": ([C.POINTER(FieldGrid), _vp, _vp, C.c_int, C.POINTER(C.c_float * 3), C.POINTER(Cameras),
+                           C.POINTER(FeatureMap), C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                           C.c_int, _vp], C.c_int),
     "njf_pack_resnetfc_backward": ([C.POINTER(ResnetFcWeights), _vp, C.c_int, _vp], C.c_int),
     "njf_resnetfc_backward": ([_vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp], C.c_int),
     "njf_pack_transformer_backward": ([_vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, _vp], C.c_int),
@@ -576,6 +587,80 @@ def points_forward(xyz, dirs, cams: Cameras, fmap: FeatureMap, goff_density: int
         jacobian_kind if mode == 1 else JACOBIAN_NONE, base, _ptr(b_density), w_c, _ptr(b_color), w_j,
         _ptr(b_jacobian) if with_j else None, _ptr(density), _ptr(color), _ptr(flow), _ptr(jacobian), _ptr(geo),
         _ptr(features, "features"), precision_code(precision, jacobian_precision))
+
+
+# ---- voxel-grid field extraction (include/njf_hip.h: NjfFieldGrid, njf_field_*) ----------------------------------------
+FIELD_SELECT_BLOCK = 1024   # NJF_FIELD_SELECT_BLOCK: list entries one workgroup of njf_field_select covers
+
+
+def make_field_grid(origin, step, dims) -> FieldGrid:
+    return FieldGrid((C.c_float * 3)(*[float(v) for v in origin]), (C.c_float * 3)(*[float(v) for v in step]),
+                     (C.c_int * 3)(*[int(v) for v in dims]))
+
+
+def _int32_ptr(t: Optional[torch.Tensor], name: str) -> Optional[int]:
+    return _ptr(t, name, torch.int32)
+
+
+def field_points(grid: FieldGrid, batch: int, indices, count, capacity: int, xyz: torch.Tensor) -> None:
+    """xyz [capacity, 3] <- coordinates of the list's nodes (indices / count: int32 device tensors or None)."""
+    if tuple(xyz.shape) != (capacity, 3):
+        raise ValueError(f"njf_hip: xyz must be [{capacity}, 3] (got {tuple(xyz.shape)})")
+    if indices is not None and indices.numel() < capacity:
+        raise ValueError("njf_hip: the index list is shorter than the capacity")
+    _launch("njf_field_points", load_library().njf_field_points, C.byref(grid), int(batch), _int32_ptr(indices, "indices"),
+            _int32_ptr(count, "count"), int(capacity), _ptr(xyz, "xyz"))
+
+
+def field_select(grid: FieldGrid, batch: int, capacity: int, out_indices, out_count: torch.Tensor, values=None,
+                 threshold: float = 0.0, cams: Optional[Cameras] = None, indices=None, count=None) -> None:
+    """Ordered selection (njf_field_select): the entries of the list (indices, count, capacity) with values[i] >= threshold
+    and / or inside the context view of ``cams`` -> their global indices in input order into ``out_indices`` (int32, its
+    length is the output capacity; None = count only), the true number of survivors into ``out_count`` (int32 [1])."""
+    if values is not None and values.numel() < capacity:
+        raise ValueError("njf_hip: field_select values are shorter than the capacity")
+    if indices is not None and indices.numel() < capacity:
+        raise ValueError("njf_hip: the index list is shorter than the capacity")
+    if out_count.numel() != 1:
+        raise ValueError("njf_hip: out_count must hold one int32")
+    blocks = max(1, (capacity + FIELD_SELECT_BLOCK - 1) // FIELD_SELECT_BLOCK)
+    workspace = torch.empty(blocks, dtype=torch.int32, device=out_count.device)
+    if cams is not None:
+        _note_device(cams, "cameras")
+    _launch("njf_field_select", load_library().njf_field_select, C.byref(grid), None if cams is None else C.byref(cams),
+            int(batch), _ptr(values, "values"), float(threshold), _int32_ptr(indices, "indices"), _int32_ptr(count, "count"),
+            int(capacity), _int32_ptr(out_indices, "out_indices"), _int32_ptr(out_count, "out_count"),
+            0 if out_indices is None else out_indices.numel(), _int32_ptr(workspace, "workspace"))
+
+
+def field_forward(grid: FieldGrid, indices, count, capacity: int, cams: Cameras, fmap: FeatureMap, goff_density: int,
+                  goff_jacobian: int, mode: int, w_all, b_density, b_color=None, b_jacobian=None,
+                  jacobian_kind: int = JACOBIAN_NONE, density=None, color=None, jacobian=None, view_direction=None,
+                  precision: Optional[str] = None, jacobian_precision: Optional[str] = None) -> None:
+    """``points_forward`` on the nodes of a list (njf_field_forward); outputs are compact [capacity, ...] tensors.  Mode 1
+    without ``color`` and without a Jacobian head runs the density network alone."""
+    for name, t, width in (("density", density, 1), ("color", color, 3)):
+        if t is not None and t.numel() < capacity * width:
+            raise ValueError(f"njf_hip: field_forward {name} is shorter than the capacity")
+    with_j = mode == 1 and jacobian_kind != JACOBIAN_NONE
+    if with_j and (jacobian is None or jacobian.numel() < capacity * 3 * cams.action_dim):
+        raise ValueError("njf_hip: field_forward jacobian must be [capacity, 3A]")
+    if indices is not None and indices.numel() < capacity:
+        raise ValueError("njf_hip: the index list is shorter than the capacity")
+    base = _ptr(w_all, "w_all")
+    with_c = mode == 1 and (color is not None or with_j)
+    w_c = base + 4 * RESNET_W_FLOATS if with_c else None
+    w_j = (w_c + 4 * COLOR_W_FLOATS) if with_j else None
+    direction = None if view_direction is None else C.byref((C.c_float * 3)(*[float(v) for v in view_direction]))
+    _note_device(cams, "cameras")
+    _note_device(fmap, "feature map")
+    _check_map_dtype(fmap, precision, *([precision if jacobian_precision is None else jacobian_precision] if with_j else []))
+    _launch("njf_field_forward", load_library().njf_field_forward, C.byref(grid), _int32_ptr(indices, "indices"),
+            _int32_ptr(count, "count"), int(capacity), direction, C.byref(cams), C.byref(fmap), goff_density, goff_jacobian,
+            mode, jacobian_kind if mode == 1 else JACOBIAN_NONE, base, _ptr(b_density), w_c,
+            _ptr(b_color) if with_c else None, w_j, _ptr(b_jacobian) if with_j else None, _ptr(density, "density"),
+            _ptr(color, "color"), _ptr(jacobian, "jacobian") if with_j else None,
+            precision_code(precision, jacobian_precision if with_j else None))
 
 
 def solve_action(mean_position, jacobian, projection, target_flow, visible_mask, init_action, iterations: int,

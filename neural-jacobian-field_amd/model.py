@@ -739,6 +739,23 @@ class Model(nn.Module):
         return head, extras
 
     @torch.no_grad()
+    def extract_field(self, camera_input: CameraInput, grid, density_threshold: float, *, cull: Optional[float] = None,
+                      proposal_level: int = -1, in_frustum: bool = True, view_direction=None, want_color: bool = True,
+                      want_jacobian: bool = True, max_points: Optional[int] = None):
+        """The 3-D Jacobian field of the context image(s) as a point cloud: every node of ``grid`` (field_volume.FieldGrid)
+        inside the context view whose proposal density reaches ``cull`` (if given) and whose decoder density reaches
+        ``density_threshold``, with density, colour and Jacobian [A, 3], in ascending global index -- what the reference
+        obtains by hand from a dense grid through compute_density (model.py:416-456) for the point-cloud colour maps of
+        inference/jacobian_color_map.py.  See ``field_volume.extract_field``; ``max_points`` selects the form without host
+        synchronisation (padded tensors + ``count``; capturable in a HIP graph after one eager call)."""
+        from .field_volume import extract_field
+        enc = PixelEncoding(features=self._encode_for_render(camera_input.input_image), extrinsics=camera_input.ctxt_extrinsics,
+                            intrinsics=camera_input.ctxt_intrinsics, action=None)
+        return extract_field(self, enc, grid, density_threshold, cull=cull, proposal_level=proposal_level, in_frustum=in_frustum,
+                             view_direction=view_direction, want_color=want_color, want_jacobian=want_jacobian,
+                             max_points=max_points)
+
+    @torch.no_grad()
     def encode_image(self, camera_input: CameraInput, rendering_input: RenderingInput,
                      robot_input: RobotInput) -> ModelInferenceEncoding:
         """model.py:458-495: proposal sampling + per-sample density/Jacobian/weights, cached for inverse dynamics."""
