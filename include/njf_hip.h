@@ -387,6 +387,59 @@ int njf_field_forward(const NjfFieldGrid* grid, const int* indices, const int* c
                       const float* w_color, const float* b_color, const float* w_jacobian, const float* b_jacobian,
                       float* density, float* color, float* jacobian, int precision, void* stream);
 
+/* ---- isosurface mesh of a scalar on the grid (additive within ABI v20): the 3-D Jacobian-field surface ---------------- */
+/* Marching tetrahedra on the Kuhn cut of every cell; the semantics are fixed so the result is
+ * checkable against a plain restatement:
+ *   inside(g) = values[g] >= threshold (NaN: outside); valid(g) = (valid == NULL || valid[g] != 0) && (cams == NULL || node g
+ *   projects inside the context image of its batch element: the predicate of njf_field_select).
+ *   Cell (ix, iy, iz) -- (nx-1)(ny-1)(nz-1) = Nc per batch element, local index (ix*(ny-1) + iy)*(nz-1) + iz, global b*Nc +
+ *   local -- is cut into six tetrahedra, one per axis order (a, b, c) in the order xyz, xzy, yxz, yzx, zxy, zyx, with the
+ *   corners c0 = (0,0,0), c1 = c0 + e_a, c2 = c1 + e_b, c3 = (1,1,1).  Every tetrahedron edge is (lower node) + direction k:
+ *   0..6 = (1,0,0) (0,1,0) (0,0,1) (1,1,0) (1,0,1) (0,1,1) (1,1,1); the lower node owns it.
+ *   VERTICES: one per edge inside the grid whose ends are both valid and differ in `inside`, in ascending (owner global
+ *   index, k).  With end 0 = owner: t = (threshold - v0) / (v1 - v0) (IEEE division), 0.5 if that is not finite, then clamped
+ *   to [0, 1]; position fmaf(t, x1 - x0, x0) per component on the node coordinates.
+ *   TRIANGLES: cells in ascending global index, tetrahedra in the order above; a tetrahedron with an invalid corner emits
+ *   nothing.  With the local corner order c0 < c1 < c2 < c3: one inside corner i (others j < k < l) -> (ij, ik, il); three
+ *   inside corners -> the same with i the outside corner; two (i < j inside, k < l outside) -> (ik, il, jl) and (ik, jl, jk).
+ *   The geometric normal points from inside to outside: where the listed order would point the other way the LAST TWO
+ *   entries of each triangle are swapped -- decided from the case and the parity of the axis order, never from coordinates
+ *   (zero-area triangles of t = 0 or 1 do not flip).  Entries are vertex ranks: rank of edge k of node g =
+ *   vertex_offset[g] + popcount(edge_mask[g] & ((1 << k) - 1)).
+ * `phase`: NJF_FIELD_MESH_COUNT runs the counting launch and the scan (the true count lands in *vertex_count /
+ * *triangle_count, device int32), NJF_FIELD_MESH_EMIT the emitting launch of a count made before on the same stream with the
+ * same arguments; both bits: all three launches without a host read in between.  Rows of ranks >= the capacity are dropped
+ * (the counts stay true; triangles keep true vertex ranks).  edge_mask: device bytes [B*N] (bits 0..6: edge k carries a
+ * vertex, bit 7: the node is valid), vertex_offset: device int32 [B*N]; both are written by njf_field_mesh_vertices and read
+ * by njf_field_mesh_triangles.  workspace: device int32 [ceil(B*N / NJF_FIELD_MESH_BLOCK)], caller-owned, per call.  Integer
+ * arithmetic apart from t and the position, no atomics: the output bytes are reproducible.  NJF_E_VALUE: a dims[c] < 2, a
+ * non-finite threshold, a negative capacity, an unknown phase. */
+#define NJF_FIELD_MESH_BLOCK 1024
+#define NJF_FIELD_MESH_COUNT 1
+#define NJF_FIELD_MESH_EMIT 2
+/* values fp32 [B*N]; vertex_node int32 / vertex_edge bytes / vertex_t fp32 [max_vertices], vertices fp32 [max_vertices, 3]
+ * (may be NULL without NJF_FIELD_MESH_EMIT or with max_vertices == 0: the emitting launch then writes vertex_offset only). */
+int njf_field_mesh_vertices(const NjfFieldGrid* grid, const NjfCameras* cams, int batch, const float* values,
+                            const unsigned char* valid, float threshold, int phase, unsigned char* edge_mask,
+                            int* vertex_offset, int* vertex_node, unsigned char* vertex_edge, float* vertex_t, float* vertices,
+                            int max_vertices, int* vertex_count, int* workspace, void* stream);
+/* triangles int32 [max_triangles, 3] vertex ranks, triangle_cell int32 [max_triangles] global cell indices. */
+int njf_field_mesh_triangles(const NjfFieldGrid* grid, int batch, const float* values, float threshold, int phase,
+                             const unsigned char* edge_mask, const int* vertex_offset, int* triangles, int* triangle_cell,
+                             int max_triangles, int* triangle_count, int* workspace, void* stream);
+
+/* The decoder (mode 1 of njf_points_forward) at stored positions of a RAGGED batch in one launch: row i is the point
+ * xyz[i] of batch element node[i] / nodes_per_batch (node: device int32, clamped into [0, B*nodes_per_batch); for a mesh
+ * the owning node of the vertex).  The entry count min(*count, capacity) is read on the device (count NULL = capacity).
+ * density [capacity] (may be NULL), color [capacity, 3] (may be NULL with a Jacobian head), jacobian [capacity, 3A] (required
+ * with a head).  Every other argument, the per-point arithmetic and the results are those of njf_field_forward /
+ * njf_points_forward on that position.  Rows past the entry count are left untouched. */
+int njf_field_forward_at(const float* xyz, const int* node, const int* count, int capacity, int nodes_per_batch,
+                         const float* view_dir, const NjfCameras* cams, const NjfFeatureMap* gmap, int gmap_offset_density,
+                         int gmap_offset_jacobian, int jacobian_kind /* NJF_JACOBIAN_* */, const float* w_density,
+                         const float* b_density, const float* w_color, const float* b_color, const float* w_jacobian,
+                         const float* b_jacobian, float* density, float* color, float* jacobian, int precision, void* stream);
+
 /* ---- stand-alone sampler / compositing ops (API parity with the un-fused reference calls) -- */
 /* RaySamples.get_weights (ray_samplers.py:77-101): deltas, densities [N,S] -> weights [N,S]. */
 int njf_alpha_weights(const float* deltas, const float* densities, int rays, int samples, float* weights, void* stream);

@@ -40,7 +40,9 @@ extern "C" const char* njf_error_string(int code) {
     case NJF_E_DOUT: return "ResnetFC d_out must be in [1, 32]";
     case NJF_E_MODE: return "unknown mode";
     case NJF_E_GMAP: return "feature map stride/offset does not cover NJF_ZDIM channels or is not 16-byte aligned";
-    case NJF_E_VALUE: return "invalid solver option (beta must be > 0, reg and damping >= 0)";
+    case NJF_E_VALUE:
+      return "invalid option value (solver: beta must be > 0, reg and damping >= 0; mesh: every grid dimension >= 2, a finite "
+             "threshold, capacities >= 0, a known phase)";
     default: return code > 0 ? "HIP runtime error (hipError_t)" : "unknown njf error";
   }
 }
@@ -2296,6 +2298,366 @@ __global__ void __launch_bounds__(NJF_SELECT_THREADS) select_scatter_kernel(Sele
   }
 }
 
+// ---- isosurface mesh of a scalar on the grid: marching tetrahedra on the Kuhn cut ------------------------------------------
+// inside(g) = values[g] >= threshold (NaN: outside).  Every cell is cut into the six tetrahedra around its main diagonal,
+// one per axis order (a, b, c) in the order xyz, xzy, yxz, yzx, zxy, zyx with the corners c0 = (0,0,0), c1 = c0 + e_a,
+// c2 = c1 + e_b, c3 = (1,1,1): the cut is translation invariant, so neighbouring cells agree on every face diagonal.  Every
+// tetrahedron edge is (lower node) + one of the seven directions k = 0..6 below; the lower node OWNS the edge.  One vertex
+// per edge whose ends are both valid and differ in `inside`, in ascending (owner, k); triangles per cell in ascending global
+// cell index, tetrahedra in the order above.  Six launches (mask + count, scan, vertex emit; count, scan, triangle emit),
+// integer arithmetic apart from the interpolation, no atomics: the output bytes do not depend on scheduling.
+#define NJF_MESH_THREADS 256
+#define NJF_MESH_ITEMS (NJF_FIELD_MESH_BLOCK / NJF_MESH_THREADS)
+#define NJF_MESH_WAVES (NJF_MESH_THREADS / 64)
+#define NJF_MESH_VALID 0x80u  // bit 7 of a node's mask byte: the node is valid; bits 0..6: edge k carries a vertex
+static_assert(NJF_MESH_ITEMS * NJF_MESH_THREADS == NJF_FIELD_MESH_BLOCK && NJF_MESH_ITEMS <= 8, "mesh block");
+struct MeshArgs {
+  SelectArgs sel;              // list: the identity over B*N; values, threshold; w2c / k: frustum part of `valid` (or null)
+  const unsigned char* valid;  // [B*N] or null
+  unsigned char* mask;         // [B*N]
+  int* offset;                 // [B*N] exclusive vertex offset of a node
+  int* vertex_node;            // [max_vertices]
+  unsigned char* vertex_edge;  // [max_vertices]
+  float* vertex_t;             // [max_vertices]
+  float* vertices;             // [max_vertices, 3]
+  int max_vertices;
+  int* triangles;              // [max_triangles, 3]
+  int* triangle_cell;          // [max_triangles]
+  int max_triangles;
+  int cells, total_cells;      // Nc = (nx-1)(ny-1)(nz-1), B*Nc
+  int* block_counts;           // per workgroup: counts, then (after the scan) exclusive offsets
+};
+
+// corner / direction codes: bit 0 = +x, bit 1 = +y, bit 2 = +z.  Direction k of the edge list -> code, and back
+__device__ __forceinline__ int mesh_dir_code(int k) { return (int)((0x7653421u >> (4 * k)) & 7u); }   // 1,2,4,3,5,6,7
+__device__ __forceinline__ int mesh_dir_index(int code) { return (int)((0x65423100u >> (4 * code)) & 7u); }  // -,0,1,3,2,4,5,6
+__device__ __forceinline__ int mesh_code_offset(const NjfFieldGrid& g, int code) {
+  return (code & 1) * g.dims[1] * g.dims[2] + ((code >> 1) & 1) * g.dims[2] + (code >> 2);
+}
+
+__device__ __forceinline__ bool mesh_node_valid(const MeshArgs& a, int gi) {
+  if (a.valid && a.valid[gi] == 0) return false;
+  return a.sel.w2c ? field_in_view(a.sel, gi) : true;
+}
+
+// sum of `v` over the workgroup (every thread calls), valid in thread 0
+__device__ __forceinline__ int mesh_block_sum(int v, int* wave_part) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+  if ((threadIdx.x & 63) == 0) wave_part[threadIdx.x >> 6] = v;
+  __syncthreads();
+  int s = 0;
+  for (int w = 0; w < NJF_MESH_WAVES; ++w) s += wave_part[w];
+  return s;
+}
+
+// rank[it] = base + (sum of c over the workgroup's entries in front of this thread's item `it`); entry order inside a
+// workgroup is item-major, then wave, then lane, which is ascending index (every thread calls)
+__device__ __forceinline__ void mesh_block_ranks(const int (&c)[NJF_MESH_ITEMS], int base, int (&rank)[NJF_MESH_ITEMS],
+                                                 int (*wave_sum)[NJF_MESH_WAVES]) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int before[NJF_MESH_ITEMS];
+#pragma unroll
+  for (int it = 0; it < NJF_MESH_ITEMS; ++it) {
+    int v = c[it];
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const int o = __shfl_up(v, d, 64);
+      if (lane >= d) v += o;
+    }
+    before[it] = v - c[it];
+    if (lane == 63) wave_sum[it][wave] = v;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int it = 0; it < NJF_MESH_ITEMS; ++it) {
+    int r = base;
+    for (int w = 0; w < wave; ++w) r += wave_sum[it][w];
+    rank[it] = r + before[it];
+    for (int w = 0; w < NJF_MESH_WAVES; ++w) base += wave_sum[it][w];
+  }
+}
+
+// launch 1: the mask byte of every node and the number of vertices per workgroup
+__global__ void __launch_bounds__(NJF_MESH_THREADS) mesh_mask_kernel(MeshArgs a) {
+  __shared__ int wave_part[NJF_MESH_WAVES];
+  const NjfFieldGrid& g = a.sel.list.grid;
+  int n_vertices = 0;
+#pragma unroll
+  for (int it = 0; it < NJF_MESH_ITEMS; ++it) {
+    const long long i = (long long)blockIdx.x * NJF_FIELD_MESH_BLOCK + it * NJF_MESH_THREADS + threadIdx.x;
+    if (i >= a.sel.list.total) continue;
+    const int gi = (int)i;
+    const int n = gi % a.sel.list.nodes;
+    const int yz = g.dims[1] * g.dims[2];
+    const int ix = n / yz, r = n - ix * yz;
+    const int iy = r / g.dims[2], iz = r - iy * g.dims[2];
+    const bool ok0 = mesh_node_valid(a, gi);
+    const bool in0 = a.sel.values[gi] >= a.sel.threshold;
+    unsigned m = ok0 ? NJF_MESH_VALID : 0u;
+    if (ok0) {
+#pragma unroll
+      for (int k = 0; k < 7; ++k) {
+        const int code = mesh_dir_code(k);
+        if (ix + (code & 1) >= g.dims[0] || iy + ((code >> 1) & 1) >= g.dims[1] || iz + (code >> 2) >= g.dims[2]) continue;
+        const int g1 = gi + mesh_code_offset(g, code);
+        if ((a.sel.values[g1] >= a.sel.threshold) != in0 && mesh_node_valid(a, g1)) m |= 1u << k;
+      }
+    }
+    a.mask[gi] = (unsigned char)m;
+    n_vertices += __popc(m & 0x7fu);
+  }
+  const int s = mesh_block_sum(n_vertices, wave_part);
+  if (threadIdx.x == 0) a.block_counts[blockIdx.x] = s;
+}
+
+// launch 3: per-node exclusive offsets (all nodes) and the vertex rows of ranks below the capacity
+__global__ void __launch_bounds__(NJF_MESH_THREADS) mesh_vertex_kernel(MeshArgs a) {
+  __shared__ int wave_sum[NJF_MESH_ITEMS][NJF_MESH_WAVES];
+  const NjfFieldGrid& g = a.sel.list.grid;
+  int c[NJF_MESH_ITEMS], rank[NJF_MESH_ITEMS];
+  unsigned m[NJF_MESH_ITEMS];
+#pragma unroll
+  for (int it = 0; it < NJF_MESH_ITEMS; ++it) {
+    const long long i = (long long)blockIdx.x * NJF_FIELD_MESH_BLOCK + it * NJF_MESH_THREADS + threadIdx.x;
+    m[it] = i < a.sel.list.total ? (a.mask[i] & 0x7fu) : 0u;
+    c[it] = __popc(m[it]);
+  }
+  mesh_block_ranks(c, a.block_counts[blockIdx.x], rank, wave_sum);
+#pragma unroll
+  for (int it = 0; it < NJF_MESH_ITEMS; ++it) {
+    const long long i = (long long)blockIdx.x * NJF_FIELD_MESH_BLOCK + it * NJF_MESH_THREADS + threadIdx.x;
+    if (i >= a.sel.list.total) continue;
+    const int gi = (int)i;
+    a.offset[gi] = rank[it];
+    if (m[it] == 0u || rank[it] >= a.max_vertices) continue;
+    int b;
+    float x0[3];
+    field_node(a.sel.list, gi, b, x0[0], x0[1], x0[2]);
+    const float v0 = a.sel.values[gi];
+    int r = rank[it];
+    for (int k = 0; k < 7; ++k) {
+      if (!((m[it] >> k) & 1u)) continue;
+      if (r < a.max_vertices) {
+        const int code = mesh_dir_code(k);
+        const int g1 = gi + mesh_code_offset(g, code);
+        float x1[3];
+        field_node(a.sel.list, g1, b, x1[0], x1[1], x1[2]);
+        const float v1 = a.sel.values[g1];
+        float t = __fdiv_rn(a.sel.threshold - v0, v1 - v0);  // IEEE division
+        if (!__builtin_isfinite(t)) t = 0.5f;                // (an infinite or NaN end)
+        t = t > 0.0f ? t : 0.0f;
+        t = t < 1.0f ? t : 1.0f;
+        a.vertex_node[r] = gi;
+        a.vertex_edge[r] = (unsigned char)k;
+        a.vertex_t[r] = t;
+#pragma unroll
+        for (int d = 0; d < 3; ++d) a.vertices[3 * (size_t)r + d] = fmaf(t, x1[d] - x0[d], x0[d]);
+      }
+      ++r;
+    }
+  }
+}
+
+// the triangles of one cell: `emit(v0, v1, v2)` per triangle in order, vertex ranks; returns their number (0..12).
+// COUNT: only the number.  Winding: the normal points from inside to outside, decided by the case and the parity of the
+// axis order alone -- with the corner list p = (the inside corners ascending, then the outside ones; for three inside
+// corners the outside one first) the sign of det[p1-p0, p2-p0, p3-p0] is (parity of the axis order) * (parity of p).
+template <bool COUNT, class F>
+__device__ __forceinline__ int mesh_cell_triangles(const MeshArgs& a, int gc, F&& emit) {
+  const NjfFieldGrid& g = a.sel.list.grid;
+  const int b = gc / a.cells, local = gc - b * a.cells;
+  const int cz = g.dims[2] - 1, cy = g.dims[1] - 1;
+  const int iz = local % cz, q = local / cz;
+  const int iy = q % cy, ix = q / cy;
+  const int g0 = b * a.sel.list.nodes + (ix * g.dims[1] + iy) * g.dims[2] + iz;
+  unsigned in8 = 0, ok8 = 0;
+#pragma unroll
+  for (int code = 0; code < 8; ++code) {
+    const int gi = g0 + mesh_code_offset(g, code);
+    ok8 |= (a.mask[gi] & NJF_MESH_VALID) ? 1u << code : 0u;
+    in8 |= a.sel.values[gi] >= a.sel.threshold ? 1u << code : 0u;
+  }
+  int n_tri = 0;
+#pragma unroll
+  for (int tet = 0; tet < 6; ++tet) {
+    const int ax = tet >> 1, bx = (0x102021 >> (4 * tet)) & 3;  // axis order (a, b, .): xyz xzy yxz yzx zxy zyx
+    const int cm[4] = {0, 1 << ax, (1 << ax) | (1 << bx), 7};
+    // parity of the axis order: xyz +, xzy -, yxz -, yzx +, zxy +, zyx -
+    const bool even_axes = tet == 0 || tet == 3 || tet == 4;
+    unsigned inm = 0;
+    bool ok = true;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      ok = ok && ((ok8 >> cm[c]) & 1u);
+      inm |= ((in8 >> cm[c]) & 1u) << c;
+    }
+    const int n_in = __popc(inm);
+    if (!ok || n_in == 0 || n_in == 4) continue;
+    if constexpr (COUNT) {
+      n_tri += n_in == 2 ? 2 : 1;
+      continue;
+    }
+    const unsigned lead = n_in == 3 ? (~inm & 15u) : inm;     // the corners listed first
+    int p[4], np = 0;
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+      if ((lead >> c) & 1u) p[np++] = c;
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+      if (!((lead >> c) & 1u)) p[np++] = c;
+    int inversions = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = i + 1; j < 4; ++j) inversions += p[i] > p[j];
+    const bool positive = (even_axes == ((inversions & 1) == 0)) != (n_in == 3);
+    auto rank_of = [&](int ci, int cj) {  // vertex rank of the edge between local corners ci and cj
+      const int lo = min(ci, cj), hi = max(ci, cj);
+      const int gi = g0 + mesh_code_offset(g, cm[lo]);
+      const int k = mesh_dir_index(cm[hi] ^ cm[lo]);
+      return a.offset[gi] + __popc(a.mask[gi] & ((1u << k) - 1u));
+    };
+    if (n_in != 2) {
+      const int v0 = rank_of(p[0], p[1]), v1 = rank_of(p[0], p[2]), v2 = rank_of(p[0], p[3]);
+      if (positive) emit(v0, v1, v2); else emit(v0, v2, v1);
+      n_tri += 1;
+    } else {
+      const int ik = rank_of(p[0], p[2]), il = rank_of(p[0], p[3]), jl = rank_of(p[1], p[3]), jk = rank_of(p[1], p[2]);
+      if (positive) {
+        emit(ik, il, jl);
+        emit(ik, jl, jk);
+      } else {
+        emit(ik, jl, il);
+        emit(ik, jk, jl);
+      }
+      n_tri += 2;
+    }
+  }
+  return n_tri;
+}
+
+// launch 4: the number of triangles per workgroup of cells
+__global__ void __launch_bounds__(NJF_MESH_THREADS) mesh_triangle_count_kernel(MeshArgs a) {
+  __shared__ int wave_part[NJF_MESH_WAVES];
+  int n = 0;
+#pragma unroll
+  for (int it = 0; it < NJF_MESH_ITEMS; ++it) {
+    const long long i = (long long)blockIdx.x * NJF_FIELD_MESH_BLOCK + it * NJF_MESH_THREADS + threadIdx.x;
+    if (i < a.total_cells) n += mesh_cell_triangles<true>(a, (int)i, [](int, int, int) {});
+  }
+  const int s = mesh_block_sum(n, wave_part);
+  if (threadIdx.x == 0) a.block_counts[blockIdx.x] = s;
+}
+
+// launch 6: the triangle rows of ranks below the capacity
+__global__ void __launch_bounds__(NJF_MESH_THREADS) mesh_triangle_kernel(MeshArgs a) {
+  __shared__ int wave_sum[NJF_MESH_ITEMS][NJF_MESH_WAVES];
+  int c[NJF_MESH_ITEMS], rank[NJF_MESH_ITEMS];
+#pragma unroll
+  for (int it = 0; it < NJF_MESH_ITEMS; ++it) {
+    const long long i = (long long)blockIdx.x * NJF_FIELD_MESH_BLOCK + it * NJF_MESH_THREADS + threadIdx.x;
+    c[it] = i < a.total_cells ? mesh_cell_triangles<true>(a, (int)i, [](int, int, int) {}) : 0;
+  }
+  mesh_block_ranks(c, a.block_counts[blockIdx.x], rank, wave_sum);
+#pragma unroll
+  for (int it = 0; it < NJF_MESH_ITEMS; ++it) {
+    if (c[it] == 0 || rank[it] >= a.max_triangles) continue;
+    const int gc = blockIdx.x * NJF_FIELD_MESH_BLOCK + it * NJF_MESH_THREADS + threadIdx.x;
+    int r = rank[it];
+    mesh_cell_triangles<false>(a, gc, [&](int v0, int v1, int v2) {
+      if (r < a.max_triangles) {
+        a.triangles[3 * (size_t)r] = v0;
+        a.triangles[3 * (size_t)r + 1] = v1;
+        a.triangles[3 * (size_t)r + 2] = v2;
+        a.triangle_cell[r] = gc;
+      }
+      ++r;
+    });
+  }
+}
+
+// ---- the decoder's heads at stored positions (the mesh vertices) ----------------------------------------------------------
+struct FieldAtArgs {
+  const float* xyz;   // [capacity, 3]
+  const int* node;    // [capacity] global node index: the batch element of row i is node[i] / nodes
+  const int* count;   // or null
+  int capacity;
+  int nodes, total;   // N, B*N
+  float dirx, diry, dirz;
+  NjfCameras cams;
+  NjfFeatureMap gmap;
+  int goff_d, goff_j;
+  const float* w_all;
+  const float* b_d;
+  const float* b_c;
+  const float* b_j;
+  float* density;   // [entries] or null
+  float* color;     // [entries, 3] or null
+  float* jacobian;  // [entries, 3A]
+};
+
+// field_points_kernel with the point read from `xyz` and its batch element from `node` (a ragged batch in one launch).
+// MODE 2: density + colour; 3: + ResnetFC Jacobian head; 4: + transformer Jacobian head -- the modes, stages, weight stream
+// and per-point arithmetic of field_points_kernel: a row's outputs equal those of njf_points_forward on its position.
+template <int MODE, int PREC, int PRECJ = PREC>
+__global__ void __launch_bounds__(NJF_THREADS, 2) field_at_kernel(FieldAtArgs a) {
+  static_assert(MODE >= 2 && MODE <= 4, "decoder modes with the colour head");
+  const int entries = a.count ? min(max(*a.count, 0), a.capacity) : a.capacity;
+  const int tid = threadIdx.x;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int lane = tid & 63, j = lane & 31, hh = lane >> 5;
+  const int wg = xcd_remap(blockIdx.x, gridDim.x);
+  if (wg * (NJF_WAVES * 32) >= entries) return;  // the whole workgroup (it shares the weight stream), before any barrier
+  const int tile = wg * NJF_WAVES + wave;
+  const int p = tile * 32 + j;
+  const bool ok = p < entries;
+  const int pc = min(p, entries - 1);
+
+  load_bias_block(a.b_d, NJF_RESNET_B_FLOATS, 0);
+  load_bias_block(a.b_c, NJF_COLOR_B_FLOATS, NJF_RESNET_B_FLOATS);
+  if (MODE == 3) load_bias_block(a.b_j, NJF_RESNET_B_FLOATS, NJF_RESNET_B_FLOATS + NJF_COLOR_B_FLOATS);
+  if (MODE == 4) load_bias_block(a.b_j, NJF_TRANSFORMER_B_FLOATS, NJF_RESNET_B_FLOATS + NJF_COLOR_B_FLOATS);
+  WeightStreamT<resnet_gap_at<PREC>(), resnet_gap<PREC>()> st;
+  stream_begin(st, a.w_all,
+               resnet_chunks<PREC>() + 1 + (MODE == 3 ? resnet_chunks<PRECJ>() : (MODE == 4 ? NJF_TRANSFORMER_CHUNKS : 0)), 1, wave,
+               lane);
+  const int b = min(max(a.node[pc], 0), a.total - 1) / a.nodes;  // (caller data: clamped into the batch)
+  const float px = a.xyz[3 * (size_t)pc], py = a.xyz[3 * (size_t)pc + 1], pz = a.xyz[3 * (size_t)pc + 2];
+  CamCtx cam;
+  load_ctx(a.cams.ctxt_w2c, a.cams.ctxt_k, b, cam);
+  PointGeom g;
+  const unsigned gbase = (unsigned)b * (unsigned)(a.gmap.height * a.gmap.width) * (unsigned)a.gmap.stride;
+  point_geometry(cam, px, py, pz, a.gmap.height, a.gmap.width, a.gmap.stride, gbase, g);
+  const int A = a.cams.action_dim;
+  constexpr int JK = MODE >= 3 ? MODE - 2 : 0;
+  const ActDump nodump{nullptr, nullptr, 0};
+  f32x16 geo[1];
+  const float sigma = density_stage<PREC, 0>(st, map_at<PREC>(a.gmap.data, a.goff_d), g, wave, lane, geo, nodump);
+  if (ok && hh == 0 && a.density) a.density[p] = sigma;
+  {
+    float rgb[3];
+    color_stage<PREC, 0>(st, geo, a.dirx, a.diry, a.dirz, wave, lane, rgb, ColorDump{nullptr, nullptr, 0});
+    if (ok && hh == 0 && a.color) {
+      a.color[3 * (size_t)p] = rgb[0];
+      a.color[3 * (size_t)p + 1] = rgb[1];
+      a.color[3 * (size_t)p + 2] = rgb[2];
+    }
+  }
+  if (JK != 0) {
+    f32x16 jac[1];
+    float flow[3];
+    jacobian_stage<JK, PRECJ, 0>(st, map_at<PRECJ>(a.gmap.data, a.goff_j), g, nullptr, A, wave, lane, jac, flow, nodump);
+    if (ok && a.jacobian) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int d = 16 * hh + r;
+        if (d < 3 * A) a.jacobian[(size_t)p * (3 * A) + d] = jac[0][r];
+      }
+    }
+  }
+}
+
 // =============================================================================================
 // inverse dynamics: Levenberg-Marquardt on the linearised flow, one workgroup per batch element
 // =============================================================================================
@@ -3946,6 +4308,155 @@ extern "C" int njf_field_forward(const NjfFieldGrid* grid, const int* indices, c
   return with_precisions(precision, [&](auto P, auto PJ) {
     if (jacobian_kind == NJF_JACOBIAN_MLP) return launch_fused(field_points_kernel<3, NJF_P, NJF_PJ>, a, tiles, s);
     return launch_fused(field_points_kernel<4, NJF_P, NJF_PJ>, a, tiles, s);
+  });
+}
+
+// ---- isosurface mesh ---------------------------------------------------------------------------------------------------
+static int make_mesh_args(const NjfFieldGrid* grid, const NjfCameras* cams, int batch, const float* values,
+                          const unsigned char* valid, float threshold, int phase, unsigned char* edge_mask, int* vertex_offset,
+                          int* workspace, MeshArgs& a) {
+  if (!grid || !values || !edge_mask || !vertex_offset || !workspace) return NJF_E_NULL;
+  int rc = make_field_list(grid, batch, nullptr, nullptr, 0, a.sel.list);
+  if (rc) return rc;
+  if (grid->dims[0] < 2 || grid->dims[1] < 2 || grid->dims[2] < 2) return NJF_E_VALUE;  // no cell
+  if (!__builtin_isfinite(threshold)) return NJF_E_VALUE;
+  if (phase < 1 || phase > 3) return NJF_E_VALUE;
+  if (cams && (!cams->ctxt_w2c || !cams->ctxt_k)) return NJF_E_NULL;
+  if (cams && cams->batch != batch) return NJF_E_SHAPE;
+  a.sel.list.capacity = a.sel.list.total;
+  a.sel.values = values;
+  a.sel.threshold = threshold;
+  a.sel.w2c = cams ? cams->ctxt_w2c : nullptr;
+  a.sel.k = cams ? cams->ctxt_k : nullptr;
+  a.sel.out_indices = nullptr;
+  a.sel.out_count = nullptr;
+  a.sel.out_capacity = 0;
+  a.sel.block_counts = nullptr;
+  a.sel.blocks = 0;
+  a.valid = valid;
+  a.mask = edge_mask;
+  a.offset = vertex_offset;
+  a.vertex_node = nullptr;
+  a.vertex_edge = nullptr;
+  a.vertex_t = nullptr;
+  a.vertices = nullptr;
+  a.max_vertices = 0;
+  a.triangles = nullptr;
+  a.triangle_cell = nullptr;
+  a.max_triangles = 0;
+  a.cells = (grid->dims[0] - 1) * (grid->dims[1] - 1) * (grid->dims[2] - 1);
+  a.total_cells = batch * a.cells;
+  a.block_counts = workspace;
+  return NJF_OK;
+}
+
+extern "C" int njf_field_mesh_vertices(const NjfFieldGrid* grid, const NjfCameras* cams, int batch, const float* values,
+                                       const unsigned char* valid, float threshold, int phase, unsigned char* edge_mask,
+                                       int* vertex_offset, int* vertex_node, unsigned char* vertex_edge, float* vertex_t,
+                                       float* vertices, int max_vertices, int* vertex_count, int* workspace, void* stream) {
+  MeshArgs a;
+  int rc = make_mesh_args(grid, cams, batch, values, valid, threshold, phase, edge_mask, vertex_offset, workspace, a);
+  if (rc) return rc;
+  if ((phase & NJF_FIELD_MESH_COUNT) && !vertex_count) return NJF_E_NULL;
+  if (max_vertices < 0) return NJF_E_VALUE;
+  if ((phase & NJF_FIELD_MESH_EMIT) && max_vertices > 0 && (!vertex_node || !vertex_edge || !vertex_t || !vertices)) return NJF_E_NULL;
+  a.vertex_node = vertex_node;
+  a.vertex_edge = vertex_edge;
+  a.vertex_t = vertex_t;
+  a.vertices = vertices;
+  a.max_vertices = max_vertices;
+  const int blocks = (int)(((long long)a.sel.list.total + NJF_FIELD_MESH_BLOCK - 1) / NJF_FIELD_MESH_BLOCK);
+  hipStream_t s = (hipStream_t)stream;
+  if (phase & NJF_FIELD_MESH_COUNT) {
+    mesh_mask_kernel<<<blocks, NJF_MESH_THREADS, 0, s>>>(a);
+    if ((rc = launch_status())) return rc;
+    select_scan_kernel<<<1, NJF_SELECT_THREADS, 0, s>>>(workspace, blocks, vertex_count);
+    if ((rc = launch_status())) return rc;
+  }
+  if (phase & NJF_FIELD_MESH_EMIT) {
+    mesh_vertex_kernel<<<blocks, NJF_MESH_THREADS, 0, s>>>(a);
+    if ((rc = launch_status())) return rc;
+  }
+  return NJF_OK;
+}
+
+extern "C" int njf_field_mesh_triangles(const NjfFieldGrid* grid, int batch, const float* values, float threshold, int phase,
+                                        const unsigned char* edge_mask, const int* vertex_offset, int* triangles,
+                                        int* triangle_cell, int max_triangles, int* triangle_count, int* workspace,
+                                        void* stream) {
+  MeshArgs a;
+  int rc = make_mesh_args(grid, nullptr, batch, values, nullptr, threshold, phase, const_cast<unsigned char*>(edge_mask),
+                          const_cast<int*>(vertex_offset), workspace, a);
+  if (rc) return rc;
+  if ((phase & NJF_FIELD_MESH_COUNT) && !triangle_count) return NJF_E_NULL;
+  if (max_triangles < 0) return NJF_E_VALUE;
+  if ((phase & NJF_FIELD_MESH_EMIT) && max_triangles > 0 && (!triangles || !triangle_cell)) return NJF_E_NULL;
+  a.triangles = triangles;
+  a.triangle_cell = triangle_cell;
+  a.max_triangles = max_triangles;
+  const int blocks = (a.total_cells + NJF_FIELD_MESH_BLOCK - 1) / NJF_FIELD_MESH_BLOCK;
+  hipStream_t s = (hipStream_t)stream;
+  if (phase & NJF_FIELD_MESH_COUNT) {
+    mesh_triangle_count_kernel<<<blocks, NJF_MESH_THREADS, 0, s>>>(a);
+    if ((rc = launch_status())) return rc;
+    select_scan_kernel<<<1, NJF_SELECT_THREADS, 0, s>>>(workspace, blocks, triangle_count);
+    if ((rc = launch_status())) return rc;
+  }
+  if ((phase & NJF_FIELD_MESH_EMIT) && max_triangles > 0) {
+    mesh_triangle_kernel<<<blocks, NJF_MESH_THREADS, 0, s>>>(a);
+    if ((rc = launch_status())) return rc;
+  }
+  return NJF_OK;
+}
+
+extern "C" int njf_field_forward_at(const float* xyz, const int* node, const int* count, int capacity, int nodes_per_batch,
+                                    const float* view_dir, const NjfCameras* cams, const NjfFeatureMap* gmap,
+                                    int gmap_offset_density, int gmap_offset_jacobian, int jacobian_kind,
+                                    const float* w_density, const float* b_density, const float* w_color, const float* b_color,
+                                    const float* w_jacobian, const float* b_jacobian, float* density, float* color,
+                                    float* jacobian, int precision, void* stream) {
+  if (!xyz || !node || !cams || !gmap || !w_density || !b_density || !w_color || !b_color) return NJF_E_NULL;
+  if (!cams->ctxt_w2c || !cams->ctxt_k || !gmap->data) return NJF_E_NULL;
+  if (capacity < 0 || cams->batch < 1) return NJF_E_SHAPE;
+  if (nodes_per_batch < 1 || (long long)nodes_per_batch * cams->batch > 0x7fffffffLL) return NJF_E_VALUE;
+  if (!valid_precision(precision)) return NJF_E_MODE;
+  if (gmap->height < 1 || gmap->width < 1) return NJF_E_SHAPE;
+  int rc;
+  if ((rc = check_gmap(gmap, gmap_offset_density, NJF_ZDIM, density_precision(precision)))) return rc;
+  if ((long long)cams->batch * gmap->height * gmap->width * gmap->stride > 0xffffffffLL) return NJF_E_SHAPE;  // PointGeom::gofs
+  if ((rc = check_jacobian(jacobian_kind, cams, gmap, gmap_offset_jacobian, w_jacobian, b_jacobian, precision))) return rc;
+  const bool with_j = jacobian_kind != NJF_JACOBIAN_NONE;
+  if (with_j ? !jacobian : !color) return NJF_E_NULL;
+  if ((rc = check_contiguous(w_density, w_color, w_jacobian, with_j))) return rc;
+  FieldAtArgs a;
+  a.xyz = xyz;
+  a.node = node;
+  a.count = count;
+  a.capacity = capacity;
+  a.nodes = nodes_per_batch;
+  a.total = nodes_per_batch * cams->batch;
+  a.dirx = view_dir ? view_dir[0] : 0.f;
+  a.diry = view_dir ? view_dir[1] : 0.f;
+  a.dirz = view_dir ? view_dir[2] : 1.f;
+  a.cams = *cams;
+  a.gmap = *gmap;
+  a.goff_d = gmap_offset_density;
+  a.goff_j = gmap_offset_jacobian;
+  a.w_all = w_density;
+  a.b_d = b_density;
+  a.b_c = b_color;
+  a.b_j = b_jacobian;
+  a.density = density;
+  a.color = color;
+  a.jacobian = jacobian;
+  if (capacity == 0) return NJF_OK;
+  const int tiles = (capacity + 31) / 32;
+  hipStream_t s = (hipStream_t)stream;
+  if (!with_j)
+    return with_precision(density_precision(precision), [&](auto P) { return launch_fused(field_at_kernel<2, NJF_P>, a, tiles, s); });
+  return with_precisions(precision, [&](auto P, auto PJ) {
+    if (jacobian_kind == NJF_JACOBIAN_MLP) return launch_fused(field_at_kernel<3, NJF_P, NJF_PJ>, a, tiles, s);
+    return launch_fused(field_at_kernel<4, NJF_P, NJF_PJ>, a, tiles, s);
   });
 }
 

@@ -103,6 +103,29 @@ class FieldGrid:
         return hip.make_field_grid(self.origin, self.step, self.dims)
 
 
+def _sensitivity_colors(owner: str, jacobian: Optional[torch.Tensor], rows: int, color_map, mode: int) -> torch.Tensor:
+    """The joint-sensitivity colouring of the first ``rows`` Jacobians ``[n, A, 3]`` (point cloud and mesh alike)."""
+    if jacobian is None:
+        raise ValueError(f"{owner}.colors needs the Jacobians (extract with want_jacobian=True)")
+    jac = jacobian[:rows]
+    if isinstance(color_map, str):
+        color_map = torch.tensor(_cm.JACOBIAN_COLORMAP[color_map], dtype=torch.float32).t()
+    color_map = torch.as_tensor(color_map, dtype=torch.float32)
+    if tuple(color_map.shape) != (3, jac.shape[1]):
+        raise ValueError(f"{owner}.colors: color_map must be [3, {jac.shape[1]}] (got {tuple(color_map.shape)})")
+    sens = _cm.compute_joint_sensitivity_point_cloud(jac)
+    return _cm.visualize_joint_sensitivity_point_cloud(sens, color_map.to(jac.device), mode)
+
+
+def _rgb8(owner: str, colors: Optional[torch.Tensor], default: Optional[torch.Tensor], n: int) -> np.ndarray:
+    """``[n, 3]`` uint8 colours of a PLY: ``colors`` in [0, 1], else ``default`` (the colour head's output), else white."""
+    rgb = default[:n] if colors is None and default is not None else colors
+    rgb = np.ones((n, 3), dtype=np.float32) if rgb is None else rgb[:n].detach().float().cpu().numpy()
+    if rgb.shape != (n, 3):
+        raise ValueError(f"{owner}: colors must be [{n}, 3] (got {rgb.shape})")
+    return np.rint(np.clip(rgb, 0.0, 1.0) * 255.0).astype(np.uint8)
+
+
 @dataclass
 class FieldPointCloud:
     """The extracted nodes in ascending global index.  Exactly sized (``count`` = number of rows) from an eager extraction;
@@ -131,30 +154,17 @@ class FieldPointCloud:
         """``[n, 3]`` display colours in [0, 1]: ``compute_joint_sensitivity_point_cloud`` chained with
         ``visualize_joint_sensitivity_point_cloud`` (inference/jacobian_color_map.py) on the valid rows.  ``color_map``: a
         ``[3, A]`` tensor or the name of a table in ``JACOBIAN_COLORMAP`` (stored ``[A, 3]``)."""
-        if self.jacobian is None:
-            raise ValueError("FieldPointCloud.colors needs the Jacobians (extract with want_jacobian=True)")
-        jac = self.jacobian[:self.valid()]
-        if isinstance(color_map, str):
-            color_map = torch.tensor(_cm.JACOBIAN_COLORMAP[color_map], dtype=torch.float32).t()
-        color_map = torch.as_tensor(color_map, dtype=torch.float32)
-        if tuple(color_map.shape) != (3, jac.shape[1]):
-            raise ValueError(f"FieldPointCloud.colors: color_map must be [3, {jac.shape[1]}] (got {tuple(color_map.shape)})")
-        sens = _cm.compute_joint_sensitivity_point_cloud(jac)
-        return _cm.visualize_joint_sensitivity_point_cloud(sens, color_map.to(jac.device), mode)
+        return _sensitivity_colors("FieldPointCloud", self.jacobian, self.valid(), color_map, mode)
 
     def save_ply(self, path, colors: Optional[torch.Tensor] = None) -> int:
         """Binary little-endian PLY of the valid rows: ``x y z`` float32, ``red green blue`` uint8, ``density`` float32.
         ``colors`` ``[n, 3]`` in [0, 1] (default: the colour head's output, white without one).  Returns the vertex count."""
         n = self.valid()
-        rgb = self.color[:n] if colors is None and self.color is not None else colors
-        rgb = np.ones((n, 3), dtype=np.float32) if rgb is None else rgb[:n].detach().float().cpu().numpy()
-        if rgb.shape != (n, 3):
-            raise ValueError(f"save_ply: colors must be [{n}, 3] (got {rgb.shape})")
+        rgb8 = _rgb8("save_ply", colors, self.color, n)
         vertex = np.empty(n, dtype=[("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1"),
                                     ("density", "<f4")])
         xyz = self.xyz[:n].detach().cpu().numpy()
         vertex["x"], vertex["y"], vertex["z"] = xyz[:, 0], xyz[:, 1], xyz[:, 2]
-        rgb8 = np.rint(np.clip(rgb, 0.0, 1.0) * 255.0).astype(np.uint8)
         vertex["red"], vertex["green"], vertex["blue"] = rgb8[:, 0], rgb8[:, 1], rgb8[:, 2]
         vertex["density"] = self.density[:n].detach().cpu().numpy()
         header = ("ply\nformat binary_little_endian 1.0\ncomment Jacobian-field point cloud\n"
@@ -283,3 +293,200 @@ def extract_field(model, pixel_encoding: PixelEncoding, grid: FieldGrid, density
         else:
             hip.field_forward(cg, index, stage.count, n, cams, fmap, density=cloud.density, **common)
     return cloud
+
+
+# ---- isosurface meshes ------------------------------------------------------------------------------------------------------
+@dataclass
+class FieldMesh:
+    """The isosurface ``values == threshold`` of a scalar on the grid (marching tetrahedra on the Kuhn cut; DESIGN.md section
+    11).  Vertices in ascending ``(vertex_node, vertex_edge)``, triangles in ascending ``triangle_cell``; the geometric normal
+    of a triangle points from inside (``values >= threshold``) to outside.  Exactly sized from an eager call; padded to the
+    capacities from a capture-safe one, where ``vertex_count`` / ``triangle_count`` hold the TRUE numbers -- they may exceed
+    the rows stored, which are the first ones -- and triangle entries are TRUE vertex ranks (check ``vertex_count <=
+    max_vertices`` before indexing with them).  A vertex is referenced by at least one triangle unless ``valid`` (or the
+    frustum) removed every tetrahedron around its edge."""
+
+    grid: FieldGrid
+    vertices: torch.Tensor                # [V, 3]
+    vertex_node: torch.Tensor             # [V] int32 global index of the node that owns the vertex's edge
+    vertex_edge: torch.Tensor             # [V] uint8 direction 0..6 of the edge (MESH_DIRECTIONS)
+    vertex_t: torch.Tensor                # [V] position on the edge: vertices = fma(t, x1 - x0, x0)
+    triangles: torch.Tensor               # [T, 3] int32 vertex ranks
+    triangle_cell: torch.Tensor           # [T] int32 global cell index
+    color: Optional[torch.Tensor]         # [V, 3]
+    jacobian: Optional[torch.Tensor]      # [V, A, 3]
+    vertex_count: torch.Tensor            # [1] int32
+    triangle_count: torch.Tensor          # [1] int32
+
+    @property
+    def batch_index(self) -> torch.Tensor:
+        """Batch element of every vertex."""
+        return torch.div(self.vertex_node, self.grid.num_nodes, rounding_mode="floor")
+
+    def valid(self) -> Tuple[int, int]:
+        """(vertex rows, triangle rows) that hold data (reads both counts: a host synchronisation)."""
+        return (min(int(self.vertex_count.item()), self.vertex_node.shape[0]),
+                min(int(self.triangle_count.item()), self.triangle_cell.shape[0]))
+
+    def colors(self, color_map, mode: int = 0) -> torch.Tensor:
+        """``[V, 3]`` display colours in [0, 1] of the valid vertices: ``FieldPointCloud.colors`` on the vertex Jacobians."""
+        return _sensitivity_colors("FieldMesh", self.jacobian, self.valid()[0], color_map, mode)
+
+    def save_ply(self, path, colors: Optional[torch.Tensor] = None) -> Tuple[int, int]:
+        """Binary little-endian PLY: vertices ``x y z`` float32 + ``red green blue`` uint8 (``colors`` ``[V, 3]`` in [0, 1];
+        default: the colour head's output, white without one), faces ``list uchar int vertex_indices``.  Returns (V, T)."""
+        v, t = self.valid()
+        if int(self.vertex_count.item()) > v:
+            raise ValueError("save_ply: the mesh was truncated (vertex_count > max_vertices): its triangles reference rows "
+                             "that were not stored")
+        rgb8 = _rgb8("save_ply", colors, self.color, v)
+        vertex = np.empty(v, dtype=[("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")])
+        xyz = self.vertices[:v].detach().cpu().numpy()
+        vertex["x"], vertex["y"], vertex["z"] = xyz[:, 0], xyz[:, 1], xyz[:, 2]
+        vertex["red"], vertex["green"], vertex["blue"] = rgb8[:, 0], rgb8[:, 1], rgb8[:, 2]
+        face = np.empty(t, dtype=[("n", "u1"), ("v", "<i4", (3,))])
+        face["n"] = 3
+        face["v"] = self.triangles[:t].detach().cpu().numpy()
+        header = ("ply\nformat binary_little_endian 1.0\ncomment Jacobian-field surface mesh\n"
+                  f"element vertex {v}\nproperty float x\nproperty float y\nproperty float z\n"
+                  "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+                  f"element face {t}\nproperty list uchar int vertex_indices\nend_header\n")
+        with open(path, "wb") as f:
+            f.write(header.encode("ascii"))
+            f.write(vertex.tobytes())
+            f.write(face.tobytes())
+        return v, t
+
+
+MESH_DIRECTIONS = ((1, 0, 0), (0, 1, 0), (0, 0, 1), (1, 1, 0), (1, 0, 1), (0, 1, 1), (1, 1, 1))   # edge k = lower node + this
+
+
+def _check_mesh_arguments(name: str, grid: FieldGrid, batch: int, threshold: float, max_vertices, max_triangles) -> None:
+    if any(d < 2 for d in grid.dims):
+        raise ValueError(f"{name}: every grid dimension must be >= 2 (got {grid.dims}): a mesh needs cells")
+    if not math.isfinite(float(threshold)):
+        raise ValueError(f"{name}: the threshold must be finite")
+    if (max_vertices is None) != (max_triangles is None):
+        raise ValueError(f"{name}: give both max_vertices and max_triangles (no host synchronisation) or neither")
+    if max_vertices is not None and (max_vertices < 1 or max_triangles < 1):
+        raise ValueError(f"{name}: max_vertices and max_triangles must be >= 1")
+    if batch < 1 or batch * grid.num_nodes >= 2 ** 31:
+        raise ValueError(f"{name}: batch * nx*ny*nz must stay below 2**31")
+
+
+def _mesh_geometry(grid: FieldGrid, values: torch.Tensor, threshold: float, valid, cams, max_vertices, max_triangles) -> FieldMesh:
+    """The six meshing launches.  Eager (no capacities): count, read the count, emit exactly -- for vertices, then triangles."""
+    b, dev = values.shape[0], values.device
+    total = b * grid.num_nodes
+    cg = grid.c_grid()
+    i32 = dict(dtype=torch.int32, device=dev)
+    f32 = dict(dtype=torch.float32, device=dev)
+    u8 = dict(dtype=torch.uint8, device=dev)
+    mask, offset = torch.empty(total, **u8), torch.empty(total, **i32)
+    v_count, t_count = torch.empty(1, **i32), torch.empty(1, **i32)
+    flat = values.reshape(-1)
+
+    def vertices(phase, cap, v_ws):
+        out = (torch.empty(cap, **i32), torch.empty(cap, **u8), torch.empty(cap, **f32), torch.empty(cap, 3, **f32))
+        hip.field_mesh_vertices(cg, b, flat, threshold, phase, mask, offset, v_count, v_ws, valid=valid, cams=cams,
+                                vertex_node=out[0] if cap else None, vertex_edge=out[1] if cap else None,
+                                vertex_t=out[2] if cap else None, vertices=out[3] if cap else None)
+        return out
+
+    def triangles(phase, cap, t_ws):
+        out = (torch.empty(cap, 3, **i32), torch.empty(cap, **i32))
+        hip.field_mesh_triangles(cg, b, flat, threshold, phase, mask, offset, t_count, t_ws,
+                                 triangles=out[0] if cap else None, triangle_cell=out[1] if cap else None)
+        return out
+
+    v_ws, t_ws = hip.field_mesh_workspace(total, dev), hip.field_mesh_workspace(total, dev)
+    both = hip.FIELD_MESH_COUNT | hip.FIELD_MESH_EMIT
+    if max_vertices is not None:
+        v_out = vertices(both, max_vertices, v_ws)
+        t_out = triangles(both, max_triangles, t_ws)
+    else:
+        hip.field_mesh_vertices(cg, b, flat, threshold, hip.FIELD_MESH_COUNT, mask, offset, v_count, v_ws, valid=valid, cams=cams)
+        v_out = vertices(hip.FIELD_MESH_EMIT, int(v_count.item()), v_ws)
+        if v_out[0].shape[0] == 0:                 # no vertex, no triangle
+            t_count.zero_()
+            t_out = (torch.empty(0, 3, **i32), torch.empty(0, **i32))
+        else:
+            hip.field_mesh_triangles(cg, b, flat, threshold, hip.FIELD_MESH_COUNT, mask, offset, t_count, t_ws)
+            t_out = triangles(hip.FIELD_MESH_EMIT, int(t_count.item()), t_ws)
+    return FieldMesh(grid=grid, vertices=v_out[3], vertex_node=v_out[0], vertex_edge=v_out[1], vertex_t=v_out[2],
+                     triangles=t_out[0], triangle_cell=t_out[1], color=None, jacobian=None, vertex_count=v_count,
+                     triangle_count=t_count)
+
+
+def mesh_from_values(grid: FieldGrid, values: torch.Tensor, threshold: float, *, valid: Optional[torch.Tensor] = None,
+                     max_vertices: Optional[int] = None, max_triangles: Optional[int] = None) -> FieldMesh:
+    """The isosurface of any scalar on the grid, geometry only (``color`` and ``jacobian`` are None): ``values`` ``[B, N]`` fp32
+    on the GPU, inside where ``values >= threshold`` (NaN is outside); ``valid`` ``[B, N]`` bool / uint8 removes nodes -- no
+    vertex on an edge with an invalid end, no triangle from a tetrahedron with an invalid corner, so the surface is open
+    there.  Without capacities: exactly sized tensors, two host reads of a device count.  With both: no host
+    synchronisation, tensors padded to the capacities, true counts (see ``FieldMesh``)."""
+    if not torch.is_tensor(values) or values.dim() != 2 or values.dtype != torch.float32 or values.shape[1] != grid.num_nodes:
+        raise ValueError(f"mesh_from_values: values must be fp32 [B, {grid.num_nodes}]")
+    _check_mesh_arguments("mesh_from_values", grid, values.shape[0], threshold, max_vertices, max_triangles)
+    if valid is not None:
+        if not torch.is_tensor(valid) or valid.dtype not in (torch.bool, torch.uint8) or valid.shape != values.shape:
+            raise ValueError(f"mesh_from_values: valid must be bool or uint8 {tuple(values.shape)}")
+        if valid.device != values.device:
+            raise ValueError("mesh_from_values: valid and values must live on the same device")
+        valid = valid.contiguous()
+    if values.device.type != "cuda":
+        raise ValueError("mesh_from_values: values must live on the GPU; there is no CPU path")
+    return _mesh_geometry(grid, values.contiguous(), float(threshold), valid, None, max_vertices, max_triangles)
+
+
+@torch.no_grad()
+def extract_mesh(model, pixel_encoding: PixelEncoding, grid: FieldGrid, density_threshold: float, *, in_frustum: bool = True,
+                 want_color: bool = True, want_jacobian: bool = True, view_direction: Optional[Sequence[float]] = None,
+                 max_vertices: Optional[int] = None, max_triangles: Optional[int] = None) -> FieldMesh:
+    """The surface ``decoder_density == density_threshold`` of the context image(s) over ``grid``, with the colour head's
+    output and the Jacobian ``[A, 3]`` AT every vertex (what ``njf_points_forward`` returns for that position and batch
+    element).  ``in_frustum``: nodes outside the context view are invalid -- the surface ends where the view ends.  The
+    density network runs on all ``B*N`` nodes, ``mesh_from_values`` on the result, one ragged launch on the vertices."""
+    dec = model.decoder
+    if not isinstance(dec, ActionDecoderJacobian):
+        raise TypeError("extract_mesh needs one of the fused action decoders")
+    is_flow = isinstance(dec, ActionDecoderFlowMlp)
+    if want_jacobian and is_flow:
+        raise NotImplementedError("flow_mlp predicts the scene flow directly; it has no Jacobian")
+    if view_direction is not None and len(view_direction) != 3:
+        raise ValueError("extract_mesh: view_direction has three components")
+    feats = pixel_encoding.features
+    dev = feats.device
+    b = pixel_encoding.extrinsics.shape[0]
+    _check_mesh_arguments("extract_mesh", grid, b, density_threshold, max_vertices, max_triangles)
+    total = b * grid.num_nodes
+    cg = grid.c_grid()
+    if dev.type == "cuda" and torch.cuda.is_current_stream_capturing():
+        model.reset_image_cache()      # a capture must contain the projection (see extract_field)
+    f32 = dict(dtype=torch.float32, device=dev)
+    cams = _cameras(pixel_encoding, False, action_dim=dec.kernel_action_dim if want_jacobian else None)
+    w, bd, bc, bj = dec.packed()
+    if is_flow:
+        gmap, base = ActionDecoderJacobian.hoisted_map(dec, feats), 0
+    else:
+        gmap, base = _map_of(dec, feats)
+    fmap = hip.make_feature_map(gmap)
+    goffs = dict(goff_density=base + dec.GOFF_DENSITY, goff_jacobian=base + dec.GOFF_JACOBIAN)
+    values = torch.empty(b, grid.num_nodes, **f32)
+    hip.field_forward(cg, None, None, total, cams, fmap, mode=1, w_all=w, b_density=bd, density=values.reshape(-1),
+                      precision=dec.precision, **goffs)
+    mesh = _mesh_geometry(grid, values, float(density_threshold), None, cams if in_frustum else None, max_vertices,
+                          max_triangles)
+    n = mesh.vertex_node.shape[0]
+    if want_color:
+        mesh.color = torch.empty(n, 3, **f32)
+    if want_jacobian:
+        mesh.jacobian = torch.empty(n, dec.kernel_action_dim, 3, **f32)
+    if n > 0 and (want_color or want_jacobian):
+        hip.field_forward_at(mesh.vertices, mesh.vertex_node, None if max_vertices is None else mesh.vertex_count, n,
+                             grid.num_nodes, cams, fmap, w_all=w, b_density=bd, b_color=bc,
+                             b_jacobian=bj if want_jacobian else None,
+                             jacobian_kind=dec.JACOBIAN_KIND if want_jacobian else hip.JACOBIAN_NONE, color=mesh.color,
+                             jacobian=mesh.jacobian, view_direction=view_direction, precision=dec.precision,
+                             jacobian_precision=dec.j_precision if want_jacobian else None, **goffs)
+    return mesh

@@ -149,6 +149,13 @@ _SIGNATURES = {
     "njf_field_forward": ([C.POINTER(FieldGrid), _vp, _vp, C.c_int, C.POINTER(C.c_float * 3), C.POINTER(Cameras),
                            C.POINTER(FeatureMap), C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                            C.c_int, _vp], C.c_int),
+    "njf_field_mesh_vertices": ([C.POINTER(FieldGrid), C.POINTER(Cameras), C.c_int, _vp, _vp, C.c_float, C.c_int, _vp, _vp, _vp, _vp,
+                                 _vp, _vp, C.c_int, _vp, _vp, _vp], C.c_int),
+    "njf_field_mesh_triangles": ([C.POINTER(FieldGrid), C.c_int, _vp, C.c_float, C.c_int, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp,
+                                  _vp], C.c_int),
+    "njf_field_forward_at": ([_vp, _vp, _vp, C.c_int, C.c_int, C.POINTER(C.c_float * 3), C.POINTER(Cameras),
+                              C.POINTER(FeatureMap), C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                              C.c_int, _vp], C.c_int),
     "njf_pack_resnetfc_backward": ([C.POINTER(ResnetFcWeights), _vp, C.c_int, _vp], C.c_int),
     "njf_resnetfc_backward": ([_vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp], C.c_int),
     "njf_pack_transformer_backward": ([_vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, _vp], C.c_int),
@@ -661,6 +668,95 @@ def field_forward(grid: FieldGrid, indices, count, capacity: int, cams: Cameras,
             _ptr(b_color) if with_c else None, w_j, _ptr(b_jacobian) if with_j else None, _ptr(density, "density"),
             _ptr(color, "color"), _ptr(jacobian, "jacobian") if with_j else None,
             precision_code(precision, jacobian_precision if with_j else None))
+
+
+# ---- isosurface mesh of a scalar on the grid (include/njf_hip.h: njf_field_mesh_*, njf_field_forward_at) ----------------
+FIELD_MESH_BLOCK = 1024     # NJF_FIELD_MESH_BLOCK: nodes (cells) one workgroup of the meshing launches covers
+FIELD_MESH_COUNT = 1        # NJF_FIELD_MESH_COUNT: the counting launch and the scan
+FIELD_MESH_EMIT = 2         # NJF_FIELD_MESH_EMIT: the emitting launch of a count made before
+
+
+def field_mesh_workspace(total_nodes: int, device) -> torch.Tensor:
+    return torch.empty(max(1, (total_nodes + FIELD_MESH_BLOCK - 1) // FIELD_MESH_BLOCK), dtype=torch.int32, device=device)
+
+
+def _byte_ptr(t: Optional[torch.Tensor], name: str) -> Optional[int]:
+    if t is not None and t.dtype not in (torch.uint8, torch.bool):
+        raise ValueError(f"njf_hip: {name} must be uint8 or bool (got {t.dtype})")
+    return None if t is None else _ptr(t.view(torch.uint8), name, torch.uint8)
+
+
+def field_mesh_vertices(grid: FieldGrid, batch: int, values: torch.Tensor, threshold: float, phase: int, edge_mask: torch.Tensor,
+                        vertex_offset: torch.Tensor, vertex_count: torch.Tensor, workspace: torch.Tensor, valid=None,
+                        cams: Optional[Cameras] = None, vertex_node=None, vertex_edge=None, vertex_t=None, vertices=None) -> None:
+    """njf_field_mesh_vertices: edge masks, per-node vertex offsets, the true vertex count and -- with FIELD_MESH_EMIT -- the
+    rows of the first ``vertex_node.numel()`` vertices.  ``values`` fp32 [B*N]; ``valid`` uint8 / bool [B*N] or None; ``cams``:
+    the frustum predicate of ``field_select`` joins ``valid``."""
+    total = batch * grid.dims[0] * grid.dims[1] * grid.dims[2]
+    for name, t in (("values", values), ("edge_mask", edge_mask), ("vertex_offset", vertex_offset)) + (
+            (("valid", valid),) if valid is not None else ()):
+        if t.numel() != total:
+            raise ValueError(f"njf_hip: field_mesh_vertices {name} must hold batch * nx*ny*nz = {total} elements")
+    if vertex_count.numel() != 1 or workspace.numel() < (total + FIELD_MESH_BLOCK - 1) // FIELD_MESH_BLOCK:
+        raise ValueError("njf_hip: field_mesh_vertices needs one int32 count and a workspace of ceil(B*N / FIELD_MESH_BLOCK)")
+    capacity = 0 if vertex_node is None else vertex_node.numel()
+    if capacity and (vertex_edge.numel() != capacity or vertex_t.numel() != capacity or vertices.numel() != 3 * capacity):
+        raise ValueError("njf_hip: field_mesh_vertices outputs must share one capacity")
+    if cams is not None:
+        _note_device(cams, "cameras")
+    _launch("njf_field_mesh_vertices", load_library().njf_field_mesh_vertices, C.byref(grid),
+            None if cams is None else C.byref(cams), int(batch), _ptr(values, "values"), _byte_ptr(valid, "valid"),
+            float(threshold), int(phase), _byte_ptr(edge_mask, "edge_mask"), _int32_ptr(vertex_offset, "vertex_offset"),
+            _int32_ptr(vertex_node, "vertex_node"), _byte_ptr(vertex_edge, "vertex_edge"), _ptr(vertex_t, "vertex_t"),
+            _ptr(vertices, "vertices"), capacity, _int32_ptr(vertex_count, "vertex_count"), _int32_ptr(workspace, "workspace"))
+
+
+def field_mesh_triangles(grid: FieldGrid, batch: int, values: torch.Tensor, threshold: float, phase: int,
+                         edge_mask: torch.Tensor, vertex_offset: torch.Tensor, triangle_count: torch.Tensor,
+                         workspace: torch.Tensor, triangles=None, triangle_cell=None) -> None:
+    """njf_field_mesh_triangles on the masks and offsets ``field_mesh_vertices`` wrote: the true triangle count and -- with
+    FIELD_MESH_EMIT -- the first ``triangle_cell.numel()`` triangles (vertex ranks) with their global cell index."""
+    total = batch * grid.dims[0] * grid.dims[1] * grid.dims[2]
+    if values.numel() != total or edge_mask.numel() != total or vertex_offset.numel() != total:
+        raise ValueError(f"njf_hip: field_mesh_triangles per-node arrays must hold batch * nx*ny*nz = {total} elements")
+    if triangle_count.numel() != 1 or workspace.numel() < (total + FIELD_MESH_BLOCK - 1) // FIELD_MESH_BLOCK:
+        raise ValueError("njf_hip: field_mesh_triangles needs one int32 count and a workspace of ceil(B*N / FIELD_MESH_BLOCK)")
+    capacity = 0 if triangle_cell is None else triangle_cell.numel()
+    if capacity and triangles.numel() != 3 * capacity:
+        raise ValueError("njf_hip: field_mesh_triangles triangles must be [capacity, 3]")
+    _launch("njf_field_mesh_triangles", load_library().njf_field_mesh_triangles, C.byref(grid), int(batch),
+            _ptr(values, "values"), float(threshold), int(phase), _byte_ptr(edge_mask, "edge_mask"),
+            _int32_ptr(vertex_offset, "vertex_offset"), _int32_ptr(triangles, "triangles"),
+            _int32_ptr(triangle_cell, "triangle_cell"), capacity, _int32_ptr(triangle_count, "triangle_count"),
+            _int32_ptr(workspace, "workspace"))
+
+
+def field_forward_at(xyz: torch.Tensor, node: torch.Tensor, count, capacity: int, nodes_per_batch: int, cams: Cameras,
+                     fmap: FeatureMap, goff_density: int, goff_jacobian: int, w_all, b_density, b_color, b_jacobian=None,
+                     jacobian_kind: int = JACOBIAN_NONE, density=None, color=None, jacobian=None, view_direction=None,
+                     precision: Optional[str] = None, jacobian_precision: Optional[str] = None) -> None:
+    """The decoder at stored positions of a ragged batch (njf_field_forward_at): row i is the point ``xyz[i]`` of batch element
+    ``node[i] // nodes_per_batch``; outputs are [capacity, ...] tensors, rows past the device count are left untouched."""
+    if xyz.numel() < 3 * capacity or node.numel() < capacity:
+        raise ValueError("njf_hip: field_forward_at xyz / node are shorter than the capacity")
+    for name, t, width in (("density", density, 1), ("color", color, 3)):
+        if t is not None and t.numel() < capacity * width:
+            raise ValueError(f"njf_hip: field_forward_at {name} is shorter than the capacity")
+    with_j = jacobian_kind != JACOBIAN_NONE
+    if with_j and (jacobian is None or jacobian.numel() < capacity * 3 * cams.action_dim):
+        raise ValueError("njf_hip: field_forward_at jacobian must be [capacity, 3A]")
+    base = _ptr(w_all, "w_all")
+    w_c = base + 4 * RESNET_W_FLOATS
+    w_j = (w_c + 4 * COLOR_W_FLOATS) if with_j else None
+    direction = None if view_direction is None else C.byref((C.c_float * 3)(*[float(v) for v in view_direction]))
+    _note_device(cams, "cameras")
+    _note_device(fmap, "feature map")
+    _check_map_dtype(fmap, precision, *([precision if jacobian_precision is None else jacobian_precision] if with_j else []))
+    _launch("njf_field_forward_at", load_library().njf_field_forward_at, _ptr(xyz, "xyz"), _int32_ptr(node, "node"),
+            _int32_ptr(count, "count"), int(capacity), int(nodes_per_batch), direction, C.byref(cams), C.byref(fmap),
+            goff_density, goff_jacobian, jacobian_kind, base, _ptr(b_density), w_c, _ptr(b_color), w_j,
+            _ptr(b_jacobian) if with_j else None, _ptr(density, "density"), _ptr(color, "color"),
+            _ptr(jacobian, "jacobian") if with_j else None, precision_code(precision, jacobian_precision if with_j else None))
 
 
 def solve_action(mean_position, jacobian, projection, target_flow, visible_mask, init_action, iterations: int,

@@ -756,6 +756,21 @@ class Model(nn.Module):
                              max_points=max_points)
 
     @torch.no_grad()
+    def extract_mesh(self, camera_input: CameraInput, grid, density_threshold: float, *, in_frustum: bool = True,
+                     want_color: bool = True, want_jacobian: bool = True, view_direction=None,
+                     max_vertices: Optional[int] = None, max_triangles: Optional[int] = None):
+        """The 3-D Jacobian field of the context image(s) as a surface mesh: the isosurface ``density == density_threshold``
+        over ``grid`` (field_volume.FieldGrid) with the colour and the Jacobian [A, 3] at every vertex.  See
+        ``field_volume.extract_mesh``; ``max_vertices`` + ``max_triangles`` select the form without host synchronisation
+        (padded tensors + true counts; capturable in a HIP graph after one eager call)."""
+        from .field_volume import extract_mesh
+        enc = PixelEncoding(features=self._encode_for_render(camera_input.input_image), extrinsics=camera_input.ctxt_extrinsics,
+                            intrinsics=camera_input.ctxt_intrinsics, action=None)
+        return extract_mesh(self, enc, grid, density_threshold, in_frustum=in_frustum, want_color=want_color,
+                            want_jacobian=want_jacobian, view_direction=view_direction, max_vertices=max_vertices,
+                            max_triangles=max_triangles)
+
+    @torch.no_grad()
     def encode_image(self, camera_input: CameraInput, rendering_input: RenderingInput,
                      robot_input: RobotInput) -> ModelInferenceEncoding:
         """model.py:458-495: proposal sampling + per-sample density/Jacobian/weights, cached for inverse dynamics."""
