@@ -440,6 +440,50 @@ int njf_field_forward_at(const float* xyz, const int* node, const int* count, in
                          const float* b_density, const float* w_color, const float* b_color, const float* w_jacobian,
                          const float* b_jacobian, float* density, float* color, float* jacobian, int precision, void* stream);
 
+/* ---- fusion of the fields of several context views (additive within ABI v20): one cloud / mesh per multi-camera scene ---- */
+/* The B context images of a call are G = B / V SCENES of V consecutive VIEWS: calibrated cameras that look at one scene in
+ * one world frame (the convention of views_per_command in the inverse-dynamics solve), batch element b = g*V + v, on one
+ * shared grid.  The per-view global index of node n is (g*V + v)*N + n, the FUSED global index g*N + n; G*V*N must stay below
+ * 2^31.  The semantics are fixed so the result is checkable against a plain restatement:
+ *   s_v(x) = the frustum predicate of njf_field_select for batch element g*V + v at the point x (cams == NULL: 1).
+ *   c = sum_v s_v; a node is VALID iff c >= min_views.
+ *   fused density of a valid node from the per-view values d_v --
+ *     NJF_FIELD_FUSE_MEAN: acc = 0; for v ascending: if (s_v) acc += d_v (fp32 adds); fused = acc / (float)c (IEEE division);
+ *     NJF_FIELD_FUSE_MIN / _MAX: m = d of the first seen view; for every later seen view, ascending: m = (d_v < m) ? d_v : m
+ *     (`>` for _MAX).  _MIN carves: a node is occupied only if every view that sees it says so.
+ *   An invalid node has fused = 0. */
+#define NJF_FIELD_MAX_VIEWS 8
+#define NJF_FIELD_FUSE_MEAN 0
+#define NJF_FIELD_FUSE_MIN 1
+#define NJF_FIELD_FUSE_MAX 2
+/* values: device fp32 [G*V*N] (what the density-only pass of njf_field_forward writes for the identity list).  fused: device
+ * fp32 [G*N]; seen: device bytes [G*N], bit v = s_v (may be NULL); valid: device bytes [G*N], 0 / 1 (may be NULL; the `valid`
+ * argument of njf_field_mesh_vertices on the fused values).  cams: only ctxt_w2c / ctxt_k are read and cams->batch must equal
+ * scenes * views (NJF_E_SHAPE; as for an oversize G*V*N).  NJF_E_VALUE: views outside [1, NJF_FIELD_MAX_VIEWS], min_views
+ * outside [1, views], an unknown mode.  One launch: a workgroup takes NJF_FIELD_SELECT_BLOCK consecutive nodes of one scene,
+ * loads the scene's cameras once and reads every view's values coalesced.  No atomics: the output bytes are a function of the
+ * inputs alone. */
+int njf_field_fuse(const NjfFieldGrid* grid, const NjfCameras* cams, int scenes, int views, const float* values, int mode,
+                   int min_views, float* fused, unsigned char* seen, unsigned char* valid, void* stream);
+
+/* Colour and Jacobian at the positions of a list -- survivor nodes or mesh vertices -- from the decoder's per-view outputs.
+ * Entry i is the point xyz[i] of scene node[i] / nodes_per_scene (node: device int32 FUSED global index, clamped into the
+ * scenes; for a mesh the owning node of the vertex); the entry count min(*count, capacity) is read on the device (count
+ * NULL = capacity).  Per-view rows are ENTRY-MAJOR, row i*views + v: density [capacity*views], color [capacity*views, 3],
+ * jacobian [capacity*views, 3*action_dim] -- what njf_field_forward / njf_field_forward_at write for the expanded list.
+ *   w_v = s_v(x) ? d_v(x) : 0;  W = sum_v w_v (fp32 adds, v ascending);  if (!(W > 0)): every w_v = 1 and W = (float)views
+ *   (no view sees a vertex between two nodes seen by different views, or every density is zero);
+ *   out = acc / W with acc = 0; for v ascending: acc = fmaf(w_v, x_v, acc), per output component.
+ * out_color [capacity, 3] (required with color), out_jacobian [capacity, 3*action_dim] (required with jacobian), out_views:
+ * device bytes [capacity], bit v = s_v(x) (may be NULL).  color and / or jacobian may be NULL; with both NULL density may be
+ * NULL too and out_views alone is written.  cams == NULL: every s_v = 1; else only ctxt_w2c / ctxt_k are read and cams->batch
+ * must be a multiple of views (NJF_E_SHAPE).  NJF_E_VALUE: views outside [1, NJF_FIELD_MAX_VIEWS], nodes_per_scene < 1;
+ * NJF_E_ACTION_DIM: a jacobian with action_dim outside [1, NJF_MAX_ACTION_DIM].  Rows past the entry count are left
+ * untouched.  One launch, no atomics: the output bytes are a function of the inputs alone. */
+int njf_field_combine(const float* xyz, const int* node, const int* count, int capacity, int nodes_per_scene, int views,
+                      const NjfCameras* cams, const float* density, const float* color, const float* jacobian, int action_dim,
+                      float* out_color, float* out_jacobian, unsigned char* out_views, void* stream);
+
 /* ---- stand-alone sampler / compositing ops (API parity with the un-fused reference calls) -- */
 /* RaySamples.get_weights (ray_samplers.py:77-101): deltas, densities [N,S] -> weights [N,S]. */
 int njf_alpha_weights(const float* deltas, const float* densities, int rays, int samples, float* weights, void* stream);

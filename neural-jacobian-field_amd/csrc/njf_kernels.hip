@@ -2197,17 +2197,21 @@ struct SelectArgs {
 };
 
 // the projection of point_geometry + point_footprint (u, v: normalised image coordinates of the feature gather)
+__device__ __forceinline__ bool point_in_view(const CamCtx& cam, float px, float py, float pz) {
+  const float xc = dot4_h(cam.m + 0, px, py, pz), yc = dot4_h(cam.m + 4, px, py, pz), zc = dot4_h(cam.m + 8, px, py, pz);
+  const float u0 = dot3(cam.k + 0, xc, yc, zc), u1 = dot3(cam.k + 3, xc, yc, zc), u2 = dot3(cam.k + 6, xc, yc, zc);
+  const float inv = __builtin_amdgcn_rcpf(u2 + 1e-9f);
+  const float u = u0 * inv, v = u1 * inv;
+  return zc > 0.0f && u >= 0.0f && u <= 1.0f && v >= 0.0f && v <= 1.0f;  // (NaN compares false)
+}
+
 __device__ __forceinline__ bool field_in_view(const SelectArgs& a, int gi) {
   int b;
   float px, py, pz;
   field_node(a.list, gi, b, px, py, pz);
   CamCtx cam;
   load_ctx(a.w2c, a.k, b, cam);
-  const float xc = dot4_h(cam.m + 0, px, py, pz), yc = dot4_h(cam.m + 4, px, py, pz), zc = dot4_h(cam.m + 8, px, py, pz);
-  const float u0 = dot3(cam.k + 0, xc, yc, zc), u1 = dot3(cam.k + 3, xc, yc, zc), u2 = dot3(cam.k + 6, xc, yc, zc);
-  const float inv = __builtin_amdgcn_rcpf(u2 + 1e-9f);
-  const float u = u0 * inv, v = u1 * inv;
-  return zc > 0.0f && u >= 0.0f && u <= 1.0f && v >= 0.0f && v <= 1.0f;  // (NaN compares false)
+  return point_in_view(cam, px, py, pz);
 }
 
 // bit `it` of the result: keep entry block*NJF_FIELD_SELECT_BLOCK + it*NJF_SELECT_THREADS + tid
@@ -2656,6 +2660,175 @@ __global__ void __launch_bounds__(NJF_THREADS, 2) field_at_kernel(FieldAtArgs a)
       }
     }
   }
+}
+
+// ---- fusion of the fields of several context views ------------------------------------------------
+// The B context images are G = B / V scenes of V consecutive views (batch element b = g*V + v) on one grid.  s_v = the frustum
+// predicate of the selection (point_in_view) for view v, all ones without cameras; c = the number of views that see a node.
+#define NJF_FUSE_THREADS 256
+#define NJF_FUSE_ITEMS (NJF_FIELD_SELECT_BLOCK / NJF_FUSE_THREADS)
+#define NJF_FUSE_CAM_FLOATS 21  // rows 0..2 of ctxt_w2c + the 9 intrinsics: a CamCtx
+static_assert(NJF_FUSE_ITEMS * NJF_FUSE_THREADS == NJF_FIELD_SELECT_BLOCK, "fusion block");
+static_assert(sizeof(CamCtx) == NJF_FUSE_CAM_FLOATS * sizeof(float), "CamCtx layout");
+struct FuseArgs {
+  NjfFieldGrid grid;
+  int nodes;              // N
+  int views;              // V
+  int blocks_per_scene;   // ceil(N / NJF_FIELD_SELECT_BLOCK)
+  int min_views;
+  const float* w2c;       // [G*V,4,4] or null (every view sees every node)
+  const float* k;         // [G*V,3,3]
+  const float* values;    // [G*V*N]
+  float* fused;           // [G*N]
+  unsigned char* seen;    // [G*N] or null
+  unsigned char* valid;   // [G*N] or null
+};
+
+// One workgroup per 1024 consecutive nodes of ONE scene (the item / thread layout of the selection kernels: consecutive
+// threads read consecutive floats of every view's values).  The scene's V cameras go to LDS once; views outermost, so a
+// thread takes a camera out of LDS once per view and keeps the running state of its four nodes in registers.  fp32 adds in
+// view order, one IEEE division, no atomics: the result is a function of the inputs alone.
+template <int MODE>
+__global__ void __launch_bounds__(NJF_FUSE_THREADS) field_fuse_kernel(FuseArgs a) {
+  __shared__ float cams[NJF_FIELD_MAX_VIEWS * NJF_FUSE_CAM_FLOATS];
+  const int g = blockIdx.x / a.blocks_per_scene;
+  const int first = (blockIdx.x - g * a.blocks_per_scene) * NJF_FIELD_SELECT_BLOCK;
+  if (a.w2c) {
+    for (int t = threadIdx.x; t < a.views * NJF_FUSE_CAM_FLOATS; t += NJF_FUSE_THREADS) {
+      const int v = t / NJF_FUSE_CAM_FLOATS, e = t - v * NJF_FUSE_CAM_FLOATS;
+      const size_t b = (size_t)g * a.views + v;
+      cams[t] = e < 12 ? a.w2c[b * 16 + e] : a.k[b * 9 + (e - 12)];
+    }
+    __syncthreads();
+  }
+  float px[NJF_FUSE_ITEMS], py[NJF_FUSE_ITEMS], pz[NJF_FUSE_ITEMS], acc[NJF_FUSE_ITEMS];
+  int count[NJF_FUSE_ITEMS];
+  unsigned mask[NJF_FUSE_ITEMS];
+  const int yz = a.grid.dims[1] * a.grid.dims[2];
+#pragma unroll
+  for (int it = 0; it < NJF_FUSE_ITEMS; ++it) {
+    const int n = min(first + it * NJF_FUSE_THREADS + (int)threadIdx.x, a.nodes - 1);  // (the node of field_node)
+    const int ix = n / yz, r = n - ix * yz;
+    const int iy = r / a.grid.dims[2], iz = r - iy * a.grid.dims[2];
+    px[it] = fmaf((float)ix, a.grid.step[0], a.grid.origin[0]);
+    py[it] = fmaf((float)iy, a.grid.step[1], a.grid.origin[1]);
+    pz[it] = fmaf((float)iz, a.grid.step[2], a.grid.origin[2]);
+    acc[it] = 0.0f;
+    count[it] = 0;
+    mask[it] = 0u;
+  }
+  for (int v = 0; v < a.views; ++v) {
+    CamCtx cam;
+    if (a.w2c) {
+#pragma unroll
+      for (int i = 0; i < 12; ++i) cam.m[i] = cams[v * NJF_FUSE_CAM_FLOATS + i];
+#pragma unroll
+      for (int i = 0; i < 9; ++i) cam.k[i] = cams[v * NJF_FUSE_CAM_FLOATS + 12 + i];
+    }
+    const float* __restrict__ row = a.values + ((size_t)g * a.views + v) * (size_t)a.nodes;
+#pragma unroll
+    for (int it = 0; it < NJF_FUSE_ITEMS; ++it) {
+      const int n = first + it * NJF_FUSE_THREADS + (int)threadIdx.x;
+      if (n >= a.nodes) continue;
+      if (a.w2c && !point_in_view(cam, px[it], py[it], pz[it])) continue;
+      const float d = row[n];
+      if (MODE == NJF_FIELD_FUSE_MEAN) acc[it] += d;
+      else if (count[it] == 0) acc[it] = d;
+      else if (MODE == NJF_FIELD_FUSE_MIN) acc[it] = (d < acc[it]) ? d : acc[it];
+      else acc[it] = (d > acc[it]) ? d : acc[it];
+      ++count[it];
+      mask[it] |= 1u << v;
+    }
+  }
+#pragma unroll
+  for (int it = 0; it < NJF_FUSE_ITEMS; ++it) {
+    const int n = first + it * NJF_FUSE_THREADS + (int)threadIdx.x;
+    if (n >= a.nodes) continue;
+    const bool ok = count[it] >= a.min_views;
+    float f = acc[it];
+    if (MODE == NJF_FIELD_FUSE_MEAN) f = f / (float)count[it];
+    const size_t o = (size_t)g * a.nodes + n;
+    a.fused[o] = ok ? f : 0.0f;
+    if (a.seen) a.seen[o] = (unsigned char)mask[it];
+    if (a.valid) a.valid[o] = ok ? 1 : 0;
+  }
+}
+
+// Colour and Jacobian at the positions of a list (survivor nodes or mesh vertices) from the per-view rows of the decoder:
+// w_v = s_v(x) ? d_v(x) : 0, W = the sum of the w_v (fp32 adds, v ascending), every w_v = 1 and W = V if not W > 0,
+// out = (fma chain over v) / W.  Per-view rows are entry-major: row i*V + v.
+#define NJF_COMBINE_THREADS 256
+struct CombineArgs {
+  const float* xyz;        // [capacity, 3]
+  const int* node;         // [capacity] fused global index: the scene of entry i is node[i] / nodes
+  const int* count;        // or null
+  int capacity;
+  int nodes, scenes;       // N, G (scenes: only with cameras)
+  int views;
+  const float* w2c;        // [G*V,4,4] or null
+  const float* k;
+  const float* density;    // [capacity*V] (null: nothing to weigh, `views` alone is written)
+  const float* color;      // [capacity*V, 3] or null
+  const float* jacobian;   // [capacity*V, 3A] or null
+  int jdim;                // 3A
+  float* out_color;        // [capacity, 3]
+  float* out_jacobian;     // [capacity, 3A]
+  unsigned char* out_views;  // [capacity] or null
+};
+
+// out[i, c] for the workgroup's entries: consecutive threads take consecutive floats of the output (and of every view's
+// input row, which is contiguous per entry)
+__device__ __forceinline__ void combine_rows(const float* __restrict__ in, float* __restrict__ out, int dim, int first, int rows,
+                                             int views, const float (*w)[NJF_COMBINE_THREADS], const float* wsum) {
+  for (int e = threadIdx.x; e < rows * dim; e += NJF_COMBINE_THREADS) {
+    const int il = e / dim, c = e - il * dim;
+    const size_t i = (size_t)first + il;
+    float acc = 0.0f;
+    for (int v = 0; v < views; ++v) acc = fmaf(w[v][il], in[(i * views + v) * dim + c], acc);
+    out[i * dim + c] = acc / wsum[il];
+  }
+}
+
+__global__ void __launch_bounds__(NJF_COMBINE_THREADS) field_combine_kernel(CombineArgs a) {
+  __shared__ float w[NJF_FIELD_MAX_VIEWS][NJF_COMBINE_THREADS];
+  __shared__ float wsum[NJF_COMBINE_THREADS];
+  const int entries = a.count ? min(max(*a.count, 0), a.capacity) : a.capacity;
+  const int first = blockIdx.x * NJF_COMBINE_THREADS;
+  if (first >= entries) return;  // the whole workgroup, before any barrier
+  const int rows = min(NJF_COMBINE_THREADS, entries - first);
+  const int il = threadIdx.x;
+  if (il < rows) {
+    const size_t i = (size_t)first + il;
+    unsigned mask = (1u << a.views) - 1u;
+    if (a.w2c) {
+      const int g = min(max(a.node[i], 0) / a.nodes, a.scenes - 1);  // (caller data: clamped into the scenes)
+      const float px = a.xyz[3 * i], py = a.xyz[3 * i + 1], pz = a.xyz[3 * i + 2];
+      mask = 0u;
+      for (int v = 0; v < a.views; ++v) {
+        CamCtx cam;
+        load_ctx(a.w2c, a.k, g * a.views + v, cam);
+        mask |= point_in_view(cam, px, py, pz) ? 1u << v : 0u;
+      }
+    }
+    if (a.out_views) a.out_views[i] = (unsigned char)mask;
+    if (a.density) {
+      float total = 0.0f;
+      for (int v = 0; v < a.views; ++v) {
+        const float wv = ((mask >> v) & 1u) ? a.density[i * a.views + v] : 0.0f;
+        w[v][il] = wv;
+        total += wv;
+      }
+      if (!(total > 0.0f)) {  // no view sees the position, or every density is zero (or NaN): the plain mean
+        for (int v = 0; v < a.views; ++v) w[v][il] = 1.0f;
+        total = (float)a.views;
+      }
+      wsum[il] = total;
+    }
+  }
+  if (!a.density) return;
+  __syncthreads();
+  if (a.color) combine_rows(a.color, a.out_color, 3, first, rows, a.views, w, wsum);
+  if (a.jacobian) combine_rows(a.jacobian, a.out_jacobian, a.jdim, first, rows, a.views, w, wsum);
 }
 
 // =============================================================================================
@@ -4458,6 +4631,77 @@ extern "C" int njf_field_forward_at(const float* xyz, const int* node, const int
     if (jacobian_kind == NJF_JACOBIAN_MLP) return launch_fused(field_at_kernel<3, NJF_P, NJF_PJ>, a, tiles, s);
     return launch_fused(field_at_kernel<4, NJF_P, NJF_PJ>, a, tiles, s);
   });
+}
+
+// ---- fusion of several context views ----------------------------------------------------------------------------------
+extern "C" int njf_field_fuse(const NjfFieldGrid* grid, const NjfCameras* cams, int scenes, int views, const float* values,
+                              int mode, int min_views, float* fused, unsigned char* seen, unsigned char* valid, void* stream) {
+  if (!grid || !values || !fused) return NJF_E_NULL;
+  if (views < 1 || views > NJF_FIELD_MAX_VIEWS) return NJF_E_VALUE;
+  if (min_views < 1 || min_views > views) return NJF_E_VALUE;
+  if (mode != NJF_FIELD_FUSE_MEAN && mode != NJF_FIELD_FUSE_MIN && mode != NJF_FIELD_FUSE_MAX) return NJF_E_VALUE;
+  if (scenes < 1 || scenes > 0x7fffffff / views) return NJF_E_SHAPE;
+  FieldList l;
+  int rc = make_field_list(grid, scenes * views, nullptr, nullptr, 0, l);  // G*V*N < 2^31
+  if (rc) return rc;
+  if (cams && (!cams->ctxt_w2c || !cams->ctxt_k)) return NJF_E_NULL;
+  if (cams && cams->batch != scenes * views) return NJF_E_SHAPE;
+  FuseArgs a;
+  a.grid = *grid;
+  a.nodes = l.nodes;
+  a.views = views;
+  a.blocks_per_scene = (l.nodes + NJF_FIELD_SELECT_BLOCK - 1) / NJF_FIELD_SELECT_BLOCK;
+  a.min_views = min_views;
+  a.w2c = cams ? cams->ctxt_w2c : nullptr;
+  a.k = cams ? cams->ctxt_k : nullptr;
+  a.values = values;
+  a.fused = fused;
+  a.seen = seen;
+  a.valid = valid;
+  const int blocks = scenes * a.blocks_per_scene;  // <= G*N
+  hipStream_t s = (hipStream_t)stream;
+  if (mode == NJF_FIELD_FUSE_MEAN) field_fuse_kernel<NJF_FIELD_FUSE_MEAN><<<blocks, NJF_FUSE_THREADS, 0, s>>>(a);
+  else if (mode == NJF_FIELD_FUSE_MIN) field_fuse_kernel<NJF_FIELD_FUSE_MIN><<<blocks, NJF_FUSE_THREADS, 0, s>>>(a);
+  else field_fuse_kernel<NJF_FIELD_FUSE_MAX><<<blocks, NJF_FUSE_THREADS, 0, s>>>(a);
+  return launch_status();
+}
+
+extern "C" int njf_field_combine(const float* xyz, const int* node, const int* count, int capacity, int nodes_per_scene,
+                                 int views, const NjfCameras* cams, const float* density, const float* color,
+                                 const float* jacobian, int action_dim, float* out_color, float* out_jacobian,
+                                 unsigned char* out_views, void* stream) {
+  if (views < 1 || views > NJF_FIELD_MAX_VIEWS || nodes_per_scene < 1) return NJF_E_VALUE;
+  if (capacity < 0) return NJF_E_SHAPE;
+  if ((color || jacobian) && !density) return NJF_E_NULL;
+  if ((color && !out_color) || (jacobian && !out_jacobian)) return NJF_E_NULL;
+  if (!color && !jacobian && !out_views) return NJF_E_NULL;  // (nothing to write)
+  if (jacobian && (action_dim < 1 || action_dim > NJF_MAX_ACTION_DIM)) return NJF_E_ACTION_DIM;
+  if (cams) {
+    if (!cams->ctxt_w2c || !cams->ctxt_k || !xyz || !node) return NJF_E_NULL;
+    if (cams->batch < views || cams->batch % views != 0) return NJF_E_SHAPE;
+    if ((long long)(cams->batch / views) * nodes_per_scene > 0x7fffffffLL) return NJF_E_SHAPE;
+  }
+  CombineArgs a;
+  a.xyz = xyz;
+  a.node = node;
+  a.count = count;
+  a.capacity = capacity;
+  a.nodes = nodes_per_scene;
+  a.scenes = cams ? cams->batch / views : 1;
+  a.views = views;
+  a.w2c = cams ? cams->ctxt_w2c : nullptr;
+  a.k = cams ? cams->ctxt_k : nullptr;
+  a.density = (color || jacobian) ? density : nullptr;
+  a.color = color;
+  a.jacobian = jacobian;
+  a.jdim = 3 * action_dim;
+  a.out_color = out_color;
+  a.out_jacobian = out_jacobian;
+  a.out_views = out_views;
+  if (capacity == 0) return NJF_OK;
+  const int blocks = (int)(((long long)capacity + NJF_COMBINE_THREADS - 1) / NJF_COMBINE_THREADS);
+  field_combine_kernel<<<blocks, NJF_COMBINE_THREADS, 0, (hipStream_t)stream>>>(a);
+  return launch_status();
 }
 
 extern "C" int njf_resnetfc_backward(const float* d_out, int d_out_dim, const float* activations, const float* w_backward,

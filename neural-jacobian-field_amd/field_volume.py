@@ -141,6 +141,7 @@ class FieldPointCloud:
     count: torch.Tensor                 # [1] int32
     stage_counts: Tuple[torch.Tensor, ...] = ()   # survivors after each enabled selection stage, in pipeline order
     stage_names: Tuple[str, ...] = ()
+    views: Optional[torch.Tensor] = None          # [n] uint8, fused extraction only: bit v = view v of the scene sees the node
 
     @property
     def batch_index(self) -> torch.Tensor:
@@ -191,7 +192,8 @@ class _Stage:
 def extract_field(model, pixel_encoding: PixelEncoding, grid: FieldGrid, density_threshold: float, *,
                   cull: Optional[float] = None, proposal_level: int = -1, in_frustum: bool = True,
                   view_direction: Optional[Sequence[float]] = None, want_color: bool = True, want_jacobian: bool = True,
-                  max_points: Optional[int] = None) -> FieldPointCloud:
+                  max_points: Optional[int] = None, views_per_scene: int = 1, fuse: str = "mean",
+                  min_views: int = 1) -> FieldPointCloud:
     """Every node of ``grid`` -- per context image of ``pixel_encoding`` -- that
 
     1. (``in_frustum``) projects inside the context image with positive camera depth,
@@ -201,10 +203,18 @@ def extract_field(model, pixel_encoding: PixelEncoding, grid: FieldGrid, density
     with its density, colour (view direction (0, 0, 1) as ``compute_density`` uses, or ``view_direction``) and Jacobian
     ``[A, 3]``, in ascending global index.  ``max_points=None``: exactly sized tensors, one host read of a device count per
     selection stage.  ``max_points=M``: no host synchronisation (safe inside ``torch.cuda.graph``), tensors padded to M rows
-    and ``count`` = the true number of survivors (the rows stored are the first M of them)."""
+    and ``count`` = the true number of survivors (the rows stored are the first M of them).
+
+    ``views_per_scene=V > 1``: the context images are B / V scenes of V consecutive calibrated views in one world frame, and
+    ONE cloud per scene comes back (``_extract_field_fused``): ``index`` is the fused global index
+    ``g*N + n``, ``density`` the ``fuse`` ("mean", "min", "max") of the views that see the node, colour and Jacobian the
+    density-weighted mean over those views, ``views`` their bitmask.  A node needs ``min_views`` views that see it."""
     dec = model.decoder
     if not isinstance(dec, ActionDecoderJacobian):
         raise TypeError("extract_field needs one of the fused action decoders")
+    _check_fusion_arguments("extract_field", pixel_encoding.extrinsics.shape[0], views_per_scene, fuse, min_views)
+    if views_per_scene > 1 and cull is not None:
+        raise ValueError("extract_field: cull with views_per_scene > 1 has no single meaning (a proposal cull is per view)")
     is_flow = isinstance(dec, ActionDecoderFlowMlp)
     if want_jacobian and is_flow:
         raise NotImplementedError("flow_mlp predicts the scene flow directly; it has no Jacobian")
@@ -229,6 +239,9 @@ def extract_field(model, pixel_encoding: PixelEncoding, grid: FieldGrid, density
     i32 = dict(dtype=torch.int32, device=dev)
     f32 = dict(dtype=torch.float32, device=dev)
     cams = _cameras(pixel_encoding, False, action_dim=dec.kernel_action_dim if want_jacobian else None)
+    if views_per_scene > 1:
+        return _extract_field_fused(model, pixel_encoding, grid, float(density_threshold), cams, in_frustum, view_direction,
+                                    want_color, want_jacobian, max_points, views_per_scene, fuse, min_views)
     stage = _Stage(total)
     counts, names = [], []
 
@@ -295,6 +308,139 @@ def extract_field(model, pixel_encoding: PixelEncoding, grid: FieldGrid, density
     return cloud
 
 
+# ---- one field per multi-camera scene -------------------------------------------------------------------
+def _check_fusion_arguments(name: str, batch: int, views_per_scene, mode, min_views) -> None:
+    if isinstance(views_per_scene, bool) or not isinstance(views_per_scene, int) or views_per_scene < 1:
+        raise ValueError(f"{name}: views_per_scene must be an integer >= 1 (got {views_per_scene!r})")
+    if views_per_scene > hip.FIELD_MAX_VIEWS:
+        raise ValueError(f"{name}: at most {hip.FIELD_MAX_VIEWS} views per scene (got {views_per_scene})")
+    if batch % views_per_scene != 0:
+        raise ValueError(f"{name}: views_per_scene = {views_per_scene} does not divide the batch of {batch} context images")
+    if mode not in hip.FIELD_FUSE_MODES:
+        raise ValueError(f"{name}: fuse must be one of {sorted(hip.FIELD_FUSE_MODES)} (got {mode!r})")
+    if isinstance(min_views, bool) or not isinstance(min_views, int) or not 1 <= min_views <= views_per_scene:
+        raise ValueError(f"{name}: min_views must be an integer in [1, views_per_scene = {views_per_scene}] (got {min_views!r})")
+
+
+def _fuse(grid: FieldGrid, values: torch.Tensor, cams, views: int, mode: str, min_views: int):
+    """values [B, N] -> (fused [G, N] fp32, seen [G, N] uint8, valid [G, N] bool): one launch."""
+    scenes, dev = values.shape[0] // views, values.device
+    fused = torch.empty(scenes, grid.num_nodes, dtype=torch.float32, device=dev)
+    seen = torch.empty(scenes, grid.num_nodes, dtype=torch.uint8, device=dev)
+    valid = torch.empty(scenes, grid.num_nodes, dtype=torch.bool, device=dev)
+    hip.field_fuse(grid.c_grid(), scenes, views, values.reshape(-1), hip.FIELD_FUSE_MODES[mode], min_views, fused, seen, valid,
+                   cams=cams)
+    return fused, seen, valid
+
+
+def fuse_views(grid: FieldGrid, values: torch.Tensor, pixel_encoding: Optional[PixelEncoding] = None, *, views_per_scene: int,
+               mode: str = "mean", min_views: int = 1):
+    """Fuse any per-view scalar on the grid, without the networks: ``values`` ``[B, N]`` fp32 on the GPU, the B batch elements
+    being B / V scenes of V = ``views_per_scene`` consecutive views.  Returns ``(fused [G, N] fp32, seen [G, N] uint8, valid
+    [G, N] bool)``: bit v of ``seen`` says that view v of the scene holds the node in its frustum (the predicate of the
+    selection on the cameras of ``pixel_encoding``; every view sees every node without one), a node is ``valid`` when at least
+    ``min_views`` views see it, and ``fused`` is the ``mode`` ("mean", "min" -- carving --, "max") of the values of the views
+    that see a valid node, 0 at an invalid one.  ``mesh_from_values(grid, fused, threshold, valid=valid)`` meshes the result."""
+    if not torch.is_tensor(values) or values.dim() != 2 or values.dtype != torch.float32 or values.shape[1] != grid.num_nodes:
+        raise ValueError(f"fuse_views: values must be fp32 [B, {grid.num_nodes}]")
+    _check_fusion_arguments("fuse_views", values.shape[0], views_per_scene, mode, min_views)
+    if values.shape[0] < 1 or values.shape[0] * grid.num_nodes >= 2 ** 31:
+        raise ValueError("fuse_views: batch * nx*ny*nz must stay below 2**31")
+    if pixel_encoding is not None and pixel_encoding.extrinsics.shape[0] != values.shape[0]:
+        raise ValueError(f"fuse_views: {pixel_encoding.extrinsics.shape[0]} cameras for {values.shape[0]} rows of values")
+    if values.device.type != "cuda":
+        raise ValueError("fuse_views: values must live on the GPU; there is no CPU path")
+    cams = None if pixel_encoding is None else _cameras(pixel_encoding, False, action_dim=None)
+    return _fuse(grid, values.contiguous(), cams, views_per_scene, mode, min_views)
+
+
+def _decoder_arguments(model, feats):
+    """(feature map, density / Jacobian offsets into it, packed weights and biases) of the decoder on ``feats``."""
+    dec = model.decoder
+    w, bd, bc, bj = dec.packed()
+    if isinstance(dec, ActionDecoderFlowMlp):
+        gmap, base = ActionDecoderJacobian.hoisted_map(dec, feats), 0
+    else:
+        gmap, base = _map_of(dec, feats)
+    goffs = dict(goff_density=base + dec.GOFF_DENSITY, goff_jacobian=base + dec.GOFF_JACOBIAN)
+    return hip.make_feature_map(gmap), goffs, w, bd, bc, bj
+
+
+def _per_view(node: torch.Tensor, count: Optional[torch.Tensor], nodes: int, views: int):
+    """Fused global indices ``g*N + n`` [n] -> the per-view global indices ``(g*V + v)*N + n`` [n*V], entry-major (row
+    ``i*V + v``), and the device count times V.  Integer index arithmetic; rows past the count hold whatever the list held
+    (the kernels clamp indices and never read past the count)."""
+    g = torch.div(node, nodes, rounding_mode="floor")
+    base = node + g * ((views - 1) * nodes)                                     # (g*V)*N + n
+    step = torch.arange(views, dtype=torch.int32, device=node.device) * nodes
+    return (base[:, None] + step[None, :]).reshape(-1), None if count is None else count * views
+
+
+def _combine(dec, xyz, node, count, n, nodes, views, cams, rows, want_color, want_jacobian):
+    """The combine launch on the per-view ``rows`` = (density, color, jacobian) -> (color, jacobian, views) of the n entries."""
+    dev = xyz.device
+    f32 = dict(dtype=torch.float32, device=dev)
+    a_dim = dec.kernel_action_dim
+    color = torch.empty(n, 3, **f32) if want_color else None
+    jacobian = torch.empty(n, a_dim, 3, **f32) if want_jacobian else None
+    seen = torch.empty(n, dtype=torch.uint8, device=dev)
+    if n > 0:
+        hip.field_combine(xyz, node, count, n, nodes, views, cams, rows[0], color=rows[1], jacobian=rows[2],
+                          action_dim=a_dim if want_jacobian else 0, out_color=color, out_jacobian=jacobian, out_views=seen)
+    return color, jacobian, seen
+
+
+def _per_view_rows(dec, n, views, want_color, want_jacobian, dev):
+    f32 = dict(dtype=torch.float32, device=dev)
+    if not (want_color or want_jacobian):
+        return None, None, None
+    return (torch.empty(n * views, **f32), torch.empty(n * views, 3, **f32) if want_color else None,
+            torch.empty(n * views, 3 * dec.kernel_action_dim, **f32) if want_jacobian else None)
+
+
+def _extract_field_fused(model, enc, grid, threshold, cams, in_frustum, view_direction, want_color, want_jacobian, max_points,
+                         views, mode, min_views) -> FieldPointCloud:
+    """extract_field for scenes of ``views`` views: dense per-view density pass, fuse, ordered selection on the fused values,
+    coordinates, the decoder on the survivors of every view, combine.  One host read (the survivor count) without
+    ``max_points``, none with it."""
+    dec = model.decoder
+    dev = enc.features.device
+    b, nodes = enc.extrinsics.shape[0], grid.num_nodes
+    scenes = b // views
+    cg = grid.c_grid()
+    i32 = dict(dtype=torch.int32, device=dev)
+    f32 = dict(dtype=torch.float32, device=dev)
+    fmap, goffs, w, bd, bc, bj = _decoder_arguments(model, enc.features)
+    common = dict(mode=1, w_all=w, b_density=bd, precision=dec.precision, **goffs)
+    values = torch.empty(b, nodes, **f32)
+    hip.field_forward(cg, None, None, b * nodes, cams, fmap, density=values.reshape(-1), **common)
+    fused, _, valid = _fuse(grid, values, cams if in_frustum else None, views, mode, min_views)
+    del values
+    # an invalid node (fused = 0) must not pass a threshold <= 0: -inf in its place, in the buffer nothing else reads
+    fused.masked_fill_(~valid, -math.inf)
+    capacity = scenes * nodes if max_points is None else max_points
+    index, count = torch.empty(max(capacity, 1), **i32), torch.empty(1, **i32)
+    hip.field_select(cg, scenes, scenes * nodes, index, count, values=fused.reshape(-1), threshold=threshold)
+    n, dev_count = (int(count.item()), None) if max_points is None else (capacity, count)
+    index = index[:n]
+    # (padded rows of a capacity form hold no index: clamped, so the gather stays inside the buffer)
+    at = index.long() if dev_count is None else index.clamp(0, scenes * nodes - 1).long()
+    cloud = FieldPointCloud(grid=grid, index=index, xyz=torch.empty(n, 3, **f32), density=fused.reshape(-1)[at], color=None,
+                            jacobian=None, count=count, stage_counts=(count,), stage_names=("density",))
+    if n > 0:
+        hip.field_points(cg, scenes, index, dev_count, n, cloud.xyz)
+    rows = _per_view_rows(dec, n, views, want_color, want_jacobian, dev)
+    if n > 0 and rows[0] is not None:
+        expanded, expanded_count = _per_view(index, dev_count, nodes, views)
+        hip.field_forward(cg, expanded, expanded_count, n * views, cams, fmap, b_color=bc, b_jacobian=bj if want_jacobian else None,
+                          jacobian_kind=dec.JACOBIAN_KIND if want_jacobian else hip.JACOBIAN_NONE, density=rows[0], color=rows[1],
+                          jacobian=rows[2], view_direction=view_direction,
+                          jacobian_precision=dec.j_precision if want_jacobian else None, **common)
+    cloud.color, cloud.jacobian, cloud.views = _combine(dec, cloud.xyz, index, dev_count, n, nodes, views,
+                                                        cams if in_frustum else None, rows, want_color, want_jacobian)
+    return cloud
+
+
 # ---- isosurface meshes ------------------------------------------------------------------------------------------------------
 @dataclass
 class FieldMesh:
@@ -317,6 +463,7 @@ class FieldMesh:
     jacobian: Optional[torch.Tensor]      # [V, A, 3]
     vertex_count: torch.Tensor            # [1] int32
     triangle_count: torch.Tensor          # [1] int32
+    vertex_views: Optional[torch.Tensor] = None   # [V] uint8, fused extraction only: bit v = view v sees the vertex position
 
     @property
     def batch_index(self) -> torch.Tensor:
@@ -442,14 +589,21 @@ def mesh_from_values(grid: FieldGrid, values: torch.Tensor, threshold: float, *,
 @torch.no_grad()
 def extract_mesh(model, pixel_encoding: PixelEncoding, grid: FieldGrid, density_threshold: float, *, in_frustum: bool = True,
                  want_color: bool = True, want_jacobian: bool = True, view_direction: Optional[Sequence[float]] = None,
-                 max_vertices: Optional[int] = None, max_triangles: Optional[int] = None) -> FieldMesh:
+                 max_vertices: Optional[int] = None, max_triangles: Optional[int] = None, views_per_scene: int = 1,
+                 fuse: str = "mean", min_views: int = 1) -> FieldMesh:
     """The surface ``decoder_density == density_threshold`` of the context image(s) over ``grid``, with the colour head's
     output and the Jacobian ``[A, 3]`` AT every vertex (what ``njf_points_forward`` returns for that position and batch
     element).  ``in_frustum``: nodes outside the context view are invalid -- the surface ends where the view ends.  The
-    density network runs on all ``B*N`` nodes, ``mesh_from_values`` on the result, one ragged launch on the vertices."""
+    density network runs on all ``B*N`` nodes, ``mesh_from_values`` on the result, one ragged launch on the vertices.
+
+    ``views_per_scene=V > 1``: ONE mesh per scene of V consecutive views -- the surface of the ``fuse``d
+    density with the nodes that fewer than ``min_views`` views see (``in_frustum``) invalid; ``vertex_node``, the cells and
+    ``batch_index`` are in scene space; colour and Jacobian are the density-weighted mean over the views that see the vertex,
+    ``vertex_views`` their bitmask."""
     dec = model.decoder
     if not isinstance(dec, ActionDecoderJacobian):
         raise TypeError("extract_mesh needs one of the fused action decoders")
+    _check_fusion_arguments("extract_mesh", pixel_encoding.extrinsics.shape[0], views_per_scene, fuse, min_views)
     is_flow = isinstance(dec, ActionDecoderFlowMlp)
     if want_jacobian and is_flow:
         raise NotImplementedError("flow_mlp predicts the scene flow directly; it has no Jacobian")
@@ -465,6 +619,9 @@ def extract_mesh(model, pixel_encoding: PixelEncoding, grid: FieldGrid, density_
         model.reset_image_cache()      # a capture must contain the projection (see extract_field)
     f32 = dict(dtype=torch.float32, device=dev)
     cams = _cameras(pixel_encoding, False, action_dim=dec.kernel_action_dim if want_jacobian else None)
+    if views_per_scene > 1:
+        return _extract_mesh_fused(model, pixel_encoding, grid, float(density_threshold), cams, in_frustum, view_direction,
+                                   want_color, want_jacobian, max_vertices, max_triangles, views_per_scene, fuse, min_views)
     w, bd, bc, bj = dec.packed()
     if is_flow:
         gmap, base = ActionDecoderJacobian.hoisted_map(dec, feats), 0
@@ -489,4 +646,35 @@ def extract_mesh(model, pixel_encoding: PixelEncoding, grid: FieldGrid, density_
                              jacobian_kind=dec.JACOBIAN_KIND if want_jacobian else hip.JACOBIAN_NONE, color=mesh.color,
                              jacobian=mesh.jacobian, view_direction=view_direction, precision=dec.precision,
                              jacobian_precision=dec.j_precision if want_jacobian else None, **goffs)
+    return mesh
+
+
+def _extract_mesh_fused(model, enc, grid, threshold, cams, in_frustum, view_direction, want_color, want_jacobian, max_vertices,
+                        max_triangles, views, mode, min_views) -> FieldMesh:
+    """extract_mesh for scenes of ``views`` views: dense per-view density pass, fuse, the six meshing launches on the fused
+    values with ``valid``, the decoder at every vertex for every view, combine."""
+    dec = model.decoder
+    dev = enc.features.device
+    b, nodes = enc.extrinsics.shape[0], grid.num_nodes
+    f32 = dict(dtype=torch.float32, device=dev)
+    fmap, goffs, w, bd, bc, bj = _decoder_arguments(model, enc.features)
+    values = torch.empty(b, nodes, **f32)
+    hip.field_forward(grid.c_grid(), None, None, b * nodes, cams, fmap, mode=1, w_all=w, b_density=bd, density=values.reshape(-1),
+                      precision=dec.precision, **goffs)
+    fused, _, valid = _fuse(grid, values, cams if in_frustum else None, views, mode, min_views)
+    del values
+    mesh = _mesh_geometry(grid, fused, threshold, valid, None, max_vertices, max_triangles)
+    n = mesh.vertex_node.shape[0]
+    dev_count = None if max_vertices is None else mesh.vertex_count
+    rows = _per_view_rows(dec, n, views, want_color, want_jacobian, dev)
+    if n > 0 and rows[0] is not None:
+        expanded, expanded_count = _per_view(mesh.vertex_node, dev_count, nodes, views)
+        xyz = mesh.vertices[:, None, :].expand(n, views, 3).reshape(n * views, 3)
+        hip.field_forward_at(xyz, expanded, expanded_count, n * views, nodes, cams, fmap, w_all=w, b_density=bd, b_color=bc,
+                             b_jacobian=bj if want_jacobian else None,
+                             jacobian_kind=dec.JACOBIAN_KIND if want_jacobian else hip.JACOBIAN_NONE, density=rows[0],
+                             color=rows[1], jacobian=rows[2], view_direction=view_direction, precision=dec.precision,
+                             jacobian_precision=dec.j_precision if want_jacobian else None, **goffs)
+    mesh.color, mesh.jacobian, mesh.vertex_views = _combine(dec, mesh.vertices, mesh.vertex_node, dev_count, n, nodes, views,
+                                                            cams if in_frustum else None, rows, want_color, want_jacobian)
     return mesh

@@ -156,6 +156,10 @@ _SIGNATURES = {
     "njf_field_forward_at": ([_vp, _vp, _vp, C.c_int, C.c_int, C.POINTER(C.c_float * 3), C.POINTER(Cameras),
                               C.POINTER(FeatureMap), C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                               C.c_int, _vp], C.c_int),
+    "njf_field_fuse": ([C.POINTER(FieldGrid), C.POINTER(Cameras), C.c_int, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp],
+                       C.c_int),
+    "njf_field_combine": ([_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.POINTER(Cameras), _vp, _vp, _vp, C.c_int, _vp, _vp, _vp,
+                           _vp], C.c_int),
     "njf_pack_resnetfc_backward": ([C.POINTER(ResnetFcWeights), _vp, C.c_int, _vp], C.c_int),
     "njf_resnetfc_backward": ([_vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp], C.c_int),
     "njf_pack_transformer_backward": ([_vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, _vp], C.c_int),
@@ -757,6 +761,53 @@ def field_forward_at(xyz: torch.Tensor, node: torch.Tensor, count, capacity: int
             goff_density, goff_jacobian, jacobian_kind, base, _ptr(b_density), w_c, _ptr(b_color), w_j,
             _ptr(b_jacobian) if with_j else None, _ptr(density, "density"), _ptr(color, "color"),
             _ptr(jacobian, "jacobian") if with_j else None, precision_code(precision, jacobian_precision if with_j else None))
+
+
+# ---- fusion of several context views (include/njf_hip.h: njf_field_fuse, njf_field_combine) ----------------------------
+FIELD_MAX_VIEWS = 8         # NJF_FIELD_MAX_VIEWS: views per scene
+FIELD_FUSE_MEAN = 0         # NJF_FIELD_FUSE_MEAN: mean of the views that see the node
+FIELD_FUSE_MIN = 1          # NJF_FIELD_FUSE_MIN: carving -- occupied only if every view that sees the node says so
+FIELD_FUSE_MAX = 2          # NJF_FIELD_FUSE_MAX
+FIELD_FUSE_MODES = {"mean": FIELD_FUSE_MEAN, "min": FIELD_FUSE_MIN, "max": FIELD_FUSE_MAX}
+
+
+def field_fuse(grid: FieldGrid, scenes: int, views: int, values: torch.Tensor, mode: int, min_views: int, fused: torch.Tensor,
+               seen=None, valid=None, cams: Optional[Cameras] = None) -> None:
+    """njf_field_fuse: per-view ``values`` fp32 [G*V*N] -> ``fused`` fp32 [G*N], ``seen`` (uint8 bitmask of the views whose
+    frustum holds the node) and ``valid`` (uint8 / bool: at least ``min_views`` of them) [G*N]; ``cams`` None: every view sees
+    every node."""
+    nodes = grid.dims[0] * grid.dims[1] * grid.dims[2]
+    if values.numel() != scenes * views * nodes:
+        raise ValueError(f"njf_hip: field_fuse values must hold scenes * views * nx*ny*nz = {scenes * views * nodes} elements")
+    for name, t in (("fused", fused), ("seen", seen), ("valid", valid)):
+        if t is not None and t.numel() != scenes * nodes:
+            raise ValueError(f"njf_hip: field_fuse {name} must hold scenes * nx*ny*nz = {scenes * nodes} elements")
+    if cams is not None:
+        _note_device(cams, "cameras")
+    _launch("njf_field_fuse", load_library().njf_field_fuse, C.byref(grid), None if cams is None else C.byref(cams), int(scenes),
+            int(views), _ptr(values, "values"), int(mode), int(min_views), _ptr(fused, "fused"), _byte_ptr(seen, "seen"),
+            _byte_ptr(valid, "valid"))
+
+
+def field_combine(xyz: torch.Tensor, node: torch.Tensor, count, capacity: int, nodes_per_scene: int, views: int,
+                  cams: Optional[Cameras], density, color=None, jacobian=None, action_dim: int = 0, out_color=None,
+                  out_jacobian=None, out_views=None) -> None:
+    """njf_field_combine: the density-weighted combination of the per-view rows (entry-major, row ``i*views + v``) at the
+    positions ``xyz`` [capacity, 3] of the scenes ``node // nodes_per_scene`` -> ``out_color`` [capacity, 3], ``out_jacobian``
+    [capacity, 3A] and ``out_views`` (uint8 [capacity]: the views whose frustum holds the position; all of them without
+    ``cams``).  Rows past the device count are left untouched."""
+    if xyz.numel() < 3 * capacity or node.numel() < capacity:
+        raise ValueError("njf_hip: field_combine xyz / node are shorter than the capacity")
+    for name, t, width in (("density", density, views), ("color", color, 3 * views), ("jacobian", jacobian, 3 * action_dim * views),
+                           ("out_color", out_color, 3), ("out_jacobian", out_jacobian, 3 * action_dim), ("out_views", out_views, 1)):
+        if t is not None and t.numel() < capacity * width:
+            raise ValueError(f"njf_hip: field_combine {name} is shorter than the capacity")
+    if cams is not None:
+        _note_device(cams, "cameras")
+    _launch("njf_field_combine", load_library().njf_field_combine, _ptr(xyz, "xyz"), _int32_ptr(node, "node"),
+            _int32_ptr(count, "count"), int(capacity), int(nodes_per_scene), int(views), None if cams is None else C.byref(cams),
+            _ptr(density, "density"), _ptr(color, "color"), _ptr(jacobian, "jacobian"), int(action_dim), _ptr(out_color, "out_color"),
+            _ptr(out_jacobian, "out_jacobian"), _byte_ptr(out_views, "out_views"))
 
 
 def solve_action(mean_position, jacobian, projection, target_flow, visible_mask, init_action, iterations: int,

@@ -741,34 +741,39 @@ class Model(nn.Module):
     @torch.no_grad()
     def extract_field(self, camera_input: CameraInput, grid, density_threshold: float, *, cull: Optional[float] = None,
                       proposal_level: int = -1, in_frustum: bool = True, view_direction=None, want_color: bool = True,
-                      want_jacobian: bool = True, max_points: Optional[int] = None):
+                      want_jacobian: bool = True, max_points: Optional[int] = None, views_per_scene: int = 1,
+                      fuse: str = "mean", min_views: int = 1):
         """The 3-D Jacobian field of the context image(s) as a point cloud: every node of ``grid`` (field_volume.FieldGrid)
         inside the context view whose proposal density reaches ``cull`` (if given) and whose decoder density reaches
         ``density_threshold``, with density, colour and Jacobian [A, 3], in ascending global index -- what the reference
         obtains by hand from a dense grid through compute_density (model.py:416-456) for the point-cloud colour maps of
         inference/jacobian_color_map.py.  See ``field_volume.extract_field``; ``max_points`` selects the form without host
-        synchronisation (padded tensors + ``count``; capturable in a HIP graph after one eager call)."""
+        synchronisation (padded tensors + ``count``; capturable in a HIP graph after one eager call).  ``views_per_scene=V``:
+        the context images are scenes of V consecutive calibrated views and one fused cloud per scene comes back (``fuse``:
+        "mean", "min", "max" of the views that see a node; ``min_views`` of them are needed)."""
         from .field_volume import extract_field
         enc = PixelEncoding(features=self._encode_for_render(camera_input.input_image), extrinsics=camera_input.ctxt_extrinsics,
                             intrinsics=camera_input.ctxt_intrinsics, action=None)
         return extract_field(self, enc, grid, density_threshold, cull=cull, proposal_level=proposal_level, in_frustum=in_frustum,
                              view_direction=view_direction, want_color=want_color, want_jacobian=want_jacobian,
-                             max_points=max_points)
+                             max_points=max_points, views_per_scene=views_per_scene, fuse=fuse, min_views=min_views)
 
     @torch.no_grad()
     def extract_mesh(self, camera_input: CameraInput, grid, density_threshold: float, *, in_frustum: bool = True,
                      want_color: bool = True, want_jacobian: bool = True, view_direction=None,
-                     max_vertices: Optional[int] = None, max_triangles: Optional[int] = None):
+                     max_vertices: Optional[int] = None, max_triangles: Optional[int] = None, views_per_scene: int = 1,
+                     fuse: str = "mean", min_views: int = 1):
         """The 3-D Jacobian field of the context image(s) as a surface mesh: the isosurface ``density == density_threshold``
         over ``grid`` (field_volume.FieldGrid) with the colour and the Jacobian [A, 3] at every vertex.  See
         ``field_volume.extract_mesh``; ``max_vertices`` + ``max_triangles`` select the form without host synchronisation
-        (padded tensors + true counts; capturable in a HIP graph after one eager call)."""
+        (padded tensors + true counts; capturable in a HIP graph after one eager call).  ``views_per_scene=V``: one fused
+        mesh per scene of V consecutive calibrated views (see ``extract_field``)."""
         from .field_volume import extract_mesh
         enc = PixelEncoding(features=self._encode_for_render(camera_input.input_image), extrinsics=camera_input.ctxt_extrinsics,
                             intrinsics=camera_input.ctxt_intrinsics, action=None)
         return extract_mesh(self, enc, grid, density_threshold, in_frustum=in_frustum, want_color=want_color,
                             want_jacobian=want_jacobian, view_direction=view_direction, max_vertices=max_vertices,
-                            max_triangles=max_triangles)
+                            max_triangles=max_triangles, views_per_scene=views_per_scene, fuse=fuse, min_views=min_views)
 
     @torch.no_grad()
     def encode_image(self, camera_input: CameraInput, rendering_input: RenderingInput,
