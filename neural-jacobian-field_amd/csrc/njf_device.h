@@ -802,6 +802,11 @@ __device__ __forceinline__ void point_footprint(const PointGeom& g, Footprint& f
 // Pipelining.  A batch = (texel t, slot s): MB loads, 4*MB MFMAs.  DEPTH batches of loads are in flight (the registers
 // `net` vacates at this point of the block); sched_barrier pins the issue order, otherwise the scheduler hoists all 16*MB
 // loads (-> scratch) or serialises them.
+#ifdef NJF_ABLATE_GATHER  // experiment builds only (tools/ablate.sh): every form below folds nothing
+#define NJF_GATHER false
+#else
+#define NJF_GATHER true
+#endif
 template <int S>
 __device__ __forceinline__ unsigned quad_bcast(unsigned v) {
   return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, S | (S << 2) | (S << 4) | (S << 6), 0xf, 0xf, true);
@@ -813,9 +818,7 @@ __device__ __forceinline__ unsigned quad_bcast_n(unsigned v, int s) {  // s is a
 template <int MB, int DEPTH = 4>
 __device__ __forceinline__ void add_hoisted_latent_quad(const float* __restrict__ gz, const PointGeom& g, int lane,
                                                         f32x16 (&h)[MB]) {
-#ifdef NJF_ABLATE_GATHER  // experiment builds only (tools/ablate.sh)
-  return;
-#endif
+  if (!NJF_GATHER) return;
   Footprint f;
   point_footprint(g, f);
   const int c = lane & 3;
@@ -859,9 +862,7 @@ __device__ __forceinline__ void add_hoisted_latent_quad(const float* __restrict_
 template <int MB, int DEPTH = 4>
 __device__ __forceinline__ void add_hoisted_latent_half(const float* __restrict__ gz, const PointGeom& g, int hh,
                                                         f32x16 (&h)[MB]) {
-#ifdef NJF_ABLATE_GATHER  // experiment builds only (tools/ablate.sh)
-  return;
-#endif
+  if (!NJF_GATHER) return;
   Footprint f;
   point_footprint(g, f);
   const float* gb = gz + (size_t)g.gofs + 4 * hh;
@@ -922,9 +923,7 @@ __device__ __forceinline__ void add_hoisted_latent_half(const float* __restrict_
 template <int MB, int DEPTH = NJF_F16_GATHER_DEPTH>
 __device__ __forceinline__ void add_hoisted_latent_f16(const _Float16* __restrict__ gz, const PointGeom& g, int hh,
                                                        f32x16 (&h)[MB], const Footprint* shared = nullptr) {
-#ifdef NJF_ABLATE_GATHER  // experiment builds only (tools/ablate.sh)
-  return;
-#endif
+  if (!NJF_GATHER) return;
   Footprint f;
   if (shared != nullptr) f = *shared;   // (compile-time known at every call site: TileShareF16)
   else point_footprint(g, f);
@@ -1089,6 +1088,110 @@ __device__ __forceinline__ void sh4(float dx, float dy, float dz, float (&o)[16]
 }
 
 // ------------------------------------------------------------------------------------------
+// Exact fp32, inference: a 128-wide chunk (MBO = 4, NKB = 2) in front of a gather, with the gather folded under it.
+//
+// mma_chunk<PREC_F32> runs (kb, q, e) outside and the output block m inside, so all four accumulator blocks become final on
+// the chunk's last K-step and the gather that follows (add_hoisted_latent_half: 64 loads, 256 v_fmac, no MFMA) finds the
+// matrix pipe idle -- 5.5 % of the render kernel (profiles/r04_ablate.txt).  Here m is the OUTER loop: the 32 MFMAs of out[0]
+// are issued first, then those of out[1], ...; every output element still accumulates the same (a, b) pairs in the same
+// (kb, q, e) order, so the sums are bit-identical, and the packed layout P[kb][q][mb][lane][4] is only read in another order.
+// As soon as out[m] is final its four texels are folded into it UNDER the MFMAs of block m + 1: two or three VALU
+// instructions behind each MFMA from the fifth on (the first four separate the fold from the MFMA that wrote out[m], and
+// with them the hazard recogniser's wait states cost no issue slot the pipe would have used).  Only the gather of the last
+// block stays exposed behind the chunk.  Texel order t = 0..3, the compiler-visible fmaf of texel 0 and the asm v_fmac of
+// texels 1-3 are those of add_hoisted_latent_half (read the comment there before touching them).
+//
+// Loads: a batch = (block m, texel t) = 4 x 16 bytes.  Two batches are in flight -- 32 landing registers: for fc_1 the half of
+// `net` the layer's first chunk consumed, for lin_in part of the whole, unused, `net` -- each refilled when it has been folded,
+// so a batch is requested half a block to a block ahead of its fold and every batch is consumed inside this chunk: the
+// vmcnt(0) in front of the next chunk barrier never waits for a gather.  The next chunk's eight DMA rounds ride behind every
+// second group of four MFMAs of blocks 0 and 1, so the last round still has half a chunk to land.
+// The ReLU of the B operand is taken once, under block 0, and kept for blocks 1-3 in the registers `in` vacates.
+// ------------------------------------------------------------------------------------------
+template <int KB0, bool RELU, int KBI, class ST>
+__device__ __forceinline__ void mma_chunk_gather_f32(ST& st, const float* __restrict__ wl, int lane, const f32x16 (&in)[KBI],
+                                                     f32x16 (&out)[4], const float* __restrict__ gz, const PointGeom& g) {
+  static_assert(NJF_DMA_ROUNDS == 8, "one DMA round behind every second group of blocks 0 and 1");
+  constexpr int DEPTH = 2;           // batches in flight
+  constexpr int FIRST = 4;           // MFMAs of a block issued before the previous block's fold starts
+  Footprint f;
+  point_footprint(g, f);
+  const float* gb = gz + (size_t)g.gofs + 4 * (lane >> 5);
+  const float* p[4] = {gb + f.t00, gb + f.t01, gb + f.t10, gb + f.t11};
+  const float w[4] = {f.w00, f.w01, f.w10, f.w11};
+  f32x4 v[DEPTH][4];
+  auto issue = [&](int b) {          // batch b = 4 * m + t
+    const float* src = p[b & 3] + 32 * (b >> 2);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) v[b % DEPTH][q] = *(const f32x4*)(src + 8 * q);
+  };
+  auto fold = [&](int m, int i) {    // value i = 16 * t + 4 * q + e of block m
+    const int t = i >> 4, r = i & 15, b = 4 * m + t;
+    if (t == 0) {
+      out[m][r] = fmaf(v[b % DEPTH][r >> 2][r & 3], w[0], out[m][r]);
+    } else {
+      float acc = out[m][r];
+      asm("v_fmac_f32 %0, %1, %2" : "+v"(acc) : "v"(v[b % DEPTH][r >> 2][r & 3]), "v"(w[t]));
+      out[m][r] = acc;
+    }
+  };
+  auto refill = [&](int m, int t) {  // batch (m, t) is folded: its registers take the batch DEPTH further on
+    asm volatile("" : "+v"(out[m]) : : "memory");
+    if (4 * m + t + DEPTH < 16) issue(4 * m + t + DEPTH);
+  };
+  // values of the previous block folded once `n` MFMAs of a block have been issued (64 over the last 32 - FIRST of them)
+  auto folded = [](int n) { return n <= FIRST ? 0 : (n - FIRST) * 64 / (32 - FIRST); };
+  if (NJF_GATHER) {
+#pragma unroll
+    for (int b = 0; b < DEPTH; ++b) issue(b);
+  }
+  const float* base = wl + lane * 4;
+  f32x16 bin[2];
+  f32x4 a = *(const f32x4*)base;
+#pragma unroll
+  for (int m = 0; m < 4; ++m) {
+#pragma unroll
+    for (int kq = 0; kq < 8; ++kq) {   // group (kb, q) of block m: four MFMAs
+      const int kb = kq >> 2, q = kq & 3, gi = 8 * m + kq;
+      f32x4 n = a;
+      if (gi + 1 < 32) n = *(const f32x4*)(base + (((gi + 1) & 7) * 4 + ((gi + 1) >> 3)) * 256);
+      if (gi < 16 && (gi & 1) == 0) dma_issue(st, gi >> 1);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        if (m == 0) {
+          float b = in[KB0 + kb][q * 4 + e];
+          if (RELU) b = relu_bits(b);
+          bin[kb][q * 4 + e] = b;
+        }
+        out[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[e], bin[kb][q * 4 + e], out[m], 0, 0, 0);
+        if (NJF_GATHER && m > 0) {
+#pragma unroll
+          for (int i = folded(4 * kq + e); i < folded(4 * kq + e + 1); ++i) fold(m - 1, i);
+        }
+      }
+      if (NJF_GATHER && m > 0) {
+#pragma unroll
+        for (int t = folded(4 * kq) / 16; t < folded(4 * kq + 4) / 16; ++t) refill(m - 1, t);
+      }
+      a = n;
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+  st.dma_next = NJF_DMA_ROUNDS;
+  NJF_STAMP(st, 4);  // the exposed part of the gather begins: block 3
+  if (NJF_GATHER) {
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+#pragma unroll
+      for (int i = 16 * t; i < 16 * t + 16; ++i) fold(3, i);
+      refill(3, t);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+  NJF_STAMP(st, 5);  // gather folded into out
+}
+
+// ------------------------------------------------------------------------------------------
 // One ResnetFC (resnet_fc.py:130-154) on a 32-point tile: 22 weight chunks.
 // bias layout (LDS): [blk: fc0 (128) | fc1 (128)] x 5 | lin_out (32).
 // ------------------------------------------------------------------------------------------
@@ -1171,6 +1274,9 @@ __device__ __forceinline__ void resnet_tile(ST& st, const float* __restrict__ bi
                                             ActDump dump = ActDump{nullptr, nullptr, 0}, const TileShareF16* share = nullptr) {
   static_assert(SHARED == 0 || (PREC == PREC_F16 && !DUMP), "the shared tile state exists for the plain-fp16 inference kernels");
   const int hh = lane >> 5;
+  // exact-fp32 inference: the gather of blocks 0-2 rides under the chunk in front of it (mma_chunk_gather_f32).  The training
+  // and dump forms write h out between gather and layer, and the other precisions have their own gather forms: serial.
+  constexpr bool FUSED = PREC == PREC_F32 && !DUMP;
   f32x16 h[4], net[4];
 #pragma unroll
   for (int m = 0; m < 4; ++m) h[m] = (f32x16)(0.f);
@@ -1188,6 +1294,7 @@ __device__ __forceinline__ void resnet_tile(ST& st, const float* __restrict__ bi
   {
     const float* wl = stream_step(st, wave, lane);
     if constexpr ((SHARED & 1) != 0) mma_lin_in_f16_packed(st, wl, lane, share->pe, h);
+    else if constexpr (FUSED) mma_chunk_gather_f32<0, false, 2>(st, wl, lane, pe, h, gz, g);  // lin_in + the gather of block 0
     else mma_chunk<PREC, 4, 2, 0, false, 2>(st, wl, lane, pe, h);  // lin_in (bias folded into slot 63)
   }
   if constexpr (PREC == PREC_F16) {
@@ -1216,7 +1323,7 @@ __device__ __forceinline__ void resnet_tile(ST& st, const float* __restrict__ bi
     }
   } else
   for (int blk = 0; blk < 5; ++blk) {
-    if (blk < 3) {
+    if (!FUSED && blk < 3) {
       NJF_STAMP(st, 4);  // gather begins (the stamp's own lgkmcnt(0) also ends the previous chunk's MFMA issue)
       add_hoisted_latent<4, PREC>(gz + blk * 128, g, lane, h);
       NJF_STAMP(st, 5);  // gather folded into h
@@ -1243,7 +1350,14 @@ __device__ __forceinline__ void resnet_tile(ST& st, const float* __restrict__ bi
       }
       {
         const float* wl = stream_step(st, wave, lane);
-        mma_chunk<PREC, 4, 2, 2, true, 4>(st, wl, lane, net, h);
+        bool plain = true;
+        if constexpr (FUSED) {
+          if (blk < 2) {
+            mma_chunk_gather_f32<2, true, 4>(st, wl, lane, net, h, gz + (blk + 1) * 128, g);  // + the gather of block blk + 1
+            plain = false;
+          }
+        }
+        if (plain) mma_chunk<PREC, 4, 2, 2, true, 4>(st, wl, lane, net, h);
       }
     }
     if (DUMP && dump.feat != nullptr) dump_vec128<false>(dump.feat + (size_t)blk * dump.stride, h);
