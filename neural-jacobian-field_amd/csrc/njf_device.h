@@ -1595,29 +1595,36 @@ __device__ __forceinline__ void transformer_tile(ST& st, const float* __restrict
 // Backward pieces of the folded transformer head on a 32-point x 64-channel tile (njf_transformer_backward)
 // ------------------------------------------------------------------------------------------
 // norm64 that also returns 1 / sqrt(var + eps): what the backward of the (affine-free) normalisation needs next to n itself
+// The pairs it emits are held against float64 at a few fp32 roundings (tests/test_transformer_backward_gpu.py), so unlike norm64
+// it sums in four interleaved partial sums (a quarter of the roundings of one 32-term chain), refines v_rsq_f32 by one Newton
+// step (the 1-ulp error of rstd is a relative error of the whole row) and rounds x - mean before the product instead of folding
+// a rounded mean * rstd into an fma: ~20 VALU instructions more per call next to the six 64 x 64 products of a layer.
 __device__ __forceinline__ float norm64_rstd(const f32x16 (&x)[2], f32x16 (&n)[2]) {
-  float s = 0.f;
+  float s[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int m = 0; m < 2; ++m)
 #pragma unroll
-    for (int r = 0; r < 16; ++r) s += x[m][r];
-  s += __shfl_xor(s, 32, 64);
-  const float mean = s / 64.0f;
-  float v = 0.f;
+    for (int r = 0; r < 16; ++r) s[r & 3] += x[m][r];
+  float sum = (s[0] + s[1]) + (s[2] + s[3]);
+  sum += __shfl_xor(sum, 32, 64);
+  const float mean = sum / 64.0f;
+  float v[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int m = 0; m < 2; ++m)
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const float d = x[m][r] - mean;
-      v = fmaf(d, d, v);
+      n[m][r] = x[m][r] - mean;
+      v[r & 3] = fmaf(n[m][r], n[m][r], v[r & 3]);
     }
-  v += __shfl_xor(v, 32, 64);
-  const float rstd = __builtin_amdgcn_rsqf(v / 64.0f + 1e-5f);
-  const float shift = -mean * rstd;
+  float var = (v[0] + v[1]) + (v[2] + v[3]);
+  var += __shfl_xor(var, 32, 64);
+  const float q = var / 64.0f + 1e-5f;
+  const float y = __builtin_amdgcn_rsqf(q);
+  const float rstd = fmaf(0.5f * y, fmaf(-q * y, y, 1.0f), y);   // y (1.5 - 0.5 q y^2)
 #pragma unroll
   for (int m = 0; m < 2; ++m)
 #pragma unroll
-    for (int r = 0; r < 16; ++r) n[m][r] = fmaf(x[m][r], rstd, shift);
+    for (int r = 0; r < 16; ++r) n[m][r] *= rstd;
   return rstd;
 }
 // n = (x - mean) * rstd over 64 channels  =>  dx = rstd * (dn - mean(dn) - n * mean(dn * n));  acc += dx

@@ -3810,13 +3810,19 @@ __global__ void __launch_bounds__(NJF_THREADS, 2) transformer_backward_kernel(Tr
         for (int k = 0; k < 8; ++k) t[m][8 * h8 + k] = e[k] * inv;       // a
       }
     put(wx, 4 * l + 1, t, 1.0f);
-    bias_init<2, false, PREC>(bl + 64, hh, xin);
-    mma_chunk<PREC, 2, 2, 0, false, 2>(st, wl + 4096, lane, t, xin);    // xm = x + Nov a + bo
+    // Nov a + bo on an accumulator of its own (u is free here), added to x once: 64 small terms accumulated onto the residual
+    // stream itself are 64 roundings at ulp(x), several times what one fp32 addition of the finished product costs
+    bias_init<2, true, PREC>(bl + 64, hh, u);
+    mma_chunk<PREC, 2, 2, 0, false, 2>(st, wl + 4096, lane, t, u);
+    xin[0] += u[0];
+    xin[1] += u[1];                                                          // xm = x + (Nov a + bo)
     const float rstd2 = norm64_rstd(xin, n2);
     put(wx, 4 * l + 2, n2, 1.0f);
-    bias_init<2, true, PREC>(bl + 128, hh, u);
+    u[0] = (f32x16)(0.f);
+    u[1] = (f32x16)(0.f);
     wl = stream_step(st, wave, lane);
-    mma_chunk<PREC, 2, 2, 0, false, 2>(st, wl, lane, n2, u);           // u = W1' n2 + b1'
+    mma_chunk<PREC, 2, 2, 0, false, 2>(st, wl, lane, n2, u);
+    bias_init<2, false, PREC>(bl + 128, hh, u);                              // u = (W1' n2) + b1': the bias, too, is added once
     {
       f32x16 hval[2];
 #pragma unroll

@@ -949,7 +949,10 @@ def power_of_two_unscale(absmax: torch.Tensor) -> torch.Tensor:
     _, e = torch.frexp(absmax)                      # absmax = f * 2^e, f in [0.5, 1): the kernel's frexpf
     k = torch.clamp(6 - e, -120, 120)
     ok = (absmax > 0) & (absmax < 3.0e38)
-    return torch.where(ok, torch.ldexp(torch.ones_like(absmax), -k), torch.ones_like(absmax))
+    # 2^-k assembled from its exponent field (|k| <= 120: a normal number): torch.ldexp multiplies by a floating-point pow(2, -k),
+    # which is not an exact power of two for every k on the device -- and the kernel's 2^k multiply is exact
+    pow2 = ((127 - k).to(torch.int32) << 23).view(torch.float32)
+    return torch.where(ok, pow2, torch.ones_like(absmax))
 
 
 def resnetfc_backward_f16_storage(d_out: torch.Tensor, w_backward: torch.Tensor, mask: torch.Tensor, precision: str = "f32"):

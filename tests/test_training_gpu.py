@@ -898,7 +898,10 @@ def test_transformer_backward_chain_equals_the_library_recomputation(setup):
     layers on the residual stream the training forward dumped, one batched GEMM for the K = points weight gradients, the fold's own
     autograd graph back to the reference's parameters) against the route it replaces -- the head recomputed in its ORIGINAL
     parameterisation (transformer.py:38-135) in library ops from the dumped encoding + footprint, differentiated by autograd
-    (NJF_TRANSFORMER_BACKWARD=torch) -- on the same forward: every "jacobian*" parameter, A = 6 (two unused key slots) and A = 8."""
+    (NJF_TRANSFORMER_BACKWARD=torch) -- on the same forward: every "jacobian*" parameter, A = 6 (two unused key slots) and A = 8.
+    This is the end-to-end check: both sides differentiate a default-precision forward with its own sample placement, hence 2e-4.
+    The kernel-level check of the chain -- float64 autograd on plain tensors, every tile shape, key count and storage / product
+    form, at a few fp32 roundings -- is tests/test_transformer_backward_gpu.py."""
     import os
     from neural_jacobian_field_amd import synthetic
     from neural_jacobian_field_amd.config import model_cfg_from_dict
