@@ -484,6 +484,42 @@ int njf_field_combine(const float* xyz, const int* node, const int* count, int c
                       const NjfCameras* cams, const float* density, const float* color, const float* jacobian, int action_dim,
                       float* out_color, float* out_jacobian, unsigned char* out_views, void* stream);
 
+/* ---- connected components of the inside nodes (additive within ABI v20): drop floaters, split a body by key -------------- */
+/* The semantics are fixed so the result is checkable against a plain restatement:
+ *   DENSE form (values != NULL, indices == NULL): node g is INSIDE iff (valid == NULL || valid[g] != 0) && (cams == NULL ||
+ *   it projects inside the context image of its batch element: the predicate of njf_field_select) && values[g] >= threshold
+ *   (NaN: outside).  LIST form (indices != NULL, values == valid == cams == NULL): the inside nodes are the first
+ *   min(*count, capacity) entries of `indices`, ASCENDING global indices (count NULL = capacity; rows past the count are
+ *   never read; entries out of order or outside [0, B*N) are dropped).
+ *   Two inside nodes of one batch element are ADJACENT iff they differ by one of the first connectivity/2 directions of the
+ *   mesh table -- 6: (1,0,0) (0,1,0) (0,0,1); 14: those and (1,1,0) (1,0,1) (0,1,1) (1,1,1), the edges of the Kuhn tetrahedra
+ *   -- in either sign, without wrap at the grid faces, and -- with keys -- iff their keys are equal as well.
+ *   labels[g] = the smallest global index of g's component, -1 outside; sizes[g] = the node count of that component, 0
+ *   outside; *component_count = the number of components (of nodes with labels[g] == g).
+ * keys: device int32, [B*N] in the dense form, [capacity] (per entry) in the list form, or NULL.  labels, sizes: device int32
+ * [B*N]; component_count, status: device int32 [1].  workspace: device int32 [2*B*N] (parents, per-root sizes), [3*B*N] in the
+ * list form with keys (the per-entry keys are scattered to a dense array).  *status: 0, or NJF_FIELD_COMPONENTS_E_* bits when a
+ * find / union loop of the lock-free union-find passed its iteration cap (a broken invariant -- the results are then
+ * unspecified, nothing hangs).  Four launches over workgroups of NJF_FIELD_COMPONENTS_BLOCK nodes behind two 4-byte memsets:
+ * a fixed sequence without a host read.  Integer arithmetic; the atomics are integer min / add / or, so the output bytes are a
+ * function of the inputs alone.  `phase`: NJF_FIELD_COMPONENTS_ALL; the single bits run one launch each, so that a caller can
+ * time them apart -- the results are defined once all four have run in order, on one stream, with the same arguments and
+ * workspace.  NJF_E_VALUE: connectivity not 6 or 14, an unknown phase, both forms at once, valid / cams with a list;
+ * NJF_E_NULL: neither form, a missing output; NJF_E_SHAPE: as for njf_field_select. */
+#define NJF_FIELD_COMPONENTS_BLOCK 1024
+#define NJF_FIELD_COMPONENTS_INIT 1   /* the memsets, inside flags, in-workgroup unions */
+#define NJF_FIELD_COMPONENTS_MERGE 2  /* unions across workgroups */
+#define NJF_FIELD_COMPONENTS_LABEL 4  /* labels, per-root sizes, the component count */
+#define NJF_FIELD_COMPONENTS_SIZES 8  /* sizes */
+#define NJF_FIELD_COMPONENTS_ALL 15
+#define NJF_FIELD_COMPONENTS_E_LOCAL 1  /* an in-workgroup (LDS) loop */
+#define NJF_FIELD_COMPONENTS_E_FIND 2   /* a find over the global parents */
+#define NJF_FIELD_COMPONENTS_E_UNION 4  /* the retries of a global union */
+int njf_field_components(const NjfFieldGrid* grid, const NjfCameras* cams, int batch, const float* values, float threshold,
+                         const unsigned char* valid, const int* indices, const int* count, int capacity, const int* keys,
+                         int connectivity, int phase, int* labels, int* sizes, int* component_count, int* status,
+                         int* workspace, void* stream);
+
 /* ---- stand-alone sampler / compositing ops (API parity with the un-fused reference calls) -- */
 /* RaySamples.get_weights (ray_samplers.py:77-101): deltas, densities [N,S] -> weights [N,S]. */
 int njf_alpha_weights(const float* deltas, const float* densities, int rays, int samples, float* weights, void* stream);

@@ -2831,6 +2831,303 @@ __global__ void __launch_bounds__(NJF_COMBINE_THREADS) field_combine_kernel(Comb
   if (a.jacobian) combine_rows(a.jacobian, a.out_jacobian, a.jdim, first, rows, a.views, w, wsum);
 }
 
+// ---- connected components of the inside nodes: lock-free union-find ---------------------------------------------------------
+// inside(g) = valid(g) && values[g] >= threshold (NaN: outside; valid = the caller's mask and / or point_in_view), or -- list
+// form -- g is an entry of an ascending index list.  Two inside nodes of one batch element are adjacent iff they differ by one
+// of the first `half` = C/2 directions of the mesh table (3: the axes; 7: the edges of the Kuhn tetrahedra), in either sign,
+// and -- with keys -- carry equal keys.  labels[g] = the smallest global index of g's component (-1 outside), sizes[g] = its
+// node count (0 outside), *count = the number of components.
+// parent[g] (int32, -1 outside) is a forest with the invariant parent[g] <= g AT ALL TIMES: launch 1 writes the minimum of the
+// in-workgroup component, every later write is an atomicMin with a smaller index of the same final component.  Hence every
+// chain strictly decreases and ends at a root (parent[r] == r), roots only ever move to smaller indices, and the final root
+// of a tree is the minimum of its component.  Four launches over workgroups of 1024 consecutive nodes, item-major:
+//   1 components_init_kernel   inside flags, in-workgroup unions in LDS, parent / per-local-root counts / zeros to memory
+//   2 components_merge_kernel  unions of the adjacent pairs whose ends lie in different workgroups
+//   3 components_label_kernel  labels = find, one atomicAdd per LOCAL ROOT into root_size[label], the component count
+//   4 components_size_kernel   sizes = root_size[labels]
+// Memory rules of launch 2 (the XCDs' L2s are not coherent for plain accesses inside a launch): every write to parent is an
+// agent-scope atomicMin, every read of it a relaxed agent-scope atomic load, and no decision rests on the freshness of a
+// load: a stale parent is an older link of the same final component (it costs a retry), and a union only ends on the value
+// an atomicMin RETURNED.  Launches 3 and 4 read what earlier launches wrote: plain loads.
+#define NJF_CC_THREADS 256
+#define NJF_CC_ITEMS (NJF_FIELD_COMPONENTS_BLOCK / NJF_CC_THREADS)
+#define NJF_CC_WAVES (NJF_CC_THREADS / 64)
+#define NJF_CC_FIND_CAP (1 << 20)   // hops of one find: a chain strictly decreases, so B*N bounds it; past this, status
+#define NJF_CC_UNION_CAP (1 << 12)  // retries of one union: each needs another workgroup's link to land in between
+static_assert(NJF_CC_ITEMS * NJF_CC_THREADS == NJF_FIELD_COMPONENTS_BLOCK && NJF_FIELD_COMPONENTS_BLOCK == NJF_FIELD_MESH_BLOCK,
+              "components block");
+struct ComponentArgs {
+  SelectArgs sel;              // list: the identity over B*N; values, threshold; w2c / k: frustum part of `valid` (or null)
+  const unsigned char* valid;  // [B*N] or null
+  const int* entries;          // list form: ascending global indices (null: the dense form)
+  const int* entry_count;      // device count of the list or null
+  int entry_capacity;
+  const int* keys;             // dense form: [B*N]; list form: [entry_capacity], per entry; or null
+  int* dense_keys;             // [B*N]: what launch 2 reads (dense form: == keys; list form: scattered by launch 1)
+  int half;                    // C / 2 directions
+  int* parent;                 // [B*N]
+  int* root_size;              // [B*N]
+  int* labels;                 // [B*N]
+  int* sizes;                  // [B*N]: launches 1..3 keep the node count of every local root here (0 elsewhere)
+  int* count;
+  int* status;
+};
+
+__device__ __forceinline__ int cc_load(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ int cc_load_lds(const int* p) {
+  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+
+// (ix, iy, iz) of global index gi
+__device__ __forceinline__ void cc_coords(const FieldList& l, int gi, int& ix, int& iy, int& iz) {
+  const int n = gi % l.nodes;
+  const int yz = l.grid.dims[1] * l.grid.dims[2];
+  ix = n / yz;
+  const int r = n - ix * yz;
+  iy = r / l.grid.dims[2];
+  iz = r - iy * l.grid.dims[2];
+}
+
+// does the neighbour of (ix, iy, iz) in direction `code` exist in the grid (no wrap at the faces)?
+__device__ __forceinline__ bool cc_in_grid(const NjfFieldGrid& g, int ix, int iy, int iz, int code) {
+  return ix + (code & 1) < g.dims[0] && iy + ((code >> 1) & 1) < g.dims[1] && iz + (code >> 2) < g.dims[2];
+}
+
+// Root of x in the LDS forest of one workgroup (lab[y] <= y: a chain strictly decreases inside [0, 1024), so it has at most
+// 1023 hops; the cap can only trip on a broken invariant).
+__device__ __forceinline__ int cc_find_lds(const int* lab, int x, int* status) {
+  for (int hop = 0; hop < NJF_FIELD_COMPONENTS_BLOCK; ++hop) {
+    const int p = cc_load_lds(lab + x);
+    if (p == x || p < 0) return x;
+    x = p;
+  }
+  atomicOr(status, NJF_FIELD_COMPONENTS_E_LOCAL);
+  return x;
+}
+
+// Union in LDS.  Terminates: a retry happens only when the atomicMin found that another thread had lowered lab[a] in
+// between, and it continues from that strictly smaller index, so a + b strictly decreases from retry to retry.
+__device__ __forceinline__ void cc_union_lds(int* lab, int a, int b, int* status) {
+  for (int t = 0; t < NJF_FIELD_COMPONENTS_BLOCK; ++t) {
+    a = cc_find_lds(lab, a, status);
+    b = cc_find_lds(lab, b, status);
+    if (a == b) return;
+    if (a < b) { const int s = a; a = b; b = s; }
+    const int old = atomicMin(lab + a, b);
+    if (old == a) return;  // a WAS a root (the atomic says so) and now hangs under b
+    a = old;               // a already hung under old < a: old and b still have to meet
+  }
+  atomicOr(status, NJF_FIELD_COMPONENTS_E_LOCAL);
+}
+
+// Root of x in the global forest, launch 2.  Terminates: every value ever stored in parent[y] is <= y, fresh or stale, so the
+// chain strictly decreases; it ends at an index that (as far as this load could see) is a root.  A stale answer is a node of
+// the same final component that has since been linked further: the caller's atomicMin finds that out.  The start of the
+// chain is then hooked to what was found (an atomicMin with a smaller index of its own component: the invariant holds).
+__device__ __forceinline__ int cc_find(int* parent, int x, int* status) {
+  const int x0 = x;
+  int first = -1;
+  for (int hop = 0; hop < NJF_CC_FIND_CAP; ++hop) {
+    const int p = cc_load(parent + x);
+    if (hop == 0) first = p;
+    if (p == x || p < 0) {
+      if (first != x && x < x0) atomicMin(parent + x0, x);
+      return x;
+    }
+    x = p;
+  }
+  atomicOr(status, NJF_FIELD_COMPONENTS_E_FIND);
+  return x;
+}
+
+// union(a, b), launch 2: find both roots, atomicMin(&parent[larger], smaller), and continue from the returned value if the
+// larger one was no longer a root.  The only exits are a == b (one node: nothing to join) and an atomicMin that returned its
+// own address' index (it WAS a root when the link landed).  Terminates: a retry continues from old < a with b unchanged, and
+// a find only lowers its argument, so a + b strictly decreases from retry to retry; every retry is caused by a link of
+// another thread that landed in between.
+__device__ __forceinline__ void cc_union(int* parent, int a, int b, int* status) {
+  for (int t = 0; t < NJF_CC_UNION_CAP; ++t) {
+    a = cc_find(parent, a, status);
+    b = cc_find(parent, b, status);
+    if (a == b) return;
+    if (a < b) { const int s = a; a = b; b = s; }
+    const int old = atomicMin(parent + a, b);
+    if (old == a) return;
+    a = old;
+  }
+  atomicOr(status, NJF_FIELD_COMPONENTS_E_UNION);
+}
+
+// first list position whose entry is >= key (the list is ascending)
+__device__ __forceinline__ int cc_lower_bound(const int* list, int n, long long key) {
+  int lo = 0, hi = n;
+  while (lo < hi) {
+    const int mid = lo + ((hi - lo) >> 1);
+    if ((long long)list[mid] < key) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+// launch 1
+template <bool LIST>
+__global__ void __launch_bounds__(NJF_CC_THREADS) components_init_kernel(ComponentArgs a) {
+  __shared__ int lab[NJF_FIELD_COMPONENTS_BLOCK];   // local parent (index inside the workgroup), -1 outside
+  __shared__ int cnt[NJF_FIELD_COMPONENTS_BLOCK];   // nodes per local root
+  __shared__ int keyl[NJF_FIELD_COMPONENTS_BLOCK];
+  __shared__ int range[2];
+  const FieldList& fl = a.sel.list;
+  const long long base = (long long)blockIdx.x * NJF_FIELD_COMPONENTS_BLOCK;
+  const int nloc = (int)min((long long)NJF_FIELD_COMPONENTS_BLOCK, (long long)fl.total - base);
+  const int tid = threadIdx.x;
+#pragma unroll
+  for (int it = 0; it < NJF_CC_ITEMS; ++it) {
+    const int l = it * NJF_CC_THREADS + tid;
+    cnt[l] = 0;
+    keyl[l] = 0;
+    if (LIST) {
+      lab[l] = -1;
+    } else {
+      bool in = l < nloc;
+      const int gi = (int)(base + min(l, nloc - 1));
+      if (in) in = a.sel.values[gi] >= a.sel.threshold;
+      if (in && a.valid) in = a.valid[gi] != 0;
+      if (in && a.sel.w2c) in = field_in_view(a.sel, gi);
+      lab[l] = in ? l : -1;
+      if (in && a.keys) keyl[l] = a.keys[gi];
+    }
+  }
+  if (LIST) {
+    const int n = a.entry_count ? min(max(*a.entry_count, 0), a.entry_capacity) : a.entry_capacity;
+    if (tid < 2) range[tid] = cc_lower_bound(a.entries, n, base + (tid ? nloc : 0));
+    __syncthreads();
+    for (int e = range[0] + tid; e < range[1]; e += NJF_CC_THREADS) {
+      const long long l = (long long)a.entries[e] - base;
+      if (l < 0 || l >= nloc) continue;   // (caller data: an unsorted list loses entries, it never addresses outside)
+      lab[l] = (int)l;
+      if (a.keys) keyl[l] = a.keys[e];
+    }
+  }
+  __syncthreads();
+  // unions of the pairs with both ends in this workgroup (the upper end lies `off` entries further on)
+#pragma unroll
+  for (int it = 0; it < NJF_CC_ITEMS; ++it) {
+    const int l = it * NJF_CC_THREADS + tid;
+    if (l >= nloc || cc_load_lds(lab + l) < 0) continue;
+    int ix, iy, iz;
+    cc_coords(fl, (int)(base + l), ix, iy, iz);
+    for (int k = 0; k < a.half; ++k) {
+      const int code = mesh_dir_code(k);
+      if (!cc_in_grid(fl.grid, ix, iy, iz, code)) continue;
+      const int l1 = l + mesh_code_offset(fl.grid, code);
+      if (l1 >= nloc || cc_load_lds(lab + l1) < 0 || keyl[l1] != keyl[l]) continue;
+      cc_union_lds(lab, l, l1, a.status);
+    }
+  }
+  __syncthreads();
+  int root[NJF_CC_ITEMS];
+#pragma unroll
+  for (int it = 0; it < NJF_CC_ITEMS; ++it) {
+    const int l = it * NJF_CC_THREADS + tid;
+    root[it] = (l < nloc && lab[l] >= 0) ? cc_find_lds(lab, l, a.status) : -1;
+    // one LDS add per wave where the wave's inside nodes share a root (the inside of a large body), else one per node
+    const bool in = root[it] >= 0;
+    const unsigned long long m = __ballot(in);
+    if (m == 0ull) continue;  // (wave-uniform)
+    const int lead = __ffsll((long long)m) - 1;
+    const int r0 = __shfl(root[it], lead, 64);
+    if (__all(!in || root[it] == r0)) {
+      if ((tid & 63) == lead) atomicAdd(cnt + r0, __popcll(m));
+    } else if (in) {
+      atomicAdd(cnt + root[it], 1);
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int it = 0; it < NJF_CC_ITEMS; ++it) {
+    const int l = it * NJF_CC_THREADS + tid;
+    if (l >= nloc) continue;
+    const int gi = (int)(base + l);
+    a.parent[gi] = root[it] >= 0 ? (int)base + root[it] : -1;
+    a.sizes[gi] = root[it] == l ? cnt[l] : 0;
+    a.root_size[gi] = 0;
+    if (LIST && a.keys) a.dense_keys[gi] = keyl[l];
+  }
+}
+
+// launch 2
+__global__ void __launch_bounds__(NJF_CC_THREADS) components_merge_kernel(ComponentArgs a) {
+  const FieldList& fl = a.sel.list;
+  const long long base = (long long)blockIdx.x * NJF_FIELD_COMPONENTS_BLOCK;
+  const int nloc = (int)min((long long)NJF_FIELD_COMPONENTS_BLOCK, (long long)fl.total - base);
+#pragma unroll
+  for (int it = 0; it < NJF_CC_ITEMS; ++it) {
+    const int l = it * NJF_CC_THREADS + (int)threadIdx.x;
+    if (l >= nloc) continue;
+    const int gi = (int)(base + l);
+    if (cc_load(a.parent + gi) < 0) continue;   // (-1 is written by launch 1 alone and never changes)
+    int ix, iy, iz;
+    cc_coords(fl, gi, ix, iy, iz);
+    for (int k = 0; k < a.half; ++k) {
+      const int code = mesh_dir_code(k);
+      if (!cc_in_grid(fl.grid, ix, iy, iz, code)) continue;
+      const int off = mesh_code_offset(fl.grid, code);
+      if (l + off < nloc) continue;             // both ends in this workgroup: launch 1 joined them
+      const int g1 = gi + off;                  // (inside the batch element's grid, hence below B*N)
+      if (cc_load(a.parent + g1) < 0) continue;
+      if (a.dense_keys && a.dense_keys[g1] != a.dense_keys[gi]) continue;
+      cc_union(a.parent, gi, g1, a.status);
+    }
+  }
+}
+
+// launch 3 (parent is final: plain loads of what launches 1 and 2 wrote)
+__global__ void __launch_bounds__(NJF_CC_THREADS) components_label_kernel(ComponentArgs a) {
+  __shared__ int wave_part[NJF_MESH_WAVES];
+  const FieldList& fl = a.sel.list;
+  const long long base = (long long)blockIdx.x * NJF_FIELD_COMPONENTS_BLOCK;
+  const int nloc = (int)min((long long)NJF_FIELD_COMPONENTS_BLOCK, (long long)fl.total - base);
+  int roots = 0;
+#pragma unroll
+  for (int it = 0; it < NJF_CC_ITEMS; ++it) {
+    const int l = it * NJF_CC_THREADS + (int)threadIdx.x;
+    if (l >= nloc) continue;
+    const int gi = (int)(base + l);
+    int x = gi, p = a.parent[gi];
+    if (p < 0) {
+      a.labels[gi] = -1;
+      continue;
+    }
+    // the chain strictly decreases (parent[y] <= y) and nothing writes parent any more: at most B*N hops
+    int hop = 0;
+    for (; p != x && p >= 0 && hop < NJF_CC_FIND_CAP; ++hop) {
+      x = p;
+      p = a.parent[x];
+    }
+    if (hop == NJF_CC_FIND_CAP) atomicOr(a.status, NJF_FIELD_COMPONENTS_E_FIND);
+    a.labels[gi] = x;
+    roots += x == gi;
+    const int c = a.sizes[gi];              // > 0 at the local roots of launch 1 only
+    if (c > 0) atomicAdd(a.root_size + x, c);
+  }
+  const int s = mesh_block_sum(roots, wave_part);
+  if (threadIdx.x == 0 && s > 0) atomicAdd(a.count, s);
+}
+
+// launch 4
+__global__ void __launch_bounds__(NJF_CC_THREADS) components_size_kernel(ComponentArgs a) {
+  const FieldList& fl = a.sel.list;
+  const long long base = (long long)blockIdx.x * NJF_FIELD_COMPONENTS_BLOCK;
+  const int nloc = (int)min((long long)NJF_FIELD_COMPONENTS_BLOCK, (long long)fl.total - base);
+#pragma unroll
+  for (int it = 0; it < NJF_CC_ITEMS; ++it) {
+    const int l = it * NJF_CC_THREADS + (int)threadIdx.x;
+    if (l >= nloc) continue;
+    const int gi = (int)(base + l);
+    const int r = a.labels[gi];
+    a.sizes[gi] = r >= 0 ? a.root_size[r] : 0;
+  }
+}
+
 // =============================================================================================
 // inverse dynamics: Levenberg-Marquardt on the linearised flow, one workgroup per batch element
 // =============================================================================================
@@ -4708,6 +5005,69 @@ extern "C" int njf_field_combine(const float* xyz, const int* node, const int* c
   const int blocks = (int)(((long long)capacity + NJF_COMBINE_THREADS - 1) / NJF_COMBINE_THREADS);
   field_combine_kernel<<<blocks, NJF_COMBINE_THREADS, 0, (hipStream_t)stream>>>(a);
   return launch_status();
+}
+
+// ---- connected components of the inside nodes -----------------------------------------------------------------------------
+extern "C" int njf_field_components(const NjfFieldGrid* grid, const NjfCameras* cams, int batch, const float* values,
+                                    float threshold, const unsigned char* valid, const int* indices, const int* count,
+                                    int capacity, const int* keys, int connectivity, int phase, int* labels, int* sizes,
+                                    int* component_count, int* status, int* workspace, void* stream) {
+  if (connectivity != 6 && connectivity != 14) return NJF_E_VALUE;
+  if (phase < 1 || phase > NJF_FIELD_COMPONENTS_ALL) return NJF_E_VALUE;
+  ComponentArgs a;
+  int rc = make_field_list(grid, batch, nullptr, nullptr, 0, a.sel.list);
+  if (rc) return rc;
+  if (capacity < 0) return NJF_E_SHAPE;
+  if ((values != nullptr) == (indices != nullptr)) return values ? NJF_E_VALUE : NJF_E_NULL;  // one form, not both
+  if (indices && (valid || cams)) return NJF_E_VALUE;  // (a list IS the inside set)
+  if (!labels || !sizes || !component_count || !status || !workspace) return NJF_E_NULL;
+  if (cams && (!cams->ctxt_w2c || !cams->ctxt_k)) return NJF_E_NULL;
+  if (cams && cams->batch != batch) return NJF_E_SHAPE;
+  const int total = a.sel.list.total;
+  a.sel.values = values;
+  a.sel.threshold = threshold;
+  a.sel.w2c = cams ? cams->ctxt_w2c : nullptr;
+  a.sel.k = cams ? cams->ctxt_k : nullptr;
+  a.sel.out_indices = nullptr;
+  a.sel.out_count = nullptr;
+  a.sel.out_capacity = 0;
+  a.sel.block_counts = nullptr;
+  a.sel.blocks = 0;
+  a.valid = valid;
+  a.entries = indices;
+  a.entry_count = count;
+  a.entry_capacity = capacity;
+  a.keys = keys;
+  a.dense_keys = !keys ? nullptr : (indices ? workspace + 2 * (size_t)total : const_cast<int*>(keys));
+  a.half = connectivity / 2;
+  a.parent = workspace;
+  a.root_size = workspace + (size_t)total;
+  a.labels = labels;
+  a.sizes = sizes;
+  a.count = component_count;
+  a.status = status;
+  hipStream_t s = (hipStream_t)stream;
+  const int blocks = (int)(((long long)total + NJF_FIELD_COMPONENTS_BLOCK - 1) / NJF_FIELD_COMPONENTS_BLOCK);
+  if (phase & NJF_FIELD_COMPONENTS_INIT) {
+    if (hipMemsetAsync(component_count, 0, sizeof(int), s) != hipSuccess) return launch_status();
+    if (hipMemsetAsync(status, 0, sizeof(int), s) != hipSuccess) return launch_status();
+    if (indices) components_init_kernel<true><<<blocks, NJF_CC_THREADS, 0, s>>>(a);
+    else components_init_kernel<false><<<blocks, NJF_CC_THREADS, 0, s>>>(a);
+    if ((rc = launch_status())) return rc;
+  }
+  if (phase & NJF_FIELD_COMPONENTS_MERGE) {
+    components_merge_kernel<<<blocks, NJF_CC_THREADS, 0, s>>>(a);
+    if ((rc = launch_status())) return rc;
+  }
+  if (phase & NJF_FIELD_COMPONENTS_LABEL) {
+    components_label_kernel<<<blocks, NJF_CC_THREADS, 0, s>>>(a);
+    if ((rc = launch_status())) return rc;
+  }
+  if (phase & NJF_FIELD_COMPONENTS_SIZES) {
+    components_size_kernel<<<blocks, NJF_CC_THREADS, 0, s>>>(a);
+    if ((rc = launch_status())) return rc;
+  }
+  return NJF_OK;
 }
 
 extern "C" int njf_resnetfc_backward(const float* d_out, int d_out_dim, const float* activations, const float* w_backward,

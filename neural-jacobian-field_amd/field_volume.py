@@ -177,6 +177,159 @@ class FieldPointCloud:
         return n
 
 
+# ---- connected components -------------------------------------------------------------------------------
+@dataclass
+class FieldComponents:
+    """Connected components of the inside nodes of a grid (``label_components``): ``labels[b, n]`` is the smallest global index
+    of the node's component (-1 outside), ``sizes[b, n]`` its node count (0 outside), ``count`` the number of components,
+    ``status`` 0 unless a loop of the device union-find passed its iteration cap (a defect: the eager entries raise on it)."""
+
+    grid: FieldGrid
+    labels: torch.Tensor    # [B, N] int32
+    sizes: torch.Tensor     # [B, N] int32
+    count: torch.Tensor     # [1] int32
+    status: torch.Tensor    # [1] int32
+
+    def keep(self, min_nodes: int = 1, largest_only: bool = False) -> torch.Tensor:
+        """``[B, N]`` bool: the nodes of the components of at least ``min_nodes`` nodes; ``largest_only``: of those, per batch
+        element, only the component of maximal size (ties go to the smallest label).  Integer torch ops on the tensors'
+        device, no host read."""
+        if isinstance(min_nodes, bool) or not isinstance(min_nodes, int) or min_nodes < 1:
+            raise ValueError(f"FieldComponents.keep: min_nodes must be an integer >= 1 (got {min_nodes!r})")
+        keep = self.sizes >= min_nodes                      # (an outside node has size 0)
+        if largest_only:
+            top = self.sizes.max(dim=1, keepdim=True).values
+            none = torch.full_like(self.labels, torch.iinfo(torch.int32).max)
+            first = torch.where((self.sizes == top) & (top > 0), self.labels, none).min(dim=1, keepdim=True).values
+            keep = keep & (self.labels == first)
+        return keep
+
+
+def _check_component_arguments(name: str, connectivity, min_component_nodes=None) -> None:
+    if isinstance(connectivity, bool) or connectivity not in hip.FIELD_COMPONENTS_CONNECTIVITIES:
+        raise ValueError(f"{name}: connectivity must be 6 or 14 (got {connectivity!r})")
+    if min_component_nodes is not None and (isinstance(min_component_nodes, bool) or not isinstance(min_component_nodes, int)
+                                            or min_component_nodes < 1):
+        raise ValueError(f"{name}: min_component_nodes must be an integer >= 1 (got {min_component_nodes!r})")
+
+
+def _check_keys(name: str, keys, shape, like: torch.Tensor):
+    if keys is None:
+        return None
+    if not torch.is_tensor(keys) or keys.dtype != torch.int32 or tuple(keys.shape) != tuple(shape):
+        raise ValueError(f"{name}: keys must be int32 {tuple(shape)}")
+    if keys.device != like.device:
+        raise ValueError(f"{name}: keys must live on the device of the other tensors")
+    return keys.contiguous()
+
+
+def _raise_on_status(name: str, status: torch.Tensor) -> None:
+    """The eager forms read the status word (a host synchronisation); nothing is read while a stream is being captured."""
+    if status.is_cuda and torch.cuda.is_current_stream_capturing():
+        return
+    code = int(status.item())
+    if code:
+        raise RuntimeError(f"{name}: the device union-find passed an iteration cap (status {code}); its invariants are broken "
+                           "and the labels are unspecified")
+
+
+def _components(grid: FieldGrid, batch: int, connectivity: int, dev, **form) -> FieldComponents:
+    """The four labelling launches on ``batch`` elements; ``form``: the dense or the list arguments of hip.field_components."""
+    i32 = dict(dtype=torch.int32, device=dev)
+    comp = FieldComponents(grid=grid, labels=torch.empty(batch, grid.num_nodes, **i32), sizes=torch.empty(batch, grid.num_nodes, **i32),
+                           count=torch.empty(1, **i32), status=torch.empty(1, **i32))
+    hip.field_components(grid.c_grid(), batch, connectivity, comp.labels, comp.sizes, comp.count, comp.status, **form)
+    return comp
+
+
+def label_components(grid: FieldGrid, values: torch.Tensor, threshold: float, *, valid: Optional[torch.Tensor] = None,
+                     pixel_encoding: Optional[PixelEncoding] = None, connectivity: int = 6,
+                     keys: Optional[torch.Tensor] = None) -> FieldComponents:
+    """Connected components of any scalar on the grid, without the networks: ``values`` ``[B, N]`` fp32
+    on the GPU; a node is inside iff it is valid -- ``valid`` ``[B, N]`` bool / uint8 and / or the frustum of the cameras of
+    ``pixel_encoding``, the predicate of the selection and the mesher -- and ``values >= threshold`` (NaN is outside).  Inside
+    nodes of one batch element are adjacent along the axes (``connectivity=6``) or along the edges of the Kuhn tetrahedra
+    (``connectivity=14``, the mesh's own connectivity), without wrap at the grid faces; with ``keys`` ``[B, N]`` int32 only
+    nodes of equal key are joined.  One host read (the status word) unless a stream is being captured."""
+    if not torch.is_tensor(values) or values.dim() != 2 or values.dtype != torch.float32 or values.shape[1] != grid.num_nodes:
+        raise ValueError(f"label_components: values must be fp32 [B, {grid.num_nodes}]")
+    _check_component_arguments("label_components", connectivity)
+    if not math.isfinite(float(threshold)):
+        raise ValueError("label_components: the threshold must be finite")
+    if values.shape[0] < 1 or values.shape[0] * grid.num_nodes >= 2 ** 31:
+        raise ValueError("label_components: batch * nx*ny*nz must stay below 2**31")
+    keys = _check_keys("label_components", keys, values.shape, values)
+    if valid is not None:
+        if not torch.is_tensor(valid) or valid.dtype not in (torch.bool, torch.uint8) or valid.shape != values.shape:
+            raise ValueError(f"label_components: valid must be bool or uint8 {tuple(values.shape)}")
+        if valid.device != values.device:
+            raise ValueError("label_components: valid and values must live on the same device")
+        valid = valid.contiguous()
+    if pixel_encoding is not None and pixel_encoding.extrinsics.shape[0] != values.shape[0]:
+        raise ValueError(f"label_components: {pixel_encoding.extrinsics.shape[0]} cameras for {values.shape[0]} rows of values")
+    if values.device.type != "cuda":
+        raise ValueError("label_components: values must live on the GPU; there is no CPU path")
+    cams = None if pixel_encoding is None else _cameras(pixel_encoding, False, action_dim=None)
+    comp = _components(grid, values.shape[0], connectivity, values.device, values=values.contiguous().reshape(-1),
+                       threshold=float(threshold), valid=valid, cams=cams, keys=None if keys is None else keys.reshape(-1))
+    _raise_on_status("label_components", comp.status)
+    return comp
+
+
+def _list_components(grid: FieldGrid, batch: int, index: torch.Tensor, count: Optional[torch.Tensor], capacity: int,
+                     connectivity: int, keys: Optional[torch.Tensor] = None) -> FieldComponents:
+    """The list form: the inside nodes are the first min(count, capacity) entries of the ascending ``index``."""
+    return _components(grid, batch, connectivity, index.device, indices=index, list_count=count, capacity=capacity, keys=keys)
+
+
+def cloud_components(cloud: FieldPointCloud, *, connectivity: int = 6, keys: Optional[torch.Tensor] = None,
+                     batch: Optional[int] = None):
+    """Components of the nodes of an extracted cloud, per row: ``(labels [n] int32, sizes [n] int32, count [1] int32)`` --
+    the label is the smallest global index of the row's component among the cloud's nodes.  A padded cloud is labelled up to
+    its ``count``, read on the device; rows past it get label -1 and size 0.  ``keys`` ``[n]`` int32 (e.g.
+    ``dominant_joint(cloud.jacobian)``) joins only rows of equal key.  ``batch``: the number of batch elements (scenes) the
+    cloud's grid was extracted for; None infers it from the largest index (one more host read)."""
+    _check_component_arguments("cloud_components", connectivity)
+    index = cloud.index
+    n = index.shape[0]
+    keys = _check_keys("cloud_components", keys, (n,), index)
+    if index.device.type != "cuda":
+        raise ValueError("cloud_components: the cloud must live on the GPU; there is no CPU path")
+    nodes = cloud.grid.num_nodes
+    rows = torch.arange(n, dtype=torch.int32, device=index.device) < cloud.count
+    if batch is None:
+        batch = int(torch.where(rows, index, torch.zeros_like(index)).max().item()) // nodes + 1 if n else 1
+    if batch < 1 or batch * nodes >= 2 ** 31:
+        raise ValueError("cloud_components: batch * nx*ny*nz must stay below 2**31")
+    comp = _list_components(cloud.grid, batch, index.contiguous(), cloud.count, n, connectivity, keys)
+    _raise_on_status("cloud_components", comp.status)
+    at = index.clamp(0, batch * nodes - 1).long()
+    minus = torch.full((n,), -1, dtype=torch.int32, device=index.device)
+    return (torch.where(rows, comp.labels.reshape(-1)[at], minus), torch.where(rows, comp.sizes.reshape(-1)[at], minus + 1),
+            comp.count)
+
+
+def dominant_joint(jacobian: torch.Tensor) -> torch.Tensor:
+    """``[n]`` int32: the action component whose Jacobian column moves the point most, ``argmax_a |J[a]|_2`` of ``jacobian``
+    ``[n, A, 3]`` (compared through the squared norms ``x*x + y*y + z*z``, ties to the lowest a).  As ``keys`` of
+    ``cloud_components`` it segments a cloud into the parts each joint moves most."""
+    if not torch.is_tensor(jacobian) or jacobian.dim() != 3 or jacobian.shape[2] != 3 or jacobian.shape[1] < 1:
+        raise ValueError("dominant_joint: jacobian must be [n, A, 3]")
+    x, y, z = jacobian.unbind(dim=2)
+    return torch.argmax(x * x + y * y + z * z, dim=1).to(torch.int32)
+
+
+def _component_flags(grid: FieldGrid, batch: int, index: torch.Tensor, count: Optional[torch.Tensor], extent: int,
+                     connectivity: int, min_nodes: Optional[int], largest_only: bool, eager: bool):
+    """fp32 0 / 1 per list entry: the entry's component (among the list's nodes) survives the filter; and the status word."""
+    comp = _list_components(grid, batch, index, count, extent, connectivity)
+    if eager:
+        _raise_on_status("extract_field", comp.status)
+    keep = comp.keep(1 if min_nodes is None else min_nodes, largest_only).reshape(-1)
+    # (rows past the device count of a capacity form hold no index: clamped, and the selection never reads their flag)
+    return keep[index[:extent].clamp(0, batch * grid.num_nodes - 1).long()].to(torch.float32), comp.status
+
+
 class _Stage:
     """The running list of the pipeline: (indices, device count, launch extent).  Eager extraction reads the count after each
     selection to size the next launch exactly; a capture-safe one keeps every intermediate list at B*N entries (4 bytes per
@@ -193,7 +346,8 @@ def extract_field(model, pixel_encoding: PixelEncoding, grid: FieldGrid, density
                   cull: Optional[float] = None, proposal_level: int = -1, in_frustum: bool = True,
                   view_direction: Optional[Sequence[float]] = None, want_color: bool = True, want_jacobian: bool = True,
                   max_points: Optional[int] = None, views_per_scene: int = 1, fuse: str = "mean",
-                  min_views: int = 1) -> FieldPointCloud:
+                  min_views: int = 1, min_component_nodes: Optional[int] = None, largest_only: bool = False,
+                  connectivity: int = 6) -> FieldPointCloud:
     """Every node of ``grid`` -- per context image of ``pixel_encoding`` -- that
 
     1. (``in_frustum``) projects inside the context image with positive camera depth,
@@ -208,11 +362,20 @@ def extract_field(model, pixel_encoding: PixelEncoding, grid: FieldGrid, density
     ``views_per_scene=V > 1``: the context images are B / V scenes of V consecutive calibrated views in one world frame, and
     ONE cloud per scene comes back (``_extract_field_fused``): ``index`` is the fused global index
     ``g*N + n``, ``density`` the ``fuse`` ("mean", "min", "max") of the views that see the node, colour and Jacobian the
-    density-weighted mean over those views, ``views`` their bitmask.  A node needs ``min_views`` views that see it."""
+    density-weighted mean over those views, ``views`` their bitmask.  A node needs ``min_views`` views that see it.
+
+    ``min_component_nodes=K`` and / or ``largest_only``: the survivors of the density selection are
+    labelled into connected components (``connectivity`` 6 or 14, among the survivors of one batch element / scene) on the
+    device, and only the rows of the components of at least K nodes -- ``largest_only``: of the largest of them, ties to the
+    smallest label -- are kept, by the same ordered selection; the coordinate pass and the full decoder pass run on the kept
+    rows only, ``stage_counts`` / ``stage_names`` get a ``"components"`` entry, and the capacity form leaves the status word of
+    the labelling in the attribute ``components_status`` of the result.  With both off nothing changes."""
     dec = model.decoder
     if not isinstance(dec, ActionDecoderJacobian):
         raise TypeError("extract_field needs one of the fused action decoders")
     _check_fusion_arguments("extract_field", pixel_encoding.extrinsics.shape[0], views_per_scene, fuse, min_views)
+    _check_component_arguments("extract_field", connectivity, min_component_nodes)
+    filtering = min_component_nodes is not None or bool(largest_only)
     if views_per_scene > 1 and cull is not None:
         raise ValueError("extract_field: cull with views_per_scene > 1 has no single meaning (a proposal cull is per view)")
     is_flow = isinstance(dec, ActionDecoderFlowMlp)
@@ -241,7 +404,8 @@ def extract_field(model, pixel_encoding: PixelEncoding, grid: FieldGrid, density
     cams = _cameras(pixel_encoding, False, action_dim=dec.kernel_action_dim if want_jacobian else None)
     if views_per_scene > 1:
         return _extract_field_fused(model, pixel_encoding, grid, float(density_threshold), cams, in_frustum, view_direction,
-                                    want_color, want_jacobian, max_points, views_per_scene, fuse, min_views)
+                                    want_color, want_jacobian, max_points, views_per_scene, fuse, min_views,
+                                    (connectivity, min_component_nodes, bool(largest_only)) if filtering else None)
     stage = _Stage(total)
     counts, names = [], []
 
@@ -282,11 +446,19 @@ def extract_field(model, pixel_encoding: PixelEncoding, grid: FieldGrid, density
     if stage.extent > 0:
         values = torch.empty(stage.extent, **f32)
         hip.field_forward(cg, stage.indices, stage.count, stage.extent, cams, fmap, density=values, **common)
-        select("density", values, density_threshold, False, True)
+        select("density", values, density_threshold, False, not filtering)
     else:
         stage.indices, stage.count = torch.empty(0, **i32), None
         counts.append(torch.zeros(1, **i32))
         names.append("density")
+    components_status = None
+    if filtering and stage.extent > 0:
+        flags, components_status = _component_flags(grid, b, stage.indices, stage.count, stage.extent, connectivity,
+                                                    min_component_nodes, bool(largest_only), eager)
+        select("components", flags, 0.5, False, True)
+    elif filtering:
+        counts.append(torch.zeros(1, **i32))
+        names.append("components")
     n = stage.extent
     a_dim = dec.kernel_action_dim
     index = stage.indices[:n]
@@ -305,6 +477,8 @@ def extract_field(model, pixel_encoding: PixelEncoding, grid: FieldGrid, density
                               jacobian_precision=dec.j_precision if want_jacobian else None, **common)
         else:
             hip.field_forward(cg, index, stage.count, n, cams, fmap, density=cloud.density, **common)
+    if components_status is not None:
+        cloud.components_status = components_status
     return cloud
 
 
@@ -399,7 +573,7 @@ def _per_view_rows(dec, n, views, want_color, want_jacobian, dev):
 
 
 def _extract_field_fused(model, enc, grid, threshold, cams, in_frustum, view_direction, want_color, want_jacobian, max_points,
-                         views, mode, min_views) -> FieldPointCloud:
+                         views, mode, min_views, components=None) -> FieldPointCloud:
     """extract_field for scenes of ``views`` views: dense per-view density pass, fuse, ordered selection on the fused values,
     coordinates, the decoder on the survivors of every view, combine.  One host read (the survivor count) without
     ``max_points``, none with it."""
@@ -418,15 +592,30 @@ def _extract_field_fused(model, enc, grid, threshold, cams, in_frustum, view_dir
     del values
     # an invalid node (fused = 0) must not pass a threshold <= 0: -inf in its place, in the buffer nothing else reads
     fused.masked_fill_(~valid, -math.inf)
-    capacity = scenes * nodes if max_points is None else max_points
+    # (with a component filter behind it the density selection keeps every survivor: a truncated list would cut components)
+    capacity = scenes * nodes if max_points is None or components is not None else max_points
     index, count = torch.empty(max(capacity, 1), **i32), torch.empty(1, **i32)
     hip.field_select(cg, scenes, scenes * nodes, index, count, values=fused.reshape(-1), threshold=threshold)
     n, dev_count = (int(count.item()), None) if max_points is None else (capacity, count)
     index = index[:n]
+    stage_counts, stage_names, components_status = (count,), ("density",), None
+    if components is not None:
+        kept, count = torch.empty(max(n if max_points is None else max_points, 1), **i32), torch.empty(1, **i32)
+        if n > 0:
+            flags, components_status = _component_flags(grid, scenes, index, dev_count, n, components[0], components[1],
+                                                        components[2], max_points is None)
+            hip.field_select(cg, scenes, n, kept, count, values=flags, threshold=0.5, indices=index, count=dev_count)
+        else:
+            count.zero_()
+        n, dev_count = (int(count.item()), None) if max_points is None else (max_points, count)
+        index = kept[:n]
+        stage_counts, stage_names = stage_counts + (count,), stage_names + ("components",)
     # (padded rows of a capacity form hold no index: clamped, so the gather stays inside the buffer)
     at = index.long() if dev_count is None else index.clamp(0, scenes * nodes - 1).long()
     cloud = FieldPointCloud(grid=grid, index=index, xyz=torch.empty(n, 3, **f32), density=fused.reshape(-1)[at], color=None,
-                            jacobian=None, count=count, stage_counts=(count,), stage_names=("density",))
+                            jacobian=None, count=count, stage_counts=stage_counts, stage_names=stage_names)
+    if components_status is not None:
+        cloud.components_status = components_status
     if n > 0:
         hip.field_points(cg, scenes, index, dev_count, n, cloud.xyz)
     rows = _per_view_rows(dec, n, views, want_color, want_jacobian, dev)
@@ -590,7 +779,8 @@ def mesh_from_values(grid: FieldGrid, values: torch.Tensor, threshold: float, *,
 def extract_mesh(model, pixel_encoding: PixelEncoding, grid: FieldGrid, density_threshold: float, *, in_frustum: bool = True,
                  want_color: bool = True, want_jacobian: bool = True, view_direction: Optional[Sequence[float]] = None,
                  max_vertices: Optional[int] = None, max_triangles: Optional[int] = None, views_per_scene: int = 1,
-                 fuse: str = "mean", min_views: int = 1) -> FieldMesh:
+                 fuse: str = "mean", min_views: int = 1, min_component_nodes: Optional[int] = None,
+                 largest_only: bool = False) -> FieldMesh:
     """The surface ``decoder_density == density_threshold`` of the context image(s) over ``grid``, with the colour head's
     output and the Jacobian ``[A, 3]`` AT every vertex (what ``njf_points_forward`` returns for that position and batch
     element).  ``in_frustum``: nodes outside the context view are invalid -- the surface ends where the view ends.  The
@@ -599,11 +789,18 @@ def extract_mesh(model, pixel_encoding: PixelEncoding, grid: FieldGrid, density_
     ``views_per_scene=V > 1``: ONE mesh per scene of V consecutive views -- the surface of the ``fuse``d
     density with the nodes that fewer than ``min_views`` views see (``in_frustum``) invalid; ``vertex_node``, the cells and
     ``batch_index`` are in scene space; colour and Jacobian are the density-weighted mean over the views that see the vertex,
-    ``vertex_views`` their bitmask."""
+    ``vertex_views`` their bitmask.
+
+    ``min_component_nodes=K`` and / or ``largest_only``: the inside nodes are labelled into connected
+    components at connectivity 14 -- the mesh's own: the edges of the Kuhn tetrahedra -- and the nodes of the components below
+    K nodes (``largest_only``: of all but the largest) become invalid for the mesher, which removes exactly the tetrahedra
+    that carry their surface.  The capacity form leaves the labelling's status word in the attribute ``components_status``."""
     dec = model.decoder
     if not isinstance(dec, ActionDecoderJacobian):
         raise TypeError("extract_mesh needs one of the fused action decoders")
     _check_fusion_arguments("extract_mesh", pixel_encoding.extrinsics.shape[0], views_per_scene, fuse, min_views)
+    _check_component_arguments("extract_mesh", 14, min_component_nodes)
+    components = (min_component_nodes, bool(largest_only)) if min_component_nodes is not None or largest_only else None
     is_flow = isinstance(dec, ActionDecoderFlowMlp)
     if want_jacobian and is_flow:
         raise NotImplementedError("flow_mlp predicts the scene flow directly; it has no Jacobian")
@@ -621,7 +818,8 @@ def extract_mesh(model, pixel_encoding: PixelEncoding, grid: FieldGrid, density_
     cams = _cameras(pixel_encoding, False, action_dim=dec.kernel_action_dim if want_jacobian else None)
     if views_per_scene > 1:
         return _extract_mesh_fused(model, pixel_encoding, grid, float(density_threshold), cams, in_frustum, view_direction,
-                                   want_color, want_jacobian, max_vertices, max_triangles, views_per_scene, fuse, min_views)
+                                   want_color, want_jacobian, max_vertices, max_triangles, views_per_scene, fuse, min_views,
+                                   components)
     w, bd, bc, bj = dec.packed()
     if is_flow:
         gmap, base = ActionDecoderJacobian.hoisted_map(dec, feats), 0
@@ -632,8 +830,12 @@ def extract_mesh(model, pixel_encoding: PixelEncoding, grid: FieldGrid, density_
     values = torch.empty(b, grid.num_nodes, **f32)
     hip.field_forward(cg, None, None, total, cams, fmap, mode=1, w_all=w, b_density=bd, density=values.reshape(-1),
                       precision=dec.precision, **goffs)
-    mesh = _mesh_geometry(grid, values, float(density_threshold), None, cams if in_frustum else None, max_vertices,
+    keep, components_status = _mesh_keep(grid, values, float(density_threshold), None, cams if in_frustum else None, components,
+                                         max_vertices is None)
+    mesh = _mesh_geometry(grid, values, float(density_threshold), keep, cams if in_frustum else None, max_vertices,
                           max_triangles)
+    if components_status is not None:
+        mesh.components_status = components_status
     n = mesh.vertex_node.shape[0]
     if want_color:
         mesh.color = torch.empty(n, 3, **f32)
@@ -649,8 +851,24 @@ def extract_mesh(model, pixel_encoding: PixelEncoding, grid: FieldGrid, density_
     return mesh
 
 
+def _mesh_keep(grid: FieldGrid, values: torch.Tensor, threshold: float, valid, cams, components, eager: bool):
+    """(``valid & ~dropped`` for the mesher, status word) of the component filter ``components`` = (min nodes, largest only) on
+    the dense values; (``valid``, None) without one.  The labelling sees the mesher's own inside and valid predicates."""
+    if components is None:
+        return valid, None
+    comp = _components(grid, values.shape[0], 14, values.device, values=values.reshape(-1), threshold=threshold, valid=valid,
+                       cams=cams)
+    if eager:
+        _raise_on_status("extract_mesh", comp.status)
+    # the mesher's mask: valid and not an inside node of a dropped component (an outside node keeps its validity -- `keep` is
+    # false on it by definition, and the surface of a kept component is made of edges that end on outside nodes)
+    inside_dropped = (comp.labels >= 0) & ~comp.keep(1 if components[0] is None else components[0], components[1])
+    keep = ~inside_dropped if valid is None else valid.to(torch.bool) & ~inside_dropped
+    return keep.contiguous(), comp.status
+
+
 def _extract_mesh_fused(model, enc, grid, threshold, cams, in_frustum, view_direction, want_color, want_jacobian, max_vertices,
-                        max_triangles, views, mode, min_views) -> FieldMesh:
+                        max_triangles, views, mode, min_views, components=None) -> FieldMesh:
     """extract_mesh for scenes of ``views`` views: dense per-view density pass, fuse, the six meshing launches on the fused
     values with ``valid``, the decoder at every vertex for every view, combine."""
     dec = model.decoder
@@ -663,7 +881,10 @@ def _extract_mesh_fused(model, enc, grid, threshold, cams, in_frustum, view_dire
                       precision=dec.precision, **goffs)
     fused, _, valid = _fuse(grid, values, cams if in_frustum else None, views, mode, min_views)
     del values
+    valid, components_status = _mesh_keep(grid, fused, threshold, valid, None, components, max_vertices is None)
     mesh = _mesh_geometry(grid, fused, threshold, valid, None, max_vertices, max_triangles)
+    if components_status is not None:
+        mesh.components_status = components_status
     n = mesh.vertex_node.shape[0]
     dev_count = None if max_vertices is None else mesh.vertex_count
     rows = _per_view_rows(dec, n, views, want_color, want_jacobian, dev)

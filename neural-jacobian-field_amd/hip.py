@@ -160,6 +160,8 @@ _SIGNATURES = {
                        C.c_int),
     "njf_field_combine": ([_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.POINTER(Cameras), _vp, _vp, _vp, C.c_int, _vp, _vp, _vp,
                            _vp], C.c_int),
+    "njf_field_components": ([C.POINTER(FieldGrid), C.POINTER(Cameras), C.c_int, _vp, C.c_float, _vp, _vp, _vp, C.c_int, _vp,
+                              C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp], C.c_int),
     "njf_pack_resnetfc_backward": ([C.POINTER(ResnetFcWeights), _vp, C.c_int, _vp], C.c_int),
     "njf_resnetfc_backward": ([_vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp], C.c_int),
     "njf_pack_transformer_backward": ([_vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, _vp], C.c_int),
@@ -808,6 +810,49 @@ def field_combine(xyz: torch.Tensor, node: torch.Tensor, count, capacity: int, n
             _int32_ptr(count, "count"), int(capacity), int(nodes_per_scene), int(views), None if cams is None else C.byref(cams),
             _ptr(density, "density"), _ptr(color, "color"), _ptr(jacobian, "jacobian"), int(action_dim), _ptr(out_color, "out_color"),
             _ptr(out_jacobian, "out_jacobian"), _byte_ptr(out_views, "out_views"))
+
+
+# ---- connected components of the inside nodes (include/njf_hip.h: njf_field_components) ---------------------------------
+FIELD_COMPONENTS_BLOCK = 1024          # NJF_FIELD_COMPONENTS_BLOCK: nodes one workgroup of the four launches covers
+FIELD_COMPONENTS_CONNECTIVITIES = (6, 14)
+FIELD_COMPONENTS_PHASES = (1, 2, 4, 8)  # NJF_FIELD_COMPONENTS_INIT / _MERGE / _LABEL / _SIZES: one launch each
+FIELD_COMPONENTS_ALL = 15              # NJF_FIELD_COMPONENTS_ALL
+FIELD_COMPONENTS_E_LOCAL = 1           # NJF_FIELD_COMPONENTS_E_*: bits of the status word (an iteration cap was passed)
+FIELD_COMPONENTS_E_FIND = 2
+FIELD_COMPONENTS_E_UNION = 4
+
+
+def field_components(grid: FieldGrid, batch: int, connectivity: int, labels: torch.Tensor, sizes: torch.Tensor,
+                     count: torch.Tensor, status: torch.Tensor, values=None, threshold: float = 0.0, valid=None,
+                     cams: Optional[Cameras] = None, indices=None, list_count=None, capacity: int = 0, keys=None,
+                     phase: int = FIELD_COMPONENTS_ALL, workspace: Optional[torch.Tensor] = None) -> None:
+    """njf_field_components: ``labels`` / ``sizes`` (int32 [B*N]), ``count`` and ``status`` (int32 [1]) of the components of the
+    inside nodes -- dense form: ``values`` >= ``threshold`` with ``valid`` and the frustum of ``cams``; list form: the first
+    min(``list_count``, ``capacity``) entries of the ascending ``indices``.  ``keys``: int32 [B*N] (dense) or [capacity]
+    (list), joining only nodes of equal key.  ``phase`` / ``workspace`` (int32 [2*B*N], [3*B*N] for a keyed list): run the
+    four launches one by one on a workspace of the caller's, to time them apart."""
+    total = batch * grid.dims[0] * grid.dims[1] * grid.dims[2]
+    for name, t in (("labels", labels), ("sizes", sizes), ("values", values), ("valid", valid)):
+        if t is not None and t.numel() != total:
+            raise ValueError(f"njf_hip: field_components {name} must hold batch * nx*ny*nz = {total} elements")
+    if count.numel() != 1 or status.numel() != 1:
+        raise ValueError("njf_hip: field_components needs one int32 count and one int32 status")
+    if indices is not None and indices.numel() < capacity:
+        raise ValueError("njf_hip: the index list is shorter than the capacity")
+    if keys is not None and keys.numel() < (total if indices is None else capacity):
+        raise ValueError("njf_hip: field_components keys are shorter than the nodes (dense form) / the capacity (list form)")
+    slabs = 3 if (indices is not None and keys is not None) else 2
+    if workspace is None:
+        workspace = torch.empty(slabs * max(total, 1), dtype=torch.int32, device=labels.device)
+    elif workspace.numel() < slabs * total:
+        raise ValueError(f"njf_hip: field_components workspace must hold {slabs} * batch * nx*ny*nz int32")
+    if cams is not None:
+        _note_device(cams, "cameras")
+    _launch("njf_field_components", load_library().njf_field_components, C.byref(grid), None if cams is None else C.byref(cams),
+            int(batch), _ptr(values, "values"), float(threshold), _byte_ptr(valid, "valid"), _int32_ptr(indices, "indices"),
+            _int32_ptr(list_count, "count"), int(capacity), _int32_ptr(keys, "keys"), int(connectivity), int(phase),
+            _int32_ptr(labels, "labels"), _int32_ptr(sizes, "sizes"), _int32_ptr(count, "component_count"),
+            _int32_ptr(status, "status"), _int32_ptr(workspace, "workspace"))
 
 
 def solve_action(mean_position, jacobian, projection, target_flow, visible_mask, init_action, iterations: int,
