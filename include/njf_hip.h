@@ -520,6 +520,46 @@ int njf_field_components(const NjfFieldGrid* grid, const NjfCameras* cams, int b
                          int connectivity, int phase, int* labels, int* sizes, int* component_count, int* status,
                          int* workspace, void* stream);
 
+/* ---- coarse-to-fine band (additive within ABI v20): the fine density pass only near the surface ------------------------- */
+/* The semantics are fixed so the result is checkable against a plain restatement.  `grid` is the FINE
+ * grid; factor k in {2, 4, 8, 16}; every axis needs (n_c - 1) % k == 0 and n_c >= k + 1; m_c = (n_c - 1) / k.  The COARSE
+ * grid has the origin of the fine one, the step k*step (exact: k is a power of two) and the dims (m_x+1, m_y+1, m_z+1), so
+ * coarse node j IS fine node k*j; M = prod(m_c + 1) coarse nodes and Nb = prod(m_c) BLOCKS per batch element, block (jx, jy,
+ * jz) with 0 <= j_c < m_c at the local index (jx*m_y + jy)*m_z + jz.
+ *   hit(b, q) = (coarse_valid == NULL || coarse_valid[b*M + q] != 0) && coarse_values[b*M + q] >= coarse_threshold
+ *   (NaN: no hit; a value equal to the threshold: a hit).
+ *   block_active(b, j) iff some coarse node q with max(0, j_c - dilate) <= q_c <= min(m_c, j_c + 1 + dilate) on every axis is
+ *   a hit (dilate 0: the block's own eight corners).
+ *   Fine node (ix, iy, iz) of element b is in the BAND iff some active block j of b has j_c*k <= i_c <= (j_c + 1)*k on every
+ *   axis (block faces are shared: a node belongs to up to eight blocks).  Nothing crosses batch elements.
+ * coarse_values: device fp32 [batch*M]; coarse_valid: device bytes [batch*M] or NULL; block_active: device bytes [batch*Nb],
+ * 0 / 1; band: device bytes [batch*N], 0 / 1; out_indices: the ASCENDING global indices of the band nodes -- the first
+ * out_capacity of them (may be NULL when out_capacity == 0); *out_count (device int32): the TRUE number of band nodes.
+ * workspace: device int32 [ceil(batch*N / NJF_FIELD_BAND_BLOCK)], caller-owned.  Four launches (blocks; band bytes + counts;
+ * the scan of njf_field_select; the scatter) in integer arithmetic without atomics: the output bytes are reproducible.
+ * NJF_E_VALUE: a factor not in the set, dims not 1 mod k or below k + 1, dilate outside [0, 2], a non-finite threshold;
+ * NJF_E_NULL: a missing pointer; NJF_E_SHAPE: as for njf_field_select.  Every check precedes the first launch. */
+#define NJF_FIELD_BAND_BLOCK 1024
+int njf_field_band(const NjfFieldGrid* grid, int factor, int dilate, int batch, const float* coarse_values,
+                   const unsigned char* coarse_valid, float coarse_threshold, unsigned char* block_active, unsigned char* band,
+                   int* out_indices, int* out_count, int out_capacity, int* workspace, void* stream);
+
+/* out[indices[i]] = values[i] for i < min(*count, capacity) (count: device int32, NULL = capacity; it is read on the device,
+ * workgroups past it leave and rows past it are never read).  values: device fp32 [capacity], indices: device int32
+ * [capacity], out: device fp32 [out_size]; an index outside [0, out_size) is skipped.  Indices that repeat give an
+ * unspecified winner (the lists of this library do not repeat).  One launch. */
+int njf_field_scatter(const float* values, const int* indices, const int* count, int capacity, float* out, int out_size,
+                      void* stream);
+
+/* *leaks (device int32) = the number of entries g of the list (`indices`: ascending global indices of INSIDE nodes, the
+ * first min(*count, capacity); count NULL = capacity; entries outside [0, batch*N) are dropped) that have a neighbour g +- one
+ * of the seven mesh directions, inside the grid and the same batch element (no wrap at the faces, as for
+ * njf_field_components), whose band byte is 0.  0 proves that every connected component the band touches lies wholly in it
+ * with all of its surface edges.  A 4-byte memset and one launch; one integer atomic add per
+ * workgroup, so the result does not depend on scheduling. */
+int njf_field_band_leaks(const NjfFieldGrid* grid, int batch, const unsigned char* band, const int* indices, const int* count,
+                         int capacity, int* leaks, void* stream);
+
 /* ---- stand-alone sampler / compositing ops (API parity with the un-fused reference calls) -- */
 /* RaySamples.get_weights (ray_samplers.py:77-101): deltas, densities [N,S] -> weights [N,S]. */
 int njf_alpha_weights(const float* deltas, const float* densities, int rays, int samples, float* weights, void* stream);

@@ -3128,6 +3128,195 @@ __global__ void __launch_bounds__(NJF_CC_THREADS) components_size_kernel(Compone
   }
 }
 
+// ---- coarse-to-fine band: the fine density pass only near the surface --------------------------------
+// The fine grid (nx, ny, nz) with (n_c - 1) % k == 0 is cut into BLOCKS of k^3 cells: m_c = (n_c - 1) / k per axis, block
+// (jx, jy, jz) has the local index (jx*m_y + jy)*m_z + jz.  Coarse node j IS fine node k*j (k is a power of two, so k*step is
+// exact), M = prod(m_c + 1) per element.  hit(b, q) = (coarse_valid == null || coarse_valid[b, q]) && coarse_values[b, q] >=
+// threshold (NaN: no hit); block j is ACTIVE iff a coarse node q with max(0, j_c - d) <= q_c <= min(m_c, j_c + 1 + d) on every
+// axis is a hit; fine node i is in the BAND iff an active block j has j_c*k <= i_c <= (j_c + 1)*k on every axis -- the
+// candidates per axis are {ceil(i_c / k) - 1, floor(i_c / k)} clipped to [0, m_c - 1].  Workgroups of 1024 consecutive nodes,
+// item-major, like the selection; integer arithmetic, no atomics apart from the one integer add per workgroup of the leak
+// count: the output bytes do not depend on scheduling.
+#define NJF_BAND_THREADS 256
+#define NJF_BAND_ITEMS (NJF_FIELD_BAND_BLOCK / NJF_BAND_THREADS)
+static_assert(NJF_BAND_ITEMS * NJF_BAND_THREADS == NJF_FIELD_BAND_BLOCK && NJF_FIELD_BAND_BLOCK == NJF_FIELD_SELECT_BLOCK,
+              "band block");
+struct BandArgs {
+  int dims[3];                   // fine grid
+  int nodes, total;              // N, B*N
+  int batch;
+  int shift;                     // log2 k
+  int m[3];                      // blocks per axis
+  int nb;                        // Nb = m_x*m_y*m_z
+  int dilate;
+  const float* cvalues;          // [B, M]
+  const unsigned char* cvalid;   // [B, M] or null
+  float cthreshold;
+  unsigned char* block_active;   // [B*Nb]
+  unsigned char* band;           // [B*N]
+  int* out_indices;
+  int* out_count;
+  int out_capacity;
+  int* block_counts;             // [ceil(B*N / 1024)]: counts, then (after the scan) exclusive offsets
+};
+
+// one thread per block: any hit among its (2d + 2)^3 clipped coarse nodes
+__global__ void __launch_bounds__(NJF_BAND_THREADS) band_blocks_kernel(BandArgs a) {
+  const int g = blockIdx.x * NJF_BAND_THREADS + threadIdx.x;
+  if (g >= a.batch * a.nb) return;
+  const int b = g / a.nb, j = g - b * a.nb;
+  const int myz = a.m[1] * a.m[2];
+  const int jx = j / myz, r = j - jx * myz;
+  const int jy = r / a.m[2], jz = r - jy * a.m[2];
+  const int cy = a.m[1] + 1, cz = a.m[2] + 1;
+  const size_t cbase = (size_t)b * (size_t)(a.m[0] + 1) * (size_t)(cy * cz);
+  const int d = a.dilate;
+  const int x0 = max(0, jx - d), x1 = min(a.m[0], jx + 1 + d);
+  const int y0 = max(0, jy - d), y1 = min(a.m[1], jy + 1 + d);
+  const int z0 = max(0, jz - d), z1 = min(a.m[2], jz + 1 + d);
+  bool hit = false;
+  for (int qx = x0; qx <= x1; ++qx)
+    for (int qy = y0; qy <= y1; ++qy)
+      for (int qz = z0; qz <= z1; ++qz) {
+        const size_t q = cbase + (size_t)((qx * cy + qy) * cz + qz);
+        hit |= (!a.cvalid || a.cvalid[q] != 0) && a.cvalues[q] >= a.cthreshold;  // (NaN compares false)
+      }
+  a.block_active[g] = hit ? 1 : 0;
+}
+
+// is node gi (a global index below B*N) inside an active block of its element?  At most eight block bytes.
+__device__ __forceinline__ bool band_node(const BandArgs& a, int gi) {
+  const int b = gi / a.nodes, n = gi - b * a.nodes;
+  const int yz = a.dims[1] * a.dims[2];
+  const int ix = n / yz, r = n - ix * yz;
+  const int iy = r / a.dims[2], iz = r - iy * a.dims[2];
+  const int round_up = (1 << a.shift) - 1;
+  const int x0 = max(((ix + round_up) >> a.shift) - 1, 0), x1 = min(ix >> a.shift, a.m[0] - 1);
+  const int y0 = max(((iy + round_up) >> a.shift) - 1, 0), y1 = min(iy >> a.shift, a.m[1] - 1);
+  const int z0 = max(((iz + round_up) >> a.shift) - 1, 0), z1 = min(iz >> a.shift, a.m[2] - 1);
+  const unsigned char* act = a.block_active + (size_t)b * (size_t)a.nb;
+  bool in = false;
+  for (int jx = x0; jx <= x1; ++jx)
+    for (int jy = y0; jy <= y1; ++jy)
+      for (int jz = z0; jz <= z1; ++jz) in |= act[(jx * a.m[1] + jy) * a.m[2] + jz] != 0;
+  return in;
+}
+
+// band bytes + per-workgroup counts
+__global__ void __launch_bounds__(NJF_BAND_THREADS) band_count_kernel(BandArgs a) {
+  __shared__ int wave_count[NJF_BAND_THREADS / 64];
+  int n = 0;
+#pragma unroll
+  for (int it = 0; it < NJF_BAND_ITEMS; ++it) {
+    const long long i = (long long)blockIdx.x * NJF_FIELD_BAND_BLOCK + it * NJF_BAND_THREADS + threadIdx.x;
+    bool in = false;
+    if (i < a.total) {
+      in = band_node(a, (int)i);
+      a.band[i] = in ? 1 : 0;
+    }
+    n += __popcll(__ballot(in));  // wave-uniform
+  }
+  if ((threadIdx.x & 63) == 0) wave_count[threadIdx.x >> 6] = n;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int s = 0;
+    for (int w = 0; w < NJF_BAND_THREADS / 64; ++w) s += wave_count[w];
+    a.block_counts[blockIdx.x] = s;
+  }
+}
+
+// the ascending global indices of the band nodes (the band bytes and the scanned offsets come from earlier launches)
+__global__ void __launch_bounds__(NJF_BAND_THREADS) band_scatter_kernel(BandArgs a) {
+  constexpr int WAVES = NJF_BAND_THREADS / 64;
+  __shared__ int wave_count[NJF_BAND_ITEMS][WAVES];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  unsigned flags = 0;
+  int before[NJF_BAND_ITEMS];
+#pragma unroll
+  for (int it = 0; it < NJF_BAND_ITEMS; ++it) {
+    const long long i = (long long)blockIdx.x * NJF_FIELD_BAND_BLOCK + it * NJF_BAND_THREADS + threadIdx.x;
+    const bool in = i < a.total && a.band[i] != 0;
+    flags |= in ? 1u << it : 0u;
+    const unsigned long long m = __ballot(in);
+    before[it] = __popcll(m & ((1ull << lane) - 1ull));
+    if (lane == 0) wave_count[it][wave] = __popcll(m);
+  }
+  __syncthreads();
+  int base = a.block_counts[blockIdx.x];
+#pragma unroll
+  for (int it = 0; it < NJF_BAND_ITEMS; ++it) {
+    int rank = base;
+    for (int w = 0; w < wave; ++w) rank += wave_count[it][w];
+    if ((flags >> it) & 1u) {
+      rank += before[it];
+      if (rank < a.out_capacity) a.out_indices[rank] = blockIdx.x * NJF_FIELD_BAND_BLOCK + it * NJF_BAND_THREADS + threadIdx.x;
+    }
+    for (int w = 0; w < WAVES; ++w) base += wave_count[it][w];
+  }
+}
+
+// out[indices[i]] = values[i] for i < min(*count, capacity); an index outside [0, out_size) is skipped
+__global__ void __launch_bounds__(256) field_scatter_kernel(const float* __restrict__ values, const int* __restrict__ indices,
+                                                            const int* __restrict__ count, int capacity, float* __restrict__ out,
+                                                            int out_size) {
+  const int entries = count ? min(max(*count, 0), capacity) : capacity;
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= entries) return;  // (a workgroup past the count leaves; rows past the count are never read)
+  const int g = indices[i];
+  if (g >= 0 && g < out_size) out[g] = values[i];
+}
+
+struct BandLeakArgs {
+  int dims[3];
+  int nodes, total;
+  const unsigned char* band;  // [B*N]
+  const int* indices;         // the inside nodes, ascending global indices
+  const int* count;           // or null
+  int capacity;
+  int* leaks;
+};
+
+// entries with a neighbour g +- dir_k (the seven mesh directions, inside the grid: no wrap at the faces) outside the band
+__global__ void __launch_bounds__(NJF_BAND_THREADS) band_leaks_kernel(BandLeakArgs a) {
+  __shared__ int wave_count[NJF_BAND_THREADS / 64];
+  const int entries = a.count ? min(max(*a.count, 0), a.capacity) : a.capacity;
+  const long long base = (long long)blockIdx.x * NJF_FIELD_BAND_BLOCK;
+  if (base >= entries) return;  // (uniform over the workgroup)
+  int n = 0;
+#pragma unroll
+  for (int it = 0; it < NJF_BAND_ITEMS; ++it) {
+    const long long i = base + it * NJF_BAND_THREADS + threadIdx.x;
+    bool leak = false;
+    if (i < entries) {
+      const int g = a.indices[i];
+      if (g >= 0 && g < a.total) {
+        const int node = g % a.nodes;
+        const int yz = a.dims[1] * a.dims[2];
+        const int ix = node / yz, r = node - ix * yz;
+        const int iy = r / a.dims[2], iz = r - iy * a.dims[2];
+#pragma unroll
+        for (int k = 0; k < 7; ++k) {
+          // direction k of the mesh table: (1,0,0) (0,1,0) (0,0,1) (1,1,0) (1,0,1) (0,1,1) (1,1,1)
+          const int dx = (0x59 >> k) & 1, dy = (0x6a >> k) & 1, dz = (0x74 >> k) & 1;
+          const int off = (dx * a.dims[1] + dy) * a.dims[2] + dz;
+          const bool up = ix + dx < a.dims[0] && iy + dy < a.dims[1] && iz + dz < a.dims[2];
+          const bool down = ix - dx >= 0 && iy - dy >= 0 && iz - dz >= 0;
+          if (up) leak |= a.band[g + off] == 0;
+          if (down) leak |= a.band[g - off] == 0;
+        }
+      }
+    }
+    n += __popcll(__ballot(leak));
+  }
+  if ((threadIdx.x & 63) == 0) wave_count[threadIdx.x >> 6] = n;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int s = 0;
+    for (int w = 0; w < NJF_BAND_THREADS / 64; ++w) s += wave_count[w];
+    if (s) atomicAdd(a.leaks, s);  // one integer add per workgroup: the sum does not depend on the order
+  }
+}
+
 // =============================================================================================
 // inverse dynamics: Levenberg-Marquardt on the linearised flow, one workgroup per batch element
 // =============================================================================================
@@ -5068,6 +5257,90 @@ extern "C" int njf_field_components(const NjfFieldGrid* grid, const NjfCameras* 
     if ((rc = launch_status())) return rc;
   }
   return NJF_OK;
+}
+
+// ---- coarse-to-fine band ------------------------------------------------------------------------------------------------------
+extern "C" int njf_field_band(const NjfFieldGrid* grid, int factor, int dilate, int batch, const float* coarse_values,
+                              const unsigned char* coarse_valid, float coarse_threshold, unsigned char* block_active,
+                              unsigned char* band, int* out_indices, int* out_count, int out_capacity, int* workspace,
+                              void* stream) {
+  if (!grid) return NJF_E_NULL;
+  if (factor != 2 && factor != 4 && factor != 8 && factor != 16) return NJF_E_VALUE;
+  if (dilate < 0 || dilate > 2) return NJF_E_VALUE;
+  if (!__builtin_isfinite(coarse_threshold)) return NJF_E_VALUE;
+  FieldList l;
+  int rc = make_field_list(grid, batch, nullptr, nullptr, 0, l);
+  if (rc) return rc;
+  BandArgs a;
+  a.shift = factor == 2 ? 1 : factor == 4 ? 2 : factor == 8 ? 3 : 4;
+  for (int c = 0; c < 3; ++c) {
+    if (grid->dims[c] < factor + 1 || (grid->dims[c] - 1) % factor != 0) return NJF_E_VALUE;
+    a.dims[c] = grid->dims[c];
+    a.m[c] = (grid->dims[c] - 1) / factor;
+  }
+  if (!coarse_values || !block_active || !band || !out_count || !workspace) return NJF_E_NULL;
+  if (out_capacity < 0 || (out_capacity > 0 && !out_indices)) return out_capacity < 0 ? NJF_E_SHAPE : NJF_E_NULL;
+  a.nodes = l.nodes;
+  a.total = l.total;
+  a.batch = batch;
+  a.nb = a.m[0] * a.m[1] * a.m[2];
+  a.dilate = dilate;
+  a.cvalues = coarse_values;
+  a.cvalid = coarse_valid;
+  a.cthreshold = coarse_threshold;
+  a.block_active = block_active;
+  a.band = band;
+  a.out_indices = out_indices;
+  a.out_count = out_count;
+  a.out_capacity = out_capacity;
+  a.block_counts = workspace;
+  hipStream_t s = (hipStream_t)stream;
+  const int blocks = (int)(((long long)a.total + NJF_FIELD_BAND_BLOCK - 1) / NJF_FIELD_BAND_BLOCK);
+  band_blocks_kernel<<<(batch * a.nb + NJF_BAND_THREADS - 1) / NJF_BAND_THREADS, NJF_BAND_THREADS, 0, s>>>(a);
+  if ((rc = launch_status())) return rc;
+  band_count_kernel<<<blocks, NJF_BAND_THREADS, 0, s>>>(a);
+  if ((rc = launch_status())) return rc;
+  select_scan_kernel<<<1, NJF_SELECT_THREADS, 0, s>>>(workspace, blocks, out_count);
+  if ((rc = launch_status())) return rc;
+  if (out_capacity > 0) {
+    band_scatter_kernel<<<blocks, NJF_BAND_THREADS, 0, s>>>(a);
+    if ((rc = launch_status())) return rc;
+  }
+  return NJF_OK;
+}
+
+extern "C" int njf_field_scatter(const float* values, const int* indices, const int* count, int capacity, float* out,
+                                 int out_size, void* stream) {
+  if (capacity < 0 || out_size < 0) return NJF_E_SHAPE;
+  if (capacity == 0) return NJF_OK;
+  if (!values || !indices || !out) return NJF_E_NULL;
+  const int blocks = (int)(((long long)capacity + 255) / 256);
+  field_scatter_kernel<<<blocks, 256, 0, (hipStream_t)stream>>>(values, indices, count, capacity, out, out_size);
+  return launch_status();
+}
+
+extern "C" int njf_field_band_leaks(const NjfFieldGrid* grid, int batch, const unsigned char* band, const int* indices,
+                                    const int* count, int capacity, int* leaks, void* stream) {
+  FieldList l;
+  int rc = make_field_list(grid, batch, nullptr, nullptr, 0, l);
+  if (rc) return rc;
+  if (capacity < 0) return NJF_E_SHAPE;
+  if (!band || !leaks || (capacity > 0 && !indices)) return NJF_E_NULL;
+  hipStream_t s = (hipStream_t)stream;
+  if (hipMemsetAsync(leaks, 0, sizeof(int), s) != hipSuccess) return launch_status();
+  if (capacity == 0) return NJF_OK;
+  BandLeakArgs a;
+  for (int c = 0; c < 3; ++c) a.dims[c] = grid->dims[c];
+  a.nodes = l.nodes;
+  a.total = l.total;
+  a.band = band;
+  a.indices = indices;
+  a.count = count;
+  a.capacity = capacity;
+  a.leaks = leaks;
+  const int blocks = (int)(((long long)capacity + NJF_FIELD_BAND_BLOCK - 1) / NJF_FIELD_BAND_BLOCK);
+  band_leaks_kernel<<<blocks, NJF_BAND_THREADS, 0, s>>>(a);
+  return launch_status();
 }
 
 extern "C" int njf_resnetfc_backward(const float* d_out, int d_out_dim, const float* activations, const float* w_backward,

@@ -330,6 +330,189 @@ def _component_flags(grid: FieldGrid, batch: int, index: torch.Tensor, count: Op
     return keep[index[:extent].clamp(0, batch * grid.num_nodes - 1).long()].to(torch.float32), comp.status
 
 
+# ---- coarse-to-fine band ----------------------------------------------------------------------------------
+@dataclass
+class FieldBand:
+    """The nodes of a fine grid near anything a coarse look at the field found occupied (``band_from_values``; the ``coarse``
+    keyword of extract_field / extract_mesh): ``block_active[b, j]`` says that block j (k^3 cells) of element b lies within
+    ``dilate`` coarse nodes of a hit, ``band[b, n]`` that node n lies in (or on the faces of) an active block; ``index`` holds
+    the ascending global indices of the band nodes -- exactly sized from an eager call, padded to the capacity otherwise --
+    and ``count`` their TRUE number."""
+
+    coarse_grid: FieldGrid
+    block_active: torch.Tensor   # [B, Nb] uint8
+    band: torch.Tensor           # [B, N] uint8
+    index: torch.Tensor          # [n] int32 global index b*N + n
+    count: torch.Tensor          # [1] int32
+
+
+def coarse_grid(grid: FieldGrid, coarse: int) -> FieldGrid:
+    """The grid of every ``coarse``-th node of ``grid`` per axis (``coarse`` in 2, 4, 8, 16; every axis of ``grid`` needs
+    ``(n - 1) % coarse == 0`` and ``n >= coarse + 1``): same origin, step ``coarse * step`` -- exact, a power of two -- so
+    coarse node j has the very coordinates of fine node ``coarse * j``."""
+    m = hip.field_band_blocks(grid.dims, coarse)
+    step = tuple(coarse * s for s in grid.step)
+    if any(float(np.float32(s)) != s for s in step):
+        raise ValueError(f"coarse_grid: {coarse} * step is not an fp32 (step {grid.step})")
+    return FieldGrid(grid.origin, step, tuple(mc + 1 for mc in m))
+
+
+def _check_band_arguments(name: str, grid: FieldGrid, coarse, coarse_threshold, dilate, default_threshold=None):
+    """The coarse threshold as a float (None without ``coarse``); ValueError on a bad factor, grid, dilation or threshold."""
+    if coarse is None:
+        if coarse_threshold is not None:
+            raise ValueError(f"{name}: coarse_threshold has no meaning without coarse")
+        return None
+    hip.field_band_blocks(grid.dims, coarse)
+    if isinstance(dilate, bool) or not isinstance(dilate, int) or not 0 <= dilate <= hip.FIELD_BAND_MAX_DILATE:
+        raise ValueError(f"{name}: coarse_dilate must be 0, 1 or 2 (got {dilate!r})")
+    threshold = default_threshold if coarse_threshold is None else coarse_threshold
+    if threshold is None or not math.isfinite(float(threshold)):
+        raise ValueError(f"{name}: coarse_threshold must be finite")
+    return float(threshold)
+
+
+def _band(grid: FieldGrid, coarse: int, values: torch.Tensor, threshold: float, valid, dilate: int, capacity: Optional[int]):
+    """The four band launches on coarse ``values`` [B, M].  ``capacity`` None: one host read (the count), ``index`` exactly
+    sized; else no host read and ``index`` padded (or cut) to the capacity."""
+    cgrid = coarse_grid(grid, coarse)
+    b, dev = values.shape[0], values.device
+    m = hip.field_band_blocks(grid.dims, coarse)
+    u8 = dict(dtype=torch.uint8, device=dev)
+    band = FieldBand(coarse_grid=cgrid, block_active=torch.empty(b, m[0] * m[1] * m[2], **u8),
+                     band=torch.empty(b, grid.num_nodes, **u8),
+                     index=torch.empty(b * grid.num_nodes if capacity is None else capacity, dtype=torch.int32, device=dev),
+                     count=torch.empty(1, dtype=torch.int32, device=dev))
+    hip.field_band(grid.c_grid(), coarse, dilate, b, values.reshape(-1), threshold, band.block_active, band.band, band.index,
+                   band.count, coarse_valid=valid)
+    if capacity is None:
+        band.index = band.index[:int(band.count.item())]
+    return band
+
+
+def band_from_values(grid: FieldGrid, coarse: int, coarse_values: torch.Tensor, coarse_threshold: float, *,
+                     coarse_valid: Optional[torch.Tensor] = None, dilate: int = 1, max_nodes: Optional[int] = None) -> FieldBand:
+    """The band of any scalar on the coarse grid, without the networks: ``coarse_values`` ``[B, M]`` fp32
+    on the GPU, M the node count of ``coarse_grid(grid, coarse)``.  A coarse node is a HIT iff it is valid (``coarse_valid``
+    ``[B, M]`` bool / uint8) and ``coarse_values >= coarse_threshold`` (NaN is none); a block of ``coarse``^3 cells is active iff
+    a hit lies among its corners or within ``dilate`` (0, 1, 2) coarse nodes of them; the band is every fine node in or on an
+    active block.  ``max_nodes=None``: one host read, ``index`` exactly sized.  ``max_nodes=M``: no host synchronisation,
+    ``index`` holds the first M band nodes and ``count`` their true number."""
+    hip.field_band_blocks(grid.dims, coarse)
+    threshold = _check_band_arguments("band_from_values", grid, coarse, coarse_threshold, dilate)
+    cgrid = coarse_grid(grid, coarse)
+    if (not torch.is_tensor(coarse_values) or coarse_values.dim() != 2 or coarse_values.dtype != torch.float32
+            or coarse_values.shape[1] != cgrid.num_nodes):
+        raise ValueError(f"band_from_values: coarse_values must be fp32 [B, {cgrid.num_nodes}]")
+    if coarse_values.shape[0] < 1 or coarse_values.shape[0] * grid.num_nodes >= 2 ** 31:
+        raise ValueError("band_from_values: batch * nx*ny*nz must stay below 2**31")
+    if max_nodes is not None and (isinstance(max_nodes, bool) or not isinstance(max_nodes, int) or max_nodes < 1):
+        raise ValueError(f"band_from_values: max_nodes must be an integer >= 1 (got {max_nodes!r})")
+    if coarse_valid is not None:
+        if (not torch.is_tensor(coarse_valid) or coarse_valid.dtype not in (torch.bool, torch.uint8)
+                or coarse_valid.shape != coarse_values.shape):
+            raise ValueError(f"band_from_values: coarse_valid must be bool or uint8 {tuple(coarse_values.shape)}")
+        if coarse_valid.device != coarse_values.device:
+            raise ValueError("band_from_values: coarse_valid and coarse_values must live on the same device")
+        coarse_valid = coarse_valid.contiguous()
+    if coarse_values.device.type != "cuda":
+        raise ValueError("band_from_values: coarse_values must live on the GPU; there is no CPU path")
+    return _band(grid, coarse, coarse_values.contiguous(), threshold, coarse_valid, dilate, max_nodes)
+
+
+def band_leaks(grid: FieldGrid, band: torch.Tensor, index: torch.Tensor, count: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``[1]`` int32 on the device: how many of the inside nodes ``index`` (ascending int32 global indices; the first ``count``
+    of them with a device count, all without) have a neighbour along one of the seven edge directions of the Kuhn tetrahedra,
+    in either sign, inside the grid and the same batch element, that is not in ``band`` (``[B, N]`` bool / uint8).  0 proves
+    that every connected component the band touches lies wholly in it, with all of its surface edges; the reverse does not
+    hold.  No host read."""
+    if not torch.is_tensor(band) or band.dim() != 2 or band.dtype not in (torch.bool, torch.uint8) or band.shape[1] != grid.num_nodes:
+        raise ValueError(f"band_leaks: band must be bool or uint8 [B, {grid.num_nodes}]")
+    if band.shape[0] < 1 or band.shape[0] * grid.num_nodes >= 2 ** 31:
+        raise ValueError("band_leaks: batch * nx*ny*nz must stay below 2**31")
+    if not torch.is_tensor(index) or index.dim() != 1 or index.dtype != torch.int32:
+        raise ValueError("band_leaks: index must be int32 [n]")
+    if count is not None and (not torch.is_tensor(count) or count.dtype != torch.int32 or count.numel() != 1):
+        raise ValueError("band_leaks: count must be one int32")
+    if band.device.type != "cuda" or index.device != band.device:
+        raise ValueError("band_leaks: band and index must live on one GPU; there is no CPU path")
+    return _leaks(grid, band.contiguous(), index.contiguous(), count, index.shape[0])
+
+
+def _leaks(grid: FieldGrid, band: torch.Tensor, index: torch.Tensor, count, extent: int) -> torch.Tensor:
+    leaks = torch.empty(1, dtype=torch.int32, device=band.device)
+    hip.field_band_leaks(grid.c_grid(), band.shape[0], band, index, count, extent, leaks)
+    return leaks
+
+
+def _extraction_band(model, enc, grid: FieldGrid, cams, coarse: int, threshold: float, dilate: int, eager: bool, views: int = 1,
+                     mode: str = "mean", min_views: int = 1, in_frustum: bool = True) -> FieldBand:
+    """The band of an extraction: the dense density-only pass on the coarse grid (a coarse node's density is the value the
+    dense fine pass gives at that node), for scenes of several views their fusion on the coarse grid, the band launches.  The
+    capacity forms keep the list at B*N entries (4 bytes per node) and read nothing on the host."""
+    dec = model.decoder
+    cgrid = coarse_grid(grid, coarse)
+    b = enc.extrinsics.shape[0]
+    fmap, goffs, w, bd, _, _ = _decoder_arguments(model, enc.features)
+    values = torch.empty(b, cgrid.num_nodes, dtype=torch.float32, device=enc.features.device)
+    hip.field_forward(cgrid.c_grid(), None, None, b * cgrid.num_nodes, cams, fmap, mode=1, w_all=w, b_density=bd,
+                      density=values.reshape(-1), precision=dec.precision, **goffs)
+    valid = None
+    if views > 1:
+        values, _, valid = _fuse(cgrid, values, cams if in_frustum else None, views, mode, min_views)
+    return _band(grid, coarse, values, threshold, valid, dilate, None if eager else (b // views) * grid.num_nodes)
+
+
+def _banded_values(model, enc, grid: FieldGrid, cams, band: FieldBand, in_frustum: bool, eager: bool, views: int = 1):
+    """What replaces the dense density pass: the per-view density [B, N] with the decoder's value at the band nodes (with
+    ``in_frustum``: at those the view sees) and 0 elsewhere -- nodes the band makes invalid downstream -- and the list the
+    values were computed on, as (index, device count, extent, compact values)."""
+    dec = model.decoder
+    dev = enc.features.device
+    b, nodes = enc.extrinsics.shape[0], grid.num_nodes
+    cg = grid.c_grid()
+    index, count, extent = band.index, None if eager else band.count, band.index.shape[0]
+    if views > 1:
+        index, count = _per_view(index, count, nodes, views)
+        extent *= views
+    values = torch.zeros(b, nodes, dtype=torch.float32, device=dev)
+    compact = torch.empty(extent, dtype=torch.float32, device=dev)
+    if extent > 0:
+        if in_frustum:
+            # the ordered frustum selection on the list: its count stays on the device, the launches keep the list's extent
+            seen, seen_count = torch.empty(extent, dtype=torch.int32, device=dev), torch.empty(1, dtype=torch.int32, device=dev)
+            hip.field_select(cg, b, extent, seen, seen_count, cams=cams, indices=index.contiguous(), count=count)
+            index, count = seen, seen_count
+        fmap, goffs, w, bd, _, _ = _decoder_arguments(model, enc.features)
+        index = index.contiguous()
+        hip.field_forward(cg, index, count, extent, cams, fmap, mode=1, w_all=w, b_density=bd, density=compact,
+                          precision=dec.precision, **goffs)
+        hip.field_scatter(compact, index, count, extent, values)
+    return values, (index, count, extent, compact)
+
+
+def _inside_leaks(grid: FieldGrid, batch: int, band: FieldBand, values: torch.Tensor, threshold: float, index=None, count=None,
+                  extent: Optional[int] = None) -> torch.Tensor:
+    """band_leaks of the nodes with ``values >= threshold``: ``values`` compact on the list (index, count, extent), or dense
+    [batch, N] (then with -inf at every node that is invalid or outside the band) without one."""
+    dev = values.device
+    total = batch * grid.num_nodes
+    extent = total if index is None else extent
+    if extent == 0:
+        return torch.zeros(1, dtype=torch.int32, device=dev)
+    inside, inside_count = torch.empty(extent, dtype=torch.int32, device=dev), torch.empty(1, dtype=torch.int32, device=dev)
+    hip.field_select(grid.c_grid(), batch, extent, inside, inside_count, values=values.reshape(-1), threshold=threshold,
+                     indices=index, count=count)
+    return _leaks(grid, band.band, inside, inside_count, extent)
+
+
+def _rows(index: torch.Tensor, rows: int) -> torch.Tensor:
+    """The first ``rows`` entries of a list, padded with zeros where it is shorter (rows past a device count are unspecified)."""
+    if index.shape[0] >= rows:
+        return index[:rows]
+    return torch.cat([index, index.new_zeros(rows - index.shape[0])])
+
+
 class _Stage:
     """The running list of the pipeline: (indices, device count, launch extent).  Eager extraction reads the count after each
     selection to size the next launch exactly; a capture-safe one keeps every intermediate list at B*N entries (4 bytes per
@@ -347,7 +530,8 @@ def extract_field(model, pixel_encoding: PixelEncoding, grid: FieldGrid, density
                   view_direction: Optional[Sequence[float]] = None, want_color: bool = True, want_jacobian: bool = True,
                   max_points: Optional[int] = None, views_per_scene: int = 1, fuse: str = "mean",
                   min_views: int = 1, min_component_nodes: Optional[int] = None, largest_only: bool = False,
-                  connectivity: int = 6) -> FieldPointCloud:
+                  connectivity: int = 6, coarse: Optional[int] = None, coarse_threshold: Optional[float] = None,
+                  coarse_dilate: int = 1) -> FieldPointCloud:
     """Every node of ``grid`` -- per context image of ``pixel_encoding`` -- that
 
     1. (``in_frustum``) projects inside the context image with positive camera depth,
@@ -369,12 +553,23 @@ def extract_field(model, pixel_encoding: PixelEncoding, grid: FieldGrid, density
     device, and only the rows of the components of at least K nodes -- ``largest_only``: of the largest of them, ties to the
     smallest label -- are kept, by the same ordered selection; the coordinate pass and the full decoder pass run on the kept
     rows only, ``stage_counts`` / ``stage_names`` get a ``"components"`` entry, and the capacity form leaves the status word of
-    the labelling in the attribute ``components_status`` of the result.  With both off nothing changes."""
+    the labelling in the attribute ``components_status`` of the result.  With both off nothing changes.
+
+    ``coarse=k`` (2, 4, 8, 16): the density network first runs on every k-th node per axis (every axis of
+    ``grid`` needs ``(n - 1) % k == 0``), and the fine pipeline only on the BAND: the nodes in or on a block of k^3 cells that
+    has a coarse node with ``density >= coarse_threshold`` (default: ``density_threshold``; lower it for parts thinner than k
+    nodes) among its corners or within ``coarse_dilate`` (0, 1, 2) coarse nodes of them.  The result is that of the same call
+    without ``coarse`` in which the nodes outside the band are additionally invalid; ``stage_counts`` / ``stage_names`` get a
+    leading ``"band"`` entry, and the result carries the attributes ``band_count`` (int32 ``[1]``, the true number of band
+    nodes) and ``band_leaks`` (int32 ``[1]``: the survivors of the density selection with a neighbour outside the band -- 0
+    proves that every body the band touches lies wholly in it; a body that no coarse node hits within ``(coarse_dilate + 1) *
+    k`` nodes is missed silently).  ``coarse=None`` changes nothing."""
     dec = model.decoder
     if not isinstance(dec, ActionDecoderJacobian):
         raise TypeError("extract_field needs one of the fused action decoders")
     _check_fusion_arguments("extract_field", pixel_encoding.extrinsics.shape[0], views_per_scene, fuse, min_views)
     _check_component_arguments("extract_field", connectivity, min_component_nodes)
+    coarse_threshold = _check_band_arguments("extract_field", grid, coarse, coarse_threshold, coarse_dilate, density_threshold)
     filtering = min_component_nodes is not None or bool(largest_only)
     if views_per_scene > 1 and cull is not None:
         raise ValueError("extract_field: cull with views_per_scene > 1 has no single meaning (a proposal cull is per view)")
@@ -405,14 +600,25 @@ def extract_field(model, pixel_encoding: PixelEncoding, grid: FieldGrid, density
     if views_per_scene > 1:
         return _extract_field_fused(model, pixel_encoding, grid, float(density_threshold), cams, in_frustum, view_direction,
                                     want_color, want_jacobian, max_points, views_per_scene, fuse, min_views,
-                                    (connectivity, min_component_nodes, bool(largest_only)) if filtering else None)
+                                    (connectivity, min_component_nodes, bool(largest_only)) if filtering else None,
+                                    None if coarse is None else (coarse, coarse_threshold, coarse_dilate))
     stage = _Stage(total)
     counts, names = [], []
+    band, leaks = None, None
+    if coarse is not None:
+        # the pipeline starts from the band list instead of the identity
+        band = _extraction_band(model, pixel_encoding, grid, cams, coarse, coarse_threshold, coarse_dilate, eager)
+        counts.append(band.count)
+        names.append("band")
+        stage.indices, stage.extent = band.index, band.index.shape[0]
+        stage.count = None if eager else band.count
+        leaks = torch.zeros(1, **i32)
 
     def select(name, values, threshold, frustum, final):
         # survivors kept: all of them when the host knows the input's length; else B*N for a list that feeds another stage
         # (4 bytes per node) and max_points for the result
-        capacity = stage.extent if eager else (max_points if final else total)
+        # (with a band the density survivors are kept whole for the leak count and cut to max_points afterwards)
+        capacity = stage.extent if eager else (max_points if final and not (band is not None and name == "density") else total)
         out_idx = torch.empty(max(capacity, 1), **i32)
         out_count = torch.empty(1, **i32)
         hip.field_select(cg, b, stage.extent, out_idx, out_count, values=values, threshold=float(threshold),
@@ -447,6 +653,11 @@ def extract_field(model, pixel_encoding: PixelEncoding, grid: FieldGrid, density
         values = torch.empty(stage.extent, **f32)
         hip.field_forward(cg, stage.indices, stage.count, stage.extent, cams, fmap, density=values, **common)
         select("density", values, density_threshold, False, not filtering)
+        if band is not None:
+            if stage.extent > 0:
+                leaks = _leaks(grid, band.band, stage.indices, stage.count, stage.extent)
+            if not eager and not filtering:
+                stage.indices, stage.extent = _rows(stage.indices, max_points), max_points
     else:
         stage.indices, stage.count = torch.empty(0, **i32), None
         counts.append(torch.zeros(1, **i32))
@@ -479,6 +690,8 @@ def extract_field(model, pixel_encoding: PixelEncoding, grid: FieldGrid, density
             hip.field_forward(cg, index, stage.count, n, cams, fmap, density=cloud.density, **common)
     if components_status is not None:
         cloud.components_status = components_status
+    if band is not None:
+        cloud.band_count, cloud.band_leaks = band.count, leaks
     return cloud
 
 
@@ -573,7 +786,7 @@ def _per_view_rows(dec, n, views, want_color, want_jacobian, dev):
 
 
 def _extract_field_fused(model, enc, grid, threshold, cams, in_frustum, view_direction, want_color, want_jacobian, max_points,
-                         views, mode, min_views, components=None) -> FieldPointCloud:
+                         views, mode, min_views, components=None, coarse=None) -> FieldPointCloud:
     """extract_field for scenes of ``views`` views: dense per-view density pass, fuse, ordered selection on the fused values,
     coordinates, the decoder on the survivors of every view, combine.  One host read (the survivor count) without
     ``max_points``, none with it."""
@@ -586,19 +799,34 @@ def _extract_field_fused(model, enc, grid, threshold, cams, in_frustum, view_dir
     f32 = dict(dtype=torch.float32, device=dev)
     fmap, goffs, w, bd, bc, bj = _decoder_arguments(model, enc.features)
     common = dict(mode=1, w_all=w, b_density=bd, precision=dec.precision, **goffs)
-    values = torch.empty(b, nodes, **f32)
-    hip.field_forward(cg, None, None, b * nodes, cams, fmap, density=values.reshape(-1), **common)
+    band = None
+    if coarse is None:
+        values = torch.empty(b, nodes, **f32)
+        hip.field_forward(cg, None, None, b * nodes, cams, fmap, density=values.reshape(-1), **common)
+    else:
+        band = _extraction_band(model, enc, grid, cams, coarse[0], coarse[1], coarse[2], max_points is None, views, mode,
+                                min_views, in_frustum)
+        values, _ = _banded_values(model, enc, grid, cams, band, in_frustum, max_points is None, views)
     fused, _, valid = _fuse(grid, values, cams if in_frustum else None, views, mode, min_views)
     del values
+    if band is not None:
+        valid = valid & band.band.to(torch.bool)
     # an invalid node (fused = 0) must not pass a threshold <= 0: -inf in its place, in the buffer nothing else reads
     fused.masked_fill_(~valid, -math.inf)
-    # (with a component filter behind it the density selection keeps every survivor: a truncated list would cut components)
-    capacity = scenes * nodes if max_points is None or components is not None else max_points
+    # (with a component filter behind it the density selection keeps every survivor: a truncated list would cut components;
+    # so would it the leak count of a band)
+    whole = max_points is None or components is not None or band is not None
+    capacity = scenes * nodes if whole else max_points
     index, count = torch.empty(max(capacity, 1), **i32), torch.empty(1, **i32)
     hip.field_select(cg, scenes, scenes * nodes, index, count, values=fused.reshape(-1), threshold=threshold)
+    leaks = None if band is None else _leaks(grid, band.band, index, count, capacity)
+    if band is not None and components is None and max_points is not None:
+        index, capacity = _rows(index, max_points), max_points
     n, dev_count = (int(count.item()), None) if max_points is None else (capacity, count)
     index = index[:n]
     stage_counts, stage_names, components_status = (count,), ("density",), None
+    if band is not None:
+        stage_counts, stage_names = (band.count,) + stage_counts, ("band",) + stage_names
     if components is not None:
         kept, count = torch.empty(max(n if max_points is None else max_points, 1), **i32), torch.empty(1, **i32)
         if n > 0:
@@ -616,6 +844,8 @@ def _extract_field_fused(model, enc, grid, threshold, cams, in_frustum, view_dir
                             jacobian=None, count=count, stage_counts=stage_counts, stage_names=stage_names)
     if components_status is not None:
         cloud.components_status = components_status
+    if band is not None:
+        cloud.band_count, cloud.band_leaks = band.count, leaks
     if n > 0:
         hip.field_points(cg, scenes, index, dev_count, n, cloud.xyz)
     rows = _per_view_rows(dec, n, views, want_color, want_jacobian, dev)
@@ -780,7 +1010,8 @@ def extract_mesh(model, pixel_encoding: PixelEncoding, grid: FieldGrid, density_
                  want_color: bool = True, want_jacobian: bool = True, view_direction: Optional[Sequence[float]] = None,
                  max_vertices: Optional[int] = None, max_triangles: Optional[int] = None, views_per_scene: int = 1,
                  fuse: str = "mean", min_views: int = 1, min_component_nodes: Optional[int] = None,
-                 largest_only: bool = False) -> FieldMesh:
+                 largest_only: bool = False, coarse: Optional[int] = None, coarse_threshold: Optional[float] = None,
+                 coarse_dilate: int = 1) -> FieldMesh:
     """The surface ``decoder_density == density_threshold`` of the context image(s) over ``grid``, with the colour head's
     output and the Jacobian ``[A, 3]`` AT every vertex (what ``njf_points_forward`` returns for that position and batch
     element).  ``in_frustum``: nodes outside the context view are invalid -- the surface ends where the view ends.  The
@@ -794,12 +1025,19 @@ def extract_mesh(model, pixel_encoding: PixelEncoding, grid: FieldGrid, density_
     ``min_component_nodes=K`` and / or ``largest_only``: the inside nodes are labelled into connected
     components at connectivity 14 -- the mesh's own: the edges of the Kuhn tetrahedra -- and the nodes of the components below
     K nodes (``largest_only``: of all but the largest) become invalid for the mesher, which removes exactly the tetrahedra
-    that carry their surface.  The capacity form leaves the labelling's status word in the attribute ``components_status``."""
+    that carry their surface.  The capacity form leaves the labelling's status word in the attribute ``components_status``.
+
+    ``coarse=k`` / ``coarse_threshold`` / ``coarse_dilate`` (see ``extract_field``): the density network
+    runs on every k-th node per axis and then on the band around the coarse hits only, instead of on all ``B*N`` nodes; the mesh
+    is that of the same call without ``coarse`` with the nodes outside the band invalid -- identical wherever the band holds
+    the surface, which ``band_leaks == 0`` (an attribute of the result, int32 ``[1]``, next to ``band_count``) proves for every
+    body the band touches.  Lower ``coarse_threshold`` (default: ``density_threshold``) for parts thinner than k nodes."""
     dec = model.decoder
     if not isinstance(dec, ActionDecoderJacobian):
         raise TypeError("extract_mesh needs one of the fused action decoders")
     _check_fusion_arguments("extract_mesh", pixel_encoding.extrinsics.shape[0], views_per_scene, fuse, min_views)
     _check_component_arguments("extract_mesh", 14, min_component_nodes)
+    coarse_threshold = _check_band_arguments("extract_mesh", grid, coarse, coarse_threshold, coarse_dilate, density_threshold)
     components = (min_component_nodes, bool(largest_only)) if min_component_nodes is not None or largest_only else None
     is_flow = isinstance(dec, ActionDecoderFlowMlp)
     if want_jacobian and is_flow:
@@ -819,7 +1057,7 @@ def extract_mesh(model, pixel_encoding: PixelEncoding, grid: FieldGrid, density_
     if views_per_scene > 1:
         return _extract_mesh_fused(model, pixel_encoding, grid, float(density_threshold), cams, in_frustum, view_direction,
                                    want_color, want_jacobian, max_vertices, max_triangles, views_per_scene, fuse, min_views,
-                                   components)
+                                   components, None if coarse is None else (coarse, coarse_threshold, coarse_dilate))
     w, bd, bc, bj = dec.packed()
     if is_flow:
         gmap, base = ActionDecoderJacobian.hoisted_map(dec, feats), 0
@@ -827,15 +1065,24 @@ def extract_mesh(model, pixel_encoding: PixelEncoding, grid: FieldGrid, density_
         gmap, base = _map_of(dec, feats)
     fmap = hip.make_feature_map(gmap)
     goffs = dict(goff_density=base + dec.GOFF_DENSITY, goff_jacobian=base + dec.GOFF_JACOBIAN)
-    values = torch.empty(b, grid.num_nodes, **f32)
-    hip.field_forward(cg, None, None, total, cams, fmap, mode=1, w_all=w, b_density=bd, density=values.reshape(-1),
-                      precision=dec.precision, **goffs)
-    keep, components_status = _mesh_keep(grid, values, float(density_threshold), None, cams if in_frustum else None, components,
-                                         max_vertices is None)
+    band = None
+    if coarse is None:
+        values = torch.empty(b, grid.num_nodes, **f32)
+        hip.field_forward(cg, None, None, total, cams, fmap, mode=1, w_all=w, b_density=bd, density=values.reshape(-1),
+                          precision=dec.precision, **goffs)
+    else:
+        band = _extraction_band(model, pixel_encoding, grid, cams, coarse, coarse_threshold, coarse_dilate, max_vertices is None)
+        values, on_list = _banded_values(model, pixel_encoding, grid, cams, band, in_frustum, max_vertices is None)
+    keep, components_status = _mesh_keep(grid, values, float(density_threshold), None if band is None else band.band,
+                                         cams if in_frustum else None, components, max_vertices is None)
     mesh = _mesh_geometry(grid, values, float(density_threshold), keep, cams if in_frustum else None, max_vertices,
                           max_triangles)
     if components_status is not None:
         mesh.components_status = components_status
+    if band is not None:
+        # the inside nodes: the list the density ran on (the band, in the view) selected by its compact values
+        mesh.band_count = band.count
+        mesh.band_leaks = _inside_leaks(grid, b, band, on_list[3], float(density_threshold), *on_list[:3])
     n = mesh.vertex_node.shape[0]
     if want_color:
         mesh.color = torch.empty(n, 3, **f32)
@@ -868,7 +1115,7 @@ def _mesh_keep(grid: FieldGrid, values: torch.Tensor, threshold: float, valid, c
 
 
 def _extract_mesh_fused(model, enc, grid, threshold, cams, in_frustum, view_direction, want_color, want_jacobian, max_vertices,
-                        max_triangles, views, mode, min_views, components=None) -> FieldMesh:
+                        max_triangles, views, mode, min_views, components=None, coarse=None) -> FieldMesh:
     """extract_mesh for scenes of ``views`` views: dense per-view density pass, fuse, the six meshing launches on the fused
     values with ``valid``, the decoder at every vertex for every view, combine."""
     dec = model.decoder
@@ -876,15 +1123,26 @@ def _extract_mesh_fused(model, enc, grid, threshold, cams, in_frustum, view_dire
     b, nodes = enc.extrinsics.shape[0], grid.num_nodes
     f32 = dict(dtype=torch.float32, device=dev)
     fmap, goffs, w, bd, bc, bj = _decoder_arguments(model, enc.features)
-    values = torch.empty(b, nodes, **f32)
-    hip.field_forward(grid.c_grid(), None, None, b * nodes, cams, fmap, mode=1, w_all=w, b_density=bd, density=values.reshape(-1),
-                      precision=dec.precision, **goffs)
+    band, leaks = None, None
+    if coarse is None:
+        values = torch.empty(b, nodes, **f32)
+        hip.field_forward(grid.c_grid(), None, None, b * nodes, cams, fmap, mode=1, w_all=w, b_density=bd,
+                          density=values.reshape(-1), precision=dec.precision, **goffs)
+    else:
+        band = _extraction_band(model, enc, grid, cams, coarse[0], coarse[1], coarse[2], max_vertices is None, views, mode,
+                                min_views, in_frustum)
+        values, _ = _banded_values(model, enc, grid, cams, band, in_frustum, max_vertices is None, views)
     fused, _, valid = _fuse(grid, values, cams if in_frustum else None, views, mode, min_views)
     del values
+    if band is not None:
+        valid = valid & band.band.to(torch.bool)
+        leaks = _inside_leaks(grid, b // views, band, fused.masked_fill(~valid, -math.inf), threshold)
     valid, components_status = _mesh_keep(grid, fused, threshold, valid, None, components, max_vertices is None)
     mesh = _mesh_geometry(grid, fused, threshold, valid, None, max_vertices, max_triangles)
     if components_status is not None:
         mesh.components_status = components_status
+    if band is not None:
+        mesh.band_count, mesh.band_leaks = band.count, leaks
     n = mesh.vertex_node.shape[0]
     dev_count = None if max_vertices is None else mesh.vertex_count
     rows = _per_view_rows(dec, n, views, want_color, want_jacobian, dev)

@@ -8,6 +8,7 @@ contiguous fp32 device tensor the call raises.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 from typing import Dict, Optional
 
@@ -162,6 +163,10 @@ _SIGNATURES = {
                            _vp], C.c_int),
     "njf_field_components": ([C.POINTER(FieldGrid), C.POINTER(Cameras), C.c_int, _vp, C.c_float, _vp, _vp, _vp, C.c_int, _vp,
                               C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp], C.c_int),
+    "njf_field_band": ([C.POINTER(FieldGrid), C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_float, _vp, _vp, _vp, _vp, C.c_int, _vp,
+                        _vp], C.c_int),
+    "njf_field_scatter": ([_vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp], C.c_int),
+    "njf_field_band_leaks": ([C.POINTER(FieldGrid), C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp], C.c_int),
     "njf_pack_resnetfc_backward": ([C.POINTER(ResnetFcWeights), _vp, C.c_int, _vp], C.c_int),
     "njf_resnetfc_backward": ([_vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp], C.c_int),
     "njf_pack_transformer_backward": ([_vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, _vp], C.c_int),
@@ -853,6 +858,76 @@ def field_components(grid: FieldGrid, batch: int, connectivity: int, labels: tor
             _int32_ptr(list_count, "count"), int(capacity), _int32_ptr(keys, "keys"), int(connectivity), int(phase),
             _int32_ptr(labels, "labels"), _int32_ptr(sizes, "sizes"), _int32_ptr(count, "component_count"),
             _int32_ptr(status, "status"), _int32_ptr(workspace, "workspace"))
+
+
+# ---- coarse-to-fine band (include/njf_hip.h: njf_field_band, njf_field_scatter, njf_field_band_leaks) --------------------
+FIELD_BAND_BLOCK = 1024                # NJF_FIELD_BAND_BLOCK: nodes one workgroup of the band launches covers
+FIELD_BAND_FACTORS = (2, 4, 8, 16)
+FIELD_BAND_MAX_DILATE = 2
+
+
+def field_band_blocks(dims, factor: int):
+    """Blocks per axis ``m_c = (n_c - 1) / factor`` of a fine grid; ValueError unless the factor is 2, 4, 8 or 16 and every axis
+    has ``(n_c - 1) % factor == 0`` and ``n_c >= factor + 1``."""
+    if isinstance(factor, bool) or not isinstance(factor, int) or factor not in FIELD_BAND_FACTORS:
+        raise ValueError(f"njf_hip: the coarse factor must be one of {FIELD_BAND_FACTORS} (got {factor!r})")
+    dims = tuple(int(d) for d in dims)
+    if any(d < factor + 1 or (d - 1) % factor for d in dims):
+        raise ValueError(f"njf_hip: coarse = {factor} needs (n - 1) % {factor} == 0 and n >= {factor + 1} on every axis of the "
+                         f"grid (got dims {dims})")
+    return tuple((d - 1) // factor for d in dims)
+
+
+def field_band(grid: FieldGrid, factor: int, dilate: int, batch: int, coarse_values: torch.Tensor, coarse_threshold: float,
+               block_active: torch.Tensor, band: torch.Tensor, out_indices, out_count: torch.Tensor, coarse_valid=None) -> None:
+    """njf_field_band: coarse values fp32 [B*M] (and ``coarse_valid`` uint8 / bool [B*M]) -> ``block_active`` (uint8 [B*Nb]),
+    ``band`` (uint8 [B*N]), the ascending global indices of the band nodes into ``out_indices`` (int32, its length is the
+    capacity; None = count only) and their true number into ``out_count`` (int32 [1])."""
+    m = field_band_blocks(tuple(grid.dims), factor)
+    if isinstance(dilate, bool) or not isinstance(dilate, int) or not 0 <= dilate <= FIELD_BAND_MAX_DILATE:
+        raise ValueError(f"njf_hip: the band dilation must be 0, 1 or 2 (got {dilate!r})")
+    if not math.isfinite(float(coarse_threshold)):
+        raise ValueError("njf_hip: the coarse threshold must be finite")
+    nodes = grid.dims[0] * grid.dims[1] * grid.dims[2]
+    coarse_nodes, blocks = (m[0] + 1) * (m[1] + 1) * (m[2] + 1), m[0] * m[1] * m[2]
+    for name, t, size in (("coarse_values", coarse_values, batch * coarse_nodes), ("coarse_valid", coarse_valid, batch * coarse_nodes),
+                          ("block_active", block_active, batch * blocks), ("band", band, batch * nodes)):
+        if t is not None and t.numel() != size:
+            raise ValueError(f"njf_hip: field_band {name} must hold {size} elements (got {t.numel()})")
+    if out_count.numel() != 1:
+        raise ValueError("njf_hip: out_count must hold one int32")
+    workspace = torch.empty(max(1, (batch * nodes + FIELD_BAND_BLOCK - 1) // FIELD_BAND_BLOCK), dtype=torch.int32,
+                            device=out_count.device)
+    _launch("njf_field_band", load_library().njf_field_band, C.byref(grid), int(factor), int(dilate), int(batch),
+            _ptr(coarse_values, "coarse_values"), _byte_ptr(coarse_valid, "coarse_valid"), float(coarse_threshold),
+            _byte_ptr(block_active, "block_active"), _byte_ptr(band, "band"), _int32_ptr(out_indices, "out_indices"),
+            _int32_ptr(out_count, "out_count"), 0 if out_indices is None else out_indices.numel(),
+            _int32_ptr(workspace, "workspace"))
+
+
+def field_scatter(values: torch.Tensor, indices: torch.Tensor, count, capacity: int, out: torch.Tensor) -> None:
+    """njf_field_scatter: ``out.reshape(-1)[indices[i]] = values[i]`` for the first min(``count``, ``capacity``) rows (``count``:
+    int32 device tensor or None); indices outside ``out`` are skipped, rows past the count never read."""
+    if values.numel() < capacity or indices.numel() < capacity:
+        raise ValueError("njf_hip: field_scatter values / indices are shorter than the capacity")
+    if out.numel() >= 2 ** 31:
+        raise ValueError("njf_hip: field_scatter out must stay below 2**31 elements")
+    _launch("njf_field_scatter", load_library().njf_field_scatter, _ptr(values, "values"), _int32_ptr(indices, "indices"),
+            _int32_ptr(count, "count"), int(capacity), _ptr(out, "out"), out.numel())
+
+
+def field_band_leaks(grid: FieldGrid, batch: int, band: torch.Tensor, indices: torch.Tensor, count, capacity: int,
+                     leaks: torch.Tensor) -> None:
+    """njf_field_band_leaks: ``leaks`` (int32 [1]) <- the number of the list's inside nodes (ascending ``indices``, the first
+    min(``count``, ``capacity``)) with a neighbour along one of the seven mesh directions, either sign, outside the band."""
+    if band.numel() != batch * grid.dims[0] * grid.dims[1] * grid.dims[2]:
+        raise ValueError("njf_hip: field_band_leaks band must hold batch * nx*ny*nz bytes")
+    if indices.numel() < capacity:
+        raise ValueError("njf_hip: the index list is shorter than the capacity")
+    if leaks.numel() != 1:
+        raise ValueError("njf_hip: leaks must hold one int32")
+    _launch("njf_field_band_leaks", load_library().njf_field_band_leaks, C.byref(grid), int(batch), _byte_ptr(band, "band"),
+            _int32_ptr(indices, "indices"), _int32_ptr(count, "count"), int(capacity), _int32_ptr(leaks, "leaks"))
 
 
 def solve_action(mean_position, jacobian, projection, target_flow, visible_mask, init_action, iterations: int,

@@ -743,7 +743,8 @@ class Model(nn.Module):
                       proposal_level: int = -1, in_frustum: bool = True, view_direction=None, want_color: bool = True,
                       want_jacobian: bool = True, max_points: Optional[int] = None, views_per_scene: int = 1,
                       fuse: str = "mean", min_views: int = 1, min_component_nodes: Optional[int] = None,
-                      largest_only: bool = False, connectivity: int = 6):
+                      largest_only: bool = False, connectivity: int = 6, coarse: Optional[int] = None,
+                      coarse_threshold: Optional[float] = None, coarse_dilate: int = 1):
         """The 3-D Jacobian field of the context image(s) as a point cloud: every node of ``grid`` (field_volume.FieldGrid)
         inside the context view whose proposal density reaches ``cull`` (if given) and whose decoder density reaches
         ``density_threshold``, with density, colour and Jacobian [A, 3], in ascending global index -- what the reference
@@ -753,35 +754,40 @@ class Model(nn.Module):
         the context images are scenes of V consecutive calibrated views and one fused cloud per scene comes back (``fuse``:
         "mean", "min", "max" of the views that see a node; ``min_views`` of them are needed).  ``min_component_nodes`` /
         ``largest_only`` / ``connectivity``: drop the connected components of survivors ("floaters") below that many nodes, or
-        all but the largest, on the device."""
+        all but the largest, on the device.  ``coarse`` / ``coarse_threshold`` / ``coarse_dilate``: look at the density on every
+        ``coarse``-th node first and run the fine pipeline only on the band of nodes around what that finds occupied."""
         from .field_volume import extract_field
         enc = PixelEncoding(features=self._encode_for_render(camera_input.input_image), extrinsics=camera_input.ctxt_extrinsics,
                             intrinsics=camera_input.ctxt_intrinsics, action=None)
         return extract_field(self, enc, grid, density_threshold, cull=cull, proposal_level=proposal_level, in_frustum=in_frustum,
                              view_direction=view_direction, want_color=want_color, want_jacobian=want_jacobian,
                              max_points=max_points, views_per_scene=views_per_scene, fuse=fuse, min_views=min_views,
-                             min_component_nodes=min_component_nodes, largest_only=largest_only, connectivity=connectivity)
+                             min_component_nodes=min_component_nodes, largest_only=largest_only, connectivity=connectivity,
+                             coarse=coarse, coarse_threshold=coarse_threshold, coarse_dilate=coarse_dilate)
 
     @torch.no_grad()
     def extract_mesh(self, camera_input: CameraInput, grid, density_threshold: float, *, in_frustum: bool = True,
                      want_color: bool = True, want_jacobian: bool = True, view_direction=None,
                      max_vertices: Optional[int] = None, max_triangles: Optional[int] = None, views_per_scene: int = 1,
                      fuse: str = "mean", min_views: int = 1, min_component_nodes: Optional[int] = None,
-                     largest_only: bool = False):
+                     largest_only: bool = False, coarse: Optional[int] = None, coarse_threshold: Optional[float] = None,
+                     coarse_dilate: int = 1):
         """The 3-D Jacobian field of the context image(s) as a surface mesh: the isosurface ``density == density_threshold``
         over ``grid`` (field_volume.FieldGrid) with the colour and the Jacobian [A, 3] at every vertex.  See
         ``field_volume.extract_mesh``; ``max_vertices`` + ``max_triangles`` select the form without host synchronisation
         (padded tensors + true counts; capturable in a HIP graph after one eager call).  ``views_per_scene=V``: one fused
         mesh per scene of V consecutive calibrated views (see ``extract_field``).  ``min_component_nodes`` / ``largest_only``:
         drop the surfaces of the connected components (connectivity 14, the mesh's own) below that many nodes, or of all but
-        the largest."""
+        the largest.  ``coarse`` / ``coarse_threshold`` / ``coarse_dilate``: the density pass on every ``coarse``-th node first and
+        then only on the band of nodes around what that finds occupied, instead of on the whole grid."""
         from .field_volume import extract_mesh
         enc = PixelEncoding(features=self._encode_for_render(camera_input.input_image), extrinsics=camera_input.ctxt_extrinsics,
                             intrinsics=camera_input.ctxt_intrinsics, action=None)
         return extract_mesh(self, enc, grid, density_threshold, in_frustum=in_frustum, want_color=want_color,
                             want_jacobian=want_jacobian, view_direction=view_direction, max_vertices=max_vertices,
                             max_triangles=max_triangles, views_per_scene=views_per_scene, fuse=fuse, min_views=min_views,
-                            min_component_nodes=min_component_nodes, largest_only=largest_only)
+                            min_component_nodes=min_component_nodes, largest_only=largest_only, coarse=coarse,
+                            coarse_threshold=coarse_threshold, coarse_dilate=coarse_dilate)
 
     @torch.no_grad()
     def encode_image(self, camera_input: CameraInput, rendering_input: RenderingInput,
