@@ -560,6 +560,58 @@ int njf_field_scatter(const float* values, const int* indices, const int* count,
 int njf_field_band_leaks(const NjfFieldGrid* grid, int batch, const unsigned char* band, const int* indices, const int* count,
                          int capacity, int* leaks, void* stream);
 
+/* ---- rigid twists of the parts of an extracted field (ABI v20, additive) --------------------------------
+ * For each part (the rows of one label) and command channel a, the least-squares rigid field J_a(x) = v_a + omega_a x (x - c)
+ * of the rows' Jacobians: a screw axis per part and channel.
+ * Inputs, all on the device: xyz [n,3] and jacobian [n,A,3] fp32, labels [n] int32 (a negative label belongs to no part),
+ * weights [n] fp32 or NULL (w_i = weights[i] > 0 ? weights[i] : 0, so NaN and negatives count as 0; NULL: w_i = 1), count
+ * (int32, NULL = n: rows from min(*count, n) on are never read), parts [K] int32 (ascending, distinct, non-negative) and
+ * parts_count (int32, NULL = K: the true number of parts; it may exceed K, then the first K are fitted).  Row i belongs to
+ * slot p iff i < *count, p < min(*parts_count, K) and labels[i] == parts[p].  A row with w_i == 0 counts in nodes[p] but its
+ * xyz and jacobian enter no sum (a NaN there is harmless).
+ * All arithmetic is in DOUBLE on the fp32 inputs converted exactly, in the order written, without contraction:
+ *   pass A  nodes, W = sum w, S = sum w*x;  c = S / W
+ *   pass B  r = x - c:  Q_ab = sum w*(r_a*r_b) stored (xx, xy, xz, yy, yz, zz);  per channel P = sum w*J,
+ *           L = sum w*(r x J) with r x J = (ry*Jz - rz*Jy, rz*Jx - rx*Jz, rx*Jy - ry*Jx),  E = sum w*((Jx*Jx + Jy*Jy) + Jz*Jz)
+ *   solve   M = tr(Q) I - Q, Cholesky in the order x, y, z; a pivot <= 1e-9 * tr(M) makes the part TRANSLATION-ONLY (omega = 0,
+ *           status bit NJF_FIELD_TWISTS_TRANSLATION: one node, collinear nodes; a planar part is not degenerate -- beyond a
+ *           condition number of about 1e9 fp32 Jacobians do not determine omega); else omega_a = M^-1 L_a.  v_a = P_a / W is
+ *           the velocity at the centroid (with centred coordinates the two blocks of the 6x6 normal equations decouple).
+ *           W == 0 or no rows: status bit NJF_FIELD_TWISTS_EMPTY and every floating-point output of the slot is 0.
+ *   pass C  residual[p][a] = sum w*|J_a - (v_a + omega_a x r)|^2, summed directly (the closed form E - W|v|^2 - omega.L cancels
+ *           to noise for a near-rigid part), and row_residual [n] fp32 = sum_a |J_a - model|^2, unweighted, rounded once from
+ *           double; 0 for the rows of no fitted part (a memset, then every row is written by the one workgroup that owns it).
+ * Outputs: out_labels [K] int32 (parts[p]; -1 for the slots >= min(*parts_count, K), whose other outputs are 0), out_count
+ * (int32: *parts_count), nodes [K] and status [K] int32; double weight [K], centroid [K,3], omega, velocity [K,A,3], energy,
+ * residual [K,A] and the raw sums q [K,6], p, l [K,A,3].
+ * No floating-point atomics: NJF_FIELD_TWISTS_CHUNK consecutive rows per chunk, workgroup (chunk, part) compacts the matching
+ * rows in order, thread t adds list entries t, t + 256, ... sequentially, then a fixed butterfly over the wave, the four wave
+ * partials in wave order and, in a finishing launch, the chunks in ascending order: every sum has an order that depends on
+ * (n, K, A) alone, two calls give equal bytes.  workspace: NJF_FIELD_TWISTS_STRIDE(A) * K * ceil(n / NJF_FIELD_TWISTS_CHUNK)
+ * doubles of the caller's (workspace_doubles says how many it holds).  One memset and six launches on `stream`, no host read
+ * (capture-safe); `phases` = NJF_FIELD_TWISTS_ALL, or a subset to time the launches apart (each reads what the earlier ones
+ * left).  Returns, before the first launch: NJF_E_VALUE for A outside [1, NJF_MAX_ACTION_DIM], K outside
+ * [1, NJF_FIELD_TWISTS_MAX_PARTS] or unknown phases; NJF_E_SHAPE for n < 0, a workspace that is too small, or K * chunks *
+ * stride past 2^31 - 1; NJF_E_NULL for a missing pointer. */
+#define NJF_FIELD_TWISTS_CHUNK 4096
+#define NJF_FIELD_TWISTS_MAX_PARTS 256
+#define NJF_FIELD_TWISTS_STRIDE(A) (6 + 7 * (A))
+#define NJF_FIELD_TWISTS_EMPTY 1        /* status bits */
+#define NJF_FIELD_TWISTS_TRANSLATION 2
+#define NJF_FIELD_TWISTS_CLEAR 1        /* phases: the memset of row_residual, then one launch each */
+#define NJF_FIELD_TWISTS_SUMS 2
+#define NJF_FIELD_TWISTS_CENTROID 4
+#define NJF_FIELD_TWISTS_MOMENTS 8
+#define NJF_FIELD_TWISTS_SOLVE 16
+#define NJF_FIELD_TWISTS_RESIDUAL 32
+#define NJF_FIELD_TWISTS_RESIDUAL_SUM 64
+#define NJF_FIELD_TWISTS_ALL 127
+int njf_field_twists(const float* xyz, const float* jacobian, const int* labels, const float* weights, const int* count, int n,
+                     int action_dim, const int* parts, const int* parts_count, int num_parts, int* out_labels, int* out_count,
+                     int* nodes, int* status, double* weight, double* centroid, double* omega, double* velocity,
+                     double* energy, double* residual, double* q, double* p, double* l, float* row_residual,
+                     double* workspace, long long workspace_doubles, int phases, void* stream);
+
 /* ---- stand-alone sampler / compositing ops (API parity with the un-fused reference calls) -- */
 /* RaySamples.get_weights (ray_samplers.py:77-101): deltas, densities [N,S] -> weights [N,S]. */
 int njf_alpha_weights(const float* deltas, const float* densities, int rays, int samples, float* weights, void* stream);

@@ -3318,6 +3318,318 @@ __global__ void __launch_bounds__(NJF_BAND_THREADS) band_leaks_kernel(BandLeakAr
 }
 
 // =============================================================================================
+// rigid twists per part and command channel (njf_field_twists)
+// =============================================================================================
+// J_a(x) = v_a + omega_a x (x - c) fitted per part (the rows of one label) and channel, in double, without floating-point atomics:
+// workgroup (chunk, part) compacts the chunk's matching rows IN ORDER into LDS, thread t accumulates list entries t, t + 256, ...
+// sequentially, a fixed butterfly and the four wave partials in wave order give partial[part][chunk][.], and a finishing
+// kernel adds the chunks in ascending order.  Every sum therefore has an order that depends on (n, K, A) alone.
+#define NJF_TWIST_THREADS 256
+#define NJF_TWIST_ITEMS (NJF_FIELD_TWISTS_CHUNK / NJF_TWIST_THREADS)
+#define NJF_TWIST_MAX_VALUES NJF_FIELD_TWISTS_STRIDE(NJF_MAX_ACTION_DIM)
+struct TwistArgs {
+  const float* xyz;       // [n,3]
+  const float* jac;       // [n,A,3]
+  const int* labels;      // [n]
+  const float* weights;   // [n] or null
+  const int* count;       // or null
+  int n, A;
+  const int* parts;       // [K]
+  const int* parts_count; // or null
+  int K, chunks, stride;
+  int *out_labels, *out_count, *nodes, *status;
+  double *weight, *centroid, *omega, *velocity, *energy, *residual, *q, *p, *l;
+  float* row_residual;
+  double* partial;        // [K][chunks][stride]
+};
+
+__device__ __forceinline__ int twist_active(const TwistArgs& a) { return a.parts_count ? min(max(*a.parts_count, 0), a.K) : a.K; }
+__device__ __forceinline__ int twist_rows(const TwistArgs& a) { return a.count ? min(max(*a.count, 0), a.n) : a.n; }
+__device__ __forceinline__ double twist_weight(const TwistArgs& a, long long i) {
+  if (!a.weights) return 1.0;
+  const float w = a.weights[i];
+  return w > 0.f ? (double)w : 0.0;  // (NaN and negatives count as 0)
+}
+
+// the chunk's rows of label `part`, as offsets into the chunk, ascending, into list[]; returns their number
+__device__ __forceinline__ int twist_compact(const TwistArgs& a, int part, int rows, int* list, int (*wave_count)[NJF_TWIST_THREADS / 64]) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const long long base = (long long)blockIdx.x * NJF_FIELD_TWISTS_CHUNK;
+  unsigned flags = 0;
+#pragma unroll
+  for (int it = 0; it < NJF_TWIST_ITEMS; ++it) {
+    const long long i = base + it * NJF_TWIST_THREADS + tid;
+    if (i < rows && a.labels[i] == part) flags |= 1u << it;
+  }
+#pragma unroll
+  for (int it = 0; it < NJF_TWIST_ITEMS; ++it) {
+    const unsigned long long m = __ballot((flags >> it) & 1u);
+    if (lane == 0) wave_count[it][wave] = __popcll(m);
+  }
+  __syncthreads();
+  int run = 0;
+#pragma unroll
+  for (int it = 0; it < NJF_TWIST_ITEMS; ++it) {
+    int off = run;
+#pragma unroll
+    for (int w = 0; w < NJF_TWIST_THREADS / 64; ++w) {
+      const int c = wave_count[it][w];
+      if (w < wave) off += c;
+      run += c;
+    }
+    const unsigned long long m = __ballot((flags >> it) & 1u);
+    if ((flags >> it) & 1u) list[off + __popcll(m & ((1ull << lane) - 1ull))] = it * NJF_TWIST_THREADS + tid;
+  }
+  __syncthreads();
+  return run;
+}
+
+__device__ __forceinline__ double twist_wave_sum(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);  // (a + b == b + a bit for bit: every lane ends with the same sum)
+  return v;
+}
+
+// pass A: nodes, W = sum w, S = sum w x
+__global__ void __launch_bounds__(NJF_TWIST_THREADS) twist_sums_kernel(TwistArgs a) {
+  __shared__ int list[NJF_FIELD_TWISTS_CHUNK];
+  __shared__ int wave_count[NJF_TWIST_ITEMS][NJF_TWIST_THREADS / 64];
+  __shared__ double red[NJF_TWIST_THREADS / 64][4];
+  const int p = blockIdx.y, tid = threadIdx.x;
+  if (p >= twist_active(a)) return;  // (uniform over the workgroup)
+  const int m = twist_compact(a, a.parts[p], twist_rows(a), list, wave_count);
+  const long long base = (long long)blockIdx.x * NJF_FIELD_TWISTS_CHUNK;
+  double acc[4] = {0.0, 0.0, 0.0, 0.0};
+  for (int e = tid; e < m; e += NJF_TWIST_THREADS) {
+    const long long i = base + list[e];
+    const double w = twist_weight(a, i);
+    if (w > 0.0) {
+      acc[0] += w;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) acc[1 + c] += w * (double)a.xyz[i * 3 + c];
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const double s = twist_wave_sum(acc[k]);
+    if ((tid & 63) == 0) red[tid >> 6][k] = s;
+  }
+  __syncthreads();
+  double* out = a.partial + ((size_t)p * a.chunks + blockIdx.x) * a.stride;
+  if (tid < 4) out[tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+  if (tid == 4) out[4] = (double)m;
+}
+
+// labels, count, nodes, weight, centroid and the empty bit of the status; an unused slot gets label -1 and zeros
+__global__ void __launch_bounds__(64) twist_centroid_kernel(TwistArgs a) {
+  __shared__ double fin[5];
+  const int p = blockIdx.x, tid = threadIdx.x;
+  const int active = twist_active(a);
+  if (p == 0 && tid == 0) *a.out_count = a.parts_count ? max(*a.parts_count, 0) : a.K;
+  if (p >= active) {
+    if (tid == 0) {
+      a.out_labels[p] = -1;
+      a.nodes[p] = 0;
+      a.status[p] = 0;
+      a.weight[p] = 0.0;
+    }
+    if (tid < 3) a.centroid[p * 3 + tid] = 0.0;
+    return;
+  }
+  if (tid < 5) {
+    double s = 0.0;
+    for (int c = 0; c < a.chunks; ++c) s += a.partial[((size_t)p * a.chunks + c) * a.stride + tid];
+    fin[tid] = s;
+  }
+  __syncthreads();
+  const bool some = fin[0] > 0.0;
+  if (tid == 0) {
+    a.out_labels[p] = a.parts[p];
+    a.nodes[p] = (int)fin[4];
+    a.status[p] = some ? 0 : NJF_FIELD_TWISTS_EMPTY;
+    a.weight[p] = some ? fin[0] : 0.0;
+  }
+  if (tid < 3) a.centroid[p * 3 + tid] = some ? fin[1 + tid] / fin[0] : 0.0;
+}
+
+// pass B, r = x - c: Q = sum w r r^T (xx xy xz yy yz zz), per channel P = sum w J, L = sum w (r x J), E = sum w J.J
+__global__ void __launch_bounds__(NJF_TWIST_THREADS) twist_moments_kernel(TwistArgs a) {
+  __shared__ int list[NJF_FIELD_TWISTS_CHUNK];
+  __shared__ int wave_count[NJF_TWIST_ITEMS][NJF_TWIST_THREADS / 64];
+  __shared__ double red[NJF_TWIST_THREADS / 64][NJF_TWIST_MAX_VALUES];
+  const int p = blockIdx.y, tid = threadIdx.x;
+  if (p >= twist_active(a)) return;
+  const int m = twist_compact(a, a.parts[p], twist_rows(a), list, wave_count);
+  const long long base = (long long)blockIdx.x * NJF_FIELD_TWISTS_CHUNK;
+  const double cx = a.centroid[p * 3], cy = a.centroid[p * 3 + 1], cz = a.centroid[p * 3 + 2];
+  {
+    double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int e = tid; e < m; e += NJF_TWIST_THREADS) {
+      const long long i = base + list[e];
+      const double w = twist_weight(a, i);
+      if (w > 0.0) {
+        const double rx = (double)a.xyz[i * 3] - cx, ry = (double)a.xyz[i * 3 + 1] - cy, rz = (double)a.xyz[i * 3 + 2] - cz;
+        acc[0] += w * (rx * rx);
+        acc[1] += w * (rx * ry);
+        acc[2] += w * (rx * rz);
+        acc[3] += w * (ry * ry);
+        acc[4] += w * (ry * rz);
+        acc[5] += w * (rz * rz);
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+      const double s = twist_wave_sum(acc[k]);
+      if ((tid & 63) == 0) red[tid >> 6][k] = s;
+    }
+  }
+  for (int ch = 0; ch < a.A; ++ch) {  // one channel at a time: seven accumulators, not 7 A
+    double acc[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int e = tid; e < m; e += NJF_TWIST_THREADS) {
+      const long long i = base + list[e];
+      const double w = twist_weight(a, i);
+      if (w > 0.0) {
+        const double rx = (double)a.xyz[i * 3] - cx, ry = (double)a.xyz[i * 3 + 1] - cy, rz = (double)a.xyz[i * 3 + 2] - cz;
+        const float* j = a.jac + ((size_t)i * a.A + ch) * 3;
+        const double jx = (double)j[0], jy = (double)j[1], jz = (double)j[2];
+        acc[0] += w * jx;
+        acc[1] += w * jy;
+        acc[2] += w * jz;
+        acc[3] += w * (ry * jz - rz * jy);
+        acc[4] += w * (rz * jx - rx * jz);
+        acc[5] += w * (rx * jy - ry * jx);
+        acc[6] += w * ((jx * jx + jy * jy) + jz * jz);
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < 7; ++k) {
+      const double s = twist_wave_sum(acc[k]);
+      if ((tid & 63) == 0) red[tid >> 6][6 + 7 * ch + k] = s;
+    }
+  }
+  __syncthreads();
+  double* out = a.partial + ((size_t)p * a.chunks + blockIdx.x) * a.stride;
+  if (tid < 6 + 7 * a.A) out[tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+}
+
+// M = tr(Q) I - Q, Cholesky in the order x, y, z; false (omega stays 0) when a pivot is <= 1e-9 tr(M) or not a number
+__device__ __forceinline__ bool twist_solve3(const double* Q, const double* L, double* om) {
+  const double tr = (Q[0] + Q[3]) + Q[5];
+  const double mxx = tr - Q[0], myy = tr - Q[3], mzz = tr - Q[5], mxy = -Q[1], mxz = -Q[2], myz = -Q[4];
+  const double floor_ = 1e-9 * ((mxx + myy) + mzz);
+  if (!(mxx > floor_)) return false;
+  const double l11 = sqrt(mxx), l21 = mxy / l11, l31 = mxz / l11;
+  const double d2 = myy - l21 * l21;
+  if (!(d2 > floor_)) return false;
+  const double l22 = sqrt(d2), l32 = (myz - l31 * l21) / l22;
+  const double d3 = mzz - (l31 * l31 + l32 * l32);
+  if (!(d3 > floor_)) return false;
+  const double l33 = sqrt(d3);
+  const double y0 = L[0] / l11, y1 = (L[1] - l21 * y0) / l22, y2 = (L[2] - (l31 * y0 + l32 * y1)) / l33;
+  om[2] = y2 / l33;
+  om[1] = (y1 - l32 * om[2]) / l22;
+  om[0] = (y0 - (l21 * om[1] + l31 * om[2])) / l11;
+  return true;
+}
+
+// the chunks of pass B in ascending order, then per channel v = P / W and omega = M^-1 L
+__global__ void __launch_bounds__(128) twist_solve_kernel(TwistArgs a) {
+  __shared__ double fin[NJF_TWIST_MAX_VALUES];
+  const int p = blockIdx.x, tid = threadIdx.x, A = a.A;
+  const bool used = p < twist_active(a);
+  if (tid < 6 + 7 * A) {
+    double s = 0.0;
+    if (used)
+      for (int c = 0; c < a.chunks; ++c) s += a.partial[((size_t)p * a.chunks + c) * a.stride + tid];
+    fin[tid] = s;
+    if (tid < 6) {
+      a.q[p * 6 + tid] = s;
+    } else {
+      const int ch = (tid - 6) / 7, k = (tid - 6) % 7;
+      if (k < 3) a.p[(p * A + ch) * 3 + k] = s;
+      else if (k < 6) a.l[(p * A + ch) * 3 + k - 3] = s;
+      else a.energy[p * A + ch] = s;
+    }
+  }
+  __syncthreads();
+  if (tid < A) {
+    double om[3] = {0.0, 0.0, 0.0}, v[3] = {0.0, 0.0, 0.0};
+    const double W = a.weight[p];
+    if (used && W > 0.0) {
+      const double* f = fin + 6 + 7 * tid;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) v[c] = f[c] / W;
+      const bool full = twist_solve3(fin, f + 3, om);
+      if (!full) om[0] = om[1] = om[2] = 0.0;
+      if (!full && tid == 0) a.status[p] |= NJF_FIELD_TWISTS_TRANSLATION;  // (M is the part's: every channel agrees)
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      a.omega[(p * A + tid) * 3 + c] = om[c];
+      a.velocity[(p * A + tid) * 3 + c] = v[c];
+    }
+  }
+}
+
+// pass C: residual[p][a] = sum w |J_a - (v_a + omega_a x r)|^2, summed directly, and the unweighted row_residual
+__global__ void __launch_bounds__(NJF_TWIST_THREADS) twist_residual_kernel(TwistArgs a) {
+  __shared__ int list[NJF_FIELD_TWISTS_CHUNK];
+  __shared__ int wave_count[NJF_TWIST_ITEMS][NJF_TWIST_THREADS / 64];
+  __shared__ double red[NJF_TWIST_THREADS / 64][NJF_MAX_ACTION_DIM];
+  __shared__ double tw[NJF_MAX_ACTION_DIM][6];
+  const int p = blockIdx.y, tid = threadIdx.x, A = a.A;
+  if (p >= twist_active(a)) return;
+  if (tid < 3 * A) {
+    tw[tid / 3][tid % 3] = a.omega[p * A * 3 + tid];
+    tw[tid / 3][3 + tid % 3] = a.velocity[p * A * 3 + tid];
+  }
+  const int m = twist_compact(a, a.parts[p], twist_rows(a), list, wave_count);  // (its barriers publish tw)
+  const long long base = (long long)blockIdx.x * NJF_FIELD_TWISTS_CHUNK;
+  const double cx = a.centroid[p * 3], cy = a.centroid[p * 3 + 1], cz = a.centroid[p * 3 + 2];
+  double acc[NJF_MAX_ACTION_DIM];
+#pragma unroll
+  for (int ch = 0; ch < NJF_MAX_ACTION_DIM; ++ch) acc[ch] = 0.0;
+  for (int e = tid; e < m; e += NJF_TWIST_THREADS) {
+    const long long i = base + list[e];
+    const double w = twist_weight(a, i);
+    const double rx = (double)a.xyz[i * 3] - cx, ry = (double)a.xyz[i * 3 + 1] - cy, rz = (double)a.xyz[i * 3 + 2] - cz;
+    double row = 0.0;
+#pragma unroll
+    for (int ch = 0; ch < NJF_MAX_ACTION_DIM; ++ch) {
+      if (ch < A) {
+        const float* j = a.jac + ((size_t)i * A + ch) * 3;
+        const double dx = (double)j[0] - (tw[ch][3] + (tw[ch][1] * rz - tw[ch][2] * ry));
+        const double dy = (double)j[1] - (tw[ch][4] + (tw[ch][2] * rx - tw[ch][0] * rz));
+        const double dz = (double)j[2] - (tw[ch][5] + (tw[ch][0] * ry - tw[ch][1] * rx));
+        const double t = (dx * dx + dy * dy) + dz * dz;
+        row += t;
+        if (w > 0.0) acc[ch] += w * t;
+      }
+    }
+    a.row_residual[i] = (float)row;
+  }
+#pragma unroll
+  for (int ch = 0; ch < NJF_MAX_ACTION_DIM; ++ch) {
+    if (ch < A) {  // (uniform)
+      const double s = twist_wave_sum(acc[ch]);
+      if ((tid & 63) == 0) red[tid >> 6][ch] = s;
+    }
+  }
+  __syncthreads();
+  double* out = a.partial + ((size_t)p * a.chunks + blockIdx.x) * a.stride;
+  if (tid < A) out[tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+}
+
+__global__ void __launch_bounds__(64) twist_residual_sum_kernel(TwistArgs a) {
+  const int p = blockIdx.x, tid = threadIdx.x;
+  if (tid >= a.A) return;
+  double s = 0.0;
+  if (p < twist_active(a) && a.status[p] != NJF_FIELD_TWISTS_EMPTY)
+    for (int c = 0; c < a.chunks; ++c) s += a.partial[((size_t)p * a.chunks + c) * a.stride + tid];
+  a.residual[p * a.A + tid] = s;
+}
+
+// =============================================================================================
 // inverse dynamics: Levenberg-Marquardt on the linearised flow, one workgroup per batch element
 // =============================================================================================
 // optical_flow(a) = proj(x + M a) - proj(x) with x = sum_s w x_s and M = sum_s w J_s (the composited outputs of the
@@ -5341,6 +5653,61 @@ extern "C" int njf_field_band_leaks(const NjfFieldGrid* grid, int batch, const u
   const int blocks = (int)(((long long)capacity + NJF_FIELD_BAND_BLOCK - 1) / NJF_FIELD_BAND_BLOCK);
   band_leaks_kernel<<<blocks, NJF_BAND_THREADS, 0, s>>>(a);
   return launch_status();
+}
+
+extern "C" int njf_field_twists(const float* xyz, const float* jacobian, const int* labels, const float* weights,
+                                const int* count, int n, int action_dim, const int* parts, const int* parts_count,
+                                int num_parts, int* out_labels, int* out_count, int* nodes, int* status, double* weight,
+                                double* centroid, double* omega, double* velocity, double* energy, double* residual,
+                                double* q, double* p, double* l, float* row_residual, double* workspace,
+                                long long workspace_doubles, int phases, void* stream) {
+  if (action_dim < 1 || action_dim > NJF_MAX_ACTION_DIM) return NJF_E_VALUE;
+  if (num_parts < 1 || num_parts > NJF_FIELD_TWISTS_MAX_PARTS) return NJF_E_VALUE;
+  if (phases < 1 || phases > NJF_FIELD_TWISTS_ALL) return NJF_E_VALUE;
+  if (n < 0) return NJF_E_SHAPE;
+  const int chunks = (int)(((long long)n + NJF_FIELD_TWISTS_CHUNK - 1) / NJF_FIELD_TWISTS_CHUNK);
+  const int stride = NJF_FIELD_TWISTS_STRIDE(action_dim);
+  const long long need = (long long)num_parts * chunks * stride;
+  if (need > 0x7fffffffLL || workspace_doubles < need) return NJF_E_SHAPE;
+  if (!parts || !out_labels || !out_count || !nodes || !status || !weight || !centroid || !omega || !velocity || !energy ||
+      !residual || !q || !p || !l)
+    return NJF_E_NULL;
+  if (n > 0 && (!xyz || !jacobian || !labels || !row_residual || !workspace)) return NJF_E_NULL;
+  TwistArgs a{xyz, jacobian, labels, weights, count, n, action_dim, parts, parts_count, num_parts, chunks, stride,
+              out_labels, out_count, nodes, status, weight, centroid, omega, velocity, energy, residual, q, p, l,
+              row_residual, workspace};
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid(chunks, num_parts);
+  int rc;
+  // (the phases exist to time the launches apart: each reads what the earlier ones left in the outputs and the workspace)
+  if (n > 0 && (phases & NJF_FIELD_TWISTS_CLEAR)) {
+    if (hipMemsetAsync(row_residual, 0, (size_t)n * sizeof(float), s) != hipSuccess) return launch_status();
+  }
+  if (n > 0 && (phases & NJF_FIELD_TWISTS_SUMS)) {
+    twist_sums_kernel<<<grid, NJF_TWIST_THREADS, 0, s>>>(a);
+    if ((rc = launch_status())) return rc;
+  }
+  if (phases & NJF_FIELD_TWISTS_CENTROID) {
+    twist_centroid_kernel<<<num_parts, 64, 0, s>>>(a);
+    if ((rc = launch_status())) return rc;
+  }
+  if (n > 0 && (phases & NJF_FIELD_TWISTS_MOMENTS)) {
+    twist_moments_kernel<<<grid, NJF_TWIST_THREADS, 0, s>>>(a);
+    if ((rc = launch_status())) return rc;
+  }
+  if (phases & NJF_FIELD_TWISTS_SOLVE) {
+    twist_solve_kernel<<<num_parts, 128, 0, s>>>(a);
+    if ((rc = launch_status())) return rc;
+  }
+  if (n > 0 && (phases & NJF_FIELD_TWISTS_RESIDUAL)) {
+    twist_residual_kernel<<<grid, NJF_TWIST_THREADS, 0, s>>>(a);
+    if ((rc = launch_status())) return rc;
+  }
+  if (phases & NJF_FIELD_TWISTS_RESIDUAL_SUM) {
+    twist_residual_sum_kernel<<<num_parts, 64, 0, s>>>(a);
+    if ((rc = launch_status())) return rc;
+  }
+  return NJF_OK;
 }
 
 extern "C" int njf_resnetfc_backward(const float* d_out, int d_out_dim, const float* activations, const float* w_backward,

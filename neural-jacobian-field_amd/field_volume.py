@@ -330,6 +330,178 @@ def _component_flags(grid: FieldGrid, batch: int, index: torch.Tensor, count: Op
     return keep[index[:extent].clamp(0, batch * grid.num_nodes - 1).long()].to(torch.float32), comp.status
 
 
+# ---- rigid twists per part and command channel -----------------------------------------------------------
+@dataclass
+class FieldTwists:
+    """The rigid field ``J_a(x) = velocity[p, a] + omega[p, a] x (x - centroid[p])`` fitted to the Jacobians of every part p and
+    command channel a (``fit_twists``; include/njf_hip.h: njf_field_twists): six numbers, a screw axis, per part and channel.
+    ``labels[p]`` is the part's label (-1: an unused slot, all zeros), ``count`` the TRUE number of parts (it may exceed the K
+    slots), ``nodes`` the rows of the part, ``status`` 0 or bits: 1 = no row of positive weight (the slot is zero), 2 =
+    translation-only (one node or collinear nodes: ``omega`` is not determined and set to 0).  ``energy = sum w |J|^2`` and
+    ``residual = sum w |J - model|^2`` per part and channel; ``Q`` (xx, xy, xz, yy, yz, zz), ``P``, ``L`` are the raw weighted
+    sums of the fit; ``row_residual[i] = sum_a |J_a - model|^2`` (unweighted, 0 for rows of no fitted part)."""
+
+    labels: torch.Tensor         # [K] int32
+    count: torch.Tensor          # [1] int32
+    nodes: torch.Tensor          # [K] int32
+    status: torch.Tensor         # [K] int32
+    weight: torch.Tensor         # [K] float64
+    centroid: torch.Tensor       # [K, 3] float64
+    omega: torch.Tensor          # [K, A, 3] float64
+    velocity: torch.Tensor       # [K, A, 3] float64: at the centroid
+    energy: torch.Tensor         # [K, A] float64
+    residual: torch.Tensor       # [K, A] float64
+    Q: torch.Tensor              # [K, 6] float64
+    P: torch.Tensor              # [K, A, 3] float64
+    L: torch.Tensor              # [K, A, 3] float64
+    row_residual: torch.Tensor   # [n] fp32
+
+    def rigidity(self) -> torch.Tensor:
+        """``[K, A]``: the share of the field the rigid model explains, ``1 - residual / energy`` (1 where the energy is 0)."""
+        zero = self.energy == 0
+        return torch.where(zero, 1.0, 1.0 - self.residual / torch.where(zero, 1.0, self.energy))
+
+    def screw(self, eps: float = 1e-9):
+        """``(direction [K, A, 3], point [K, A, 3], pitch [K, A])`` of the screw axis of every twist: the unit direction of
+        ``omega``, the point ``c + omega x v / |omega|^2`` of the axis nearest the centroid and the pitch ``omega . v /
+        |omega|^2`` (translation along the axis per radian).  Where ``|omega| * extent <= eps * |v|`` (prismatic; extent =
+        ``sqrt(tr Q / W)``, the part's RMS radius) the direction is that of ``v``, the point the centroid and the pitch inf; a
+        zero twist has direction 0."""
+        w, v = self.omega, self.velocity
+        wn, vn = torch.linalg.vector_norm(w, dim=-1), torch.linalg.vector_norm(v, dim=-1)
+        safe = torch.where(self.weight > 0, self.weight, torch.ones_like(self.weight))
+        extent = torch.sqrt((self.Q[:, 0] + self.Q[:, 3] + self.Q[:, 5]) / safe)[:, None]
+        prismatic = wn * extent <= eps * vn
+        w2 = torch.where(prismatic, torch.ones_like(wn), wn * wn)
+        centre = self.centroid[:, None, :].expand_as(w)
+        unit_v = v / torch.where(vn > 0, vn, torch.ones_like(vn))[..., None]
+        direction = torch.where(prismatic[..., None], unit_v, w / torch.sqrt(w2)[..., None])
+        point = torch.where(prismatic[..., None], centre, centre + torch.linalg.cross(w, v, dim=-1) / w2[..., None])
+        pitch = torch.where(prismatic, torch.full_like(wn, math.inf), (w * v).sum(-1) / w2)
+        return direction, point, pitch
+
+    def jacobian_at(self, xyz: torch.Tensor, slot: int) -> torch.Tensor:
+        """The model's Jacobians ``[m, A, 3]`` (float64) of part ``slot`` at the points ``xyz`` ``[m, 3]``."""
+        r = xyz.to(self.centroid.dtype) - self.centroid[slot]
+        return self.velocity[slot][None] + torch.linalg.cross(self.omega[slot][None].expand(r.shape[0], -1, 3),
+                                                               r[:, None, :].expand(-1, self.omega.shape[1], 3), dim=-1)
+
+
+def _one_int32(name: str, what: str, t, like: torch.Tensor):
+    if t is None:
+        return None
+    if not torch.is_tensor(t) or t.dtype != torch.int32 or t.numel() != 1:
+        raise ValueError(f"{name}: {what} must be one int32 (a device tensor)")
+    if t.device != like.device:
+        raise ValueError(f"{name}: {what} must live on the device of the other tensors")
+    return t
+
+
+def fit_twists(xyz: torch.Tensor, jacobian: torch.Tensor, labels: torch.Tensor, parts: torch.Tensor, *,
+               parts_count: Optional[torch.Tensor] = None, count: Optional[torch.Tensor] = None,
+               weights: Optional[torch.Tensor] = None) -> FieldTwists:
+    """Least-squares rigid twist of every part and command channel: rows ``xyz`` ``[n, 3]`` and
+    ``jacobian`` ``[n, A, 3]`` fp32 -- of a cloud, or the vertices of a mesh --, ``labels`` ``[n]`` int32 (negative: no part),
+    ``parts`` ``[K]`` int32, ascending, distinct and non-negative, K <= 256, of which the first ``min(parts_count, K)`` are
+    fitted (``parts_count``: int32 device tensor, the true number of parts; None = K); rows from ``count`` (int32 device
+    tensor; None = n) on are never read; ``weights`` ``[n]`` fp32 (NaN and negatives count as 0; None = 1).  All sums are in
+    float64 in a fixed order, without atomics: two calls give equal bytes, and nothing is read on the host."""
+    name = "fit_twists"
+    if not torch.is_tensor(xyz) or xyz.dim() != 2 or xyz.shape[1] != 3 or xyz.dtype != torch.float32:
+        raise ValueError(f"{name}: xyz must be fp32 [n, 3]")
+    n = xyz.shape[0]
+    if (not torch.is_tensor(jacobian) or jacobian.dim() != 3 or jacobian.dtype != torch.float32 or jacobian.shape[0] != n
+            or jacobian.shape[2] != 3 or jacobian.shape[1] < 1):
+        raise ValueError(f"{name}: jacobian must be fp32 [{n}, A, 3]")
+    a_dim = jacobian.shape[1]
+    if a_dim > hip.MAX_ACTION_DIM:
+        raise ValueError(f"{name}: at most {hip.MAX_ACTION_DIM} command channels (got {a_dim})")
+    if not torch.is_tensor(labels) or labels.dtype != torch.int32 or tuple(labels.shape) != (n,):
+        raise ValueError(f"{name}: labels must be int32 [{n}]")
+    if not torch.is_tensor(parts) or parts.dtype != torch.int32 or parts.dim() != 1:
+        raise ValueError(f"{name}: parts must be int32 [K]")
+    k = parts.shape[0]
+    if not 1 <= k <= hip.FIELD_TWISTS_MAX_PARTS:
+        raise ValueError(f"{name}: parts must hold 1 to {hip.FIELD_TWISTS_MAX_PARTS} labels (got {k})")
+    if weights is not None and (not torch.is_tensor(weights) or weights.dtype != torch.float32 or tuple(weights.shape) != (n,)):
+        raise ValueError(f"{name}: weights must be fp32 [{n}]")
+    for what, t in (("jacobian", jacobian), ("labels", labels), ("parts", parts), ("weights", weights)):
+        if t is not None and t.device != xyz.device:
+            raise ValueError(f"{name}: {what} must live on the device of xyz")
+    count = _one_int32(name, "count", count, xyz)
+    parts_count = _one_int32(name, "parts_count", parts_count, xyz)
+    if hip.field_twists_workspace(n, k, a_dim) >= 2 ** 31:
+        raise ValueError(f"{name}: {n} rows with {k} parts overflow the partial sums")
+    if xyz.device.type != "cuda":
+        raise ValueError(f"{name}: the rows must live on the GPU; there is no CPU path")
+    dev = xyz.device
+    i32, f64 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.float64, device=dev)
+    tw = FieldTwists(labels=torch.empty(k, **i32), count=torch.empty(1, **i32), nodes=torch.empty(k, **i32),
+                     status=torch.empty(k, **i32), weight=torch.empty(k, **f64), centroid=torch.empty(k, 3, **f64),
+                     omega=torch.empty(k, a_dim, 3, **f64), velocity=torch.empty(k, a_dim, 3, **f64),
+                     energy=torch.empty(k, a_dim, **f64), residual=torch.empty(k, a_dim, **f64), Q=torch.empty(k, 6, **f64),
+                     P=torch.empty(k, a_dim, 3, **f64), L=torch.empty(k, a_dim, 3, **f64),
+                     row_residual=torch.empty(n, dtype=torch.float32, device=dev))
+    out = dict(labels=tw.labels, count=tw.count, nodes=tw.nodes, status=tw.status, weight=tw.weight, centroid=tw.centroid,
+               omega=tw.omega, velocity=tw.velocity, energy=tw.energy, residual=tw.residual, q=tw.Q, p=tw.P, l=tw.L,
+               row_residual=tw.row_residual)
+    hip.field_twists(xyz.contiguous(), jacobian.contiguous(), labels.contiguous(), parts.contiguous(), out,
+                     weights=None if weights is None else weights.contiguous(), count=count, parts_count=parts_count)
+    return tw
+
+
+def cloud_twists(cloud: FieldPointCloud, *, labels: Optional[torch.Tensor] = None, sizes: Optional[torch.Tensor] = None,
+                 connectivity: int = 6, keys: Optional[torch.Tensor] = None, min_nodes: int = 1, max_parts: int = 32,
+                 weights="density", batch: Optional[int] = None) -> FieldTwists:
+    """``fit_twists`` on the parts of an extracted cloud.  ``labels`` / ``sizes`` ``[n]`` int32: the per-row result of
+    ``cloud_components`` (both or neither; without them it runs here with ``connectivity``, ``keys`` -- e.g.
+    ``dominant_joint(cloud.jacobian)`` -- and ``batch``).  The parts are the components of at least ``min_nodes`` nodes, in
+    ascending label; the first ``max_parts`` (1..256) of them are fitted and ``count`` holds their true number.  The part
+    list is built on the device: the root rows (``labels == cloud.index``, ``sizes >= min_nodes``, row < ``cloud.count``) pass
+    through the ordered selection on ``cloud.index``, so nothing is read on the host (given ``batch``, or the labels).
+    ``weights``: ``"density"`` (the cloud's), None (uniform) or an fp32 ``[n]`` tensor."""
+    name = "cloud_twists"
+    if cloud.jacobian is None:
+        raise ValueError(f"{name} needs the Jacobians (extract with want_jacobian=True)")
+    if isinstance(max_parts, bool) or not isinstance(max_parts, int) or not 1 <= max_parts <= hip.FIELD_TWISTS_MAX_PARTS:
+        raise ValueError(f"{name}: max_parts must be an integer in [1, {hip.FIELD_TWISTS_MAX_PARTS}] (got {max_parts!r})")
+    if isinstance(min_nodes, bool) or not isinstance(min_nodes, int) or min_nodes < 1:
+        raise ValueError(f"{name}: min_nodes must be an integer >= 1 (got {min_nodes!r})")
+    _check_component_arguments(name, connectivity)
+    index = cloud.index
+    n = index.shape[0]
+    if cloud.jacobian.shape[1] > hip.MAX_ACTION_DIM:
+        raise ValueError(f"{name}: at most {hip.MAX_ACTION_DIM} command channels (got {cloud.jacobian.shape[1]})")
+    if (labels is None) != (sizes is None):
+        raise ValueError(f"{name}: labels and sizes come together (the per-row result of cloud_components)")
+    for what, t in (("labels", labels), ("sizes", sizes)):
+        if t is not None and (not torch.is_tensor(t) or t.dtype != torch.int32 or tuple(t.shape) != (n,) or t.device != index.device):
+            raise ValueError(f"{name}: {what} must be int32 [{n}] on the cloud's device")
+    if isinstance(weights, str):
+        if weights != "density":
+            raise ValueError(f"{name}: weights must be \"density\", None or a tensor (got {weights!r})")
+        weights = cloud.density
+    if weights is not None and (not torch.is_tensor(weights) or weights.dtype != torch.float32 or tuple(weights.shape) != (n,)
+                                or weights.device != index.device):
+        raise ValueError(f"{name}: weights must be fp32 [{n}] on the cloud's device")
+    if index.device.type != "cuda":
+        raise ValueError(f"{name}: the cloud must live on the GPU; there is no CPU path")
+    if labels is None:
+        labels, sizes, _ = cloud_components(cloud, connectivity=connectivity, keys=keys, batch=batch)
+    dev = index.device
+    parts = torch.full((max_parts,), -1, dtype=torch.int32, device=dev)
+    parts_count = torch.zeros(1, dtype=torch.int32, device=dev)
+    if n > 0:
+        rows = torch.arange(n, dtype=torch.int32, device=dev) < cloud.count
+        roots = ((labels == index) & (sizes >= min_nodes) & rows).to(torch.float32)
+        nodes = cloud.grid.num_nodes
+        # (the selection needs only an upper bound of the batch: it clamps the indices it copies into the grid's range)
+        span = (2 ** 31 - 1) // nodes if batch is None else batch
+        hip.field_select(cloud.grid.c_grid(), span, n, parts, parts_count, values=roots, threshold=0.5, indices=index.contiguous(),
+                         count=cloud.count)
+    return fit_twists(cloud.xyz, cloud.jacobian, labels, parts, parts_count=parts_count, count=cloud.count, weights=weights)
+
+
 # ---- coarse-to-fine band (DESIGN.md section 14) ----------------------------------------------------------------------------------
 @dataclass
 class FieldBand:

@@ -167,6 +167,8 @@ _SIGNATURES = {
                         _vp], C.c_int),
     "njf_field_scatter": ([_vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp], C.c_int),
     "njf_field_band_leaks": ([C.POINTER(FieldGrid), C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp], C.c_int),
+    "njf_field_twists": ([_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, C.c_int] + [_vp] * 15 + [C.c_longlong, C.c_int, _vp],
+                         C.c_int),
     "njf_pack_resnetfc_backward": ([C.POINTER(ResnetFcWeights), _vp, C.c_int, _vp], C.c_int),
     "njf_resnetfc_backward": ([_vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp], C.c_int),
     "njf_pack_transformer_backward": ([_vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, _vp], C.c_int),
@@ -928,6 +930,57 @@ def field_band_leaks(grid: FieldGrid, batch: int, band: torch.Tensor, indices: t
         raise ValueError("njf_hip: leaks must hold one int32")
     _launch("njf_field_band_leaks", load_library().njf_field_band_leaks, C.byref(grid), int(batch), _byte_ptr(band, "band"),
             _int32_ptr(indices, "indices"), _int32_ptr(count, "count"), int(capacity), _int32_ptr(leaks, "leaks"))
+
+
+# ---- rigid twists per part and command channel (include/njf_hip.h: njf_field_twists) -------------------------------------
+FIELD_TWISTS_CHUNK = 4096              # NJF_FIELD_TWISTS_CHUNK: consecutive rows one workgroup scans for one part
+FIELD_TWISTS_MAX_PARTS = 256           # NJF_FIELD_TWISTS_MAX_PARTS
+FIELD_TWISTS_EMPTY = 1                 # NJF_FIELD_TWISTS_EMPTY: status bit, no row of positive weight
+FIELD_TWISTS_TRANSLATION = 2           # NJF_FIELD_TWISTS_TRANSLATION: status bit, omega is not determined (set to 0)
+FIELD_TWISTS_PHASES = (1, 2, 4, 8, 16, 32, 64)   # NJF_FIELD_TWISTS_CLEAR .. _RESIDUAL_SUM: the memset and one launch each
+FIELD_TWISTS_PHASE_NAMES = ("clear", "sums", "centroid", "moments", "solve", "residual", "residual_sum")
+FIELD_TWISTS_ALL = 127                 # NJF_FIELD_TWISTS_ALL
+
+
+def field_twists_workspace(rows: int, parts: int, action_dim: int) -> int:
+    """Doubles of workspace njf_field_twists needs: NJF_FIELD_TWISTS_STRIDE(A) * K * ceil(n / NJF_FIELD_TWISTS_CHUNK)."""
+    return (6 + 7 * action_dim) * parts * ((rows + FIELD_TWISTS_CHUNK - 1) // FIELD_TWISTS_CHUNK)
+
+
+def _double_ptr(t: Optional[torch.Tensor], name: str) -> Optional[int]:
+    return _ptr(t, name, torch.float64)
+
+
+def field_twists(xyz: torch.Tensor, jacobian: torch.Tensor, labels: torch.Tensor, parts: torch.Tensor, out: dict,
+                 weights=None, count=None, parts_count=None, phase: int = FIELD_TWISTS_ALL,
+                 workspace: Optional[torch.Tensor] = None) -> None:
+    """njf_field_twists on ``xyz`` [n, 3], ``jacobian`` [n, A, 3] (fp32), ``labels`` [n] and ``parts`` [K] (int32): ``out`` maps
+    the names of the C outputs -- labels, count, nodes, status (int32), weight, centroid, omega, velocity, energy, residual, q,
+    p, l (float64), row_residual (fp32) -- to tensors of their shapes.  ``phase`` / ``workspace`` (float64,
+    ``field_twists_workspace`` elements): run the launches one by one on a workspace of the caller's, to time them apart."""
+    n, k = xyz.shape[0], parts.numel()
+    if jacobian.dim() != 3 or jacobian.shape[0] != n or jacobian.shape[2] != 3 or tuple(xyz.shape) != (n, 3):
+        raise ValueError("njf_hip: field_twists needs xyz [n, 3] and jacobian [n, A, 3]")
+    a = jacobian.shape[1]
+    if labels.numel() != n or (weights is not None and weights.numel() != n):
+        raise ValueError("njf_hip: field_twists labels / weights must hold one entry per row")
+    for name, t in (("count", count), ("parts_count", parts_count), ("out count", out["count"])):
+        if t is not None and t.numel() != 1:
+            raise ValueError(f"njf_hip: field_twists {name} must hold one int32")
+    sizes = dict(labels=k, nodes=k, status=k, weight=k, centroid=3 * k, omega=3 * a * k, velocity=3 * a * k, energy=a * k,
+                 residual=a * k, q=6 * k, p=3 * a * k, l=3 * a * k, row_residual=n)
+    for name, size in sizes.items():
+        if out[name].numel() != size:
+            raise ValueError(f"njf_hip: field_twists output {name} must hold {size} elements (got {out[name].numel()})")
+    need = field_twists_workspace(n, k, a)
+    if workspace is None:
+        workspace = torch.empty(max(need, 1), dtype=torch.float64, device=xyz.device)
+    _launch("njf_field_twists", load_library().njf_field_twists, _ptr(xyz, "xyz"), _ptr(jacobian, "jacobian"),
+            _int32_ptr(labels, "labels"), _ptr(weights, "weights"), _int32_ptr(count, "count"), int(n), int(a),
+            _int32_ptr(parts, "parts"), _int32_ptr(parts_count, "parts_count"), int(k), _int32_ptr(out["labels"], "out labels"),
+            _int32_ptr(out["count"], "out count"), _int32_ptr(out["nodes"], "nodes"), _int32_ptr(out["status"], "status"),
+            *[_double_ptr(out[f], f) for f in ("weight", "centroid", "omega", "velocity", "energy", "residual", "q", "p", "l")],
+            _ptr(out["row_residual"], "row_residual"), _double_ptr(workspace, "workspace"), int(workspace.numel()), int(phase))
 
 
 def solve_action(mean_position, jacobian, projection, target_flow, visible_mask, init_action, iterations: int,
