@@ -1919,123 +1919,9 @@ extern "C" int njf_assemble_frame(const float* packets, int world, int packet_fl
   return launch_status();
 }
 
-// =============================================================================================
-// point-list evaluation
-// =============================================================================================
-struct PointsArgs {
-  const float* xyz;
-  const float* dirs;
-  int points_per_batch;
-  int total_points;
-  NjfCameras cams;
-  NjfFeatureMap gmap;
-  int goff_d, goff_j;
-  const float* w_all;
-  const float* b_d;
-  const float* b_c;
-  const float* b_j;
-  float* density;
-  float* color;
-  float* flow;
-  float* jacobian;
-  float* geo;
-  float* features;  // [5, P, 128] or null (FEAT instantiation only)
-};
-
-// MODE 0: proposal net (density only); 1: decoder without Jacobian head; 2: decoder + ResnetFC Jacobian head;
-// 3: decoder + transformer Jacobian head.  FEAT (MODE 2): the head also stores its residual stream after every block
-// (ResnetFC.forward(compute_features=True), resnet_fc.py:141-151) through the training instantiation of resnet_tile
-template <int MODE, int PREC, int PRECJ = PREC, bool FEAT = false>
-__global__ void __launch_bounds__(NJF_THREADS, 2) points_kernel(PointsArgs a) {
-  const int tid = threadIdx.x;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int lane = tid & 63, j = lane & 31, hh = lane >> 5;
-  const int wg = xcd_remap(blockIdx.x, gridDim.x);
-  const int tile = wg * NJF_WAVES + wave;
-  const int p = tile * 32 + j;
-  const bool ok = p < a.total_points;
-  const int pc = min(p, a.total_points - 1);
-  const int b = pc / a.points_per_batch;  // per lane: a tile may straddle batch elements
-
-  load_bias_block(a.b_d, NJF_RESNET_B_FLOATS, 0);
-  if (MODE >= 1) load_bias_block(a.b_c, NJF_COLOR_B_FLOATS, NJF_RESNET_B_FLOATS);
-  if (MODE == 2) load_bias_block(a.b_j, NJF_RESNET_B_FLOATS, NJF_RESNET_B_FLOATS + NJF_COLOR_B_FLOATS);
-  if (MODE == 3) load_bias_block(a.b_j, NJF_TRANSFORMER_B_FLOATS, NJF_RESNET_B_FLOATS + NJF_COLOR_B_FLOATS);
-  WeightStreamT<resnet_gap_at<PREC>(), resnet_gap<PREC>()> st;
-  stream_begin(st, a.w_all,
-               MODE == 0 ? resnet_chunks<PREC>()
-                         : resnet_chunks<PREC>() + 1 + (MODE == 2 ? resnet_chunks<PRECJ>() : (MODE == 3 ? NJF_TRANSFORMER_CHUNKS : 0)),
-               1, wave, lane);
-  CamCtx cam;
-  load_ctx(a.cams.ctxt_w2c, a.cams.ctxt_k, b, cam);
-  const float px = a.xyz[3 * (size_t)pc], py = a.xyz[3 * (size_t)pc + 1], pz = a.xyz[3 * (size_t)pc + 2];
-  PointGeom g;
-  // the batch element's offset travels with the point (PointGeom::gofs): the gathers take the map itself as base
-  const unsigned gbase = (unsigned)b * (unsigned)(a.gmap.height * a.gmap.width) * (unsigned)a.gmap.stride;
-  point_geometry(cam, px, py, pz, a.gmap.height, a.gmap.width, a.gmap.stride, gbase, g);
-  const float* bias = njf_lds + LDS_BIAS;
-  if (MODE == 0) {
-    f32x16 pe[2], out[1];
-    positional_encoding(g.xc, g.yc, g.zc, hh, pe);
-    resnet_tile<PREC>(st, bias, map_at<PREC>(a.gmap.data, a.goff_d), g, pe, wave, lane, out);
-    if (ok && hh == 0 && a.density) a.density[p] = expf(out[0][0] - 1.0f);
-  } else {
-    float dx = 0.f, dy = 0.f, dz = 1.f;
-    if (a.dirs) {
-      dx = a.dirs[3 * (size_t)pc];
-      dy = a.dirs[3 * (size_t)pc + 1];
-      dz = a.dirs[3 * (size_t)pc + 2];
-    }
-    const int A = a.cams.action_dim;
-    const float* action = a.cams.action ? a.cams.action + (size_t)b * A : nullptr;
-    constexpr int JK = MODE >= 2 ? MODE - 1 : 0;
-    const ActDump nodump{nullptr, nullptr, 0};
-    // stage by stage, each result stored before the next network starts (nothing but the point itself stays live)
-    f32x16 geo[1];
-    const float sigma = density_stage<PREC, 0>(st, map_at<PREC>(a.gmap.data, a.goff_d), g, wave, lane, geo, nodump);
-    if (ok && hh == 0) {
-      if (a.density) a.density[p] = sigma;
-      if (a.geo) {
-#pragma unroll
-        for (int r = 0; r < 15; ++r) a.geo[15 * (size_t)p + r] = geo[0][r];
-      }
-    }
-    {
-      float rgb[3];
-      color_stage<PREC, 0>(st, geo, dx, dy, dz, wave, lane, rgb, ColorDump{nullptr, nullptr, 0});
-      if (ok && hh == 0 && a.color) {
-        a.color[3 * (size_t)p] = rgb[0];
-        a.color[3 * (size_t)p + 1] = rgb[1];
-        a.color[3 * (size_t)p + 2] = rgb[2];
-      }
-    }
-    if (JK != 0) {
-      f32x16 jac[1];
-      float flow[3];
-      // NOTE: `action` is per lane here (tiles may straddle batch elements)
-      if constexpr (FEAT) {
-        static_assert(MODE == 2, "feature dump: ResnetFC head");
-        ActDump fdump{nullptr, nullptr, (size_t)a.total_points * 128};
-        if (ok) fdump.feat = a.features + (size_t)p * 128 + 64 * hh;
-        jacobian_stage<JK, PRECJ, 1>(st, map_at<PRECJ>(a.gmap.data, a.goff_j), g, action, A, wave, lane, jac, flow, fdump);
-      } else
-      jacobian_stage<JK, PRECJ, 0>(st, map_at<PRECJ>(a.gmap.data, a.goff_j), g, action, A, wave, lane, jac, flow, nodump);
-      if (ok) {
-        if (hh == 0 && a.flow) {
-          a.flow[3 * (size_t)p] = flow[0];
-          a.flow[3 * (size_t)p + 1] = flow[1];
-          a.flow[3 * (size_t)p + 2] = flow[2];
-        }
-        if (a.jacobian) {
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int d = 16 * hh + r;
-            if (d < 3 * A) a.jacobian[(size_t)p * (3 * A) + d] = jac[0][r];
-          }
-        }
-      }
-    }
-  }
+// a length that lives on the device: min(*count, capacity), the capacity without a count (what a capture-safe caller launches for)
+__device__ __forceinline__ int counted_length(const int* count, int capacity) {
+  return count ? min(max(*count, 0), capacity) : capacity;
 }
 
 // =============================================================================================
@@ -2055,7 +1941,7 @@ struct FieldList {
 };
 
 __device__ __forceinline__ int field_entries(const FieldList& l) {
-  return l.count ? min(max(*l.count, 0), l.capacity) : l.capacity;
+  return counted_length(l.count, l.capacity);
 }
 
 // global index of list entry i, clamped into the grid (an index list is caller data: nothing may address outside the
@@ -2076,9 +1962,9 @@ __device__ __forceinline__ void field_node(const FieldList& l, int gi, int& b, f
   pz = fmaf((float)iz, l.grid.step[2], l.grid.origin[2]);
 }
 
-struct FieldArgs {
-  FieldList list;
-  float dirx, diry, dirz;  // constant view direction of the colour head
+// ---- the decoder at points: one evaluator, three sources of points ------------------------------------------------------
+// What every source shares; the last three outputs exist for the point list alone (SRC::EXTRAS).
+struct DecoderArgs {
   NjfCameras cams;
   NjfFeatureMap gmap;
   int goff_d, goff_j;
@@ -2086,23 +1972,76 @@ struct FieldArgs {
   const float* b_d;
   const float* b_c;
   const float* b_j;
-  float* density;   // [entries]
-  float* color;     // [entries, 3]
-  float* jacobian;  // [entries, 3A]
+  float* density;   // [entries] or null
+  float* color;     // [entries, 3] or null
+  float* jacobian;  // [entries, 3A] or null
+  float* flow;      // [entries, 3] or null
+  float* geo;       // [entries, 15] or null
+  float* features;  // [5, entries, 128] or null (FEAT instantiation only)
 };
 
-// The point-list evaluator (points_kernel) fed from a grid descriptor + list: row i of every output is list entry i.
+// A source says how many entries there are, which batch element and position entry i has, and the view direction of its
+// colour head.  COUNTED: the entry count lives on the device (surplus workgroups leave at once); EXTRAS: the per-lane action
+// (hence `flow`), `geo` and the feature dump; MODES: bit m = the source has evaluator MODE m.
+struct PointList {  // njf_points_forward
+  static constexpr bool COUNTED = false, EXTRAS = true;
+  static constexpr int MODES = 0b11101;
+  const float* xyz;
+  const float* dirs;  // or null
+  int points_per_batch;
+  int total;
+  __device__ __forceinline__ int entries() const { return total; }
+  __device__ __forceinline__ void point(int i, int& b, float& px, float& py, float& pz) const {
+    b = i / points_per_batch;  // per lane: a tile may straddle batch elements
+    px = xyz[3 * (size_t)i], py = xyz[3 * (size_t)i + 1], pz = xyz[3 * (size_t)i + 2];
+  }
+  __device__ __forceinline__ void direction(int i, float& dx, float& dy, float& dz) const {
+    dx = 0.f, dy = 0.f, dz = 1.f;
+    if (dirs) dx = dirs[3 * (size_t)i], dy = dirs[3 * (size_t)i + 1], dz = dirs[3 * (size_t)i + 2];
+  }
+};
+struct ConstantDirection {
+  float dirx, diry, dirz;
+  __device__ __forceinline__ void direction(int, float& dx, float& dy, float& dz) const { dx = dirx, dy = diry, dz = dirz; }
+};
+struct GridNodes : ConstantDirection {  // njf_field_forward: row i of every output is list entry i
+  static constexpr bool COUNTED = true, EXTRAS = false;
+  static constexpr int MODES = 0b11111;
+  FieldList list;
+  __device__ __forceinline__ int entries() const { return field_entries(list); }
+  __device__ __forceinline__ void point(int i, int& b, float& px, float& py, float& pz) const {
+    field_node(list, field_global_index(list, i), b, px, py, pz);
+  }
+};
+struct StoredNodes : ConstantDirection {  // njf_field_forward_at (the mesh vertices): a ragged batch in one launch
+  static constexpr bool COUNTED = true, EXTRAS = false;
+  static constexpr int MODES = 0b11100;
+  const float* xyz;  // [capacity, 3]
+  const int* node;   // [capacity] global node index: the batch element of row i is node[i] / nodes
+  const int* count;  // or null
+  int capacity;
+  int nodes, total;  // N, B*N
+  __device__ __forceinline__ int entries() const { return counted_length(count, capacity); }
+  __device__ __forceinline__ void point(int i, int& b, float& px, float& py, float& pz) const {
+    b = min(max(node[i], 0), total - 1) / nodes;  // (caller data: clamped into the batch)
+    px = xyz[3 * (size_t)i], py = xyz[3 * (size_t)i + 1], pz = xyz[3 * (size_t)i + 2];
+  }
+};
+
 // MODE 0: proposal net; 1: decoder density only (the density net alone is streamed); 2: density + colour; 3: density +
-// colour + ResnetFC Jacobian head; 4: density + colour + transformer Jacobian head.  Same stages, same weight stream and
-// the same per-point arithmetic as points_kernel: a node's outputs equal those of njf_points_forward on its coordinate.
-template <int MODE, int PREC, int PRECJ = PREC>
-__global__ void __launch_bounds__(NJF_THREADS, 2) field_points_kernel(FieldArgs a) {
-  const int entries = field_entries(a.list);
+// colour + ResnetFC Jacobian head; 4: density + colour + transformer Jacobian head.  FEAT (MODE 3): the head also stores
+// its residual stream after every block (ResnetFC.forward(compute_features=True), resnet_fc.py:141-151) through the
+// training instantiation of resnet_tile.  One body for every source: a row's outputs are the same function of its
+// position, batch element and view direction whichever entry point evaluates it.
+template <class SRC, int MODE, int PREC, int PRECJ = PREC, bool FEAT = false>
+__global__ void __launch_bounds__(NJF_THREADS, 2) points_kernel(DecoderArgs a, SRC src) {
+  static_assert((SRC::MODES >> MODE) & 1, "a mode this source does not have");
+  const int entries = src.entries();
   const int tid = threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int lane = tid & 63, j = lane & 31, hh = lane >> 5;
   const int wg = xcd_remap(blockIdx.x, gridDim.x);
-  if (wg * (NJF_WAVES * 32) >= entries) return;  // the whole workgroup (it shares the weight stream), before any barrier
+  if (SRC::COUNTED && wg * (NJF_WAVES * 32) >= entries) return;  // the whole workgroup (it shares the weight stream), before any barrier
   const int tile = wg * NJF_WAVES + wave;
   const int p = tile * 32 + j;
   const bool ok = p < entries;
@@ -2119,10 +2058,11 @@ __global__ void __launch_bounds__(NJF_THREADS, 2) field_points_kernel(FieldArgs 
                1, wave, lane);
   int b;
   float px, py, pz;
-  field_node(a.list, field_global_index(a.list, pc), b, px, py, pz);
+  src.point(pc, b, px, py, pz);
   CamCtx cam;
   load_ctx(a.cams.ctxt_w2c, a.cams.ctxt_k, b, cam);
   PointGeom g;
+  // the batch element's offset travels with the point (PointGeom::gofs): the gathers take the map itself as base
   const unsigned gbase = (unsigned)b * (unsigned)(a.gmap.height * a.gmap.width) * (unsigned)a.gmap.stride;
   point_geometry(cam, px, py, pz, a.gmap.height, a.gmap.width, a.gmap.stride, gbase, g);
   const float* bias = njf_lds + LDS_BIAS;
@@ -2130,17 +2070,25 @@ __global__ void __launch_bounds__(NJF_THREADS, 2) field_points_kernel(FieldArgs 
     f32x16 pe[2], out[1];
     positional_encoding(g.xc, g.yc, g.zc, hh, pe);
     resnet_tile<PREC>(st, bias, map_at<PREC>(a.gmap.data, a.goff_d), g, pe, wave, lane, out);
-    if (ok && hh == 0) a.density[p] = expf(out[0][0] - 1.0f);
+    if (ok && hh == 0 && (!SRC::EXTRAS || a.density)) a.density[p] = expf(out[0][0] - 1.0f);  // (mandatory but for the point list)
   } else {
     const int A = a.cams.action_dim;
     constexpr int JK = MODE >= 3 ? MODE - 2 : 0;
     const ActDump nodump{nullptr, nullptr, 0};
+    // stage by stage, each result stored before the next network starts (nothing but the point itself stays live)
     f32x16 geo[1];
     const float sigma = density_stage<PREC, 0>(st, map_at<PREC>(a.gmap.data, a.goff_d), g, wave, lane, geo, nodump);
-    if (ok && hh == 0 && a.density) a.density[p] = sigma;
+    if (ok && hh == 0) {
+      if (a.density) a.density[p] = sigma;
+      if (SRC::EXTRAS && a.geo) {
+#pragma unroll
+        for (int r = 0; r < 15; ++r) a.geo[15 * (size_t)p + r] = geo[0][r];
+      }
+    }
     if (MODE >= 2) {
-      float rgb[3];
-      color_stage<PREC, 0>(st, geo, a.dirx, a.diry, a.dirz, wave, lane, rgb, ColorDump{nullptr, nullptr, 0});
+      float dx, dy, dz, rgb[3];
+      src.direction(pc, dx, dy, dz);
+      color_stage<PREC, 0>(st, geo, dx, dy, dz, wave, lane, rgb, ColorDump{nullptr, nullptr, 0});
       if (ok && hh == 0 && a.color) {
         a.color[3 * (size_t)p] = rgb[0];
         a.color[3 * (size_t)p + 1] = rgb[1];
@@ -2150,19 +2098,34 @@ __global__ void __launch_bounds__(NJF_THREADS, 2) field_points_kernel(FieldArgs 
     if (JK != 0) {
       f32x16 jac[1];
       float flow[3];
-      jacobian_stage<JK, PRECJ, 0>(st, map_at<PRECJ>(a.gmap.data, a.goff_j), g, nullptr, A, wave, lane, jac, flow, nodump);
-      if (ok && a.jacobian) {
+      // per lane (tiles may straddle batch elements); a literal null without EXTRAS: no flow arithmetic is compiled
+      const float* action = SRC::EXTRAS && a.cams.action ? a.cams.action + (size_t)b * A : nullptr;
+      if constexpr (FEAT) {
+        static_assert(MODE == 3 && SRC::EXTRAS, "feature dump: ResnetFC head of the point list");
+        ActDump fdump{nullptr, nullptr, (size_t)entries * 128};
+        if (ok) fdump.feat = a.features + (size_t)p * 128 + 64 * hh;
+        jacobian_stage<JK, PRECJ, 1>(st, map_at<PRECJ>(a.gmap.data, a.goff_j), g, action, A, wave, lane, jac, flow, fdump);
+      } else
+      jacobian_stage<JK, PRECJ, 0>(st, map_at<PRECJ>(a.gmap.data, a.goff_j), g, action, A, wave, lane, jac, flow, nodump);
+      if (ok) {
+        if (SRC::EXTRAS && hh == 0 && a.flow) {
+          a.flow[3 * (size_t)p] = flow[0];
+          a.flow[3 * (size_t)p + 1] = flow[1];
+          a.flow[3 * (size_t)p + 2] = flow[2];
+        }
+        if (a.jacobian) {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int d = 16 * hh + r;
-          if (d < 3 * A) a.jacobian[(size_t)p * (3 * A) + d] = jac[0][r];
+          for (int r = 0; r < 16; ++r) {
+            const int d = 16 * hh + r;
+            if (d < 3 * A) a.jacobian[(size_t)p * (3 * A) + d] = jac[0][r];
+          }
         }
       }
     }
   }
 }
 
-// xyz [entries, 3]: the coordinates of a list's nodes (the very floats field_points_kernel evaluates)
+// xyz [entries, 3]: the coordinates of a list's nodes (the very floats points_kernel<GridNodes> evaluates)
 __global__ void __launch_bounds__(256) field_xyz_kernel(FieldList l, float* __restrict__ xyz) {
   const int entries = field_entries(l);
   const int i = blockIdx.x * 256 + threadIdx.x;
@@ -2581,87 +2544,6 @@ __global__ void __launch_bounds__(NJF_MESH_THREADS) mesh_triangle_kernel(MeshArg
   }
 }
 
-// ---- the decoder's heads at stored positions (the mesh vertices) ----------------------------------------------------------
-struct FieldAtArgs {
-  const float* xyz;   // [capacity, 3]
-  const int* node;    // [capacity] global node index: the batch element of row i is node[i] / nodes
-  const int* count;   // or null
-  int capacity;
-  int nodes, total;   // N, B*N
-  float dirx, diry, dirz;
-  NjfCameras cams;
-  NjfFeatureMap gmap;
-  int goff_d, goff_j;
-  const float* w_all;
-  const float* b_d;
-  const float* b_c;
-  const float* b_j;
-  float* density;   // [entries] or null
-  float* color;     // [entries, 3] or null
-  float* jacobian;  // [entries, 3A]
-};
-
-// field_points_kernel with the point read from `xyz` and its batch element from `node` (a ragged batch in one launch).
-// MODE 2: density + colour; 3: + ResnetFC Jacobian head; 4: + transformer Jacobian head -- the modes, stages, weight stream
-// and per-point arithmetic of field_points_kernel: a row's outputs equal those of njf_points_forward on its position.
-template <int MODE, int PREC, int PRECJ = PREC>
-__global__ void __launch_bounds__(NJF_THREADS, 2) field_at_kernel(FieldAtArgs a) {
-  static_assert(MODE >= 2 && MODE <= 4, "decoder modes with the colour head");
-  const int entries = a.count ? min(max(*a.count, 0), a.capacity) : a.capacity;
-  const int tid = threadIdx.x;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int lane = tid & 63, j = lane & 31, hh = lane >> 5;
-  const int wg = xcd_remap(blockIdx.x, gridDim.x);
-  if (wg * (NJF_WAVES * 32) >= entries) return;  // the whole workgroup (it shares the weight stream), before any barrier
-  const int tile = wg * NJF_WAVES + wave;
-  const int p = tile * 32 + j;
-  const bool ok = p < entries;
-  const int pc = min(p, entries - 1);
-
-  load_bias_block(a.b_d, NJF_RESNET_B_FLOATS, 0);
-  load_bias_block(a.b_c, NJF_COLOR_B_FLOATS, NJF_RESNET_B_FLOATS);
-  if (MODE == 3) load_bias_block(a.b_j, NJF_RESNET_B_FLOATS, NJF_RESNET_B_FLOATS + NJF_COLOR_B_FLOATS);
-  if (MODE == 4) load_bias_block(a.b_j, NJF_TRANSFORMER_B_FLOATS, NJF_RESNET_B_FLOATS + NJF_COLOR_B_FLOATS);
-  WeightStreamT<resnet_gap_at<PREC>(), resnet_gap<PREC>()> st;
-  stream_begin(st, a.w_all,
-               resnet_chunks<PREC>() + 1 + (MODE == 3 ? resnet_chunks<PRECJ>() : (MODE == 4 ? NJF_TRANSFORMER_CHUNKS : 0)), 1, wave,
-               lane);
-  const int b = min(max(a.node[pc], 0), a.total - 1) / a.nodes;  // (caller data: clamped into the batch)
-  const float px = a.xyz[3 * (size_t)pc], py = a.xyz[3 * (size_t)pc + 1], pz = a.xyz[3 * (size_t)pc + 2];
-  CamCtx cam;
-  load_ctx(a.cams.ctxt_w2c, a.cams.ctxt_k, b, cam);
-  PointGeom g;
-  const unsigned gbase = (unsigned)b * (unsigned)(a.gmap.height * a.gmap.width) * (unsigned)a.gmap.stride;
-  point_geometry(cam, px, py, pz, a.gmap.height, a.gmap.width, a.gmap.stride, gbase, g);
-  const int A = a.cams.action_dim;
-  constexpr int JK = MODE >= 3 ? MODE - 2 : 0;
-  const ActDump nodump{nullptr, nullptr, 0};
-  f32x16 geo[1];
-  const float sigma = density_stage<PREC, 0>(st, map_at<PREC>(a.gmap.data, a.goff_d), g, wave, lane, geo, nodump);
-  if (ok && hh == 0 && a.density) a.density[p] = sigma;
-  {
-    float rgb[3];
-    color_stage<PREC, 0>(st, geo, a.dirx, a.diry, a.dirz, wave, lane, rgb, ColorDump{nullptr, nullptr, 0});
-    if (ok && hh == 0 && a.color) {
-      a.color[3 * (size_t)p] = rgb[0];
-      a.color[3 * (size_t)p + 1] = rgb[1];
-      a.color[3 * (size_t)p + 2] = rgb[2];
-    }
-  }
-  if (JK != 0) {
-    f32x16 jac[1];
-    float flow[3];
-    jacobian_stage<JK, PRECJ, 0>(st, map_at<PRECJ>(a.gmap.data, a.goff_j), g, nullptr, A, wave, lane, jac, flow, nodump);
-    if (ok && a.jacobian) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int d = 16 * hh + r;
-        if (d < 3 * A) a.jacobian[(size_t)p * (3 * A) + d] = jac[0][r];
-      }
-    }
-  }
-}
-
 // ---- fusion of the fields of several context views ------------------------------------------------
 // The B context images are G = B / V scenes of V consecutive views (batch element b = g*V + v) on one grid.  s_v = the frustum
 // predicate of the selection (point_in_view) for view v, all ones without cameras; c = the number of views that see a node.
@@ -2792,7 +2674,7 @@ __device__ __forceinline__ void combine_rows(const float* __restrict__ in, float
 __global__ void __launch_bounds__(NJF_COMBINE_THREADS) field_combine_kernel(CombineArgs a) {
   __shared__ float w[NJF_FIELD_MAX_VIEWS][NJF_COMBINE_THREADS];
   __shared__ float wsum[NJF_COMBINE_THREADS];
-  const int entries = a.count ? min(max(*a.count, 0), a.capacity) : a.capacity;
+  const int entries = counted_length(a.count, a.capacity);
   const int first = blockIdx.x * NJF_COMBINE_THREADS;
   if (first >= entries) return;  // the whole workgroup, before any barrier
   const int rows = min(NJF_COMBINE_THREADS, entries - first);
@@ -2997,7 +2879,7 @@ __global__ void __launch_bounds__(NJF_CC_THREADS) components_init_kernel(Compone
     }
   }
   if (LIST) {
-    const int n = a.entry_count ? min(max(*a.entry_count, 0), a.entry_capacity) : a.entry_capacity;
+    const int n = counted_length(a.entry_count, a.entry_capacity);
     if (tid < 2) range[tid] = cc_lower_bound(a.entries, n, base + (tid ? nloc : 0));
     __syncthreads();
     for (int e = range[0] + tid; e < range[1]; e += NJF_CC_THREADS) {
@@ -3259,7 +3141,7 @@ __global__ void __launch_bounds__(NJF_BAND_THREADS) band_scatter_kernel(BandArgs
 __global__ void __launch_bounds__(256) field_scatter_kernel(const float* __restrict__ values, const int* __restrict__ indices,
                                                             const int* __restrict__ count, int capacity, float* __restrict__ out,
                                                             int out_size) {
-  const int entries = count ? min(max(*count, 0), capacity) : capacity;
+  const int entries = counted_length(count, capacity);
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   if (i >= entries) return;  // (a workgroup past the count leaves; rows past the count are never read)
   const int g = indices[i];
@@ -3279,7 +3161,7 @@ struct BandLeakArgs {
 // entries with a neighbour g +- dir_k (the seven mesh directions, inside the grid: no wrap at the faces) outside the band
 __global__ void __launch_bounds__(NJF_BAND_THREADS) band_leaks_kernel(BandLeakArgs a) {
   __shared__ int wave_count[NJF_BAND_THREADS / 64];
-  const int entries = a.count ? min(max(*a.count, 0), a.capacity) : a.capacity;
+  const int entries = counted_length(a.count, a.capacity);
   const long long base = (long long)blockIdx.x * NJF_FIELD_BAND_BLOCK;
   if (base >= entries) return;  // (uniform over the workgroup)
   int n = 0;
@@ -3343,8 +3225,8 @@ struct TwistArgs {
   double* partial;        // [K][chunks][stride]
 };
 
-__device__ __forceinline__ int twist_active(const TwistArgs& a) { return a.parts_count ? min(max(*a.parts_count, 0), a.K) : a.K; }
-__device__ __forceinline__ int twist_rows(const TwistArgs& a) { return a.count ? min(max(*a.count, 0), a.n) : a.n; }
+__device__ __forceinline__ int twist_active(const TwistArgs& a) { return counted_length(a.parts_count, a.K); }
+__device__ __forceinline__ int twist_rows(const TwistArgs& a) { return counted_length(a.count, a.n); }
 __device__ __forceinline__ double twist_weight(const TwistArgs& a, long long i) {
   if (!a.weights) return 1.0;
   const float w = a.weights[i];
@@ -4934,9 +4816,10 @@ extern "C" int njf_debug_read_stamps(unsigned* host_out, int n) {
 }
 #endif
 
-template <typename K, typename A>
-static int launch_fused(K kernel, const A& args, int work_items, hipStream_t s, int lds_floats = LDS_FLOATS_RENDER) {
-  static_assert(sizeof(A) <= 4096, "kernel args too large");
+template <typename K, typename A, typename... More>
+static int launch_fused(K kernel, const A& args, int work_items, hipStream_t s, int lds_floats = LDS_FLOATS_RENDER,
+                        const More&... more) {
+  static_assert(sizeof(A) + (sizeof(More) + ... + 0) <= 4096, "kernel args too large");
   const int grid = (work_items + NJF_WAVES - 1) / NJF_WAVES;
 #ifdef NJF_STAMPS
   const size_t lds = (size_t)(lds_floats + NJF_STAMP_SLOTS) * sizeof(float);
@@ -4948,7 +4831,7 @@ static int launch_fused(K kernel, const A& args, int work_items, hipStream_t s, 
     if (e != hipSuccess) return (int)e;
     lds_attribute_remember((const void*)kernel);
   }
-  kernel<<<grid, NJF_THREADS, lds, s>>>(args);
+  kernel<<<grid, NJF_THREADS, lds, s>>>(args, more...);
   return launch_status();
 }
 
@@ -5110,61 +4993,93 @@ extern "C" int njf_render_forward(const float* origins, const float* directions,
   });
 }
 
+// ---- the decoder at points (points_kernel): what its three entry points share ----------------------------------------------
+// Validation and the shared kernel arguments; returns the evaluator's MODE, or an error (< 0).  mode 0: the proposal net; mode 1:
+// the decoder, of which `density_only` (no Jacobian head asked for either) runs the density net alone.  The outputs are the caller's.
+static int make_decoder_args(const NjfCameras* cams, const NjfFeatureMap* gmap, int gmap_offset_density, int gmap_offset_jacobian,
+                             int mode, int jacobian_kind, bool density_only, const float* w_density, const float* b_density,
+                             const float* w_color, const float* b_color, const float* w_jacobian, const float* b_jacobian,
+                             int precision, DecoderArgs& a) {
+  if (!cams || !gmap || !w_density || !b_density) return NJF_E_NULL;
+  if (!cams->ctxt_w2c || !cams->ctxt_k || !gmap->data) return NJF_E_NULL;
+  if (cams->batch < 1) return NJF_E_SHAPE;
+  if (mode != 0 && mode != 1) return NJF_E_MODE;
+  if (!valid_precision(precision)) return NJF_E_MODE;
+  if (gmap->height < 1 || gmap->width < 1) return NJF_E_SHAPE;
+  int rc;
+  if ((rc = check_gmap(gmap, gmap_offset_density, NJF_ZDIM, density_precision(precision)))) return rc;
+  // a point carries the float index of its batch element in 32 bits (PointGeom::gofs): maps up to 16 GiB
+  if ((long long)cams->batch * gmap->height * gmap->width * gmap->stride > 0xffffffffLL) return NJF_E_SHAPE;
+  int kmode = 0;
+  if (mode == 1) {
+    if ((rc = check_jacobian(jacobian_kind, cams, gmap, gmap_offset_jacobian, w_jacobian, b_jacobian, precision))) return rc;
+    const bool with_j = jacobian_kind != NJF_JACOBIAN_NONE;
+    static_assert(NJF_JACOBIAN_MLP == 1 && NJF_JACOBIAN_TRANSFORMER == 2, "MODE 3 / 4 = 2 + the head's kind");
+    kmode = !with_j && density_only ? 1 : 2 + jacobian_kind;
+    if (kmode >= 2) {
+      if (!w_color || !b_color) return NJF_E_NULL;
+      if ((rc = check_contiguous(w_density, w_color, w_jacobian, with_j))) return rc;
+    }
+  }
+  a = DecoderArgs{*cams, *gmap, gmap_offset_density, gmap_offset_jacobian, w_density, b_density, b_color, b_jacobian};
+  return kmode;
+}
+
+// the one dispatch on (MODE, precisions, FEAT): a source has the instantiations of its SRC::MODES, the feature dump those of
+// the point list's ResnetFC head
+template <int MODE, class SRC>
+static int launch_points_mode(const SRC& src, const DecoderArgs& a, int tiles, int precision, hipStream_t s) {
+  auto launch = [&](auto kernel) { return launch_fused(kernel, a, tiles, s, LDS_FLOATS_RENDER, src); };
+  if constexpr (!((SRC::MODES >> MODE) & 1)) return NJF_E_MODE;
+  else if constexpr (MODE <= 2)
+    return with_precision(density_precision(precision), [&](auto P) { return launch(points_kernel<SRC, MODE, NJF_P>); });
+  else
+    return with_precisions(precision, [&](auto P, auto PJ) {
+      if constexpr (MODE == 3 && SRC::EXTRAS) {
+        if (a.features) {  // (the plain-fp16 mode has no training instantiation of resnet_tile: its block biases ride elsewhere)
+          if constexpr (NJF_PJ == PREC_F16) return (int)NJF_E_MODE;
+          else return launch(points_kernel<SRC, 3, NJF_P, NJF_PJ, true>);
+        }
+      }
+      return launch(points_kernel<SRC, MODE, NJF_P, NJF_PJ>);
+    });
+}
+
+template <class SRC>
+static int launch_points(const SRC& src, const DecoderArgs& a, int kmode, int entries, int precision, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  const int tiles = (entries + 31) / 32;
+  switch (kmode) {
+    case 0: return launch_points_mode<0>(src, a, tiles, precision, s);
+    case 1: return launch_points_mode<1>(src, a, tiles, precision, s);
+    case 2: return launch_points_mode<2>(src, a, tiles, precision, s);
+    case 3: return launch_points_mode<3>(src, a, tiles, precision, s);
+    default: return launch_points_mode<4>(src, a, tiles, precision, s);
+  }
+}
+
+static ConstantDirection view_direction(const float* view_dir) {
+  return view_dir ? ConstantDirection{view_dir[0], view_dir[1], view_dir[2]} : ConstantDirection{0.f, 0.f, 1.f};
+}
+
 extern "C" int njf_points_forward(const float* xyz, const float* dirs, int points_per_batch, const NjfCameras* cams,
                                   const NjfFeatureMap* gmap, int gmap_offset_density, int gmap_offset_jacobian, int mode,
                                   int jacobian_kind, const float* w_density, const float* b_density, const float* w_color,
                                   const float* b_color, const float* w_jacobian, const float* b_jacobian, float* density,
                                   float* color, float* flow, float* jacobian, float* geo, float* features, int precision,
                                   void* stream) {
-  if (!xyz || !cams || !gmap || !w_density || !b_density) return NJF_E_NULL;
-  if (!cams->ctxt_w2c || !cams->ctxt_k || !gmap->data) return NJF_E_NULL;
-  if (points_per_batch < 1 || cams->batch < 1) return NJF_E_SHAPE;
-  if (mode != 0 && mode != 1) return NJF_E_MODE;
-  if (!valid_precision(precision)) return NJF_E_MODE;
-  int rc;
-  if ((rc = check_gmap(gmap, gmap_offset_density, NJF_ZDIM, density_precision(precision)))) return rc;
-  // a point carries the float index of its batch element in 32 bits (PointGeom::gofs): maps up to 16 GiB
-  if ((long long)cams->batch * gmap->height * gmap->width * gmap->stride > 0xffffffffLL) return NJF_E_SHAPE;
-  PointsArgs a;
-  a.xyz = xyz;
-  a.dirs = dirs;
-  a.points_per_batch = points_per_batch;
-  a.total_points = points_per_batch * cams->batch;
-  a.cams = *cams;
-  a.gmap = *gmap;
-  a.goff_d = gmap_offset_density;
-  a.goff_j = gmap_offset_jacobian;
-  a.w_all = w_density;
-  a.b_d = b_density;
-  a.b_c = b_color;
-  a.b_j = b_jacobian;
-  a.density = density;
-  a.color = color;
-  a.flow = flow;
-  a.jacobian = jacobian;
-  a.geo = geo;
-  a.features = features;
+  if (!xyz) return NJF_E_NULL;
+  if (points_per_batch < 1) return NJF_E_SHAPE;
+  DecoderArgs a;
+  const int kmode = make_decoder_args(cams, gmap, gmap_offset_density, gmap_offset_jacobian, mode, jacobian_kind, false, w_density,
+                                      b_density, w_color, b_color, w_jacobian, b_jacobian, precision, a);
+  if (kmode < 0) return kmode;
+  const PointList src{xyz, dirs, points_per_batch, points_per_batch * cams->batch};
   // the per-block features exist for a ResnetFC head evaluated next to the decoder (mode 1, NJF_JACOBIAN_MLP)
-  if (features && (mode != 1 || jacobian_kind != NJF_JACOBIAN_MLP)) return NJF_E_MODE;
-  if (features && (long long)a.total_points * 5 * 128 > 0x7fffffffffLL) return NJF_E_SHAPE;
-  const int tiles = (a.total_points + 31) / 32;
-  hipStream_t s = (hipStream_t)stream;
-  if (mode == 0)
-    return with_precision(density_precision(precision), [&](auto P) { return launch_fused(points_kernel<0, NJF_P>, a, tiles, s); });
-  if (!w_color || !b_color) return NJF_E_NULL;
-  if ((rc = check_jacobian(jacobian_kind, cams, gmap, gmap_offset_jacobian, w_jacobian, b_jacobian, precision))) return rc;
-  const bool with_j = jacobian_kind != NJF_JACOBIAN_NONE;
-  if ((rc = check_contiguous(w_density, w_color, w_jacobian, with_j))) return rc;
-  if (!with_j)
-    return with_precision(density_precision(precision), [&](auto P) { return launch_fused(points_kernel<1, NJF_P>, a, tiles, s); });
-  return with_precisions(precision, [&](auto P, auto PJ) {
-    if (features) {   // (the plain-fp16 mode has no training instantiation of resnet_tile: its block biases ride elsewhere)
-      if constexpr (NJF_PJ == PREC_F16) return (int)NJF_E_MODE;
-      else return launch_fused(points_kernel<2, NJF_P, NJF_PJ, true>, a, tiles, s);
-    }
-    if (jacobian_kind == NJF_JACOBIAN_MLP) return launch_fused(points_kernel<2, NJF_P, NJF_PJ>, a, tiles, s);
-    return launch_fused(points_kernel<3, NJF_P, NJF_PJ>, a, tiles, s);
-  });
+  if (features && kmode != 3) return NJF_E_MODE;
+  if (features && (long long)src.total * 5 * 128 > 0x7fffffffffLL) return NJF_E_SHAPE;
+  a.density = density, a.color = color, a.jacobian = jacobian, a.flow = flow, a.geo = geo, a.features = features;
+  return launch_points(src, a, kmode, src.total, precision, stream);
 }
 
 // ---- voxel-grid field extraction ---------------------------------------------------------------------------------
@@ -5238,54 +5153,18 @@ extern "C" int njf_field_forward(const NjfFieldGrid* grid, const int* indices, c
                                  const float* w_density, const float* b_density, const float* w_color, const float* b_color,
                                  const float* w_jacobian, const float* b_jacobian, float* density, float* color,
                                  float* jacobian, int precision, void* stream) {
-  if (!grid || !cams || !gmap || !w_density || !b_density) return NJF_E_NULL;
-  if (!cams->ctxt_w2c || !cams->ctxt_k || !gmap->data) return NJF_E_NULL;
-  FieldArgs a;
-  int rc = make_field_list(grid, cams->batch, indices, count, capacity, a.list);
+  if (!grid || !cams) return NJF_E_NULL;
+  GridNodes src{view_direction(view_dir)};
+  int rc = make_field_list(grid, cams->batch, indices, count, capacity, src.list);
   if (rc) return rc;
-  if (mode != 0 && mode != 1) return NJF_E_MODE;
-  if (!valid_precision(precision)) return NJF_E_MODE;
-  if (gmap->height < 1 || gmap->width < 1) return NJF_E_SHAPE;
-  if ((rc = check_gmap(gmap, gmap_offset_density, NJF_ZDIM, density_precision(precision)))) return rc;
-  if ((long long)cams->batch * gmap->height * gmap->width * gmap->stride > 0xffffffffLL) return NJF_E_SHAPE;  // PointGeom::gofs
-  if (mode == 0 && !density) return NJF_E_NULL;
-  a.dirx = view_dir ? view_dir[0] : 0.f;
-  a.diry = view_dir ? view_dir[1] : 0.f;
-  a.dirz = view_dir ? view_dir[2] : 1.f;
-  a.cams = *cams;
-  a.gmap = *gmap;
-  a.goff_d = gmap_offset_density;
-  a.goff_j = gmap_offset_jacobian;
-  a.w_all = w_density;
-  a.b_d = b_density;
-  a.b_c = b_color;
-  a.b_j = b_jacobian;
-  a.density = density;
-  a.color = color;
-  a.jacobian = jacobian;
-  const int tiles = (capacity + 31) / 32;
-  hipStream_t s = (hipStream_t)stream;
-  if (mode == 0) {
-    if (capacity == 0) return NJF_OK;
-    return with_precision(density_precision(precision), [&](auto P) { return launch_fused(field_points_kernel<0, NJF_P>, a, tiles, s); });
-  }
-  if ((rc = check_jacobian(jacobian_kind, cams, gmap, gmap_offset_jacobian, w_jacobian, b_jacobian, precision))) return rc;
-  const bool with_j = jacobian_kind != NJF_JACOBIAN_NONE;
-  if (with_j && !jacobian) return NJF_E_NULL;
-  if (!with_j && !color) {  // density only: the density net's blob is all that is streamed
-    if (!density) return NJF_E_NULL;
-    if (capacity == 0) return NJF_OK;
-    return with_precision(density_precision(precision), [&](auto P) { return launch_fused(field_points_kernel<1, NJF_P>, a, tiles, s); });
-  }
-  if (!w_color || !b_color) return NJF_E_NULL;
-  if ((rc = check_contiguous(w_density, w_color, w_jacobian, with_j))) return rc;
+  DecoderArgs a;  // (no head and no colour output: the density net's blob is all that is streamed)
+  const int kmode = make_decoder_args(cams, gmap, gmap_offset_density, gmap_offset_jacobian, mode, jacobian_kind, !color, w_density,
+                                      b_density, w_color, b_color, w_jacobian, b_jacobian, precision, a);
+  if (kmode < 0) return kmode;
+  if (kmode <= 1 ? !density : (kmode == 2 ? !color : !jacobian)) return NJF_E_NULL;  // the last stage's output
+  a.density = density, a.color = color, a.jacobian = jacobian;
   if (capacity == 0) return NJF_OK;
-  if (!with_j)
-    return with_precision(density_precision(precision), [&](auto P) { return launch_fused(field_points_kernel<2, NJF_P>, a, tiles, s); });
-  return with_precisions(precision, [&](auto P, auto PJ) {
-    if (jacobian_kind == NJF_JACOBIAN_MLP) return launch_fused(field_points_kernel<3, NJF_P, NJF_PJ>, a, tiles, s);
-    return launch_fused(field_points_kernel<4, NJF_P, NJF_PJ>, a, tiles, s);
-  });
+  return launch_points(src, a, kmode, capacity, precision, stream);
 }
 
 // ---- isosurface mesh ---------------------------------------------------------------------------------------------------
@@ -5392,49 +5271,18 @@ extern "C" int njf_field_forward_at(const float* xyz, const int* node, const int
                                     const float* w_density, const float* b_density, const float* w_color, const float* b_color,
                                     const float* w_jacobian, const float* b_jacobian, float* density, float* color,
                                     float* jacobian, int precision, void* stream) {
-  if (!xyz || !node || !cams || !gmap || !w_density || !b_density || !w_color || !b_color) return NJF_E_NULL;
-  if (!cams->ctxt_w2c || !cams->ctxt_k || !gmap->data) return NJF_E_NULL;
-  if (capacity < 0 || cams->batch < 1) return NJF_E_SHAPE;
+  if (!xyz || !node || !cams) return NJF_E_NULL;
+  if (capacity < 0) return NJF_E_SHAPE;
   if (nodes_per_batch < 1 || (long long)nodes_per_batch * cams->batch > 0x7fffffffLL) return NJF_E_VALUE;
-  if (!valid_precision(precision)) return NJF_E_MODE;
-  if (gmap->height < 1 || gmap->width < 1) return NJF_E_SHAPE;
-  int rc;
-  if ((rc = check_gmap(gmap, gmap_offset_density, NJF_ZDIM, density_precision(precision)))) return rc;
-  if ((long long)cams->batch * gmap->height * gmap->width * gmap->stride > 0xffffffffLL) return NJF_E_SHAPE;  // PointGeom::gofs
-  if ((rc = check_jacobian(jacobian_kind, cams, gmap, gmap_offset_jacobian, w_jacobian, b_jacobian, precision))) return rc;
-  const bool with_j = jacobian_kind != NJF_JACOBIAN_NONE;
-  if (with_j ? !jacobian : !color) return NJF_E_NULL;
-  if ((rc = check_contiguous(w_density, w_color, w_jacobian, with_j))) return rc;
-  FieldAtArgs a;
-  a.xyz = xyz;
-  a.node = node;
-  a.count = count;
-  a.capacity = capacity;
-  a.nodes = nodes_per_batch;
-  a.total = nodes_per_batch * cams->batch;
-  a.dirx = view_dir ? view_dir[0] : 0.f;
-  a.diry = view_dir ? view_dir[1] : 0.f;
-  a.dirz = view_dir ? view_dir[2] : 1.f;
-  a.cams = *cams;
-  a.gmap = *gmap;
-  a.goff_d = gmap_offset_density;
-  a.goff_j = gmap_offset_jacobian;
-  a.w_all = w_density;
-  a.b_d = b_density;
-  a.b_c = b_color;
-  a.b_j = b_jacobian;
-  a.density = density;
-  a.color = color;
-  a.jacobian = jacobian;
+  DecoderArgs a;
+  const int kmode = make_decoder_args(cams, gmap, gmap_offset_density, gmap_offset_jacobian, 1, jacobian_kind, false, w_density,
+                                      b_density, w_color, b_color, w_jacobian, b_jacobian, precision, a);
+  if (kmode < 0) return kmode;
+  if (kmode == 2 ? !color : !jacobian) return NJF_E_NULL;  // the last stage's output
+  a.density = density, a.color = color, a.jacobian = jacobian;
   if (capacity == 0) return NJF_OK;
-  const int tiles = (capacity + 31) / 32;
-  hipStream_t s = (hipStream_t)stream;
-  if (!with_j)
-    return with_precision(density_precision(precision), [&](auto P) { return launch_fused(field_at_kernel<2, NJF_P>, a, tiles, s); });
-  return with_precisions(precision, [&](auto P, auto PJ) {
-    if (jacobian_kind == NJF_JACOBIAN_MLP) return launch_fused(field_at_kernel<3, NJF_P, NJF_PJ>, a, tiles, s);
-    return launch_fused(field_at_kernel<4, NJF_P, NJF_PJ>, a, tiles, s);
-  });
+  const StoredNodes src{view_direction(view_dir), xyz, node, count, capacity, nodes_per_batch, nodes_per_batch * cams->batch};
+  return launch_points(src, a, kmode, capacity, precision, stream);
 }
 
 // ---- fusion of several context views ----------------------------------------------------------------------------------

@@ -157,10 +157,10 @@ def _check_rows(cloud, dense, common, grid, exact=False, fields=("density", "col
 @pytest.mark.parametrize("precision", ["f32", None, "f16"])
 @pytest.mark.parametrize("kind,adim", [("jacobian_mlp", 8), ("jacobian_transformer", 6)])
 def test_exact_mode_equals_the_dense_route(models, dev, kind, adim, precision, batch):
-    """cull=None, in_frustum=False: by definition the dense route restricted to density >= threshold.  Observed on the MI355X:
-    density, colour and Jacobian rows are BIT-EQUAL to the gathered dense rows in all twelve cases (the evaluator shares every
-    stage with the point-list kernel and a point's result does not depend on its tile); asserted with torch.equal for "f32",
-    with the 1e-4 bound for the other precisions (the (rel, bit-equal) pairs are printed)."""
+    """cull=None, in_frustum=False: by definition the dense route restricted to density >= threshold.  Density, colour and
+    Jacobian rows are BIT-EQUAL to the gathered dense rows in all twelve cases, asserted with torch.equal in every precision:
+    both routes run the one evaluator body (points_kernel, fed from the grid list here and from the point list there) and a
+    point's result does not depend on its tile.  (Observed on the MI355X also while the two routes had a kernel each.)"""
     from neural_jacobian_field_amd import hip
     from neural_jacobian_field_amd.field_volume import extract_field
     model = models(kind, adim)
@@ -177,7 +177,7 @@ def test_exact_mode_equals_the_dense_route(models, dev, kind, adim, precision, b
         assert cloud.stage_names == ("density",)
         common = _check_set(cloud.index, keep, _band(dense["density"], thr), int(keep.sum()))
         assert common.numel() > 0.2 * keep.numel()
-        _check_rows(cloud, dense, common, grid, exact=precision == "f32")
+        _check_rows(cloud, dense, common, grid, exact=True)
     finally:
         model.set_precision(hip.DEFAULT_PRECISION)
 

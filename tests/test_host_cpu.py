@@ -850,7 +850,7 @@ def test_static_isa_properties_of_the_fused_kernels():
     # the plain-fp16 kernels (round 5): no spilled VGPR in any inference instantiation -- the shared tile state of the render kernel
     # (TileShareF16, 16-24 registers) is only instantiated where it fits -- and the weight stream is the LDS DMA here too
     for name in ("void render_kernel<1, 3, 0, false, 3>", "void render_kernel<1, 3, 0, true, 3>", "void render_kernel<2, 3, 0, false, 3>",
-                 "void render_kernel<2, 3, 0, true, 3>", "void proposal_kernel<3, false>", "void points_kernel<2, 3, 3, false>"):
+                 "void render_kernel<2, 3, 0, true, 3>", "void proposal_kernel<3, false>", "void points_kernel<PointList, 3, 3, 3, false>"):
         r = row(name)
         assert r["spill"] == 0 and r["lds_dma"] > 0, (name, r)
 

@@ -665,8 +665,9 @@ def test_footprint_and_camera_transform_vs_reference_fixture(dev, golden):
 
 
 def test_points_tile_straddling_batch_elements(dev, golden):
-    """A 32-point tile of points_kernel that spans two batch elements with DIFFERENT cameras and actions (40 points per
-    element: tile 1 holds points 32..39 of element 0 and 0..23 of element 1) equals the per-element evaluation."""
+    """A 32-point tile of points_kernel (the point-list source) that spans two batch elements with DIFFERENT cameras and
+    actions (40 points per element: tile 1 holds points 32..39 of element 0 and 0..23 of element 1) equals the
+    per-element evaluation."""
     from neural_jacobian_field_amd import synthetic
     from neural_jacobian_field_amd.config import model_cfg_from_dict
     from neural_jacobian_field_amd.decoder import PixelEncoding
