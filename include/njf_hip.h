@@ -612,6 +612,54 @@ int njf_field_twists(const float* xyz, const float* jacobian, const int* labels,
                      double* energy, double* residual, double* q, double* p, double* l, float* row_residual,
                      double* workspace, long long workspace_doubles, int phases, void* stream);
 
+/* ---- joints between the parts of an extracted field (ABI v20, additive) ---------------------------------
+ * Which parts touch on the grid, where, and how one moves relative to the other under each command channel: the relative twist
+ * of two parts in contact is the joint, its screw axis the hinge.
+ * Inputs, all on the device: grid and batch B (N = nx*ny*nz, B*N < 2^31); the list of a cloud -- indices [n] int32, ascending
+ * global indices, and count (int32, NULL = n: rows from min(*count, n) on are never read; an index outside [0, B*N) is
+ * dropped) --; labels [n] int32 per row (negative: no part); the part list and twists of njf_field_twists: parts [K] (ascending
+ * in the used slots), parts_count (int32, NULL = K: the true number, it may exceed K), part_status [K], double centroid [K,3],
+ * omega, velocity [K,A,3]; connectivity 6 or 14 (the direction table of njf_field_components); min_contacts >= 1; max_joints J.
+ * SLOTS  row i has slot p iff i < *count, p < min(*parts_count, K) and labels[i] == parts[p] (the rule of njf_field_twists);
+ *        every other row has none.
+ * CONTACTS  for every row with slot p at node g = (b, ix, iy, iz) and every direction d among the FIRST connectivity/2 of the
+ *        table -- the positive sense only, so each unordered node pair is seen once --, the neighbour g' = g + d must lie inside
+ *        the grid (no wrap at the faces, nothing crosses batch elements) and be a list row with slot q != p.  Then, with lo =
+ *        min(p, q), hi = max(p, q): contacts[lo][hi] += 1 and sum2[lo][hi][c] += i_c + i'_c for c = x, y, z, in 64-bit
+ *        integers: sum2 is twice the contact midpoint in node units, exact, whatever the order of the adds.
+ * LIST   the pairs with contacts >= min_contacts in ascending (lo, hi); the first J are stored and *out_count is their true
+ *        number.  part_a, part_b [J] int32 = lo, hi; contacts [J] int64; status [J] int32 = part_status[lo] | part_status[hi].
+ *        Unused rows hold -1 in part_a and part_b and 0 elsewhere.
+ * TWISTS anchor [J,3] double, per component m = (double)sum2_c / (2.0 * (double)contacts), x_c = (double)origin_c +
+ *        (double)step_c * m (a multiply, then an add).  Per joint and channel a, all in double in this order, s = lo, hi:
+ *        r_s = x - c_s;  u_s = v_{s,a} + cross(omega_{s,a}, r_s) with cross(w, r) = (wy*rz - wz*ry, wz*rx - wx*rz, wx*ry - wy*rx);
+ *        out_omega [J,A,3] = omega_hi - omega_lo;  out_velocity [J,A,3] = u_hi - u_lo.  No sum runs over rows.
+ * workspace: NJF_FIELD_JOINTS_WORKSPACE(B*N, K) 64-bit words of the caller's (workspace_words says how many it holds): the table
+ * [K][K][4] (contacts, sum2), then the dense int32 slot volume [B*N] (-1: no slot).  Two memsets and four launches on `stream`,
+ * no host read (capture-safe); the only atomics are 64-bit integer adds.  `phases` = NJF_FIELD_JOINTS_ALL, or a subset to time
+ * the launches apart (each reads what the earlier ones left); with NJF_FIELD_JOINTS_PER_LANE the contacts launch runs in its
+ * per-lane form -- every lane adds for itself instead of the wave combining equal pairs first: the same table, kept to be
+ * measured against.  Returns, before the first launch: NJF_E_VALUE for a connectivity not 6 or 14, K outside
+ * [1, NJF_FIELD_TWISTS_MAX_PARTS], A outside [1, NJF_MAX_ACTION_DIM], J outside [1, NJF_FIELD_JOINTS_MAX], min_contacts < 1 or
+ * unknown phases; NJF_E_SHAPE for n < 0, batch < 1, B*N >= 2^31 or a workspace that is too small; NJF_E_NULL for a missing
+ * pointer (indices and labels may be NULL when n == 0). */
+#define NJF_FIELD_JOINTS_MAX 4096
+#define NJF_FIELD_JOINTS_TABLE_WORDS(K) (4LL * (K) * (K))
+#define NJF_FIELD_JOINTS_WORKSPACE(total, K) (NJF_FIELD_JOINTS_TABLE_WORDS(K) + ((long long)(total) + 1) / 2)
+#define NJF_FIELD_JOINTS_CLEAR 1        /* phases: the two memsets, then one launch each */
+#define NJF_FIELD_JOINTS_SLOTS 2
+#define NJF_FIELD_JOINTS_CONTACTS 4
+#define NJF_FIELD_JOINTS_LIST 8
+#define NJF_FIELD_JOINTS_TWISTS 16
+#define NJF_FIELD_JOINTS_ALL 31
+#define NJF_FIELD_JOINTS_PER_LANE 32    /* modifier of _CONTACTS, not part of _ALL */
+int njf_field_joints(const NjfFieldGrid* grid, int batch, const int* indices, const int* labels, const int* count, int n,
+                     const int* parts, const int* parts_count, int num_parts, const int* part_status, const double* centroid,
+                     const double* omega, const double* velocity, int action_dim, int connectivity, int min_contacts,
+                     int max_joints, int* part_a, int* part_b, long long* contacts, int* status, int* out_count, double* anchor,
+                     double* out_omega, double* out_velocity, long long* workspace, long long workspace_words, int phases,
+                     void* stream);
+
 /* ---- stand-alone sampler / compositing ops (API parity with the un-fused reference calls) -- */
 /* RaySamples.get_weights (ray_samplers.py:77-101): deltas, densities [N,S] -> weights [N,S]. */
 int njf_alpha_weights(const float* deltas, const float* densities, int rays, int samples, float* weights, void* stream);

@@ -3512,6 +3512,203 @@ __global__ void __launch_bounds__(64) twist_residual_sum_kernel(TwistArgs a) {
 }
 
 // =============================================================================================
+// joints between parts: grid contacts and relative twists (njf_field_joints)
+// =============================================================================================
+// Two parts TOUCH where a node of one has a node of the other as its neighbour along one of the first C/2 mesh directions.  The
+// rows' slots go into a dense int32 volume [B*N] (-1: no slot), every row then looks up its 3 or 7 positive neighbours and adds
+// (1, ix + ix', iy + iy', iz + iz') to entry (lo, hi) of a K x K x 4 table of 64-bit integers: integer atomics only, so the
+// table is a function of the inputs alone.  One workgroup lists the pairs of at least min_contacts contacts in ascending
+// (lo, hi); thread (j, a) forms the anchor -- the contact midpoint -- and the relative twist there, in double.
+#define NJF_JOINT_THREADS 256
+#define NJF_JOINT_LIST_THREADS 1024
+struct JointArgs {
+  int dims[3];
+  float origin[3], step[3];
+  int nodes, total;        // N, B*N
+  const int* indices;      // [n] ascending global indices
+  const int* labels;       // [n]
+  const int* count;        // or null
+  int n;
+  const int* parts;        // [K]
+  const int* parts_count;  // or null
+  int K, A, half, min_contacts, J;
+  const int* part_status;  // [K]
+  const double *centroid, *omega, *velocity;   // [K,3], [K,A,3], [K,A,3]
+  int* volume;             // [B*N] slot of the node, -1 without one
+  unsigned long long* table;   // [K][K][4]: contacts, sum2 x, y, z
+  int *part_a, *part_b, *status, *out_count;   // [J], [J], [J], [1]
+  long long* contacts;     // [J]
+  double *anchor, *out_omega, *out_velocity;   // [J,3], [J,A,3], [J,A,3]
+};
+
+// each row binary-searches its label in parts[0 : min(parts_count, K)] and writes its slot at its node
+__global__ void __launch_bounds__(NJF_JOINT_THREADS) joint_slots_kernel(JointArgs a) {
+  const int rows = counted_length(a.count, a.n);
+  const long long i = (long long)blockIdx.x * NJF_JOINT_THREADS + threadIdx.x;
+  if (i >= rows) return;  // (rows past the count are never read)
+  const int g = a.indices[i], label = a.labels[i];
+  if (g < 0 || g >= a.total || label < 0) return;
+  const int active = counted_length(a.parts_count, a.K);
+  const int p = cc_lower_bound(a.parts, active, label);
+  if (p < active && a.parts[p] == label) a.volume[g] = p;  // g < B*N
+}
+
+__device__ __forceinline__ long long joint_wave_sum(long long v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+
+// One thread per row: the slots of its positive neighbours, 64-bit integer adds into the pair table.  COMBINE: the lanes of a
+// wave that hold the same pair in one direction (a flat face: all of them) are added up first -- a leader loop over the wave's
+// distinct keys -- and the leader alone touches memory; otherwise every lane adds for itself.  Same table either way.
+template <bool COMBINE>
+__global__ void __launch_bounds__(NJF_JOINT_THREADS) joint_contacts_kernel(JointArgs a) {
+  const int rows = counted_length(a.count, a.n);
+  const long long i = (long long)blockIdx.x * NJF_JOINT_THREADS + threadIdx.x;
+  const int lane = threadIdx.x & 63;
+  int g = -1, p = -1, ix = 0, iy = 0, iz = 0;
+  if (i < rows) {
+    g = a.indices[i];
+    if (g >= 0 && g < a.total) {
+      p = a.volume[g];
+      const int node = g % a.nodes;
+      const int yz = a.dims[1] * a.dims[2];
+      ix = node / yz;
+      const int r = node - ix * yz;
+      iy = r / a.dims[2];
+      iz = r - iy * a.dims[2];
+    }
+  }
+  // (no early return: the shuffles below need every lane of the wave)
+  for (int k = 0; k < a.half; ++k) {
+    // direction k of the mesh table: (1,0,0) (0,1,0) (0,0,1) (1,1,0) (1,0,1) (0,1,1) (1,1,1)
+    const int dx = (0x59 >> k) & 1, dy = (0x6a >> k) & 1, dz = (0x74 >> k) & 1;
+    int key = -1;
+    if (p >= 0 && ix + dx < a.dims[0] && iy + dy < a.dims[1] && iz + dz < a.dims[2]) {
+      // the neighbour is inside the grid, hence in the same batch element, hence below B*N
+      const int q = a.volume[g + (dx * a.dims[1] + dy) * a.dims[2] + dz];
+      if (q >= 0 && q != p) key = min(p, q) * a.K + max(p, q);  // < K*K
+    }
+    const long long sx = 2ll * ix + dx, sy = 2ll * iy + dy, sz = 2ll * iz + dz;
+    if (!COMBINE) {
+      if (key >= 0) {
+        unsigned long long* e = a.table + (size_t)key * 4;
+        atomicAdd(e, 1ull);
+        atomicAdd(e + 1, (unsigned long long)sx);
+        atomicAdd(e + 2, (unsigned long long)sy);
+        atomicAdd(e + 3, (unsigned long long)sz);
+      }
+    } else {
+      unsigned long long pending = __ballot(key >= 0);
+      while (pending) {  // (uniform over the wave)
+        const int leader = __ffsll((long long)pending) - 1;
+        const int k0 = __shfl(key, leader);
+        const bool mine = key == k0;
+        const unsigned long long same = __ballot(mine);
+        long long tx = mine ? sx : 0, ty = mine ? sy : 0, tz = mine ? sz : 0;
+        if (same & (same - 1)) {  // more than one lane holds the key
+          tx = joint_wave_sum(tx);
+          ty = joint_wave_sum(ty);
+          tz = joint_wave_sum(tz);
+        }
+        if (lane == leader) {
+          unsigned long long* e = a.table + (size_t)k0 * 4;
+          atomicAdd(e, (unsigned long long)__popcll(same));
+          atomicAdd(e + 1, (unsigned long long)tx);
+          atomicAdd(e + 2, (unsigned long long)ty);
+          atomicAdd(e + 3, (unsigned long long)tz);
+        }
+        pending &= ~same;
+      }
+    }
+  }
+}
+
+// One workgroup: the ordered compaction of the K*K table entries with at least min_contacts contacts (entry lo*K + hi ascending
+// is (lo, hi) ascending), the true count, and the padding of the rows past it.
+__global__ void __launch_bounds__(NJF_JOINT_LIST_THREADS) joint_list_kernel(JointArgs a) {
+  __shared__ int wave_count[NJF_JOINT_LIST_THREADS / 64];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int entries = a.K * a.K;
+  int run = 0;
+  for (int base = 0; base < entries; base += NJF_JOINT_LIST_THREADS) {
+    const int e = base + tid;
+    long long c = 0;
+    if (e < entries) c = (long long)a.table[(size_t)e * 4];
+    const bool keep = c >= (long long)a.min_contacts;  // (min_contacts >= 1: an empty entry never passes)
+    const unsigned long long m = __ballot(keep);
+    if (lane == 0) wave_count[wave] = __popcll(m);
+    __syncthreads();
+    int off = run;
+#pragma unroll
+    for (int w = 0; w < NJF_JOINT_LIST_THREADS / 64; ++w) {
+      const int n = wave_count[w];
+      if (w < wave) off += n;
+      run += n;
+    }
+    if (keep) {
+      const int j = off + __popcll(m & ((1ull << lane) - 1ull));
+      if (j < a.J) {
+        const int lo = e / a.K, hi = e - lo * a.K;
+        a.part_a[j] = lo;
+        a.part_b[j] = hi;
+        a.contacts[j] = c;
+        a.status[j] = a.part_status[lo] | a.part_status[hi];
+      }
+    }
+    __syncthreads();
+  }
+  if (tid == 0) *a.out_count = run;  // (at most K*(K-1)/2 < 2^15)
+  for (int j = min(run, a.J) + tid; j < a.J; j += NJF_JOINT_LIST_THREADS) {
+    a.part_a[j] = -1;
+    a.part_b[j] = -1;
+    a.contacts[j] = 0;
+    a.status[j] = 0;
+  }
+}
+
+// thread (j, a): the anchor of joint j and the relative twist of channel a there; zeros for the unused rows
+__global__ void __launch_bounds__(NJF_JOINT_THREADS) joint_twists_kernel(JointArgs a) {
+  const int t = blockIdx.x * NJF_JOINT_THREADS + threadIdx.x;
+  if (t >= a.J * a.A) return;
+  const int j = t / a.A, ch = t - j * a.A;
+  const int lo = a.part_a[j], hi = a.part_b[j];
+  double x[3] = {0.0, 0.0, 0.0}, w[3] = {0.0, 0.0, 0.0}, v[3] = {0.0, 0.0, 0.0};
+  if (lo >= 0) {
+    const unsigned long long* e = a.table + ((size_t)lo * a.K + hi) * 4;  // lo, hi < K
+    const double twice = 2.0 * (double)(long long)e[0];
+    double u[2][3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const double m = (double)(long long)e[1 + c] / twice;
+      x[c] = (double)a.origin[c] + (double)a.step[c] * m;
+    }
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      const int part = s ? hi : lo;
+      const double* cs = a.centroid + (size_t)part * 3;
+      const double* ws = a.omega + ((size_t)part * a.A + ch) * 3;
+      const double* vs = a.velocity + ((size_t)part * a.A + ch) * 3;
+      const double rx = x[0] - cs[0], ry = x[1] - cs[1], rz = x[2] - cs[2];
+      u[s][0] = vs[0] + (ws[1] * rz - ws[2] * ry);
+      u[s][1] = vs[1] + (ws[2] * rx - ws[0] * rz);
+      u[s][2] = vs[2] + (ws[0] * ry - ws[1] * rx);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) w[c] = s ? ws[c] - w[c] : ws[c];  // omega_hi - omega_lo
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) v[c] = u[1][c] - u[0][c];
+  }
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    if (ch == 0) a.anchor[(size_t)j * 3 + c] = x[c];
+    a.out_omega[((size_t)j * a.A + ch) * 3 + c] = w[c];
+    a.out_velocity[((size_t)j * a.A + ch) * 3 + c] = v[c];
+  }
+}
+
+// =============================================================================================
 // inverse dynamics: Levenberg-Marquardt on the linearised flow, one workgroup per batch element
 // =============================================================================================
 // optical_flow(a) = proj(x + M a) - proj(x) with x = sum_s w x_s and M = sum_s w J_s (the composited outputs of the
@@ -5553,6 +5750,90 @@ extern "C" int njf_field_twists(const float* xyz, const float* jacobian, const i
   }
   if (phases & NJF_FIELD_TWISTS_RESIDUAL_SUM) {
     twist_residual_sum_kernel<<<num_parts, 64, 0, s>>>(a);
+    if ((rc = launch_status())) return rc;
+  }
+  return NJF_OK;
+}
+
+extern "C" int njf_field_joints(const NjfFieldGrid* grid, int batch, const int* indices, const int* labels, const int* count,
+                                int n, const int* parts, const int* parts_count, int num_parts, const int* part_status,
+                                const double* centroid, const double* omega, const double* velocity, int action_dim,
+                                int connectivity, int min_contacts, int max_joints, int* part_a, int* part_b,
+                                long long* contacts, int* status, int* out_count, double* anchor, double* out_omega,
+                                double* out_velocity, long long* workspace, long long workspace_words, int phases,
+                                void* stream) {
+  if (connectivity != 6 && connectivity != 14) return NJF_E_VALUE;
+  if (num_parts < 1 || num_parts > NJF_FIELD_TWISTS_MAX_PARTS) return NJF_E_VALUE;
+  if (action_dim < 1 || action_dim > NJF_MAX_ACTION_DIM) return NJF_E_VALUE;
+  if (max_joints < 1 || max_joints > NJF_FIELD_JOINTS_MAX) return NJF_E_VALUE;
+  if (min_contacts < 1) return NJF_E_VALUE;
+  if (phases < 1 || phases > (NJF_FIELD_JOINTS_ALL | NJF_FIELD_JOINTS_PER_LANE)) return NJF_E_VALUE;
+  if (n < 0) return NJF_E_SHAPE;
+  FieldList l;
+  int rc = make_field_list(grid, batch, nullptr, nullptr, 0, l);  // B*N < 2^31
+  if (rc) return rc;
+  // the table [K][K][4] of 64-bit words first, the volume [B*N] of 32-bit words behind it
+  const long long table_words = NJF_FIELD_JOINTS_TABLE_WORDS(num_parts);
+  if (workspace_words < NJF_FIELD_JOINTS_WORKSPACE(l.total, num_parts)) return NJF_E_SHAPE;
+  if (!parts || !part_status || !centroid || !omega || !velocity || !part_a || !part_b || !contacts || !status || !out_count ||
+      !anchor || !out_omega || !out_velocity || !workspace)
+    return NJF_E_NULL;
+  if (n > 0 && (!indices || !labels)) return NJF_E_NULL;
+  JointArgs a;
+  for (int c = 0; c < 3; ++c) {
+    a.dims[c] = grid->dims[c];
+    a.origin[c] = grid->origin[c];
+    a.step[c] = grid->step[c];
+  }
+  a.nodes = l.nodes;
+  a.total = l.total;
+  a.indices = indices;
+  a.labels = labels;
+  a.count = count;
+  a.n = n;
+  a.parts = parts;
+  a.parts_count = parts_count;
+  a.K = num_parts;
+  a.A = action_dim;
+  a.half = connectivity / 2;
+  a.min_contacts = min_contacts;
+  a.J = max_joints;
+  a.part_status = part_status;
+  a.centroid = centroid;
+  a.omega = omega;
+  a.velocity = velocity;
+  a.table = (unsigned long long*)workspace;
+  a.volume = (int*)(workspace + table_words);
+  a.part_a = part_a;
+  a.part_b = part_b;
+  a.status = status;
+  a.out_count = out_count;
+  a.contacts = contacts;
+  a.anchor = anchor;
+  a.out_omega = out_omega;
+  a.out_velocity = out_velocity;
+  hipStream_t s = (hipStream_t)stream;
+  const int blocks = (int)(((long long)n + NJF_JOINT_THREADS - 1) / NJF_JOINT_THREADS);
+  // (the phases exist to time the launches apart: each reads what the earlier ones left in the workspace and the outputs)
+  if (phases & NJF_FIELD_JOINTS_CLEAR) {
+    if (hipMemsetAsync(a.volume, 0xff, (size_t)l.total * sizeof(int), s) != hipSuccess) return launch_status();
+    if (hipMemsetAsync(a.table, 0, (size_t)table_words * sizeof(long long), s) != hipSuccess) return launch_status();
+  }
+  if (n > 0 && (phases & NJF_FIELD_JOINTS_SLOTS)) {
+    joint_slots_kernel<<<blocks, NJF_JOINT_THREADS, 0, s>>>(a);
+    if ((rc = launch_status())) return rc;
+  }
+  if (n > 0 && (phases & NJF_FIELD_JOINTS_CONTACTS)) {
+    if (phases & NJF_FIELD_JOINTS_PER_LANE) joint_contacts_kernel<false><<<blocks, NJF_JOINT_THREADS, 0, s>>>(a);
+    else joint_contacts_kernel<true><<<blocks, NJF_JOINT_THREADS, 0, s>>>(a);
+    if ((rc = launch_status())) return rc;
+  }
+  if (phases & NJF_FIELD_JOINTS_LIST) {
+    joint_list_kernel<<<1, NJF_JOINT_LIST_THREADS, 0, s>>>(a);
+    if ((rc = launch_status())) return rc;
+  }
+  if (phases & NJF_FIELD_JOINTS_TWISTS) {
+    joint_twists_kernel<<<(max_joints * action_dim + NJF_JOINT_THREADS - 1) / NJF_JOINT_THREADS, NJF_JOINT_THREADS, 0, s>>>(a);
     if ((rc = launch_status())) return rc;
   }
   return NJF_OK;

@@ -502,6 +502,199 @@ def cloud_twists(cloud: FieldPointCloud, *, labels: Optional[torch.Tensor] = Non
     return fit_twists(cloud.xyz, cloud.jacobian, labels, parts, parts_count=parts_count, count=cloud.count, weights=weights)
 
 
+# ---- joints between parts: grid contacts and relative twists ---------------------------------------------
+@dataclass
+class FieldJoints:
+    """The pairs of parts that touch on the grid (``part_joints``; include/njf_hip.h: njf_field_joints), in ascending
+    ``(part_a, part_b)`` -- slots of ``twists``, ``part_a < part_b``; ``labels`` are the twists' part labels, so joint j joins
+    the parts ``labels[part_a[j]]`` and ``labels[part_b[j]]``.  ``contacts`` counts the adjacent node pairs, ``anchor`` is their
+    mean midpoint, ``omega`` / ``velocity`` the twist of part_b relative to part_a per command channel, the velocity taken AT
+    the anchor: the relative twist is the joint, its screw axis the hinge, and the velocity at the contact says how far the
+    pair is from a revolute one.  ``status`` = the two parts' twist status bits or-ed.  ``count`` is the TRUE number of joints
+    (it may exceed the J rows); unused rows hold -1 in ``part_a`` / ``part_b`` and zeros elsewhere."""
+
+    grid: FieldGrid
+    labels: torch.Tensor      # [K] int32: the twists' part labels
+    part_a: torch.Tensor      # [J] int32
+    part_b: torch.Tensor      # [J] int32
+    contacts: torch.Tensor    # [J] int64
+    status: torch.Tensor      # [J] int32
+    count: torch.Tensor       # [1] int32
+    anchor: torch.Tensor      # [J, 3] float64
+    omega: torch.Tensor       # [J, A, 3] float64
+    velocity: torch.Tensor    # [J, A, 3] float64: at the anchor
+    twists: Optional[FieldTwists] = None   # the parts' own twists (``parents`` takes its default root from them)
+
+    def _length(self, length) -> float:
+        return float(max(abs(s) for s in self.grid.step)) if length is None else float(length)
+
+    def screw(self, eps: float = 1e-9):
+        """``(direction [J, A, 3], point [J, A, 3], pitch [J, A])`` of the screw axis of every relative twist: the definition
+        of ``FieldTwists.screw`` with the anchor in place of the centroid -- the unit direction of ``omega``, the point ``anchor
+        + omega x v / |omega|^2`` of the axis nearest the anchor, the pitch ``omega . v / |omega|^2``.  A contact has no RMS
+        radius, so the prismatic test ``|omega| * extent <= eps * |v|`` takes the largest grid step as ``extent``; there the
+        direction is that of ``v``, the point the anchor and the pitch inf; a zero twist has direction 0."""
+        w, v = self.omega, self.velocity
+        wn, vn = torch.linalg.vector_norm(w, dim=-1), torch.linalg.vector_norm(v, dim=-1)
+        prismatic = wn * self._length(None) <= eps * vn
+        w2 = torch.where(prismatic, torch.ones_like(wn), wn * wn)
+        centre = self.anchor[:, None, :].expand_as(w)
+        unit_v = v / torch.where(vn > 0, vn, torch.ones_like(vn))[..., None]
+        direction = torch.where(prismatic[..., None], unit_v, w / torch.sqrt(w2)[..., None])
+        point = torch.where(prismatic[..., None], centre, centre + torch.linalg.cross(w, v, dim=-1) / w2[..., None])
+        pitch = torch.where(prismatic, torch.full_like(wn, math.inf), (w * v).sum(-1) / w2)
+        return direction, point, pitch
+
+    def drive(self, length: Optional[float] = None) -> torch.Tensor:
+        """``[J]`` int64: the command channel that moves the pair most, ``argmax_a (|omega_rel|^2 * length^2 + |v_rel|^2)``, ties
+        to the lowest a (0 for an unused row).  ``length`` turns a rotation into a speed; default: the largest grid step."""
+        length = self._length(length)
+        w2, v2 = (self.omega * self.omega).sum(-1), (self.velocity * self.velocity).sum(-1)
+        return torch.argmax(w2 * (length * length) + v2, dim=1)
+
+    def parents(self, root: Optional[int] = None):
+        """``(parent [K], joint_of [K])``, int64 CPU tensors: the kinematic tree.  The stored joints form a graph on the slots;
+        its MAXIMUM SPANNING FOREST by ``contacts`` (ties to the smaller ``(part_a, part_b)``) is oriented away from a root per
+        body.  ``parent[p]`` is the slot p hangs on and ``joint_of[p]`` the row of the joint between them; both are -1 for a
+        root and for an unused slot.  ``root``: a slot; its body hangs on it.  Every other body -- every body with ``root=None``
+        -- hangs on its slot of smallest ``sum_a energy / weight`` among those of twist status 0, the base (ties, or no such
+        slot, or no ``twists``: the smallest slot).  Host-side numpy on ONE host read of the few numbers it needs."""
+        k, rows = self.labels.shape[0], self.part_a.shape[0]
+        if root is not None and (isinstance(root, bool) or not isinstance(root, int) or not 0 <= root < k):
+            raise ValueError(f"FieldJoints.parents: root must be a slot in [0, {k}) (got {root!r})")
+        f64 = dict(dtype=torch.float64, device=self.part_a.device)
+        mobility = torch.zeros(k, **f64)
+        if self.twists is not None:
+            tw = self.twists
+            base = (tw.status == 0) & (tw.weight > 0)
+            mobility = torch.where(base, tw.energy.sum(1) / torch.where(base, tw.weight, torch.ones_like(tw.weight)),
+                                   torch.full_like(tw.weight, math.inf)).to(**f64)
+        packed = torch.cat([self.count.to(**f64), self.labels.to(**f64), mobility, self.part_a.to(**f64), self.part_b.to(**f64),
+                            self.contacts.to(**f64)]).cpu().numpy()        # the one host read
+        stored = min(max(int(packed[0]), 0), rows)
+        labels, mobility = packed[1:1 + k], packed[1 + k:1 + 2 * k]
+        lo, hi, contacts = (packed[1 + 2 * k + i * rows:1 + 2 * k + i * rows + stored].astype(np.int64) for i in range(3))
+        if root is not None and labels[root] < 0:
+            raise ValueError(f"FieldJoints.parents: slot {root} is unused")
+        group = np.arange(k)
+
+        def find(x):
+            while group[x] != x:
+                group[x] = group[group[x]]
+                x = group[x]
+            return x
+
+        links = [[] for _ in range(k)]
+        for j in sorted(range(stored), key=lambda j: (-contacts[j], lo[j], hi[j])):
+            a, b = find(lo[j]), find(hi[j])
+            if a != b:
+                group[max(a, b)] = min(a, b)
+                links[lo[j]].append((int(hi[j]), j))
+                links[hi[j]].append((int(lo[j]), j))
+        parent, joint_of = np.full(k, -1, dtype=np.int64), np.full(k, -1, dtype=np.int64)
+        bodies = {}
+        for p in range(k):
+            if labels[p] >= 0:
+                bodies.setdefault(find(p), []).append(p)
+        for members in bodies.values():
+            start = root if root in members else min(members, key=lambda p: (mobility[p], p))
+            seen, queue = {start}, [start]
+            while queue:
+                p = queue.pop()
+                for q, j in links[p]:
+                    if q not in seen:
+                        seen.add(q)
+                        parent[q], joint_of[q] = p, j
+                        queue.append(q)
+        return torch.from_numpy(parent), torch.from_numpy(joint_of)
+
+
+def part_joints(grid: FieldGrid, index: torch.Tensor, labels: torch.Tensor, twists: FieldTwists, *, batch: int,
+                count: Optional[torch.Tensor] = None, connectivity: int = 6, min_contacts: int = 1,
+                max_joints: int = 256) -> FieldJoints:
+    """The joints between the parts of a labelled list of grid nodes: ``index`` ``[n]`` int32, the
+    ascending global indices of the rows on ``grid`` x ``batch`` (rows from ``count`` -- int32 device tensor; None = n -- on are
+    never read, an index outside the grid is dropped), ``labels`` ``[n]`` int32, the per-row result of ``cloud_components``
+    (negative: no part), and ``twists``, the ``FieldTwists`` fitted to those labels, whose part list defines the slots.  Two
+    slots are in contact where a node of one has a node of the other as its neighbour along the axes (``connectivity=6``) or
+    the edges of the Kuhn tetrahedra (``14``), inside the grid and one batch element; pairs with at least ``min_contacts``
+    contacts are listed in ascending ``(part_a, part_b)``, the first ``max_joints`` (1..4096) stored.  Integer atomics and
+    per-joint double arithmetic only: two calls give equal bytes, and nothing is read on the host."""
+    return _joints("part_joints", grid, index, labels, twists, batch, count, connectivity, min_contacts, max_joints)
+
+
+def _joints(name: str, grid: FieldGrid, index, labels, twists, batch, count, connectivity, min_contacts, max_joints,
+            infer_batch: bool = False) -> FieldJoints:
+    """The argument checks (under the caller's ``name``) and the launches of part_joints / cloud_joints.  ``infer_batch``: a
+    ``batch`` of None is read from the largest index once every check has passed."""
+    _check_component_arguments(name, connectivity)
+    for what, v, top in (("min_contacts", min_contacts, 2 ** 31 - 1), ("max_joints", max_joints, hip.FIELD_JOINTS_MAX)):
+        if isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= top:
+            raise ValueError(f"{name}: {what} must be an integer in [1, {top}] (got {v!r})")
+    if not (batch is None and infer_batch) and (isinstance(batch, bool) or not isinstance(batch, int) or batch < 1
+                                                or batch * grid.num_nodes >= 2 ** 31):
+        raise ValueError(f"{name}: batch must be an integer >= 1 with batch * nx*ny*nz below 2**31 (got {batch!r})")
+    if not torch.is_tensor(index) or index.dtype != torch.int32 or index.dim() != 1:
+        raise ValueError(f"{name}: index must be int32 [n]")
+    n = index.shape[0]
+    if not torch.is_tensor(labels) or labels.dtype != torch.int32 or tuple(labels.shape) != (n,):
+        raise ValueError(f"{name}: labels must be int32 [{n}]")
+    if not isinstance(twists, FieldTwists):
+        raise ValueError(f"{name}: twists must be a FieldTwists")
+    parts = twists.labels
+    if not torch.is_tensor(parts) or parts.dtype != torch.int32 or parts.dim() != 1:
+        raise ValueError(f"{name}: twists.labels must be int32 [K]")
+    k = parts.shape[0]
+    if not 1 <= k <= hip.FIELD_TWISTS_MAX_PARTS:
+        raise ValueError(f"{name}: the twists must hold 1 to {hip.FIELD_TWISTS_MAX_PARTS} parts (got {k})")
+    omega = twists.omega
+    if not torch.is_tensor(omega) or omega.dtype != torch.float64 or omega.dim() != 3 or omega.shape[0] != k or omega.shape[2] != 3:
+        raise ValueError(f"{name}: twists.omega must be float64 [{k}, A, 3]")
+    a_dim = omega.shape[1]
+    if not 1 <= a_dim <= hip.MAX_ACTION_DIM:
+        raise ValueError(f"{name}: 1 to {hip.MAX_ACTION_DIM} command channels (got {a_dim})")
+    for what, t, dtype, shape in (("velocity", twists.velocity, torch.float64, (k, a_dim, 3)),
+                                  ("centroid", twists.centroid, torch.float64, (k, 3)), ("status", twists.status, torch.int32, (k,))):
+        if not torch.is_tensor(t) or t.dtype != dtype or tuple(t.shape) != shape:
+            raise ValueError(f"{name}: twists.{what} must be {str(dtype).replace('torch.', '')} {list(shape)}")
+    count = _one_int32(name, "count", count, index)
+    parts_count = _one_int32(name, "twists.count", twists.count, index)
+    for what, t in (("labels", labels), ("twists.labels", parts), ("twists.omega", omega), ("twists.velocity", twists.velocity),
+                    ("twists.centroid", twists.centroid), ("twists.status", twists.status)):
+        if t.device != index.device:
+            raise ValueError(f"{name}: {what} must live on the device of index")
+    if index.device.type != "cuda":
+        raise ValueError(f"{name}: the rows must live on the GPU; there is no CPU path")
+    dev = index.device
+    if batch is None:
+        rows = torch.arange(n, dtype=torch.int32, device=dev) < (n if count is None else count)
+        batch = int(torch.where(rows, index, torch.zeros_like(index)).max().item()) // grid.num_nodes + 1 if n else 1
+        if batch * grid.num_nodes >= 2 ** 31:
+            raise ValueError(f"{name}: batch * nx*ny*nz must stay below 2**31")
+    i32, f64 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.float64, device=dev)
+    j = max_joints
+    joints = FieldJoints(grid=grid, labels=parts, part_a=torch.empty(j, **i32), part_b=torch.empty(j, **i32),
+                         contacts=torch.empty(j, dtype=torch.int64, device=dev), status=torch.empty(j, **i32),
+                         count=torch.empty(1, **i32), anchor=torch.empty(j, 3, **f64), omega=torch.empty(j, a_dim, 3, **f64),
+                         velocity=torch.empty(j, a_dim, 3, **f64), twists=twists)
+    out = dict(part_a=joints.part_a, part_b=joints.part_b, contacts=joints.contacts, status=joints.status, count=joints.count,
+               anchor=joints.anchor, omega=joints.omega, velocity=joints.velocity)
+    hip.field_joints(grid.c_grid(), batch, index.contiguous(), labels.contiguous(), parts.contiguous(), twists.status.contiguous(),
+                     twists.centroid.contiguous(), omega.contiguous(), twists.velocity.contiguous(), out, count=count,
+                     parts_count=parts_count, connectivity=connectivity, min_contacts=min_contacts)
+    return joints
+
+
+def cloud_joints(cloud: FieldPointCloud, labels: torch.Tensor, twists: FieldTwists, *, batch: Optional[int] = None,
+                 connectivity: int = 6, min_contacts: int = 1, max_joints: int = 256) -> FieldJoints:
+    """``part_joints`` on an extracted cloud: its grid, ``cloud.index`` and ``cloud.count``, with ``labels`` ``[n]`` int32 (the
+    per-row result of ``cloud_components``) and the ``twists`` of ``cloud_twists(cloud, labels=, sizes=)``.  ``batch``: the
+    number of batch elements (scenes) the cloud's grid was extracted for; None infers it from the largest index, as
+    ``cloud_components`` does (one host read); given ``batch``, nothing is read."""
+    return _joints("cloud_joints", cloud.grid, cloud.index, labels, twists, batch, cloud.count, connectivity, min_contacts,
+                   max_joints, infer_batch=True)
+
+
 # ---- coarse-to-fine band (DESIGN.md section 14) ----------------------------------------------------------------------------------
 @dataclass
 class FieldBand:

@@ -169,6 +169,8 @@ _SIGNATURES = {
     "njf_field_band_leaks": ([C.POINTER(FieldGrid), C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp], C.c_int),
     "njf_field_twists": ([_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, C.c_int] + [_vp] * 15 + [C.c_longlong, C.c_int, _vp],
                          C.c_int),
+    "njf_field_joints": ([C.POINTER(FieldGrid), C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int,
+                          C.c_int, C.c_int, C.c_int] + [_vp] * 9 + [C.c_longlong, C.c_int, _vp], C.c_int),
     "njf_pack_resnetfc_backward": ([C.POINTER(ResnetFcWeights), _vp, C.c_int, _vp], C.c_int),
     "njf_resnetfc_backward": ([_vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp], C.c_int),
     "njf_pack_transformer_backward": ([_vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, _vp], C.c_int),
@@ -981,6 +983,56 @@ def field_twists(xyz: torch.Tensor, jacobian: torch.Tensor, labels: torch.Tensor
             _int32_ptr(out["count"], "out count"), _int32_ptr(out["nodes"], "nodes"), _int32_ptr(out["status"], "status"),
             *[_double_ptr(out[f], f) for f in ("weight", "centroid", "omega", "velocity", "energy", "residual", "q", "p", "l")],
             _ptr(out["row_residual"], "row_residual"), _double_ptr(workspace, "workspace"), int(workspace.numel()), int(phase))
+
+
+# ---- joints between parts: grid contacts and relative twists (include/njf_hip.h: njf_field_joints) ------------------------
+FIELD_JOINTS_MAX = 4096                # NJF_FIELD_JOINTS_MAX: rows of the joint list
+FIELD_JOINTS_PHASES = (1, 2, 4, 8, 16)  # NJF_FIELD_JOINTS_CLEAR .. _TWISTS: the two memsets and one launch each
+FIELD_JOINTS_PHASE_NAMES = ("clear", "slots", "contacts", "list", "twists")
+FIELD_JOINTS_ALL = 31                  # NJF_FIELD_JOINTS_ALL
+FIELD_JOINTS_PER_LANE = 32             # NJF_FIELD_JOINTS_PER_LANE: the contacts launch without the in-wave combination
+
+
+def field_joints_workspace(total_nodes: int, parts: int) -> int:
+    """64-bit words of workspace njf_field_joints needs: NJF_FIELD_JOINTS_WORKSPACE(B*N, K) -- the K x K x 4 pair table and the
+    int32 slot volume of B*N nodes."""
+    return 4 * parts * parts + (total_nodes + 1) // 2
+
+
+def field_joints(grid: FieldGrid, batch: int, indices: torch.Tensor, labels: torch.Tensor, parts: torch.Tensor,
+                 part_status: torch.Tensor, centroid: torch.Tensor, omega: torch.Tensor, velocity: torch.Tensor, out: dict,
+                 count=None, parts_count=None, connectivity: int = 6, min_contacts: int = 1, phase: int = FIELD_JOINTS_ALL,
+                 workspace: Optional[torch.Tensor] = None) -> None:
+    """njf_field_joints on the list ``indices`` / ``labels`` [n] (int32) of a cloud on ``grid`` x ``batch`` and the part list and
+    twists ``parts``, ``part_status`` [K] (int32), ``centroid`` [K, 3], ``omega``, ``velocity`` [K, A, 3] (float64): ``out`` maps
+    the names of the C outputs -- part_a, part_b, status [J], count [1] (int32), contacts [J] (int64), anchor [J, 3], omega,
+    velocity [J, A, 3] (float64) -- to tensors of their shapes.  ``phase`` / ``workspace`` (int64, ``field_joints_workspace``
+    elements): run the launches one by one on a workspace of the caller's, to time them apart."""
+    n, k, j = indices.numel(), parts.numel(), out["part_a"].numel()
+    if omega.dim() != 3 or omega.shape[0] != k or omega.shape[2] != 3 or velocity.shape != omega.shape:
+        raise ValueError("njf_hip: field_joints needs omega and velocity [K, A, 3]")
+    a = omega.shape[1]
+    if labels.numel() != n or part_status.numel() != k or centroid.numel() != 3 * k:
+        raise ValueError("njf_hip: field_joints needs one label per row, one status and one centroid per part")
+    for name, t in (("count", count), ("parts_count", parts_count), ("out count", out["count"])):
+        if t is not None and t.numel() != 1:
+            raise ValueError(f"njf_hip: field_joints {name} must hold one int32")
+    sizes = dict(part_a=j, part_b=j, status=j, contacts=j, anchor=3 * j, omega=3 * a * j, velocity=3 * a * j)
+    for name, size in sizes.items():
+        if out[name].numel() != size:
+            raise ValueError(f"njf_hip: field_joints output {name} must hold {size} elements (got {out[name].numel()})")
+    total = int(batch) * grid.dims[0] * grid.dims[1] * grid.dims[2]
+    if workspace is None:
+        workspace = torch.empty(field_joints_workspace(total, k), dtype=torch.int64, device=indices.device)
+    _launch("njf_field_joints", load_library().njf_field_joints, C.byref(grid), int(batch), _int32_ptr(indices, "indices"),
+            _int32_ptr(labels, "labels"), _int32_ptr(count, "count"), int(n), _int32_ptr(parts, "parts"),
+            _int32_ptr(parts_count, "parts_count"), int(k), _int32_ptr(part_status, "part_status"),
+            _double_ptr(centroid, "centroid"), _double_ptr(omega, "omega"), _double_ptr(velocity, "velocity"), int(a),
+            int(connectivity), int(min_contacts), int(j), _int32_ptr(out["part_a"], "part_a"), _int32_ptr(out["part_b"], "part_b"),
+            _ptr(out["contacts"], "contacts", torch.int64), _int32_ptr(out["status"], "status"),
+            _int32_ptr(out["count"], "out count"), _double_ptr(out["anchor"], "anchor"), _double_ptr(out["omega"], "out omega"),
+            _double_ptr(out["velocity"], "out velocity"), _ptr(workspace, "workspace", torch.int64), int(workspace.numel()),
+            int(phase))
 
 
 def solve_action(mean_position, jacobian, projection, target_flow, visible_mask, init_action, iterations: int,
