@@ -660,6 +660,58 @@ int njf_field_joints(const NjfFieldGrid* grid, int batch, const int* indices, co
                      double* out_omega, double* out_velocity, long long* workspace, long long workspace_words, int phases,
                      void* stream);
 
+/* ---- posing the parts under a command: twist exponentials along the tree (ABI v20, additive) --------------
+ * Where every part, and every labelled point, goes under each of M commands: the finite rigid motion of a part is the product
+ * of the exponentials of the joint twists along its chain to the root, the space-frame product of exponentials.
+ * Inputs, all on the device: the part list and twists of njf_field_twists -- parts [K], parts_count (int32, NULL = K), part_status
+ * [K], double centroid [K,3], omega, velocity [K,A,3]; used slots are p < Ku = min(*parts_count, K) --; optionally the joints of
+ * njf_field_joints -- part_a, part_b [J], joints_count (int32, NULL = J; stored joints are j < Ju = min(*joints_count, J)),
+ * double anchor [J,3], joint_omega, joint_velocity [J,A,3] -- WITH a tree parent, joint_of [K] int32 (all of them or none;
+ * joints_count alone may be NULL); commands [M,A] float, converted exactly to double.
+ * LINK   G[m,p] = (R, t), x -> R x + t, in double.  With u = commands[m]: w = sum_a u_a omega_a, v = sum_a u_a v_a in ascending
+ *        a from 0.0, of the slot's own twist about c = centroid[p] (no tree, or parent[p] < 0) or, with q = parent[p] >= 0 and
+ *        j = joint_of[p], of joint j's relative twist about c = anchor[j], times +1 when part_a[j] == q and -1 when part_b[j]
+ *        == q.  th2 = (wx*wx + wy*wy) + wz*wz.  th2 <= 1e-6: a = (1 - th2/6) + th4/120, b = (1/2 - th2/24) + th4/720, g = (1/6 -
+ *        th2/120) + th4/5040; otherwise th = sqrt(th2), a = sin(th)/th, b = 2 sin(th/2)^2 / th2, g = (th - sin(th)) / (th2 th).
+ *        R = I + a [w]x + b [w]x^2, V = I + b [w]x + g [w]x^2, [w]x^2 = w w^T - th2 I, t = (c - R c) + V v.
+ * LINK BITS  1: p >= Ku or part_status[p] & 1.  2 (bad link): parent[p] >= 0 and (q >= Ku, or q == p, or j outside [0, Ju), or
+ *        {part_a[j], part_b[j]} != {p, q}).  A slot with a bit set has G = identity.
+ * POSE   T = G[m,p], q = parent[p]; while q != -1: T <- G[m,q] o T (R = R_q R_T, t = (R_q t_T) + t_q, sums of three products in
+ *        ascending index), q = parent[q].  The identity, with status bit 2, when p or a slot on the walk is a bad link, when
+ *        the walk would take more than K steps (a cycle) or meets a q outside [-1, K).  rotation [M,K,3,3], translation [M,K,3]
+ *        double; status [K] int32 = the link bits | that bit; depth [K] int32 = the steps taken (neither depends on m).
+ * POINTS (xyz != NULL and n > 0): xyz [n,3] float, labels [n] int32, count (int32, NULL = n), jacobian [n,A,3] float or NULL,
+ *        posed [M,n,3] float.  Row i < min(*count, n) has slot p iff labels[i] >= 0, p < Ku and labels[i] == parts[p] (parts
+ *        ascending in the used slots).  With a slot of status 0: x'_c = (float)(((R_c0 x + R_c1 y) + R_c2 z) + t_c) in double.
+ *        Otherwise, with a jacobian: x'_c = (float)(x_c + u_0 J_0c + u_1 J_1c + ...), in double, one add per term in ascending a;
+ *        without: x' = x.  Rows from min(*count, n) on are neither read nor written.  Offsets are 64-bit.
+ * workspace: NJF_FIELD_POSE_WORKSPACE(M, K) doubles of the caller's: G [M][K][12], then the int32 link bits [K].  Three launches
+ * on `stream`, no atomics, no host read (capture-safe).  `phases` = NJF_FIELD_POSE_ALL or a subset, to time the launches apart
+ * (each reads what the earlier ones left); two modifiers select the other forms of the points launch, which give the same
+ * bytes and are kept to be measured against: NJF_FIELD_POSE_STAGED copies one command's transforms of the used slots into LDS
+ * instead of reading them per lane from L2, NJF_FIELD_POSE_WIDE lays a workgroup's output out in LDS and writes 16-byte
+ * stores instead of three dwords per lane.  Returns, before the first launch: NJF_E_VALUE for K outside [1,
+ * NJF_FIELD_TWISTS_MAX_PARTS], A outside [1, NJF_MAX_ACTION_DIM], M outside [1, NJF_FIELD_POSE_MAX_COMMANDS], with joints J
+ * outside [1, NJF_FIELD_JOINTS_MAX], or unknown phases; NJF_E_SHAPE for n < 0 or a workspace that is too small; NJF_E_NULL for
+ * a missing pointer, joints without a tree or a tree without joints, or points without xyz, labels or posed.  Only the links
+ * launch reads part_status and the twists, only the links and chain launches the workspace: a call of the points launch alone
+ * may pass NULL for them. */
+#define NJF_FIELD_POSE_MAX_COMMANDS 65535
+#define NJF_FIELD_POSE_WORKSPACE(M, K) (12LL * (M) * (K) + ((K) + 1) / 2)
+#define NJF_FIELD_POSE_LINKS 1          /* phases: one launch each */
+#define NJF_FIELD_POSE_CHAIN 2
+#define NJF_FIELD_POSE_POINTS 4
+#define NJF_FIELD_POSE_ALL 7
+#define NJF_FIELD_POSE_STAGED 8         /* modifiers of _POINTS, not part of _ALL */
+#define NJF_FIELD_POSE_WIDE 16
+int njf_field_pose(const int* parts, const int* parts_count, int num_parts, const int* part_status, const double* centroid,
+                   const double* omega, const double* velocity, int action_dim, const int* part_a, const int* part_b,
+                   const int* joints_count, int max_joints, const double* anchor, const double* joint_omega,
+                   const double* joint_velocity, const int* parent, const int* joint_of, const float* commands, int num_commands,
+                   double* rotation, double* translation, int* status, int* depth, const float* xyz, const int* labels,
+                   const int* count, int n, const float* jacobian, float* posed, double* workspace, long long workspace_doubles,
+                   int phases, void* stream);
+
 /* ---- stand-alone sampler / compositing ops (API parity with the un-fused reference calls) -- */
 /* RaySamples.get_weights (ray_samplers.py:77-101): deltas, densities [N,S] -> weights [N,S]. */
 int njf_alpha_weights(const float* deltas, const float* densities, int rays, int samples, float* weights, void* stream);

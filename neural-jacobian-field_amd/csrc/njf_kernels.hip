@@ -3709,6 +3709,280 @@ __global__ void __launch_bounds__(NJF_JOINT_THREADS) joint_twists_kernel(JointAr
 }
 
 // =============================================================================================
+// posing the parts under a command: twist exponentials along the tree (njf_field_pose)
+// =============================================================================================
+// Thread (m, p) of the links launch turns the twist of slot p under command m -- its own about its centroid, or the relative
+// twist of the joint it hangs on about the joint's anchor -- into the rigid motion G = (R, t) in double; thread (m, p) of the
+// chain launch multiplies the G of p's ancestors onto it, the root last, over a walk of at most K steps; a thread of the
+// points launch owns one row and applies its part's transform for every command of a tile.  No atomics anywhere.
+#define NJF_POSE_THREADS 256
+#define NJF_POSE_COMMAND_TILE 32
+struct PoseArgs {
+  const int* parts;        // [K]
+  const int* parts_count;  // or null
+  int K, A, J, M;
+  const int* part_status;  // [K]
+  const double *centroid, *omega, *velocity;             // [K,3], [K,A,3], [K,A,3]
+  const int *part_a, *part_b, *joints_count;             // [J], [J], [1] or null (part_a null: no tree)
+  const double *anchor, *joint_omega, *joint_velocity;   // [J,3], [J,A,3], [J,A,3]
+  const int *parent, *joint_of;                          // [K]
+  const float* commands;   // [M,A]
+  double* link;            // [M,K,12]: R row-major, then t
+  int* link_bits;          // [K]
+  double *rotation, *translation;   // [M,K,9], [M,K,3]
+  int *status, *depth;     // [K]
+  const float* xyz;        // [n,3]
+  const int* labels;       // [n]
+  const int* count;        // or null
+  int n;
+  const float* jacobian;   // [n,A,3] or null
+  float* posed;            // [M,n,3]
+};
+
+// the link bits of slot p: 1 = unused or empty (its motion is the identity), 2 = a parent it cannot hang on
+__device__ __forceinline__ int pose_link_bits(const PoseArgs& a, int p, int active, int& q, int& j, double& sign) {
+  int bits = 0;
+  if (p >= active || (a.part_status[p] & 1)) bits |= 1;
+  q = a.parent ? a.parent[p] : -1;
+  j = -1;
+  sign = 1.0;
+  if (q >= 0) {
+    j = a.joint_of[p];
+    bool bad = q >= active || q == p || j < 0 || j >= counted_length(a.joints_count, a.J);
+    if (!bad) {  // j < J
+      const int lo = a.part_a[j], hi = a.part_b[j];
+      if (lo == q && hi == p) sign = 1.0;
+      else if (hi == q && lo == p) sign = -1.0;
+      else bad = true;
+    }
+    if (bad) bits |= 2;
+  }
+  return bits;
+}
+
+__global__ void __launch_bounds__(NJF_POSE_THREADS) pose_links_kernel(PoseArgs a) {
+  const int t = blockIdx.x * NJF_POSE_THREADS + threadIdx.x;  // M*K <= 65535 * 256 < 2^31
+  if (t >= a.M * a.K) return;
+  const int m = t / a.K, p = t - m * a.K;
+  int q, j;
+  double sign;
+  const int bits = pose_link_bits(a, p, counted_length(a.parts_count, a.K), q, j, sign);
+  double R[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0}, tr[3] = {0.0, 0.0, 0.0};
+  if (bits == 0) {
+    const bool hung = q >= 0;  // (then j is a stored joint)
+    const double* ws = hung ? a.joint_omega + (size_t)j * a.A * 3 : a.omega + (size_t)p * a.A * 3;
+    const double* vs = hung ? a.joint_velocity + (size_t)j * a.A * 3 : a.velocity + (size_t)p * a.A * 3;
+    const double* cs = hung ? a.anchor + (size_t)j * 3 : a.centroid + (size_t)p * 3;
+    const float* u = a.commands + (size_t)m * a.A;
+    double w[3] = {0.0, 0.0, 0.0}, v[3] = {0.0, 0.0, 0.0};
+    for (int ch = 0; ch < a.A; ++ch) {
+      const double uc = (double)u[ch];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        w[c] += uc * ws[ch * 3 + c];
+        v[c] += uc * vs[ch * 3 + c];
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      w[c] *= sign;
+      v[c] *= sign;
+    }
+    const double th2 = (w[0] * w[0] + w[1] * w[1]) + w[2] * w[2];
+    double ca, cb, cg;
+    if (th2 <= 1e-6) {
+      const double th4 = th2 * th2;
+      ca = (1.0 - th2 / 6.0) + th4 / 120.0;
+      cb = (0.5 - th2 / 24.0) + th4 / 720.0;
+      cg = (1.0 / 6.0 - th2 / 120.0) + th4 / 5040.0;
+    } else {
+      const double th = sqrt(th2), s = sin(th), sh = sin(0.5 * th);
+      ca = s / th;
+      cb = 2.0 * (sh * sh) / th2;       // (not 1 - cos: it cancels)
+      cg = (th - s) / (th2 * th);
+    }
+    // [w]x and its square w w^T - th2 I
+    const double W[9] = {0.0, -w[2], w[1], w[2], 0.0, -w[0], -w[1], w[0], 0.0};
+    double V[9];
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const double d = r == c ? 1.0 : 0.0;
+        const double W2 = w[r] * w[c] - d * th2;
+        R[r * 3 + c] = (d + ca * W[r * 3 + c]) + cb * W2;
+        V[r * 3 + c] = (d + cb * W[r * 3 + c]) + cg * W2;
+      }
+    const double c0 = cs[0], c1 = cs[1], c2 = cs[2];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+      const double rc = (R[r * 3] * c0 + R[r * 3 + 1] * c1) + R[r * 3 + 2] * c2;
+      const double vv = (V[r * 3] * v[0] + V[r * 3 + 1] * v[1]) + V[r * 3 + 2] * v[2];
+      tr[r] = (cs[r] - rc) + vv;
+    }
+  }
+  double* g = a.link + (size_t)t * 12;  // t < M*K
+#pragma unroll
+  for (int e = 0; e < 9; ++e) g[e] = R[e];
+#pragma unroll
+  for (int e = 0; e < 3; ++e) g[9 + e] = tr[e];
+  if (m == 0) a.link_bits[p] = bits;
+}
+
+// T = G[m,p], then T <- G[m,q] o T up the parents: bounded by K steps, every index checked before it is used
+__global__ void __launch_bounds__(NJF_POSE_THREADS) pose_chain_kernel(PoseArgs a) {
+  const int t = blockIdx.x * NJF_POSE_THREADS + threadIdx.x;
+  if (t >= a.M * a.K) return;
+  const int m = t / a.K, p = t - m * a.K;
+  const double* base = a.link + (size_t)m * a.K * 12;
+  double T[12];
+#pragma unroll
+  for (int e = 0; e < 12; ++e) T[e] = base[(size_t)p * 12 + e];
+  const int own = a.link_bits[p];
+  bool ok = !(own & 2);
+  int steps = 0;
+  int q = a.parent ? a.parent[p] : -1;
+  while (ok && q != -1) {
+    if (q < -1 || q >= a.K || steps >= a.K || (a.link_bits[q] & 2)) {  // (q checked before link_bits[q])
+      ok = false;
+      break;
+    }
+    const double* g = base + (size_t)q * 12;  // q < K
+    double N[12];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c)
+        N[r * 3 + c] = (g[r * 3] * T[c] + g[r * 3 + 1] * T[3 + c]) + g[r * 3 + 2] * T[6 + c];
+      N[9 + r] = ((g[r * 3] * T[9] + g[r * 3 + 1] * T[10]) + g[r * 3 + 2] * T[11]) + g[9 + r];
+    }
+#pragma unroll
+    for (int e = 0; e < 12; ++e) T[e] = N[e];
+    ++steps;
+    q = a.parent[q];
+  }
+  if (!ok) {
+#pragma unroll
+    for (int e = 0; e < 12; ++e) T[e] = (e == 0 || e == 4 || e == 8) ? 1.0 : 0.0;
+  }
+#pragma unroll
+  for (int e = 0; e < 9; ++e) a.rotation[(size_t)t * 9 + e] = T[e];
+#pragma unroll
+  for (int e = 0; e < 3; ++e) a.translation[(size_t)t * 3 + e] = T[9 + e];
+  if (m == 0) {
+    a.status[p] = own | (ok ? 0 : 2);
+    a.depth[p] = steps;
+  }
+}
+
+// One thread per row, a tile of commands per blockIdx.y.  The row's coordinates, label, slot and (for a first-order row) Jacobian
+// are read once; per command the thread reads its part's 12 doubles and writes 3 floats.  STAGE: one command's transforms of
+// the used slots go through LDS first (rotation and translation rows copied by the whole workgroup) instead of being read by
+// every lane from L2.  WIDE: the workgroup's 3 * rows floats of a command are contiguous in the output, so they are laid out in
+// LDS and written as 16-byte stores between a scalar head and tail (the output of command m starts at 12 * m * n bytes, which
+// need not be a multiple of 16) instead of three dword stores per lane.
+template <bool STAGE, bool WIDE>
+__global__ void __launch_bounds__(NJF_POSE_THREADS) pose_points_kernel(PoseArgs a) {
+  __shared__ double staged[STAGE ? NJF_FIELD_TWISTS_MAX_PARTS * 12 : 1];
+  __shared__ float tile[WIDE ? NJF_POSE_THREADS * 3 : 1];
+  const int rows = counted_length(a.count, a.n);
+  const int tid = threadIdx.x;
+  const long long first = (long long)blockIdx.x * NJF_POSE_THREADS;
+  if (first >= rows) return;  // the whole workgroup, before any barrier
+  const long long i = first + tid;
+  const bool live = i < rows;  // (rows past the count are neither read nor written)
+  const int active = counted_length(a.parts_count, a.K);
+  float x = 0.f, y = 0.f, z = 0.f;
+  int slot = -1;
+  float jac[NJF_MAX_ACTION_DIM * 3];
+#pragma unroll
+  for (int e = 0; e < NJF_MAX_ACTION_DIM * 3; ++e) jac[e] = 0.f;
+  if (live) {
+    x = a.xyz[i * 3], y = a.xyz[i * 3 + 1], z = a.xyz[i * 3 + 2];
+    const int label = a.labels[i];
+    if (label >= 0) {
+      const int p = cc_lower_bound(a.parts, active, label);
+      if (p < active && a.parts[p] == label && a.status[p] == 0) slot = p;  // p < K
+    }
+    if (slot < 0 && a.jacobian) {
+      const float* jr = a.jacobian + (size_t)i * a.A * 3;
+#pragma unroll
+      for (int ch = 0; ch < NJF_MAX_ACTION_DIM; ++ch)  // (static indices: the array stays in registers)
+        if (ch < a.A) {
+          jac[ch * 3] = jr[ch * 3];
+          jac[ch * 3 + 1] = jr[ch * 3 + 1];
+          jac[ch * 3 + 2] = jr[ch * 3 + 2];
+        }
+    }
+  }
+  const int block_rows = (int)min((long long)NJF_POSE_THREADS, rows - first);
+  const int m0 = blockIdx.y * NJF_POSE_COMMAND_TILE, m1 = min(a.M, m0 + NJF_POSE_COMMAND_TILE);
+  for (int m = m0; m < m1; ++m) {
+    const double* rot = a.rotation + (size_t)m * a.K * 9;
+    const double* trn = a.translation + (size_t)m * a.K * 3;
+    if (STAGE) {
+      __syncthreads();  // (the previous command's reads are done)
+      for (int e = tid; e < active * 9; e += NJF_POSE_THREADS) staged[(e / 9) * 12 + e % 9] = rot[e];      // active <= K
+      for (int e = tid; e < active * 3; e += NJF_POSE_THREADS) staged[(e / 3) * 12 + 9 + e % 3] = trn[e];
+      __syncthreads();
+    }
+    float o0 = x, o1 = y, o2 = z;
+    if (slot >= 0) {
+      double T[12];
+      if (STAGE) {
+#pragma unroll
+        for (int e = 0; e < 12; ++e) T[e] = staged[slot * 12 + e];
+      } else {
+#pragma unroll
+        for (int e = 0; e < 9; ++e) T[e] = rot[(size_t)slot * 9 + e];
+#pragma unroll
+        for (int e = 0; e < 3; ++e) T[9 + e] = trn[(size_t)slot * 3 + e];
+      }
+      const double dx = (double)x, dy = (double)y, dz = (double)z;
+      o0 = (float)(((T[0] * dx + T[1] * dy) + T[2] * dz) + T[9]);
+      o1 = (float)(((T[3] * dx + T[4] * dy) + T[5] * dz) + T[10]);
+      o2 = (float)(((T[6] * dx + T[7] * dy) + T[8] * dz) + T[11]);
+    } else if (live && a.jacobian) {
+      const float* u = a.commands + (size_t)m * a.A;
+      double s0 = (double)x, s1 = (double)y, s2 = (double)z;
+#pragma unroll
+      for (int ch = 0; ch < NJF_MAX_ACTION_DIM; ++ch)
+        if (ch < a.A) {
+          const double uc = (double)u[ch];
+          s0 += uc * (double)jac[ch * 3];
+          s1 += uc * (double)jac[ch * 3 + 1];
+          s2 += uc * (double)jac[ch * 3 + 2];
+        }
+      o0 = (float)s0, o1 = (float)s1, o2 = (float)s2;
+    }
+    float* out = a.posed + ((size_t)m * a.n + (size_t)first) * 3;  // the workgroup's 3 * block_rows floats of command m
+    if (!WIDE) {
+      if (live) {
+        out[tid * 3] = o0;
+        out[tid * 3 + 1] = o1;
+        out[tid * 3 + 2] = o2;
+      }
+    } else {
+      __syncthreads();  // (the previous command's tile has been written out)
+      tile[tid * 3] = o0;
+      tile[tid * 3 + 1] = o1;
+      tile[tid * 3 + 2] = o2;
+      __syncthreads();
+      const int floats = block_rows * 3;
+      const int head = min(floats, (int)((4 - (((size_t)out >> 2) & 3)) & 3));  // floats up to the next 16-byte boundary
+      const int quads = (floats - head) >> 2;
+      if (tid < head) out[tid] = tile[tid];
+      if (tid < quads) {  // quads <= 192
+        const int e = head + tid * 4;
+        *reinterpret_cast<float4*>(out + e) = make_float4(tile[e], tile[e + 1], tile[e + 2], tile[e + 3]);
+      }
+      const int done = head + quads * 4;
+      if (tid < floats - done) out[done + tid] = tile[done + tid];
+    }
+  }
+}
+
+// =============================================================================================
 // inverse dynamics: Levenberg-Marquardt on the linearised flow, one workgroup per batch element
 // =============================================================================================
 // optical_flow(a) = proj(x + M a) - proj(x) with x = sum_s w x_s and M = sum_s w J_s (the composited outputs of the
@@ -5834,6 +6108,86 @@ extern "C" int njf_field_joints(const NjfFieldGrid* grid, int batch, const int* 
   }
   if (phases & NJF_FIELD_JOINTS_TWISTS) {
     joint_twists_kernel<<<(max_joints * action_dim + NJF_JOINT_THREADS - 1) / NJF_JOINT_THREADS, NJF_JOINT_THREADS, 0, s>>>(a);
+    if ((rc = launch_status())) return rc;
+  }
+  return NJF_OK;
+}
+
+extern "C" int njf_field_pose(const int* parts, const int* parts_count, int num_parts, const int* part_status,
+                              const double* centroid, const double* omega, const double* velocity, int action_dim,
+                              const int* part_a, const int* part_b, const int* joints_count, int max_joints,
+                              const double* anchor, const double* joint_omega, const double* joint_velocity, const int* parent,
+                              const int* joint_of, const float* commands, int num_commands, double* rotation,
+                              double* translation, int* status, int* depth, const float* xyz, const int* labels,
+                              const int* count, int n, const float* jacobian, float* posed, double* workspace,
+                              long long workspace_doubles, int phases, void* stream) {
+  if (num_parts < 1 || num_parts > NJF_FIELD_TWISTS_MAX_PARTS) return NJF_E_VALUE;
+  if (action_dim < 1 || action_dim > NJF_MAX_ACTION_DIM) return NJF_E_VALUE;
+  if (num_commands < 1 || num_commands > NJF_FIELD_POSE_MAX_COMMANDS) return NJF_E_VALUE;
+  const bool tree = part_a || part_b || joints_count || anchor || joint_omega || joint_velocity || parent || joint_of;
+  if (tree && (max_joints < 1 || max_joints > NJF_FIELD_JOINTS_MAX)) return NJF_E_VALUE;
+  if (phases < 1 || phases > (NJF_FIELD_POSE_ALL | NJF_FIELD_POSE_STAGED | NJF_FIELD_POSE_WIDE)) return NJF_E_VALUE;
+  if (n < 0) return NJF_E_SHAPE;
+  // (the links launch reads the twists, links and chain the workspace; the points launch needs neither)
+  const bool links = phases & NJF_FIELD_POSE_LINKS, walk = phases & (NJF_FIELD_POSE_LINKS | NJF_FIELD_POSE_CHAIN);
+  if (walk && workspace_doubles < NJF_FIELD_POSE_WORKSPACE(num_commands, num_parts)) return NJF_E_SHAPE;
+  if (!parts || !commands || !rotation || !translation || !status || !depth || (walk && !workspace)) return NJF_E_NULL;
+  if (links && (!part_status || !centroid || !omega || !velocity)) return NJF_E_NULL;
+  // joints and tree come together or not at all (joints_count alone may be absent: NULL = max_joints)
+  if (tree && (!part_a || !part_b || !anchor || !joint_omega || !joint_velocity || !parent || !joint_of)) return NJF_E_NULL;
+  const bool points = xyz || labels || posed || jacobian || count;
+  if (points && n > 0 && (!xyz || !labels || !posed)) return NJF_E_NULL;
+  PoseArgs a;
+  a.parts = parts;
+  a.parts_count = parts_count;
+  a.K = num_parts;
+  a.A = action_dim;
+  a.J = tree ? max_joints : 0;
+  a.M = num_commands;
+  a.part_status = part_status;
+  a.centroid = centroid;
+  a.omega = omega;
+  a.velocity = velocity;
+  a.part_a = part_a;
+  a.part_b = part_b;
+  a.joints_count = joints_count;
+  a.anchor = anchor;
+  a.joint_omega = joint_omega;
+  a.joint_velocity = joint_velocity;
+  a.parent = parent;
+  a.joint_of = joint_of;
+  a.commands = commands;
+  a.link = workspace;
+  a.link_bits = (int*)(workspace + 12LL * num_commands * num_parts);
+  a.rotation = rotation;
+  a.translation = translation;
+  a.status = status;
+  a.depth = depth;
+  a.xyz = xyz;
+  a.labels = labels;
+  a.count = count;
+  a.n = n;
+  a.jacobian = jacobian;
+  a.posed = posed;
+  hipStream_t s = (hipStream_t)stream;
+  int rc;
+  const int blocks = (num_commands * num_parts + NJF_POSE_THREADS - 1) / NJF_POSE_THREADS;  // M*K <= 65535 * 256
+  if (phases & NJF_FIELD_POSE_LINKS) {
+    pose_links_kernel<<<blocks, NJF_POSE_THREADS, 0, s>>>(a);
+    if ((rc = launch_status())) return rc;
+  }
+  if (phases & NJF_FIELD_POSE_CHAIN) {
+    pose_chain_kernel<<<blocks, NJF_POSE_THREADS, 0, s>>>(a);
+    if ((rc = launch_status())) return rc;
+  }
+  if (points && n > 0 && (phases & NJF_FIELD_POSE_POINTS)) {
+    const dim3 grid((unsigned)(((long long)n + NJF_POSE_THREADS - 1) / NJF_POSE_THREADS),
+                    (unsigned)((num_commands + NJF_POSE_COMMAND_TILE - 1) / NJF_POSE_COMMAND_TILE));  // y <= 2048
+    const bool staged = phases & NJF_FIELD_POSE_STAGED, wide = phases & NJF_FIELD_POSE_WIDE;
+    if (staged && wide) pose_points_kernel<true, true><<<grid, NJF_POSE_THREADS, 0, s>>>(a);
+    else if (staged) pose_points_kernel<true, false><<<grid, NJF_POSE_THREADS, 0, s>>>(a);
+    else if (wide) pose_points_kernel<false, true><<<grid, NJF_POSE_THREADS, 0, s>>>(a);
+    else pose_points_kernel<false, false><<<grid, NJF_POSE_THREADS, 0, s>>>(a);
     if ((rc = launch_status())) return rc;
   }
   return NJF_OK;

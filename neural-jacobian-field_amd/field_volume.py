@@ -608,6 +608,11 @@ class FieldJoints:
                         queue.append(q)
         return torch.from_numpy(parent), torch.from_numpy(joint_of)
 
+    def tree(self, root: Optional[int] = None):
+        """``parents(root)`` as the two int32 tensors on the joints' device that ``part_poses`` / ``cloud_pose`` take."""
+        parent, joint_of = self.parents(root)
+        return parent.to(device=self.part_a.device, dtype=torch.int32), joint_of.to(device=self.part_a.device, dtype=torch.int32)
+
 
 def part_joints(grid: FieldGrid, index: torch.Tensor, labels: torch.Tensor, twists: FieldTwists, *, batch: int,
                 count: Optional[torch.Tensor] = None, connectivity: int = 6, min_contacts: int = 1,
@@ -693,6 +698,178 @@ def cloud_joints(cloud: FieldPointCloud, labels: torch.Tensor, twists: FieldTwis
     ``cloud_components`` does (one host read); given ``batch``, nothing is read."""
     return _joints("cloud_joints", cloud.grid, cloud.index, labels, twists, batch, cloud.count, connectivity, min_contacts,
                    max_joints, infer_batch=True)
+
+
+# ---- posing the parts under a command: twist exponentials along the tree (DESIGN.md section 17) ---------------------------------
+@dataclass
+class FieldPose:
+    """The rigid motion of every part under every command (``part_poses``; include/njf_hip.h: njf_field_pose): ``x -> rotation[m,
+    p] x + translation[m, p]`` takes a point of part ``labels[p]`` from the present configuration to the one under ``commands[m]``
+    -- the product of the exponentials of the joint twists along the part's chain to the root, or, without a tree, the
+    exponential of the part's own twist about its centroid.  ``status`` 0 or bits: 1 = the slot is unused or its twist is empty
+    (its own motion is the identity), 2 = the slot hangs on a bad link, a cycle or a parent outside the list (its pose is the
+    identity).  ``depth`` counts the links above the slot.  ``count`` is the twists' TRUE number of parts."""
+
+    labels: torch.Tensor        # [K] int32: the twists' part labels
+    count: torch.Tensor         # [1] int32
+    rotation: torch.Tensor      # [M, K, 3, 3] float64
+    translation: torch.Tensor   # [M, K, 3] float64
+    status: torch.Tensor        # [K] int32
+    depth: torch.Tensor         # [K] int32
+    commands: torch.Tensor      # [M, A] fp32
+
+    def matrix(self) -> torch.Tensor:
+        """``[M, K, 4, 4]`` float64: the homogeneous matrices."""
+        m, k = self.rotation.shape[:2]
+        out = torch.zeros(m, k, 4, 4, dtype=self.rotation.dtype, device=self.rotation.device)
+        out[..., :3, :3] = self.rotation
+        out[..., :3, 3] = self.translation
+        out[..., 3, 3] = 1.0
+        return out
+
+    def apply(self, xyz: torch.Tensor, labels: torch.Tensor, *, count: Optional[torch.Tensor] = None,
+              jacobian: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``[M, n, 3]`` fp32: the points ``xyz`` ``[n, 3]`` (fp32) with part labels ``labels`` ``[n]`` (int32; the rows of a
+        cloud, mesh vertices with the label of their owner node, ...) under every command.  A row whose label is a part of
+        status 0 moves with the part, in double, rounded once.  Every other row below ``count`` (int32 device tensor; None = n)
+        takes the field's own first-order step ``x + sum_a u_a J_a`` when ``jacobian`` ``[n, A, 3]`` (fp32) is given, and stays
+        where it is otherwise.  Rows from ``count`` on are not written (the result is allocated, not cleared)."""
+        name = "FieldPose.apply"
+        m, a_dim = self.commands.shape
+        n = _check_points(name, xyz, labels, jacobian, a_dim)
+        count = _one_int32(name, "count", count, xyz)
+        for what, t in (("labels", labels), ("jacobian", jacobian), ("the pose", self.rotation)):
+            if t is not None and t.device != xyz.device:
+                raise ValueError(f"{name}: {what} must live on the device of xyz")
+        if xyz.device.type != "cuda":
+            raise ValueError(f"{name}: the points must live on the GPU; there is no CPU path")
+        posed = torch.empty(m, n, 3, dtype=torch.float32, device=xyz.device)
+        if n:
+            points = dict(xyz=xyz.contiguous(), labels=labels.contiguous(), count=count,
+                          jacobian=None if jacobian is None else jacobian.contiguous(), posed=posed)
+            hip.field_pose(self.labels, None, None, None, None, self.commands,
+                           dict(rotation=self.rotation, translation=self.translation, status=self.status, depth=self.depth),
+                           parts_count=self.count, points=points, phase=hip.FIELD_POSE_POINTS)
+        return posed
+
+
+def _check_points(name: str, xyz, labels, jacobian, a_dim: int) -> int:
+    if not torch.is_tensor(xyz) or xyz.dtype != torch.float32 or xyz.dim() != 2 or xyz.shape[1] != 3:
+        raise ValueError(f"{name}: xyz must be fp32 [n, 3]")
+    n = xyz.shape[0]
+    if not torch.is_tensor(labels) or labels.dtype != torch.int32 or tuple(labels.shape) != (n,):
+        raise ValueError(f"{name}: labels must be int32 [{n}]")
+    if jacobian is not None and (not torch.is_tensor(jacobian) or jacobian.dtype != torch.float32
+                                 or tuple(jacobian.shape) != (n, a_dim, 3)):
+        raise ValueError(f"{name}: jacobian must be fp32 [{n}, {a_dim}, 3] or None")
+    return n
+
+
+def _pose(name: str, twists, commands, joints, tree, points=None):
+    """The argument checks (under the caller's ``name``) and the launches of part_poses / cloud_pose.  ``points``: None or
+    ``(xyz, labels, count, jacobian)``; then the result is ``(FieldPose, posed)``."""
+    if not isinstance(twists, FieldTwists):
+        raise ValueError(f"{name}: twists must be a FieldTwists")
+    parts = twists.labels
+    if not torch.is_tensor(parts) or parts.dtype != torch.int32 or parts.dim() != 1:
+        raise ValueError(f"{name}: twists.labels must be int32 [K]")
+    k = parts.shape[0]
+    if not 1 <= k <= hip.FIELD_TWISTS_MAX_PARTS:
+        raise ValueError(f"{name}: the twists must hold 1 to {hip.FIELD_TWISTS_MAX_PARTS} parts (got {k})")
+    omega = twists.omega
+    if not torch.is_tensor(omega) or omega.dtype != torch.float64 or omega.dim() != 3 or omega.shape[0] != k or omega.shape[2] != 3:
+        raise ValueError(f"{name}: twists.omega must be float64 [{k}, A, 3]")
+    a_dim = omega.shape[1]
+    if not 1 <= a_dim <= hip.MAX_ACTION_DIM:
+        raise ValueError(f"{name}: 1 to {hip.MAX_ACTION_DIM} command channels (got {a_dim})")
+    for what, t, dtype, shape in (("velocity", twists.velocity, torch.float64, (k, a_dim, 3)),
+                                  ("centroid", twists.centroid, torch.float64, (k, 3)), ("status", twists.status, torch.int32, (k,))):
+        if not torch.is_tensor(t) or t.dtype != dtype or tuple(t.shape) != shape:
+            raise ValueError(f"{name}: twists.{what} must be {str(dtype).replace('torch.', '')} {list(shape)}")
+    if not torch.is_tensor(commands) or commands.dtype != torch.float32 or commands.dim() != 2 or commands.shape[1] != a_dim:
+        raise ValueError(f"{name}: commands must be fp32 [M, {a_dim}]")
+    m = commands.shape[0]
+    if not 1 <= m <= hip.FIELD_POSE_MAX_COMMANDS:
+        raise ValueError(f"{name}: 1 to {hip.FIELD_POSE_MAX_COMMANDS} commands (got {m})")
+    if (joints is None) != (tree is None):
+        raise ValueError(f"{name}: joints and tree come together or not at all")
+    parts_count = _one_int32(name, "twists.count", twists.count, commands)
+    same = [("twists.labels", parts), ("twists.omega", omega), ("twists.velocity", twists.velocity),
+            ("twists.centroid", twists.centroid), ("twists.status", twists.status)]
+    links = None
+    if joints is not None:
+        if not isinstance(joints, FieldJoints):
+            raise ValueError(f"{name}: joints must be a FieldJoints")
+        if not torch.is_tensor(joints.part_a) or joints.part_a.dtype != torch.int32 or joints.part_a.dim() != 1:
+            raise ValueError(f"{name}: joints.part_a must be int32 [J]")
+        j = joints.part_a.shape[0]
+        if not 1 <= j <= hip.FIELD_JOINTS_MAX:
+            raise ValueError(f"{name}: the joints must hold 1 to {hip.FIELD_JOINTS_MAX} rows (got {j})")
+        for what, t, dtype, shape in (("part_b", joints.part_b, torch.int32, (j,)), ("anchor", joints.anchor, torch.float64, (j, 3)),
+                                      ("omega", joints.omega, torch.float64, (j, a_dim, 3)),
+                                      ("velocity", joints.velocity, torch.float64, (j, a_dim, 3))):
+            if not torch.is_tensor(t) or t.dtype != dtype or tuple(t.shape) != shape:
+                raise ValueError(f"{name}: joints.{what} must be {str(dtype).replace('torch.', '')} {list(shape)}")
+        if not isinstance(tree, (tuple, list)) or len(tree) != 2:
+            raise ValueError(f"{name}: tree must be (parent, joint_of), as FieldJoints.tree() returns it")
+        for what, t in zip(("parent", "joint_of"), tree):
+            if not torch.is_tensor(t) or t.dtype != torch.int32 or tuple(t.shape) != (k,):
+                raise ValueError(f"{name}: tree {what} must be int32 [{k}] (FieldJoints.tree(), not parents())")
+        joints_count = _one_int32(name, "joints.count", joints.count, commands)
+        same += [("joints.part_a", joints.part_a), ("joints.part_b", joints.part_b), ("joints.anchor", joints.anchor),
+                 ("joints.omega", joints.omega), ("joints.velocity", joints.velocity), ("tree parent", tree[0]),
+                 ("tree joint_of", tree[1])]
+        links = dict(part_a=joints.part_a.contiguous(), part_b=joints.part_b.contiguous(), count=joints_count,
+                     anchor=joints.anchor.contiguous(), omega=joints.omega.contiguous(), velocity=joints.velocity.contiguous(),
+                     parent=tree[0].contiguous(), joint_of=tree[1].contiguous())
+    n = 0
+    if points is not None:
+        xyz, labels, count, jacobian = points
+        n = _check_points(name, xyz, labels, jacobian, a_dim)
+        count = _one_int32(name, "count", count, commands)
+        same += [("xyz", xyz), ("labels", labels)] + ([] if jacobian is None else [("jacobian", jacobian)])
+    for what, t in same:
+        if t.device != commands.device:
+            raise ValueError(f"{name}: {what} must live on the device of commands")
+    if commands.device.type != "cuda":
+        raise ValueError(f"{name}: the tensors must live on the GPU; there is no CPU path")
+    dev = commands.device
+    i32, f64 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.float64, device=dev)
+    pose = FieldPose(labels=parts, count=twists.count, rotation=torch.empty(m, k, 3, 3, **f64), translation=torch.empty(m, k, 3, **f64),
+                     status=torch.empty(k, **i32), depth=torch.empty(k, **i32), commands=commands.contiguous())
+    out = dict(rotation=pose.rotation, translation=pose.translation, status=pose.status, depth=pose.depth)
+    posed, rows = None, None
+    if points is not None:
+        posed = torch.empty(m, n, 3, dtype=torch.float32, device=dev)
+        if n:
+            rows = dict(xyz=xyz.contiguous(), labels=labels.contiguous(), count=count,
+                        jacobian=None if jacobian is None else jacobian.contiguous(), posed=posed)
+    hip.field_pose(parts.contiguous(), twists.status.contiguous(), twists.centroid.contiguous(), omega.contiguous(),
+                   twists.velocity.contiguous(), pose.commands, out, parts_count=parts_count, joints=links, points=rows)
+    return pose if points is None else (pose, posed)
+
+
+def part_poses(twists: FieldTwists, commands: torch.Tensor, *, joints: Optional[FieldJoints] = None, tree=None) -> FieldPose:
+    """Where every part goes under each of the M commands ``commands`` ``[M, A]`` (fp32): the rigid motion ``x -> R x + t`` per
+    command and part, in double.  With ``joints`` (``cloud_joints``) and ``tree`` (``joints.tree()``:
+    parent and joint_of, int32 on the device) a part's motion is the product of the exponentials of the relative twists of
+    the joints along its chain, about their anchors, and of the root's own twist about its centroid, the root applied last;
+    without them every part moves by the exponential of its own twist about its centroid.  The tree is caller data: a cycle,
+    a self-parent, a joint that does not join the two slots or a parent outside the list give the identity and status bit
+    2, after a walk of at most K steps.  No atomics, no host read: equal bytes from call to call, capturable."""
+    return _pose("part_poses", twists, commands, joints, tree)
+
+
+def cloud_pose(cloud: FieldPointCloud, labels: torch.Tensor, twists: FieldTwists, commands: torch.Tensor, *,
+               joints: Optional[FieldJoints] = None, tree=None, first_order_elsewhere: bool = True):
+    """``(FieldPose, posed [M, n, 3] fp32)``: ``part_poses`` and, in the same sequence of launches, the rows of an extracted
+    cloud under every command -- ``cloud.xyz``, ``cloud.count`` and ``labels`` ``[n]`` int32, the per-row result of
+    ``cloud_components``.  A row of a part of status 0 moves rigidly with it; every other row takes the field's own first-order
+    step ``x + sum_a u_a J_a(x)`` from ``cloud.jacobian`` (``first_order_elsewhere=True``) or stays where it is."""
+    if not isinstance(cloud, FieldPointCloud):
+        raise ValueError("cloud_pose: cloud must be a FieldPointCloud")
+    jacobian = cloud.jacobian if first_order_elsewhere else None
+    return _pose("cloud_pose", twists, commands, joints, tree, points=(cloud.xyz, labels, cloud.count, jacobian))
 
 
 # ---- coarse-to-fine band (DESIGN.md section 14) ----------------------------------------------------------------------------------

@@ -171,6 +171,8 @@ _SIGNATURES = {
                          C.c_int),
     "njf_field_joints": ([C.POINTER(FieldGrid), C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int,
                           C.c_int, C.c_int, C.c_int] + [_vp] * 9 + [C.c_longlong, C.c_int, _vp], C.c_int),
+    "njf_field_pose": ([_vp, _vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int,
+                        _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_longlong, C.c_int, _vp], C.c_int),
     "njf_pack_resnetfc_backward": ([C.POINTER(ResnetFcWeights), _vp, C.c_int, _vp], C.c_int),
     "njf_resnetfc_backward": ([_vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp], C.c_int),
     "njf_pack_transformer_backward": ([_vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, _vp], C.c_int),
@@ -1032,6 +1034,82 @@ def field_joints(grid: FieldGrid, batch: int, indices: torch.Tensor, labels: tor
             _ptr(out["contacts"], "contacts", torch.int64), _int32_ptr(out["status"], "status"),
             _int32_ptr(out["count"], "out count"), _double_ptr(out["anchor"], "anchor"), _double_ptr(out["omega"], "out omega"),
             _double_ptr(out["velocity"], "out velocity"), _ptr(workspace, "workspace", torch.int64), int(workspace.numel()),
+            int(phase))
+
+
+# ---- posing the parts under a command: twist exponentials along the tree (include/njf_hip.h: njf_field_pose) ---------------
+FIELD_POSE_MAX_COMMANDS = 65535        # NJF_FIELD_POSE_MAX_COMMANDS
+FIELD_POSE_LINKS, FIELD_POSE_CHAIN, FIELD_POSE_POINTS = 1, 2, 4   # NJF_FIELD_POSE_LINKS, _CHAIN, _POINTS: one launch each
+FIELD_POSE_PHASES = (FIELD_POSE_LINKS, FIELD_POSE_CHAIN, FIELD_POSE_POINTS)
+FIELD_POSE_PHASE_NAMES = ("links", "chain", "points")
+FIELD_POSE_ALL = 7                     # NJF_FIELD_POSE_ALL
+FIELD_POSE_STAGED = 8                  # NJF_FIELD_POSE_STAGED: the points launch with one command's transforms staged in LDS
+FIELD_POSE_WIDE = 16                   # NJF_FIELD_POSE_WIDE: the points launch with 16-byte stores through an LDS tile
+
+
+def field_pose_workspace(commands: int, parts: int) -> int:
+    """Doubles of workspace njf_field_pose needs: NJF_FIELD_POSE_WORKSPACE(M, K) -- the link motions [M, K, 12] and the int32
+    link bits of the K slots."""
+    return 12 * commands * parts + (parts + 1) // 2
+
+
+def field_pose(parts: torch.Tensor, part_status: torch.Tensor, centroid: torch.Tensor, omega: torch.Tensor,
+               velocity: torch.Tensor, commands: torch.Tensor, out: dict, parts_count=None, joints: Optional[dict] = None,
+               points: Optional[dict] = None, phase: int = FIELD_POSE_ALL, workspace: Optional[torch.Tensor] = None) -> None:
+    """njf_field_pose on the part list and twists ``parts``, ``part_status`` [K] (int32), ``centroid`` [K, 3], ``omega``,
+    ``velocity`` [K, A, 3] (float64) and ``commands`` [M, A] (fp32).  ``out`` maps rotation [M, K, 3, 3], translation [M, K, 3]
+    (float64), status and depth [K] (int32) to tensors of their shapes; a ``phase`` without the first two launches reads them
+    instead, and takes None for ``part_status`` and the twists.  ``joints``: None, or a dict of part_a, part_b [J] (int32), count ([1] int32 or None), anchor [J, 3],
+    omega, velocity [J, A, 3] (float64) and the tree parent, joint_of [K] (int32).  ``points``: None, or a dict of xyz [n, 3]
+    (fp32), labels [n] (int32), count ([1] int32 or None), jacobian ([n, A, 3] fp32 or None) and posed [M, n, 3] (fp32), which
+    is written.  ``phase`` / ``workspace`` (float64, ``field_pose_workspace`` elements): run the launches one by one on a
+    workspace of the caller's, to time them apart; FIELD_POSE_STAGED / FIELD_POSE_WIDE select the other forms of the points
+    launch."""
+    k = parts.numel()
+    if commands.dim() != 2:
+        raise ValueError("njf_hip: field_pose needs commands [M, A]")
+    m, a = commands.shape
+    links = bool(phase & FIELD_POSE_LINKS)   # only the links launch reads the twists: the others take None for them
+    if links or omega is not None:
+        if omega.dim() != 3 or tuple(omega.shape) != (k, a, 3) or velocity.shape != omega.shape:
+            raise ValueError(f"njf_hip: field_pose needs omega and velocity [K, {a}, 3]")
+        if part_status.numel() != k or centroid.numel() != 3 * k:
+            raise ValueError("njf_hip: field_pose needs one status and one centroid per part")
+    sizes = dict(rotation=9 * m * k, translation=3 * m * k, status=k, depth=k)
+    for name, size in sizes.items():
+        if out[name].numel() != size:
+            raise ValueError(f"njf_hip: field_pose output {name} must hold {size} elements (got {out[name].numel()})")
+    one = [("parts_count", parts_count)]
+    j = 0
+    if joints is not None:
+        j = joints["part_a"].numel()
+        if joints["part_b"].numel() != j or joints["anchor"].numel() != 3 * j or joints["omega"].numel() != 3 * a * j or \
+                joints["velocity"].numel() != 3 * a * j or joints["parent"].numel() != k or joints["joint_of"].numel() != k:
+            raise ValueError("njf_hip: field_pose needs part_a, part_b [J], anchor [J, 3], omega, velocity [J, A, 3] of the "
+                             "joints and parent, joint_of [K]")
+        one.append(("joints count", joints.get("count")))
+    n = 0
+    if points is not None:
+        n = points["labels"].numel()
+        jac = points.get("jacobian")
+        if points["xyz"].numel() != 3 * n or points["posed"].numel() != 3 * m * n or (jac is not None and jac.numel() != 3 * a * n):
+            raise ValueError("njf_hip: field_pose needs xyz [n, 3], labels [n], jacobian [n, A, 3] or None and posed [M, n, 3]")
+        one.append(("count", points.get("count")))
+    for name, t in one:
+        if t is not None and t.numel() != 1:
+            raise ValueError(f"njf_hip: field_pose {name} must hold one int32")
+    if workspace is None and phase & (FIELD_POSE_LINKS | FIELD_POSE_CHAIN):
+        workspace = torch.empty(field_pose_workspace(m, k), dtype=torch.float64, device=commands.device)
+    jt = (lambda key, ptr=_double_ptr: None if joints is None else ptr(joints.get(key), "joints " + key))   # noqa: E731
+    pt = (lambda key, ptr=_ptr: None if points is None else ptr(points.get(key), key))                       # noqa: E731
+    _launch("njf_field_pose", load_library().njf_field_pose, _int32_ptr(parts, "parts"), _int32_ptr(parts_count, "parts_count"),
+            int(k), _int32_ptr(part_status, "part_status"), _double_ptr(centroid, "centroid"), _double_ptr(omega, "omega"),
+            _double_ptr(velocity, "velocity"), int(a), jt("part_a", _int32_ptr), jt("part_b", _int32_ptr),
+            jt("count", _int32_ptr), int(j), jt("anchor"), jt("omega"), jt("velocity"), jt("parent", _int32_ptr),
+            jt("joint_of", _int32_ptr), _ptr(commands, "commands"), int(m), _double_ptr(out["rotation"], "rotation"),
+            _double_ptr(out["translation"], "translation"), _int32_ptr(out["status"], "status"),
+            _int32_ptr(out["depth"], "depth"), pt("xyz"), pt("labels", _int32_ptr), pt("count", _int32_ptr), int(n),
+            pt("jacobian"), pt("posed"), _double_ptr(workspace, "workspace"), 0 if workspace is None else int(workspace.numel()),
             int(phase))
 
 
