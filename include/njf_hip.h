@@ -712,6 +712,61 @@ int njf_field_pose(const int* parts, const int* parts_count, int num_parts, cons
                    const int* count, int n, const float* jacobian, float* posed, double* workspace, long long workspace_doubles,
                    int phases, void* stream);
 
+/* ---- inverse kinematics on the part tree: commands from 3-D point targets (ABI v20, additive) --------------
+ * For each of M problems, the command u whose finite pose (njf_field_pose's, not its linearisation) brings labelled points to
+ * their targets: L_m(u) = (1/W_m) sum_i w_i |R_p(u) x_i + t_p(u) - y_mi|^2 + (reg/A) |u|^2, in double.
+ * Inputs, all on the device: the part list, twists, optional joints and tree exactly as njf_field_pose takes them; the points xyz
+ * [n,3] float, labels [n] int32, count (int32, NULL = n); targets [M,n,3] float; weights float, NULL, [n] (weights_per_problem 0)
+ * or [M,n] (1); init, lower, upper [M,A] float or NULL (zeros, -inf, +inf).
+ * COUNTED ROWS of problem m: i < min(*count, n); the label has a slot p by njf_field_pose's rule; the slot's pose status is 0; the
+ *        weight is finite and > 0 (1 without weights; a NaN or a negative weight counts as 0); the three target coordinates are
+ *        finite (a NaN target leaves a row unconstrained).  Every other row is neither in the objective nor an error.
+ * MOMENTS [M,K,23] double per (problem, slot), centred on c = centroid[p], x~ = x - c, y~ = y - c: s0 = sum w; s1 = sum w x~ [3];
+ *        S2 = sum (w x~_r) x~_c [6: xx xy xz yy yz zz]; t1 = sum w y~ [3]; C[r][c] = sum (w y~_r) x~_c [9]; e = sum w ((y~0 y~0 +
+ *        y~1 y~1) + y~2 y~2).  Workgroup (chunk of NJF_FIELD_TWISTS_CHUNK rows, slot, tile of problems) compacts the chunk's rows
+ *        of the slot in order; a wave owns a problem, lane l adds the list entries l, l + 64, ..., a butterfly adds the lanes, and
+ *        the finishing launch adds the chunks in ascending order: the order depends on (n, K, M) alone, there are no
+ *        floating-point atomics, two calls give equal bytes.  A slot whose pose status is not 0 has zeros.
+ * SOLVE  One workgroup per problem, thread p owns slot p.  At a point u: the link motions G and, per link and channel, the
+ *        spatial derivative twist (W, U) -- W = V w', U = -W x (c + V v) + V v' + dV v, dV = 2 (w.w') (b2 [w]x + g2 [w]x^2) + b
+ *        [w']x + g ([w']x [w]x + [w]x [w']x), b2 = db/dth2 and g2 = dg/dth2 by their series up to th2 <= 1e-2 and in closed form
+ *        above --; up the parents S <- Ad_G(S) + S_q, then T <- G_q o T, a walk of at most K steps with every index checked; cost,
+ *        half-gradient g and Gauss-Newton matrix H per part from the moments, added in a fixed order.  Then the rule of
+ *        njf_solve_action_robust in double: u = (float)clamp(init), lam = damping; per iteration g~ = g + (reg/A) u, H~ = H +
+ *        (reg/A) I, a coordinate on a bound whose g~ points out of the box is frozen, H~_ii += lam max(H~_ii, 1e-12), un-pivoted
+ *        Gauss-Jordan, cand = (float)clamp(u - step), accepted iff L(cand) < L(u) (a NaN rejects), lam <- clamp(accepted ? lam /
+ *        3 : 4 lam, 1e-9, 1e9).  `iterations` rounds follow the first evaluation; the iterate lives on the fp32 lattice.
+ * Outputs: commands [M,A] float; cost, initial_cost, weight [M] double (the mean squared distance at commands and at the start,
+ *        clamped at 0; W_m); steps [M] int32 (accepted); gradient [M,A] double (g~ at commands); status [M] int32, bit
+ *        NJF_FIELD_COMMANDS_NO_ROWS: no counted row, NJF_FIELD_COMMANDS_NOT_FINITE: the starting objective is not finite (either
+ *        way commands = the clamped init); part_status, depth [K] int32: njf_field_pose's status and depth.
+ * workspace: NJF_FIELD_COMMANDS_WORKSPACE(M, K, A, n) doubles of the caller's: the chunks' partial moments [chunks,K,M,23], then
+ * the twists of the links and of the chains [M,2,K,A,6].
+ * `phases`: NJF_FIELD_COMMANDS_MOMENTS (two launches; writes moments, part_status, depth) | NJF_FIELD_COMMANDS_SOLVE (one launch;
+ * READS moments, so it can be fed given ones, and writes every other output, and part_status and depth once more with the same
+ * values: it walks the tree itself and does not trust what a caller may have left there).  One stream, no host read (capture-safe).
+ * Returns, before the first launch: NJF_E_VALUE for K, A, M or J outside njf_field_pose's ranges, iterations outside [0, 1000],
+ * damping not > 0, reg not >= 0, weights_per_problem not 0 or 1, or unknown phases; NJF_E_SHAPE for n < 0 or a workspace that is
+ * too small; NJF_E_NULL for a missing pointer, or joints without a tree or a tree without joints. */
+#define NJF_FIELD_COMMANDS_MOMENTS_PER_PART 23
+#define NJF_FIELD_COMMANDS_MAX_ITERATIONS 1000
+#define NJF_FIELD_COMMANDS_WORKSPACE(M, K, A, n) \
+  ((23LL * (((n) + NJF_FIELD_TWISTS_CHUNK - 1LL) / NJF_FIELD_TWISTS_CHUNK) + 12LL * (A)) * (M) * (K))
+#define NJF_FIELD_COMMANDS_MOMENTS 1    /* phases */
+#define NJF_FIELD_COMMANDS_SOLVE 2
+#define NJF_FIELD_COMMANDS_ALL 3
+#define NJF_FIELD_COMMANDS_NO_ROWS 1    /* status bits */
+#define NJF_FIELD_COMMANDS_NOT_FINITE 2
+int njf_field_commands(const int* parts, const int* parts_count, int num_parts, const int* part_status, const double* centroid,
+                       const double* omega, const double* velocity, int action_dim, const int* part_a, const int* part_b,
+                       const int* joints_count, int max_joints, const double* anchor, const double* joint_omega,
+                       const double* joint_velocity, const int* parent, const int* joint_of, const float* xyz, const int* labels,
+                       const int* count, int n, const float* targets, int num_problems, const float* weights,
+                       int weights_per_problem, const float* init, const float* lower, const float* upper, double reg,
+                       int iterations, double damping, float* commands, double* cost, double* initial_cost, double* weight,
+                       int* steps, double* gradient, int* status, int* out_part_status, int* depth, double* moments,
+                       double* workspace, long long workspace_doubles, int phases, void* stream);
+
 /* ---- stand-alone sampler / compositing ops (API parity with the un-fused reference calls) -- */
 /* RaySamples.get_weights (ray_samplers.py:77-101): deltas, densities [N,S] -> weights [N,S]. */
 int njf_alpha_weights(const float* deltas, const float* densities, int rays, int samples, float* weights, void* stream);

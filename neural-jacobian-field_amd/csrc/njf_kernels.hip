@@ -3234,14 +3234,14 @@ __device__ __forceinline__ double twist_weight(const TwistArgs& a, long long i) 
 }
 
 // the chunk's rows of label `part`, as offsets into the chunk, ascending, into list[]; returns their number
-__device__ __forceinline__ int twist_compact(const TwistArgs& a, int part, int rows, int* list, int (*wave_count)[NJF_TWIST_THREADS / 64]) {
+__device__ __forceinline__ int twist_compact(const int* labels, int part, int rows, int* list, int (*wave_count)[NJF_TWIST_THREADS / 64]) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const long long base = (long long)blockIdx.x * NJF_FIELD_TWISTS_CHUNK;
   unsigned flags = 0;
 #pragma unroll
   for (int it = 0; it < NJF_TWIST_ITEMS; ++it) {
     const long long i = base + it * NJF_TWIST_THREADS + tid;
-    if (i < rows && a.labels[i] == part) flags |= 1u << it;
+    if (i < rows && labels[i] == part) flags |= 1u << it;
   }
 #pragma unroll
   for (int it = 0; it < NJF_TWIST_ITEMS; ++it) {
@@ -3264,6 +3264,10 @@ __device__ __forceinline__ int twist_compact(const TwistArgs& a, int part, int r
   }
   __syncthreads();
   return run;
+}
+
+__device__ __forceinline__ int twist_compact(const TwistArgs& a, int part, int rows, int* list, int (*wave_count)[NJF_TWIST_THREADS / 64]) {
+  return twist_compact(a.labels, part, rows, list, wave_count);
 }
 
 __device__ __forceinline__ double twist_wave_sum(double v) {
@@ -3979,6 +3983,503 @@ __global__ void __launch_bounds__(NJF_POSE_THREADS) pose_points_kernel(PoseArgs 
       const int done = head + quads * 4;
       if (tid < floats - done) out[done + tid] = tile[done + tid];
     }
+  }
+}
+
+// =============================================================================================
+// inverse kinematics on the part tree: commands from 3-D point targets (njf_field_commands)
+// =============================================================================================
+// A part moves rigidly, so the least-squares objective sum_i w_i |R_p(u) x_i + t_p(u) - y_mi|^2, its gradient and its
+// Gauss-Newton matrix depend on the rows of part p only through 23 weighted moments of (point, target).  The moments launch
+// streams the rows once: workgroup (chunk, part, tile of problems) compacts the chunk's rows of the part in order (as the twists
+// do), then each WAVE owns whole problems -- lane l adds list entries l, l + 64, ... and one butterfly finishes the 23 sums, so
+// no barrier and no LDS traffic lies inside the loop over problems.  The finishing launch adds the chunks in ascending order
+// and zeroes the parts whose pose status is not 0.  The solver launch never looks at a row: one workgroup per problem, thread p
+// owns slot p.  No floating-point atomics anywhere: every sum has an order that depends on (n, K, M) alone.
+#define NJF_IK_THREADS 256
+#define NJF_IK_PROBLEM_TILE 16   // problems per workgroup of the moments launch (4 per wave)
+#define NJF_IK_FINISH_TILE 64    // problems per workgroup of the finishing launch
+#define NJF_IK_MOMENTS NJF_FIELD_COMMANDS_MOMENTS_PER_PART
+// the solver's reduced entries: cost, W, g [A], H upper triangle -- at fixed places, whatever A is
+#define NJF_IK_G 2
+#define NJF_IK_H (NJF_IK_G + NJF_MAX_ACTION_DIM)
+#define NJF_IK_ENTRIES (NJF_IK_H + NJF_MAX_ACTION_DIM * (NJF_MAX_ACTION_DIM + 1) / 2)
+struct IkArgs {
+  PoseArgs pose;           // the part list, twists, joints, tree and points of the pose (its outputs are unused); M = problems
+  const float* targets;    // [M,n,3]
+  const float* weights;    // null, [n] (weight_stride 0) or [M,n] (weight_stride n)
+  long long weight_stride;
+  const float *init, *lower, *upper;   // [M,A] or null
+  double reg, damping;
+  int iterations, chunks;
+  double* partial;         // [chunks][K][M][23]
+  double* link_twist;      // [M][2][K][A][6]: (W, U) per channel of every link, then of every chain, at the point being evaluated
+  double* moments;         // [M][K][23]
+  float* commands;         // [M,A]
+  double *cost, *initial_cost, *weight, *gradient;
+  int *steps, *status, *part_status, *depth;
+};
+
+// status and depth of slot p from the link bits of every slot: the walk of pose_chain_kernel without the transforms
+__device__ __forceinline__ int ik_walk_status(const int* parent, const int* bits, int K, int p, int& depth) {
+  const int own = bits[p];
+  bool ok = !(own & 2);
+  int steps = 0;
+  int q = parent ? parent[p] : -1;
+  while (ok && q != -1) {
+    if (q < -1 || q >= K || steps >= K || (bits[q] & 2)) {  // (q checked before bits[q])
+      ok = false;
+      break;
+    }
+    ++steps;
+    q = parent[q];
+  }
+  depth = steps;
+  return own | (ok ? 0 : 2);
+}
+
+__global__ void __launch_bounds__(NJF_IK_THREADS) ik_moments_kernel(IkArgs a) {
+  __shared__ int list[NJF_FIELD_TWISTS_CHUNK];
+  __shared__ int wave_count[NJF_TWIST_ITEMS][NJF_TWIST_THREADS / 64];
+  static_assert(NJF_IK_THREADS == NJF_TWIST_THREADS, "twist_compact is written for this workgroup size");
+  const PoseArgs& s = a.pose;
+  const int p = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (p >= counted_length(s.parts_count, s.K) || s.parts[p] < 0) return;  // (uniform; the finishing launch does not read it)
+  const int cnt = twist_compact(s.labels, s.parts[p], counted_length(s.count, s.n), list, wave_count);
+  const long long base = (long long)blockIdx.x * NJF_FIELD_TWISTS_CHUNK;
+  const double c0 = s.centroid[p * 3], c1 = s.centroid[p * 3 + 1], c2 = s.centroid[p * 3 + 2];
+  const int m0 = blockIdx.z * NJF_IK_PROBLEM_TILE, m1 = min(s.M, m0 + NJF_IK_PROBLEM_TILE);
+  for (int m = m0 + wave; m < m1; m += NJF_IK_THREADS / 64) {
+    const float* y = a.targets + (size_t)m * s.n * 3;
+    const float* wt = a.weights ? a.weights + (size_t)m * a.weight_stride : nullptr;
+    double* out = a.partial + (((size_t)blockIdx.x * s.K + p) * s.M + m) * NJF_IK_MOMENTS;  // p < K, m < M
+    if (cnt == 0) {  // (uniform) most (chunk, slot) pairs of a cloud in grid order: the sums of nothing, without the butterflies
+      if (lane < NJF_IK_MOMENTS) out[lane] = 0.0;
+      continue;
+    }
+    double acc[NJF_IK_MOMENTS];
+#pragma unroll
+    for (int k = 0; k < NJF_IK_MOMENTS; ++k) acc[k] = 0.0;
+    for (int e = lane; e < cnt; e += 64) {
+      const long long i = base + list[e];  // a row below min(count, n)
+      const float w32 = wt ? wt[i] : 1.f;
+      const float y0 = y[i * 3], y1 = y[i * 3 + 1], y2 = y[i * 3 + 2];
+      // (every comparison with a NaN is false: a NaN weight or target leaves the row out)
+      if (w32 > 0.f && w32 < INFINITY && fabsf(y0) < INFINITY && fabsf(y1) < INFINITY && fabsf(y2) < INFINITY) {
+        const double w = (double)w32;
+        const double x[3] = {(double)s.xyz[i * 3] - c0, (double)s.xyz[i * 3 + 1] - c1, (double)s.xyz[i * 3 + 2] - c2};
+        const double t[3] = {(double)y0 - c0, (double)y1 - c1, (double)y2 - c2};
+        const double wx[3] = {w * x[0], w * x[1], w * x[2]}, wy[3] = {w * t[0], w * t[1], w * t[2]};
+        acc[0] += w;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          acc[1 + c] += wx[c];
+          acc[10 + c] += wy[c];
+#pragma unroll
+          for (int d = 0; d < 3; ++d) acc[13 + c * 3 + d] += wy[c] * x[d];
+        }
+        acc[4] += wx[0] * x[0];
+        acc[5] += wx[0] * x[1];
+        acc[6] += wx[0] * x[2];
+        acc[7] += wx[1] * x[1];
+        acc[8] += wx[1] * x[2];
+        acc[9] += wx[2] * x[2];
+        acc[22] += w * ((t[0] * t[0] + t[1] * t[1]) + t[2] * t[2]);
+      }
+    }
+    double mine = 0.0;
+#pragma unroll
+    for (int k = 0; k < NJF_IK_MOMENTS; ++k) {
+      const double v = twist_wave_sum(acc[k]);
+      if (lane == k) mine = v;
+    }
+    if (lane < NJF_IK_MOMENTS) out[lane] = mine;
+  }
+}
+
+// moments[m][p] = the chunks' partials in ascending order, or zeros for a slot whose pose status is not 0; status and depth
+__global__ void __launch_bounds__(NJF_IK_THREADS) ik_finish_kernel(IkArgs a) {
+  __shared__ int bits[NJF_FIELD_TWISTS_MAX_PARTS];
+  __shared__ int result[2];
+  const PoseArgs& s = a.pose;
+  const int p = blockIdx.x, tid = threadIdx.x;  // p < K
+  const int active = counted_length(s.parts_count, s.K);
+  for (int t = tid; t < s.K; t += NJF_IK_THREADS) {
+    int q, j;
+    double sign;
+    bits[t] = pose_link_bits(s, t, active, q, j, sign);
+  }
+  __syncthreads();
+  if (tid == 0) {
+    int depth;
+    result[0] = ik_walk_status(s.parent, bits, s.K, p, depth);
+    result[1] = depth;
+    if (blockIdx.y == 0) {
+      a.part_status[p] = result[0];
+      a.depth[p] = depth;
+    }
+  }
+  __syncthreads();
+  const bool live = result[0] == 0 && s.parts[p] >= 0;  // (status 0: p < active)
+  const int m0 = blockIdx.y * NJF_IK_FINISH_TILE, items = (min(s.M, m0 + NJF_IK_FINISH_TILE) - m0) * NJF_IK_MOMENTS;
+  for (int e = tid; e < items; e += NJF_IK_THREADS) {
+    const int m = m0 + e / NJF_IK_MOMENTS, k = e % NJF_IK_MOMENTS;  // m < M
+    double sum = 0.0;
+    if (live)
+      for (int c = 0; c < a.chunks; ++c) sum += a.partial[(((size_t)c * s.K + p) * s.M + m) * NJF_IK_MOMENTS + k];
+    a.moments[((size_t)m * s.K + p) * NJF_IK_MOMENTS + k] = sum;
+  }
+}
+
+__device__ __forceinline__ void ik_cross(const double* x, const double* y, double* out) {
+  out[0] = x[1] * y[2] - x[2] * y[1];
+  out[1] = x[2] * y[0] - x[0] * y[2];
+  out[2] = x[0] * y[1] - x[1] * y[0];
+}
+__device__ __forceinline__ double ik_dot(const double* x, const double* y) { return (x[0] * y[0] + x[1] * y[1]) + x[2] * y[2]; }
+__device__ __forceinline__ void ik_matvec(const double* m, const double* x, double* out) {  // m: 3 x 3 row-major
+#pragma unroll
+  for (int r = 0; r < 3; ++r) out[r] = (m[r * 3] * x[0] + m[r * 3 + 1] * x[1]) + m[r * 3 + 2] * x[2];
+}
+__device__ __forceinline__ int ik_triangle(int i, int j) {  // the place of H[i][j], i <= j, in the upper triangle
+  return NJF_IK_H + i * NJF_MAX_ACTION_DIM - i * (i - 1) / 2 + (j - i);
+}
+
+__device__ __forceinline__ bool ik_entry_used(int e, int A) {  // does entry e belong to channels below A?
+  if (e < NJF_IK_G) return true;
+  if (e < NJF_IK_H) return e - NJF_IK_G < A;
+  int i = 0, rest = e - NJF_IK_H;
+  while (rest >= NJF_MAX_ACTION_DIM - i) rest -= NJF_MAX_ACTION_DIM - i, ++i;
+  return i + rest < A;  // (j = i + rest >= i)
+}
+
+// One workgroup per problem, thread p owns slot p (K <= 256).  An evaluation at a point u: every thread forms its link's motion
+// G (into LDS) and derivative twists (into the workspace), walks up its parents composing both, turns its part's moments into
+// its share of cost, g and H, and a butterfly plus the four wave partials in wave order add the shares.  Then the A x A system
+// of the robust solve's Levenberg-Marquardt rule, in double; the candidate is evaluated in full and kept if it lowers L.
+__global__ void __launch_bounds__(NJF_IK_THREADS) ik_solve_kernel(IkArgs a) {
+  __shared__ double G[NJF_FIELD_TWISTS_MAX_PARTS][12];
+  __shared__ double red[NJF_IK_THREADS / 64][NJF_IK_ENTRIES];
+  __shared__ double ev[NJF_IK_ENTRIES], cur[NJF_IK_ENTRIES];
+  __shared__ double hmat[NJF_MAX_ACTION_DIM][NJF_MAX_ACTION_DIM + 1];
+  __shared__ double grad[NJF_MAX_ACTION_DIM], lo[NJF_MAX_ACTION_DIM], hi[NJF_MAX_ACTION_DIM];
+  __shared__ float u[NJF_MAX_ACTION_DIM], cand[NJF_MAX_ACTION_DIM];
+  __shared__ int bits[NJF_FIELD_TWISTS_MAX_PARTS];
+  __shared__ int frozen[NJF_MAX_ACTION_DIM];
+  __shared__ double lam, objective, cost_now, cost_first;
+  __shared__ int take, stop, accepted;
+  const PoseArgs& s = a.pose;
+  const int m = blockIdx.x, tid = threadIdx.x, A = s.A, K = s.K;  // m < M
+  const double reg_a = a.reg / (double)A;
+  const int active = counted_length(s.parts_count, K);
+  int q0 = -1, j0 = -1;
+  double sign = 1.0;
+  if (tid < K) bits[tid] = pose_link_bits(s, tid, active, q0, j0, sign);
+  if (tid < A) {
+    const float l = a.lower ? a.lower[(size_t)m * A + tid] : -INFINITY, h = a.upper ? a.upper[(size_t)m * A + tid] : INFINITY;
+    lo[tid] = (double)l;
+    hi[tid] = (double)h;
+    u[tid] = fminf(fmaxf(a.init ? a.init[(size_t)m * A + tid] : 0.f, l), h);
+  }
+  if (tid == 0) {
+    lam = a.damping;
+    accepted = 0;
+  }
+  __syncthreads();
+  int part_state = 1, depth = 0;
+  if (tid < K) {
+    part_state = ik_walk_status(s.parent, bits, K, tid, depth);
+    if (m == 0) {
+      a.part_status[tid] = part_state;
+      a.depth[tid] = depth;
+    }
+  }
+  const bool linked = tid < K && bits[tid] == 0;  // the slot's link moves
+  const bool counted = tid < K && part_state == 0 && s.parts[tid] >= 0;
+  const bool hung = linked && q0 >= 0;  // (then j0 is a stored joint)
+  const double* ws = hung ? s.joint_omega + (size_t)j0 * A * 3 : s.omega + (size_t)tid * A * 3;
+  const double* vs = hung ? s.joint_velocity + (size_t)j0 * A * 3 : s.velocity + (size_t)tid * A * 3;
+  const double* cs = hung ? s.anchor + (size_t)j0 * 3 : s.centroid + (size_t)tid * 3;
+  // (W, U) of this problem's links and, after them, of its chains: [K][A][6].  A thread keeps its chain's twists here, not in
+  // registers, and reads them back itself
+  double* link_tw = a.link_twist + (size_t)m * 2 * K * A * 6;
+  double* chain_tw = link_tw + (size_t)K * A * 6;
+  const double* mom = a.moments + ((size_t)m * K + tid) * NJF_IK_MOMENTS;
+
+  for (int it = 0;; ++it) {
+    const float* pt = it == 0 ? u : cand;
+    // ---- the link: G = (R, t) as pose_links_kernel forms it, and its derivative twist (W, U) per channel --------------------
+    double T[12] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0};
+    if (linked) {
+      double w[3] = {0.0, 0.0, 0.0}, v[3] = {0.0, 0.0, 0.0};
+      for (int ch = 0; ch < A; ++ch) {
+        const double uc = (double)pt[ch];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          w[c] += uc * ws[ch * 3 + c];
+          v[c] += uc * vs[ch * 3 + c];
+        }
+      }
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        w[c] *= sign;
+        v[c] *= sign;
+      }
+      const double th2 = (w[0] * w[0] + w[1] * w[1]) + w[2] * w[2];
+      double ca, cb, cg;
+      if (th2 <= 1e-6) {
+        const double th4 = th2 * th2;
+        ca = (1.0 - th2 / 6.0) + th4 / 120.0;
+        cb = (0.5 - th2 / 24.0) + th4 / 720.0;
+        cg = (1.0 / 6.0 - th2 / 120.0) + th4 / 5040.0;
+      } else {
+        const double th = sqrt(th2), sn = sin(th), sh = sin(0.5 * th);
+        ca = sn / th;
+        cb = 2.0 * (sh * sh) / th2;
+        cg = (th - sn) / (th2 * th);
+      }
+      double b2, g2;  // db / dth2, dg / dth2: they only steer the iteration
+      if (th2 <= 1e-2) {
+        b2 = (((1.0 / 907200.0) * th2 - 1.0 / 13440.0) * th2 + 1.0 / 360.0) * th2 - 1.0 / 24.0;
+        g2 = (((1.0 / 9979200.0) * th2 - 1.0 / 120960.0) * th2 + 1.0 / 2520.0) * th2 - 1.0 / 120.0;
+      } else {
+        b2 = (ca - 2.0 * cb) / (2.0 * th2);
+        g2 = (cb - 3.0 * cg) / (2.0 * th2);
+      }
+      const double X[9] = {0.0, -w[2], w[1], w[2], 0.0, -w[0], -w[1], w[0], 0.0};
+      double V[9], D[9];  // V, and b2 [w]x + g2 [w]x^2
+#pragma unroll
+      for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          const double d = r == c ? 1.0 : 0.0;
+          const double X2 = w[r] * w[c] - d * th2;
+          T[r * 3 + c] = (d + ca * X[r * 3 + c]) + cb * X2;
+          V[r * 3 + c] = (d + cb * X[r * 3 + c]) + cg * X2;
+          D[r * 3 + c] = b2 * X[r * 3 + c] + g2 * X2;
+        }
+      double Vv[3], Dv[3], wxv[3];
+      ik_matvec(V, v, Vv);
+      ik_matvec(D, v, Dv);
+      ik_cross(w, v, wxv);
+      const double c3[3] = {cs[0], cs[1], cs[2]};
+      double base[3];  // c + V v
+#pragma unroll
+      for (int r = 0; r < 3; ++r) {
+        const double rc = (T[r * 3] * c3[0] + T[r * 3 + 1] * c3[1]) + T[r * 3 + 2] * c3[2];
+        T[9 + r] = (c3[r] - rc) + Vv[r];
+        base[r] = c3[r] + Vv[r];
+      }
+      for (int ch = 0; ch < A; ++ch) {
+        const double wd[3] = {sign * ws[ch * 3], sign * ws[ch * 3 + 1], sign * ws[ch * 3 + 2]};
+        const double vd[3] = {sign * vs[ch * 3], sign * vs[ch * 3 + 1], sign * vs[ch * 3 + 2]};
+        double W[3], Vvd[3], Wxb[3], wdxv[3], t1[3], t2[3];
+        ik_matvec(V, wd, W);
+        ik_matvec(V, vd, Vvd);
+        ik_cross(W, base, Wxb);
+        // dV v = 2 (w . w') (b2 [w]x + g2 [w]x^2) v + b w' x v + g (w' x (w x v) + w x (w' x v))
+        ik_cross(wd, v, wdxv);
+        ik_cross(wd, wxv, t1);
+        ik_cross(w, wdxv, t2);
+        const double ww = 2.0 * ik_dot(w, wd);
+        const size_t at = ((size_t)tid * A + ch) * 6;  // tid < K, ch < A
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          const double U = (Vvd[c] - Wxb[c]) + ((ww * Dv[c] + cb * wdxv[c]) + cg * (t1[c] + t2[c]));
+          link_tw[at + c] = chain_tw[at + c] = W[c];
+          link_tw[at + 3 + c] = chain_tw[at + 3 + c] = U;
+        }
+      }
+    } else if (tid < K) {  // a slot with a link bit does not move
+      for (int e = 0; e < A * 6; ++e) link_tw[(size_t)tid * A * 6 + e] = chain_tw[(size_t)tid * A * 6 + e] = 0.0;
+    }
+    if (tid < K) {
+#pragma unroll
+      for (int e = 0; e < 12; ++e) G[tid][e] = T[e];
+    }
+    __syncthreads();  // (G and the link twists of every slot are written)
+    // ---- the chain: S <- Ad_G(S) + S_q, then T <- G_q o T, up the parents ------------------------------------------------------
+    if (counted) {
+      int steps = 0;
+      int q = s.parent ? s.parent[tid] : -1;
+      while (q != -1) {
+        if (q < -1 || q >= K || steps >= K) break;  // (cannot happen at status 0; every index is checked all the same)
+        double g[12];  // q < K
+#pragma unroll
+        for (int e = 0; e < 12; ++e) g[e] = G[q][e];
+        for (int ch = 0; ch < A; ++ch) {
+          double* mine = chain_tw + ((size_t)tid * A + ch) * 6;
+          const double* theirs = link_tw + ((size_t)q * A + ch) * 6;
+          const double Wc[3] = {mine[0], mine[1], mine[2]}, Uc[3] = {mine[3], mine[4], mine[5]};
+          double W[3], RU[3], Wxt[3];
+          ik_matvec(g, Wc, W);
+          ik_matvec(g, Uc, RU);
+          ik_cross(W, g + 9, Wxt);
+#pragma unroll
+          for (int c = 0; c < 3; ++c) {
+            mine[c] = W[c] + theirs[c];
+            mine[3 + c] = (RU[c] - Wxt[c]) + theirs[3 + c];
+          }
+        }
+        double N[12];
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+#pragma unroll
+          for (int c = 0; c < 3; ++c) N[r * 3 + c] = (g[r * 3] * T[c] + g[r * 3 + 1] * T[3 + c]) + g[r * 3 + 2] * T[6 + c];
+          N[9 + r] = ((g[r * 3] * T[9] + g[r * 3 + 1] * T[10]) + g[r * 3 + 2] * T[11]) + g[9 + r];
+        }
+#pragma unroll
+        for (int e = 0; e < 12; ++e) T[e] = N[e];
+        ++steps;
+        q = s.parent[q];
+      }
+    }
+    // ---- the part's share of cost, W, g and H from its moments, each added over the workgroup as it is formed -------------------------
+    {
+      const int lane = tid & 63, wave = tid >> 6;
+      auto add = [&](int e, double share) {  // (called under conditions that are the same in every thread)
+        const double v = twist_wave_sum(counted ? share : 0.0);
+        if (lane == 0) red[wave][e] = v;
+      };
+      double mo[NJF_IK_MOMENTS];
+#pragma unroll
+      for (int k = 0; k < NJF_IK_MOMENTS; ++k) mo[k] = counted ? mom[k] : 0.0;
+      const double s0 = mo[0];
+      const double* s1 = mo + 1;
+      const double* t1 = mo + 10;
+      const double* C = mo + 13;
+      const double S2[9] = {mo[4], mo[5], mo[6], mo[5], mo[7], mo[8], mo[6], mo[8], mo[9]};
+      const double* cp = s.centroid + (size_t)(tid < K ? tid : 0) * 3;
+      const double c3[3] = {cp[0], cp[1], cp[2]};
+      double d[3], dt[3], rs1[3], k1[3];
+      ik_matvec(T, c3, d);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        d[c] += T[9 + c];
+        dt[c] = d[c] - c3[c];
+      }
+      ik_matvec(T, s1, rs1);
+      // M = R S2 R^T (symmetric), N = R C^T
+      double RS[9], Mx[9], Nx[9];
+#pragma unroll
+      for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) RS[r * 3 + c] = (T[r * 3] * S2[c] + T[r * 3 + 1] * S2[3 + c]) + T[r * 3 + 2] * S2[6 + c];
+#pragma unroll
+      for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          Mx[r * 3 + c] = (RS[r * 3] * T[c * 3] + RS[r * 3 + 1] * T[c * 3 + 1]) + RS[r * 3 + 2] * T[c * 3 + 2];
+          Nx[r * 3 + c] = (T[r * 3] * C[c * 3] + T[r * 3 + 1] * C[c * 3 + 1]) + T[r * 3 + 2] * C[c * 3 + 2];
+        }
+      const double trS = (mo[4] + mo[7]) + mo[9], trM = (Mx[0] + Mx[4]) + Mx[8], trN = (Nx[0] + Nx[4]) + Nx[8];
+      const double axial[3] = {Nx[5] - Nx[7], Nx[6] - Nx[2], Nx[1] - Nx[3]};  // tr([W]x N) = W . axial
+      add(0, ((trS + 2.0 * ik_dot(dt, rs1)) + s0 * ik_dot(dt, dt)) - 2.0 * trN - 2.0 * ik_dot(dt, t1) + mo[22]);
+      add(1, s0);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) k1[c] = (rs1[c] + s0 * dt[c]) - t1[c];
+      // beta_a = W_a x d + U_a; q_a = W_a x R s1.  tr(A_a S2 R^T) = tr([W_a]x M) is 0: M is symmetric
+      const double* mine = chain_tw + (size_t)(tid < K ? tid : 0) * A * 6;
+      auto twist = [&](int ch, double* W, double* beta) {  // ch < A
+        double Wxd[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) W[c] = counted ? mine[ch * 6 + c] : 0.0;
+        ik_cross(W, d, Wxd);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) beta[c] = Wxd[c] + (counted ? mine[ch * 6 + 3 + c] : 0.0);
+      };
+      for (int i = 0; i < A; ++i) {
+        double Wi[3], bi[3], qi[3], MW[3];
+        twist(i, Wi, bi);
+        ik_cross(Wi, rs1, qi);
+        ik_matvec(Mx, Wi, MW);
+        add(NJF_IK_G + i, (ik_dot(qi, dt) - ik_dot(Wi, axial)) + ik_dot(bi, k1));
+        for (int j = i; j < A; ++j) {
+          double Wj[3], bj[3], qj[3];
+          twist(j, Wj, bj);
+          ik_cross(Wj, rs1, qj);
+          add(ik_triangle(i, j), ((ik_dot(Wi, Wj) * trM - ik_dot(Wj, MW)) + (ik_dot(bi, qj) + ik_dot(bj, qi))) + s0 * ik_dot(bi, bj));
+        }
+      }
+    }
+    __syncthreads();
+    if (tid < NJF_IK_ENTRIES)  // (the entries of channels past A were not formed: they stay 0 and are never read)
+      ev[tid] = ik_entry_used(tid, A) ? ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid] : 0.0;
+    __syncthreads();
+    // ---- accept or reject ---------------------------------------------------------------------------------------------------------
+    if (tid == 0) {
+      const double W = ev[1];
+      double c = W > 0.0 ? ev[0] / W : 0.0;
+      c = c < 0.0 ? 0.0 : c;  // (the expansion can land a few 1e-16 E below zero; a NaN stays)
+      double sq = 0.0;
+      for (int k = 0; k < A; ++k) sq += (double)pt[k] * (double)pt[k];
+      const double obj = c + reg_a * sq;
+      if (it == 0) {
+        stop = !(W > 0.0) ? NJF_FIELD_COMMANDS_NO_ROWS : (isfinite(obj) ? 0 : NJF_FIELD_COMMANDS_NOT_FINITE);
+        cost_first = c;
+        take = 1;
+      } else {
+        take = obj < objective;  // (a NaN rejects)
+        accepted += take;
+        lam = fmin(fmax(take ? lam / 3.0 : lam * 4.0, 1e-9), 1e9);
+      }
+      if (take) {
+        objective = obj;
+        cost_now = c;
+      }
+    }
+    __syncthreads();
+    if (take) {
+      if (it > 0 && tid < A) u[tid] = cand[tid];
+      if (tid < NJF_IK_ENTRIES) cur[tid] = ev[1] > 0.0 ? ev[tid] / ev[1] : 0.0;  // (cur[1] is not used)
+    }
+    __syncthreads();
+    if (it >= a.iterations || stop) break;  // (uniform)
+    // ---- the damped system: frozen coordinates, Gauss-Jordan, the clamped candidate on the fp32 lattice ------------------------------
+    if (tid < A) {
+      const double gi = cur[NJF_IK_G + tid] + reg_a * (double)u[tid];
+      grad[tid] = gi;
+      frozen[tid] = ((double)u[tid] <= lo[tid] && gi > 0.0) || ((double)u[tid] >= hi[tid] && gi < 0.0);
+    }
+    __syncthreads();
+    const int entries = A * (A + 1);  // <= 110
+    if (tid < entries) {
+      const int i = tid / (A + 1), j = tid % (A + 1);
+      double v;
+      if (j == A)
+        v = frozen[i] ? 0.0 : grad[i];
+      else if (frozen[i] || frozen[j])
+        v = i == j ? 1.0 : 0.0;
+      else
+        v = cur[ik_triangle(min(i, j), max(i, j))] + (i == j ? reg_a : 0.0);
+      if (i == j) v += lam * fmax(v, 1e-12);
+      hmat[i][j] = v;
+    }
+    __syncthreads();
+    for (int p = 0; p < A; ++p) {
+      double nv = 0.0;
+      if (tid < entries) {
+        const int i = tid / (A + 1), j = tid % (A + 1);
+        const double pj = hmat[p][j] * (1.0 / hmat[p][p]);
+        nv = i == p ? pj : hmat[i][j] - hmat[i][p] * pj;
+      }
+      __syncthreads();
+      if (tid < entries) hmat[tid / (A + 1)][tid % (A + 1)] = nv;
+      __syncthreads();
+    }
+    if (tid < A) cand[tid] = (float)fmin(fmax((double)u[tid] - hmat[tid][A], lo[tid]), hi[tid]);
+    __syncthreads();
+  }
+  if (tid < A) {
+    a.commands[(size_t)m * A + tid] = u[tid];
+    a.gradient[(size_t)m * A + tid] = cur[NJF_IK_G + tid] + reg_a * (double)u[tid];
+  }
+  if (tid == 0) {
+    a.status[m] = stop;
+    a.weight[m] = ev[1];
+    a.initial_cost[m] = cost_first;
+    a.cost[m] = cost_now;
+    a.steps[m] = accepted;
   }
 }
 
@@ -6188,6 +6689,104 @@ extern "C" int njf_field_pose(const int* parts, const int* parts_count, int num_
     else if (staged) pose_points_kernel<true, false><<<grid, NJF_POSE_THREADS, 0, s>>>(a);
     else if (wide) pose_points_kernel<false, true><<<grid, NJF_POSE_THREADS, 0, s>>>(a);
     else pose_points_kernel<false, false><<<grid, NJF_POSE_THREADS, 0, s>>>(a);
+    if ((rc = launch_status())) return rc;
+  }
+  return NJF_OK;
+}
+
+extern "C" int njf_field_commands(const int* parts, const int* parts_count, int num_parts, const int* part_status,
+                                  const double* centroid, const double* omega, const double* velocity, int action_dim,
+                                  const int* part_a, const int* part_b, const int* joints_count, int max_joints,
+                                  const double* anchor, const double* joint_omega, const double* joint_velocity, const int* parent,
+                                  const int* joint_of, const float* xyz, const int* labels, const int* count, int n,
+                                  const float* targets, int num_problems, const float* weights, int weights_per_problem,
+                                  const float* init, const float* lower, const float* upper, double reg, int iterations,
+                                  double damping, float* commands, double* cost, double* initial_cost, double* weight, int* steps,
+                                  double* gradient, int* status, int* out_part_status, int* depth, double* moments,
+                                  double* workspace, long long workspace_doubles, int phases, void* stream) {
+  if (num_parts < 1 || num_parts > NJF_FIELD_TWISTS_MAX_PARTS) return NJF_E_VALUE;
+  if (action_dim < 1 || action_dim > NJF_MAX_ACTION_DIM) return NJF_E_VALUE;
+  if (num_problems < 1 || num_problems > NJF_FIELD_POSE_MAX_COMMANDS) return NJF_E_VALUE;
+  const bool tree = part_a || part_b || joints_count || anchor || joint_omega || joint_velocity || parent || joint_of;
+  if (tree && (max_joints < 1 || max_joints > NJF_FIELD_JOINTS_MAX)) return NJF_E_VALUE;
+  if (phases < 1 || phases > NJF_FIELD_COMMANDS_ALL) return NJF_E_VALUE;
+  if (iterations < 0 || iterations > NJF_FIELD_COMMANDS_MAX_ITERATIONS) return NJF_E_VALUE;
+  if (!(damping > 0.0) || !(reg >= 0.0) || weights_per_problem < 0 || weights_per_problem > 1) return NJF_E_VALUE;
+  if (n < 0) return NJF_E_SHAPE;
+  if (workspace_doubles < NJF_FIELD_COMMANDS_WORKSPACE(num_problems, num_parts, action_dim, n)) return NJF_E_SHAPE;
+  if (!parts || !part_status || !centroid || !omega || !velocity || !moments || !out_part_status || !depth || !workspace)
+    return NJF_E_NULL;
+  if (tree && (!part_a || !part_b || !anchor || !joint_omega || !joint_velocity || !parent || !joint_of)) return NJF_E_NULL;
+  const bool sums = phases & NJF_FIELD_COMMANDS_MOMENTS, solve = phases & NJF_FIELD_COMMANDS_SOLVE;
+  if (sums && n > 0 && (!xyz || !labels || !targets)) return NJF_E_NULL;
+  if (solve && (!commands || !cost || !initial_cost || !weight || !steps || !gradient || !status)) return NJF_E_NULL;
+  IkArgs a;
+  PoseArgs& p = a.pose;
+  p.parts = parts;
+  p.parts_count = parts_count;
+  p.K = num_parts;
+  p.A = action_dim;
+  p.J = tree ? max_joints : 0;
+  p.M = num_problems;
+  p.part_status = part_status;
+  p.centroid = centroid;
+  p.omega = omega;
+  p.velocity = velocity;
+  p.part_a = part_a;
+  p.part_b = part_b;
+  p.joints_count = joints_count;
+  p.anchor = anchor;
+  p.joint_omega = joint_omega;
+  p.joint_velocity = joint_velocity;
+  p.parent = parent;
+  p.joint_of = joint_of;
+  p.commands = nullptr;
+  p.link = nullptr;
+  p.link_bits = nullptr;
+  p.rotation = p.translation = nullptr;
+  p.status = p.depth = nullptr;
+  p.xyz = xyz;
+  p.labels = labels;
+  p.count = count;
+  p.n = n;
+  p.jacobian = nullptr;
+  p.posed = nullptr;
+  a.targets = targets;
+  a.weights = weights;
+  a.weight_stride = weights_per_problem ? n : 0;
+  a.init = init;
+  a.lower = lower;
+  a.upper = upper;
+  a.reg = reg;
+  a.damping = damping;
+  a.iterations = iterations;
+  a.chunks = (int)(((long long)n + NJF_FIELD_TWISTS_CHUNK - 1) / NJF_FIELD_TWISTS_CHUNK);
+  a.partial = workspace;
+  a.link_twist = workspace + (size_t)NJF_IK_MOMENTS * a.chunks * num_problems * num_parts;  // [M][2][K][A][6]
+  a.moments = moments;
+  a.commands = commands;
+  a.cost = cost;
+  a.initial_cost = initial_cost;
+  a.weight = weight;
+  a.gradient = gradient;
+  a.steps = steps;
+  a.status = status;
+  a.part_status = out_part_status;
+  a.depth = depth;
+  hipStream_t s = (hipStream_t)stream;
+  int rc;
+  if (sums) {
+    if (n > 0) {  // chunks <= 2^31 / 4096, K <= 256, tiles <= 4096
+      const dim3 grid((unsigned)a.chunks, (unsigned)num_parts, (unsigned)((num_problems + NJF_IK_PROBLEM_TILE - 1) / NJF_IK_PROBLEM_TILE));
+      ik_moments_kernel<<<grid, NJF_IK_THREADS, 0, s>>>(a);
+      if ((rc = launch_status())) return rc;
+    }
+    const dim3 grid((unsigned)num_parts, (unsigned)((num_problems + NJF_IK_FINISH_TILE - 1) / NJF_IK_FINISH_TILE));
+    ik_finish_kernel<<<grid, NJF_IK_THREADS, 0, s>>>(a);
+    if ((rc = launch_status())) return rc;
+  }
+  if (solve) {
+    ik_solve_kernel<<<num_problems, NJF_IK_THREADS, 0, s>>>(a);
     if ((rc = launch_status())) return rc;
   }
   return NJF_OK;

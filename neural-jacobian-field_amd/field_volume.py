@@ -765,9 +765,8 @@ def _check_points(name: str, xyz, labels, jacobian, a_dim: int) -> int:
     return n
 
 
-def _pose(name: str, twists, commands, joints, tree, points=None):
-    """The argument checks (under the caller's ``name``) and the launches of part_poses / cloud_pose.  ``points``: None or
-    ``(xyz, labels, count, jacobian)``; then the result is ``(FieldPose, posed)``."""
+def _check_twists(name: str, twists):
+    """The checks of a FieldTwists that the pose and the inverse kinematics share; ``(K, A)``."""
     if not isinstance(twists, FieldTwists):
         raise ValueError(f"{name}: twists must be a FieldTwists")
     parts = twists.labels
@@ -786,15 +785,16 @@ def _pose(name: str, twists, commands, joints, tree, points=None):
                                   ("centroid", twists.centroid, torch.float64, (k, 3)), ("status", twists.status, torch.int32, (k,))):
         if not torch.is_tensor(t) or t.dtype != dtype or tuple(t.shape) != shape:
             raise ValueError(f"{name}: twists.{what} must be {str(dtype).replace('torch.', '')} {list(shape)}")
-    if not torch.is_tensor(commands) or commands.dtype != torch.float32 or commands.dim() != 2 or commands.shape[1] != a_dim:
-        raise ValueError(f"{name}: commands must be fp32 [M, {a_dim}]")
-    m = commands.shape[0]
-    if not 1 <= m <= hip.FIELD_POSE_MAX_COMMANDS:
-        raise ValueError(f"{name}: 1 to {hip.FIELD_POSE_MAX_COMMANDS} commands (got {m})")
+    return k, a_dim
+
+
+def _check_links(name: str, twists, joints, tree, k: int, a_dim: int, like: torch.Tensor):
+    """The checks of the joints and the tree; ``(parts_count, same, links)``: the twists' count, the (name, tensor) pairs that
+    must share a device, and the joints dict of hip.field_pose (None without joints)."""
     if (joints is None) != (tree is None):
         raise ValueError(f"{name}: joints and tree come together or not at all")
-    parts_count = _one_int32(name, "twists.count", twists.count, commands)
-    same = [("twists.labels", parts), ("twists.omega", omega), ("twists.velocity", twists.velocity),
+    parts_count = _one_int32(name, "twists.count", twists.count, like)
+    same = [("twists.labels", twists.labels), ("twists.omega", twists.omega), ("twists.velocity", twists.velocity),
             ("twists.centroid", twists.centroid), ("twists.status", twists.status)]
     links = None
     if joints is not None:
@@ -815,13 +815,27 @@ def _pose(name: str, twists, commands, joints, tree, points=None):
         for what, t in zip(("parent", "joint_of"), tree):
             if not torch.is_tensor(t) or t.dtype != torch.int32 or tuple(t.shape) != (k,):
                 raise ValueError(f"{name}: tree {what} must be int32 [{k}] (FieldJoints.tree(), not parents())")
-        joints_count = _one_int32(name, "joints.count", joints.count, commands)
+        joints_count = _one_int32(name, "joints.count", joints.count, like)
         same += [("joints.part_a", joints.part_a), ("joints.part_b", joints.part_b), ("joints.anchor", joints.anchor),
                  ("joints.omega", joints.omega), ("joints.velocity", joints.velocity), ("tree parent", tree[0]),
                  ("tree joint_of", tree[1])]
         links = dict(part_a=joints.part_a.contiguous(), part_b=joints.part_b.contiguous(), count=joints_count,
                      anchor=joints.anchor.contiguous(), omega=joints.omega.contiguous(), velocity=joints.velocity.contiguous(),
                      parent=tree[0].contiguous(), joint_of=tree[1].contiguous())
+    return parts_count, same, links
+
+
+def _pose(name: str, twists, commands, joints, tree, points=None):
+    """The argument checks (under the caller's ``name``) and the launches of part_poses / cloud_pose.  ``points``: None or
+    ``(xyz, labels, count, jacobian)``; then the result is ``(FieldPose, posed)``."""
+    k, a_dim = _check_twists(name, twists)
+    parts, omega = twists.labels, twists.omega
+    if not torch.is_tensor(commands) or commands.dtype != torch.float32 or commands.dim() != 2 or commands.shape[1] != a_dim:
+        raise ValueError(f"{name}: commands must be fp32 [M, {a_dim}]")
+    m = commands.shape[0]
+    if not 1 <= m <= hip.FIELD_POSE_MAX_COMMANDS:
+        raise ValueError(f"{name}: 1 to {hip.FIELD_POSE_MAX_COMMANDS} commands (got {m})")
+    parts_count, same, links = _check_links(name, twists, joints, tree, k, a_dim, commands)
     n = 0
     if points is not None:
         xyz, labels, count, jacobian = points
@@ -870,6 +884,125 @@ def cloud_pose(cloud: FieldPointCloud, labels: torch.Tensor, twists: FieldTwists
         raise ValueError("cloud_pose: cloud must be a FieldPointCloud")
     jacobian = cloud.jacobian if first_order_elsewhere else None
     return _pose("cloud_pose", twists, commands, joints, tree, points=(cloud.xyz, labels, cloud.count, jacobian))
+
+
+# ---- inverse kinematics on the part tree: commands from 3-D point targets ------------------------------------
+@dataclass
+class FieldCommands:
+    """The commands that bring labelled points to 3-D targets (``solve_commands``; include/njf_hip.h: njf_field_commands), one
+    per problem: ``commands[m]`` minimises the weighted mean squared distance between the points under the finite pose of
+    ``part_poses`` and ``targets[m]``, plus ``(reg / A) |u|^2``, inside the box.  ``commands`` is the iterate itself, on the
+    fp32 lattice: ``part_poses(twists, fit.commands, ...)`` reproduces the pose whose ``cost`` is reported.  ``status`` 0 or
+    bits: 1 = the problem has no counted row (``commands`` = the clamped init, cost 0), 2 = the starting objective is not
+    finite (``commands`` = the clamped init).  ``part_status`` and ``depth`` are those of ``part_poses``; a part whose status is
+    not 0 is not in the objective.  ``moments`` are the 23 weighted moments of (point, target) per problem and part about
+    the part's centroid: s0, s1 [3], S2 [6], t1 [3], C [9], e -- all the solver reads of the rows."""
+
+    commands: torch.Tensor       # [M, A] fp32
+    cost: torch.Tensor           # [M] float64: the mean squared distance at commands
+    initial_cost: torch.Tensor   # [M] float64: the mean squared distance at the start
+    weight: torch.Tensor         # [M] float64: W_m, the sum of the counted rows' weights
+    steps: torch.Tensor          # [M] int32: accepted steps
+    gradient: torch.Tensor       # [M, A] float64: the half-gradient with the regulariser at commands
+    status: torch.Tensor         # [M] int32
+    part_status: torch.Tensor    # [K] int32
+    depth: torch.Tensor          # [K] int32
+    moments: torch.Tensor        # [M, K, 23] float64
+
+    def rms(self) -> torch.Tensor:
+        """``[M]`` float64: the root of the weighted mean squared distance at ``commands``."""
+        return self.cost.sqrt()
+
+
+def _box(name: str, what: str, v, m: int, a_dim: int, like: torch.Tensor):
+    """``[M, A]`` fp32 on the device from None, a Python number, or an fp32 tensor ``[A]`` or ``[M, A]``."""
+    if v is None:
+        return None
+    if isinstance(v, (int, float)) and not isinstance(v, bool):
+        return torch.full((m, a_dim), float(v), dtype=torch.float32, device=like.device)
+    if not torch.is_tensor(v) or v.dtype != torch.float32 or tuple(v.shape) not in ((a_dim,), (m, a_dim)):
+        raise ValueError(f"{name}: {what} must be fp32 [{a_dim}] or [{m}, {a_dim}]")
+    if v.device != like.device:
+        raise ValueError(f"{name}: {what} must live on the device of targets")
+    return v.expand(m, a_dim).contiguous()
+
+
+def solve_commands(twists: FieldTwists, xyz: torch.Tensor, labels: torch.Tensor, targets: torch.Tensor, *,
+                   joints: Optional[FieldJoints] = None, tree=None, weights: Optional[torch.Tensor] = None,
+                   count: Optional[torch.Tensor] = None, init: Optional[torch.Tensor] = None, lower=None, upper=None,
+                   reg: float = 0.0, iterations: int = 20, damping: float = 1e-3) -> FieldCommands:
+    """Inverse kinematics on the part tree: for each of the M target sets ``targets`` ``[M, n, 3]`` (fp32)
+    of the points ``xyz`` ``[n, 3]`` (fp32) with part labels ``labels`` ``[n]`` (int32), the command whose finite pose --
+    ``part_poses`` with the same ``twists``, ``joints`` and ``tree`` -- brings the points to their targets in the weighted
+    least-squares sense.  A row counts when it lies below ``count`` (int32 device tensor; None = n), its label is a part of
+    pose status 0, its weight (``weights`` fp32 ``[n]`` or ``[M, n]``; None = 1) is finite and positive and its target is finite:
+    a NaN target leaves a row unconstrained.  ``init`` ``[M, A]`` (fp32; None = zeros) starts the iteration, ``lower`` and
+    ``upper`` (a number, fp32 ``[A]`` or ``[M, A]``) box it, ``reg`` weighs ``|u|^2 / A``.  One pass over the rows forms 23 moments
+    per problem and part; the ``iterations`` Levenberg-Marquardt rounds that follow never look at a row again.  In double,
+    without atomics or a host read: equal bytes from call to call, capturable."""
+    name = "solve_commands"
+    k, a_dim = _check_twists(name, twists)
+    n = _check_points(name, xyz, labels, None, a_dim)
+    if not torch.is_tensor(targets) or targets.dtype != torch.float32 or targets.dim() != 3 or tuple(targets.shape[1:]) != (n, 3):
+        raise ValueError(f"{name}: targets must be fp32 [M, {n}, 3]")
+    m = targets.shape[0]
+    if not 1 <= m <= hip.FIELD_POSE_MAX_COMMANDS:
+        raise ValueError(f"{name}: 1 to {hip.FIELD_POSE_MAX_COMMANDS} target sets (got {m})")
+    if weights is not None and (not torch.is_tensor(weights) or weights.dtype != torch.float32
+                                or tuple(weights.shape) not in ((n,), (m, n))):
+        raise ValueError(f"{name}: weights must be fp32 [{n}] or [{m}, {n}]")
+    if init is not None and (not torch.is_tensor(init) or init.dtype != torch.float32 or tuple(init.shape) != (m, a_dim)):
+        raise ValueError(f"{name}: init must be fp32 [{m}, {a_dim}]")
+    for what, v in (("reg", reg), ("damping", damping)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)):
+            raise ValueError(f"{name}: {what} must be a number")
+    if not reg >= 0.0:
+        raise ValueError(f"{name}: reg must be >= 0 (got {reg})")
+    if not damping > 0.0:
+        raise ValueError(f"{name}: damping must be > 0 (got {damping})")
+    if isinstance(iterations, bool) or not isinstance(iterations, int) or not 0 <= iterations <= hip.FIELD_COMMANDS_MAX_ITERATIONS:
+        raise ValueError(f"{name}: iterations must be an integer in [0, {hip.FIELD_COMMANDS_MAX_ITERATIONS}] (got {iterations})")
+    number = lambda v: isinstance(v, (int, float)) and not isinstance(v, bool)   # noqa: E731
+    if number(lower) and number(upper) and lower > upper:
+        raise ValueError(f"{name}: lower > upper ({lower} > {upper})")
+    lower, upper = _box(name, "lower", lower, m, a_dim, targets), _box(name, "upper", upper, m, a_dim, targets)
+    parts_count, same, links = _check_links(name, twists, joints, tree, k, a_dim, targets)
+    count = _one_int32(name, "count", count, targets)
+    same += [("xyz", xyz), ("labels", labels)] + [(what, t) for what, t in (("weights", weights), ("init", init)) if t is not None]
+    for what, t in same:
+        if t.device != targets.device:
+            raise ValueError(f"{name}: {what} must live on the device of targets")
+    if targets.device.type != "cuda":
+        raise ValueError(f"{name}: the tensors must live on the GPU; there is no CPU path")
+    dev = targets.device
+    i32, f64 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.float64, device=dev)
+    fit = FieldCommands(commands=torch.empty(m, a_dim, dtype=torch.float32, device=dev), cost=torch.empty(m, **f64),
+                        initial_cost=torch.empty(m, **f64), weight=torch.empty(m, **f64), steps=torch.empty(m, **i32),
+                        gradient=torch.empty(m, a_dim, **f64), status=torch.empty(m, **i32), part_status=torch.empty(k, **i32),
+                        depth=torch.empty(k, **i32), moments=torch.empty(m, k, hip.FIELD_COMMANDS_MOMENTS_PER_PART, **f64))
+    points = dict(xyz=xyz.contiguous(), labels=labels.contiguous(), count=count, targets=targets.contiguous())
+    hip.field_commands(twists.labels.contiguous(), twists.status.contiguous(), twists.centroid.contiguous(),
+                       twists.omega.contiguous(), twists.velocity.contiguous(), points, {f: getattr(fit, f) for f in fit.__dataclass_fields__},
+                       parts_count=parts_count, joints=links, weights=None if weights is None else weights.contiguous(),
+                       init=None if init is None else init.contiguous(), lower=lower, upper=upper, reg=reg,
+                       iterations=iterations, damping=damping)
+    return fit
+
+
+def cloud_commands(cloud: FieldPointCloud, labels: torch.Tensor, twists: FieldTwists, targets: torch.Tensor, *,
+                   joints: Optional[FieldJoints] = None, tree=None, weights: Optional[torch.Tensor] = None,
+                   init: Optional[torch.Tensor] = None, lower=None, upper=None, reg: float = 0.0, iterations: int = 20,
+                   damping: float = 1e-3) -> FieldCommands:
+    """``solve_commands`` on the rows of an extracted cloud: ``cloud.xyz`` and ``cloud.count`` with ``labels`` ``[n]`` int32, the
+    per-row result of ``cloud_components`` -- the inverse of ``cloud_pose``: targets ``[M, n, 3]`` for the cloud's rows in,
+    commands out."""
+    if not isinstance(cloud, FieldPointCloud):
+        raise ValueError("cloud_commands: cloud must be a FieldPointCloud")
+    try:
+        return solve_commands(twists, cloud.xyz, labels, targets, joints=joints, tree=tree, weights=weights, count=cloud.count,
+                              init=init, lower=lower, upper=upper, reg=reg, iterations=iterations, damping=damping)
+    except ValueError as err:
+        raise ValueError(str(err).replace("solve_commands:", "cloud_commands:", 1)) from None
 
 
 # ---- coarse-to-fine band (DESIGN.md section 14) ----------------------------------------------------------------------------------
