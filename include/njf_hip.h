@@ -767,6 +767,60 @@ int njf_field_commands(const int* parts, const int* parts_count, int num_parts, 
                        int* steps, double* gradient, int* status, int* out_part_status, int* depth, double* moments,
                        double* workspace, long long workspace_doubles, int phases, void* stream);
 
+/* ---- closest points of an unlabelled cloud against a cell list (ABI v20, additive) -------------------------
+ * For each of M problems and each row of a set of query points, the closest valid point of an observed cloud: the
+ * correspondence step between the posed rows of a body and an observation of it (njf_field_commands takes `matched` as its
+ * targets unchanged).  The result is the exact brute-force arg-min of the fp32 expression below; the cell list changes only
+ * the cost.
+ * Inputs, all on the device: observed [Mo,T,3] float; observed_count int32 [Mo] or NULL (= T); queries [Mq,n,3] float; count
+ * int32 [1] or NULL (= n); labels int32 [n] or NULL.  Mo and Mq are each 1 or M: with Mo = 1 every problem searches the same
+ * cloud, and its cell list is built once.  `cells`: the lattice -- origin = its lower corner, the three steps equal to one
+ * cell > 0, dims = cells per axis.
+ * VALID POINT j of problem m: j < min(observed_count[m], T) and three finite coordinates.
+ * SEARCHED ROW i: i < min(*count, n), three finite coordinates, and labels[i] >= 0 when labels are given.
+ * DISTANCE d2(q, p) = (dx*dx + dy*dy) + dz*dz in float, dx = q.x - p.x and so on, in exactly this order, no contraction.
+ * RESULT of a searched row: the valid point of the smallest d2, ties to the LOWEST j; accepted iff d2 <= (float)max_distance *
+ *        (float)max_distance, a float product.
+ * Outputs: index [M,n] int32 (-1 = none); distance2 [M,n] float (+inf = none); matched [M,n,3] float: the observed point itself,
+ *        bit for bit, or three NaNs (njf_field_commands' "this row is free"); found [M] int32: the accepted rows.  Every row i <
+ *        n is written; a row that is not searched -- rows from the count on included -- is not READ and gets -1 / +inf / NaN.
+ * CELLS  cell(p)_c = clamp(floor((p_c - origin_c) * (1 / cell)), 0, dims_c - 1) in float, for points and queries alike: what lies
+ *        outside the box lands in a boundary cell and is still found.  Cell (cx, cy, cz) has the index (cx*dy + cy)*dz + cz.
+ * BUILD  one memset and five launches: counts per (problem, cell) with integer atomics; an exclusive scan over the Mo * C
+ *        counts (sums of blocks of 1024, one workgroup over those sums, the cells of every block); a fill that writes each
+ *        valid point as one 16-byte record (x, y, z, j) at its cell's range.  The slot inside a range is taken with an integer
+ *        atomic: the order inside a cell, and with it the workspace bytes, may differ from run to run; the outputs may not --
+ *        the arg-min with its lowest-j tie-break does not depend on the visiting order.
+ * QUERY  one memset (found) and one launch, one lane per (m, i): Chebyshev rings r = 0, 1, ... of cells around the query's
+ *        cell (ring 0), clipped to the lattice; after ring r >= 1 the search stops when best_d2 < ((r - 1/128) * cell)^2 or (r -
+ *        1/128) * cell > max_distance (float), after any ring when no cell is left beyond it, and at the latest after ring
+ *        NJF_FIELD_NEAREST_MAX_RINGS -- which the second test reaches first for every max_distance the entry admits.  The
+ *        clamp is 1-Lipschitz per axis, so a point in a ring beyond r is at least r cells away up to the rounding of the
+ *        cell coordinate (< 2^-12 cells) and of d2 (~2^-22): the slack of cell / 128 covers both.  Every cell index is
+ *        checked against [0, Mo * C) and every range against [0, Mo * T) before use.
+ *        NJF_FIELD_NEAREST_WAVE: the same search with one wave per (m, i), the lanes sharing a range's records.
+ * workspace: NJF_FIELD_NEAREST_WORKSPACE(Mo, C, T) 32-bit words of the caller's, C = dims[0]*dims[1]*dims[2]: Mo (C + 1) starts,
+ * Mo C cursors, 4 Mo T record words and 3 words to bring the records to a 16-byte boundary.
+ * `phases`: NJF_FIELD_NEAREST_BUILD (reads observed, writes the workspace) | NJF_FIELD_NEAREST_QUERY (reads the workspace and
+ * the queries, writes the outputs) [| NJF_FIELD_NEAREST_WAVE]: build once, query many times.  One stream, no host read
+ * (capture-safe).
+ * Returns, before the first launch: NJF_E_VALUE for M outside [1, NJF_FIELD_POSE_MAX_COMMANDS], Mo or Mq not 1 or M, a dims[c]
+ * outside [1, NJF_FIELD_NEAREST_MAX_DIM], unequal, non-positive or non-finite steps (or 1 / cell not finite), a non-finite
+ * origin, max_distance not > 0 or not finite as a float, ceil(max_distance / cell) + 1 > NJF_FIELD_NEAREST_MAX_RINGS, Mo * C >=
+ * 2^31, or unknown phases; NJF_E_SHAPE for n < 0, T < 1, Mo * T >= 2^31 or a workspace that is too small; NJF_E_NULL for a
+ * missing pointer. */
+#define NJF_FIELD_NEAREST_MAX_RINGS 64
+#define NJF_FIELD_NEAREST_MAX_DIM 1024
+#define NJF_FIELD_NEAREST_WORKSPACE(Mo, C, T) ((long long)(Mo) * (2LL * (C) + 1LL + 4LL * (T)) + 3LL)
+#define NJF_FIELD_NEAREST_BUILD 1    /* phases */
+#define NJF_FIELD_NEAREST_QUERY 2
+#define NJF_FIELD_NEAREST_ALL 3
+#define NJF_FIELD_NEAREST_WAVE 4     /* with QUERY: a wave per query */
+int njf_field_nearest(const float* observed, const int* observed_count, int num_observed, int points, const float* queries,
+                      const int* count, const int* labels, int num_queries, int n, int num_problems, const NjfFieldGrid* cells,
+                      double max_distance, int* index, float* distance2, float* matched, int* found, int* workspace,
+                      long long workspace_words, int phases, void* stream);
+
 /* ---- stand-alone sampler / compositing ops (API parity with the un-fused reference calls) -- */
 /* RaySamples.get_weights (ray_samplers.py:77-101): deltas, densities [N,S] -> weights [N,S]. */
 int njf_alpha_weights(const float* deltas, const float* densities, int rays, int samples, float* weights, void* stream);

@@ -4483,6 +4483,236 @@ __global__ void __launch_bounds__(NJF_IK_THREADS) ik_solve_kernel(IkArgs a) {
   }
 }
 
+// ---- closest points against a cell list (njf_field_nearest) -------------------------------------------
+// The valid points of every observed cloud are sorted into the cells of a lattice -- counts per (problem, cell) with integer
+// atomics, an exclusive scan over the Mo * C counts in three launches (sums of blocks of 1024 counts, parked in the slot of
+// each block's first cell; one workgroup scans those sums; every block writes its cells' offsets and clears the counts), a
+// fill that writes each point as one 16-byte record (x, y, z, j) at its cell's range -- and a query walks the Chebyshev rings
+// around its own cell.  The order inside a cell depends on scheduling; the outputs do not: the arg-min of (d2, j) is the same
+// in any visiting order.  Cells along z are contiguous in the list, so a column of a ring is one range of records.
+#define NJF_NN_THREADS 256
+#define NJF_NN_SCAN_BLOCK 1024
+#define NJF_NN_SCAN_ITEMS (NJF_NN_SCAN_BLOCK / NJF_NN_THREADS)
+struct NnArgs {
+  const float* observed;      // [Mo,T,3]
+  const int* observed_count;  // [Mo] or null
+  const float* queries;       // [Mq,n,3]
+  const int* count;           // [1] or null
+  const int* labels;          // [n] or null
+  int Mo, Mq, M, T, n;
+  float origin[3];
+  float cell, inv_cell;
+  int dims[3];
+  int C;                      // cells per problem
+  long long L;                // Mo * C < 2^31
+  long long slots;            // Mo * T < 2^31
+  float max_distance, max_d2;
+  int* start;                 // [L + 1]: the first record of every (problem, cell), the total at the end
+  int* cursor;                // [L]: counts, then (after the scan) the fill's slot counters
+  int4* records;              // [slots]: (x, y, z as their bits, j)
+  int* index;                 // [M,n]
+  float* distance2;           // [M,n]
+  int* matched;               // [M,n,3] (the bits of the floats)
+  int* found;                 // [M]
+};
+
+__device__ __forceinline__ bool nn_finite(float x, float y, float z) {
+  return fabsf(x) < INFINITY && fabsf(y) < INFINITY && fabsf(z) < INFINITY;  // (NaN compares false)
+}
+
+__device__ __forceinline__ int nn_cell_axis(float p, float origin, float inv_cell, int dim) {
+  const float f = floorf((p - origin) * inv_cell);
+  return (int)fminf(fmaxf(f, 0.0f), (float)(dim - 1));  // dim <= 1024: exact
+}
+
+// FILL false: count the valid points per (problem, cell); true: write their records
+template <bool FILL>
+__global__ void __launch_bounds__(NJF_NN_THREADS) nn_points_kernel(NnArgs a) {
+  const long long e = (long long)blockIdx.x * NJF_NN_THREADS + threadIdx.x;
+  if (e >= a.slots) return;
+  const int mo = (int)(e / a.T), j = (int)(e % a.T);
+  if (j >= counted_length(a.observed_count ? a.observed_count + mo : nullptr, a.T)) return;
+  const float* p = a.observed + e * 3;
+  const float x = p[0], y = p[1], z = p[2];
+  if (!nn_finite(x, y, z)) return;
+  const int cx = nn_cell_axis(x, a.origin[0], a.inv_cell, a.dims[0]), cy = nn_cell_axis(y, a.origin[1], a.inv_cell, a.dims[1]),
+            cz = nn_cell_axis(z, a.origin[2], a.inv_cell, a.dims[2]);
+  const long long c = (long long)mo * a.C + ((long long)cx * a.dims[1] + cy) * a.dims[2] + cz;
+  if (c < 0 || c >= a.L) return;
+  if (!FILL) {
+    atomicAdd(&a.cursor[c], 1);
+  } else {
+    const long long s = (long long)a.start[c] + atomicAdd(&a.cursor[c], 1);
+    if (s >= 0 && s < a.slots) a.records[s] = make_int4(__float_as_int(x), __float_as_int(y), __float_as_int(z), j);
+  }
+}
+
+// workgroup b: the sum of the counts [b * 1024, (b + 1) * 1024) to start[b * 1024]
+__global__ void __launch_bounds__(NJF_NN_THREADS) nn_scan_sums_kernel(NnArgs a) {
+  __shared__ int wave_sum[NJF_NN_THREADS / 64];
+  const long long base = (long long)blockIdx.x * NJF_NN_SCAN_BLOCK + threadIdx.x * NJF_NN_SCAN_ITEMS;
+  int v = 0;
+#pragma unroll
+  for (int e = 0; e < NJF_NN_SCAN_ITEMS; ++e)
+    if (base + e < a.L) v += a.cursor[base + e];
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = v;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int s = 0;
+    for (int w = 0; w < NJF_NN_THREADS / 64; ++w) s += wave_sum[w];
+    a.start[(long long)blockIdx.x * NJF_NN_SCAN_BLOCK] = s;
+  }
+}
+
+// one workgroup: the block sums at start[b * 1024] -> their exclusive prefix sums in place, the total to start[L]
+// (select_scan_kernel's scheme on a strided array)
+__global__ void __launch_bounds__(NJF_NN_THREADS) nn_scan_blocks_kernel(NnArgs a, int blocks) {
+  __shared__ int part[NJF_NN_THREADS];
+  const int t = threadIdx.x;
+  const int per = (blocks + NJF_NN_THREADS - 1) / NJF_NN_THREADS;  // a contiguous run per thread
+  const int lo = min(t * per, blocks), hi = min(lo + per, blocks);
+  int s = 0;
+  for (int i = lo; i < hi; ++i) s += a.start[(long long)i * NJF_NN_SCAN_BLOCK];
+  part[t] = s;
+  __syncthreads();
+  if (t == 0) {
+    int run = 0;
+    for (int i = 0; i < NJF_NN_THREADS; ++i) {
+      const int c = part[i];
+      part[i] = run;
+      run += c;
+    }
+    a.start[a.L] = run;
+  }
+  __syncthreads();
+  int run = part[t];
+  for (int i = lo; i < hi; ++i) {
+    const int c = a.start[(long long)i * NJF_NN_SCAN_BLOCK];
+    a.start[(long long)i * NJF_NN_SCAN_BLOCK] = run;
+    run += c;
+  }
+}
+
+// workgroup b: start[c] for its 1024 cells from the block's offset and the counts, which are cleared for the fill
+__global__ void __launch_bounds__(NJF_NN_THREADS) nn_scan_cells_kernel(NnArgs a) {
+  __shared__ int wave_sum[NJF_NN_THREADS / 64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const long long base = (long long)blockIdx.x * NJF_NN_SCAN_BLOCK + threadIdx.x * NJF_NN_SCAN_ITEMS;
+  int c[NJF_NN_SCAN_ITEMS], mine = 0;
+#pragma unroll
+  for (int e = 0; e < NJF_NN_SCAN_ITEMS; ++e) {
+    c[e] = base + e < a.L ? a.cursor[base + e] : 0;
+    mine += c[e];
+  }
+  int incl = mine;
+  for (int o = 1; o < 64; o <<= 1) {
+    const int t = __shfl_up(incl, o, 64);
+    if (lane >= o) incl += t;
+  }
+  if (lane == 63) wave_sum[wave] = incl;
+  const int offset = a.start[(long long)blockIdx.x * NJF_NN_SCAN_BLOCK];  // (read by all before thread 0 overwrites it)
+  __syncthreads();
+  int run = offset + incl - mine;
+  for (int w = 0; w < wave; ++w) run += wave_sum[w];
+#pragma unroll
+  for (int e = 0; e < NJF_NN_SCAN_ITEMS; ++e)
+    if (base + e < a.L) {
+      a.start[base + e] = run;
+      a.cursor[base + e] = 0;
+      run += c[e];
+    }
+}
+
+struct NnBest {
+  float d2;
+  int j, x, y, z;  // the record's index and the bits of its coordinates
+};
+
+__device__ __forceinline__ void nn_take(NnBest& b, float d2, int j, int x, int y, int z) {
+  if (d2 < b.d2 || (d2 == b.d2 && j < b.j)) b = NnBest{d2, j, x, y, z};
+}
+
+// the records of the cells c0 .. c1 (one problem, consecutive along z) against the query
+template <bool WAVE>
+__device__ __forceinline__ void nn_visit(const NnArgs& a, long long c0, long long c1, int lane, float qx, float qy, float qz,
+                                         NnBest& b) {
+  if (c0 < 0 || c1 >= a.L || c0 > c1) return;
+  long long lo = a.start[c0], hi = a.start[c1 + 1];
+  lo = min(max(lo, 0LL), a.slots);
+  hi = min(min(max(hi, lo), a.slots), lo + a.T);
+  for (long long s = lo + (WAVE ? lane : 0); s < hi; s += WAVE ? 64 : 1) {
+    const int4 rec = a.records[s];
+    const float dx = qx - __int_as_float(rec.x), dy = qy - __int_as_float(rec.y), dz = qz - __int_as_float(rec.z);
+    nn_take(b, (dx * dx + dy * dy) + dz * dz, rec.w, rec.x, rec.y, rec.z);
+  }
+}
+
+// WAVE false: one lane per (problem, row); true: one wave per (problem, row), the lanes share a range's records and agree on
+// the best after every ring
+template <bool WAVE>
+__global__ void __launch_bounds__(NJF_NN_THREADS) nn_query_kernel(NnArgs a) {
+  const int lane = threadIdx.x & 63;
+  const int m = blockIdx.y;
+  const long long i = WAVE ? (long long)blockIdx.x * (NJF_NN_THREADS / 64) + (threadIdx.x >> 6)
+                           : (long long)blockIdx.x * NJF_NN_THREADS + threadIdx.x;
+  const bool live = i < a.n;
+  bool searched = live && i < counted_length(a.count, a.n);  // (rows from the count on are not read)
+  if (searched && a.labels) searched = a.labels[i] >= 0;
+  float qx = 0.f, qy = 0.f, qz = 0.f;
+  if (searched) {
+    const float* q = a.queries + ((long long)(a.Mq == 1 ? 0 : m) * a.n + i) * 3;
+    qx = q[0], qy = q[1], qz = q[2];
+    searched = nn_finite(qx, qy, qz);
+  }
+  NnBest b{INFINITY, 0x7fffffff, 0, 0, 0};
+  if (searched) {
+    const long long cells = (long long)(a.Mo == 1 ? 0 : m) * a.C;
+    const int dx = a.dims[0], dy = a.dims[1], dz = a.dims[2];
+    const int cx = nn_cell_axis(qx, a.origin[0], a.inv_cell, dx), cy = nn_cell_axis(qy, a.origin[1], a.inv_cell, dy),
+              cz = nn_cell_axis(qz, a.origin[2], a.inv_cell, dz);
+    // the centre cell and at most NJF_FIELD_NEAREST_MAX_RINGS rings: with ceil(max_distance / cell) + 1 <= MAX_RINGS the
+    // second test below ends the search by itself, after ring MAX_RINGS at the latest
+    for (int r = 0; r <= NJF_FIELD_NEAREST_MAX_RINGS; ++r) {
+      if (r >= 2) {  // rings 0 .. r - 1 are done: what is left is (r - 1) cells away or more, up to rounding
+        const float lim = ((float)(r - 1) - 0.0078125f) * a.cell;
+        if (b.d2 < lim * lim || lim > a.max_distance) break;
+      }
+      // no cell at this distance, nor at a larger one
+      if (cx - r < 0 && cx + r >= dx && cy - r < 0 && cy + r >= dy && cz - r < 0 && cz + r >= dz) break;
+      const int x0 = max(cx - r, 0), x1 = min(cx + r, dx - 1), y0 = max(cy - r, 0), y1 = min(cy + r, dy - 1);
+      const int z0 = max(cz - r, 0), z1 = min(cz + r, dz - 1);
+      for (int x = x0; x <= x1; ++x)
+        for (int y = y0; y <= y1; ++y) {
+          const long long column = cells + ((long long)x * dy + y) * dz;
+          if (x == cx - r || x == cx + r || y == cy - r || y == cy + r) {  // a face of the ring: the whole column
+            nn_visit<WAVE>(a, column + z0, column + z1, lane, qx, qy, qz, b);
+          } else {  // (r >= 1) inside: the two ends
+            if (cz - r >= 0) nn_visit<WAVE>(a, column + cz - r, column + cz - r, lane, qx, qy, qz, b);
+            if (cz + r < dz) nn_visit<WAVE>(a, column + cz + r, column + cz + r, lane, qx, qy, qz, b);
+          }
+        }
+      if (WAVE)
+        for (int o = 32; o > 0; o >>= 1)
+          nn_take(b, __shfl_xor(b.d2, o, 64), __shfl_xor(b.j, o, 64), __shfl_xor(b.x, o, 64), __shfl_xor(b.y, o, 64),
+                  __shfl_xor(b.z, o, 64));
+    }
+  }
+  const bool writer = live && (!WAVE || lane == 0);
+  const bool ok = writer && searched && b.j != 0x7fffffff && b.d2 <= a.max_d2;
+  if (writer) {
+    const long long row = (long long)m * a.n + i;
+    const int nan = 0x7fc00000;
+    a.index[row] = ok ? b.j : -1;
+    a.distance2[row] = ok ? b.d2 : INFINITY;
+    a.matched[row * 3] = ok ? b.x : nan;
+    a.matched[row * 3 + 1] = ok ? b.y : nan;
+    a.matched[row * 3 + 2] = ok ? b.z : nan;
+  }
+  const int accepted = __popcll(__ballot(ok));
+  if (lane == 0 && accepted) atomicAdd(&a.found[m], accepted);
+}
+
 // =============================================================================================
 // inverse dynamics: Levenberg-Marquardt on the linearised flow, one workgroup per batch element
 // =============================================================================================
@@ -6788,6 +7018,97 @@ extern "C" int njf_field_commands(const int* parts, const int* parts_count, int 
   if (solve) {
     ik_solve_kernel<<<num_problems, NJF_IK_THREADS, 0, s>>>(a);
     if ((rc = launch_status())) return rc;
+  }
+  return NJF_OK;
+}
+
+extern "C" int njf_field_nearest(const float* observed, const int* observed_count, int num_observed, int points,
+                                 const float* queries, const int* count, const int* labels, int num_queries, int n,
+                                 int num_problems, const NjfFieldGrid* cells, double max_distance, int* index, float* distance2,
+                                 float* matched, int* found, int* workspace, long long workspace_words, int phases,
+                                 void* stream) {
+  if (num_problems < 1 || num_problems > NJF_FIELD_POSE_MAX_COMMANDS) return NJF_E_VALUE;
+  if ((num_observed != 1 && num_observed != num_problems) || (num_queries != 1 && num_queries != num_problems)) return NJF_E_VALUE;
+  if (phases < 1 || phases > (NJF_FIELD_NEAREST_ALL | NJF_FIELD_NEAREST_WAVE) || !(phases & NJF_FIELD_NEAREST_ALL) ||
+      ((phases & NJF_FIELD_NEAREST_WAVE) && !(phases & NJF_FIELD_NEAREST_QUERY)))
+    return NJF_E_VALUE;
+  if (!cells) return NJF_E_NULL;
+  const float cell = cells->step[0], inv_cell = 1.0f / cell, reach = (float)max_distance;
+  if (!(cell > 0.0f) || cells->step[1] != cell || cells->step[2] != cell || !(inv_cell > 0.0f) || !(cell < INFINITY) ||
+      !(inv_cell < INFINITY))
+    return NJF_E_VALUE;
+  long long C = 1;
+  for (int c = 0; c < 3; ++c) {
+    if (cells->dims[c] < 1 || cells->dims[c] > NJF_FIELD_NEAREST_MAX_DIM) return NJF_E_VALUE;
+    if (!(fabsf(cells->origin[c]) < INFINITY)) return NJF_E_VALUE;
+    C *= cells->dims[c];
+  }
+  if (!(max_distance > 0.0) || !(reach > 0.0f) || !(reach < INFINITY)) return NJF_E_VALUE;
+  if (ceil((double)reach / (double)cell) + 1.0 > (double)NJF_FIELD_NEAREST_MAX_RINGS) return NJF_E_VALUE;
+  const long long L = (long long)num_observed * C;
+  if (L >= (1LL << 31)) return NJF_E_VALUE;
+  if (n < 0 || points < 1 || (long long)num_observed * points >= (1LL << 31)) return NJF_E_SHAPE;
+  if (workspace_words < NJF_FIELD_NEAREST_WORKSPACE(num_observed, C, points)) return NJF_E_SHAPE;
+  const bool build = phases & NJF_FIELD_NEAREST_BUILD, query = phases & NJF_FIELD_NEAREST_QUERY;
+  if (!workspace || (build && !observed) || (query && (!found || (n > 0 && (!queries || !index || !distance2 || !matched)))))
+    return NJF_E_NULL;
+  NnArgs a;
+  a.observed = observed;
+  a.observed_count = observed_count;
+  a.queries = queries;
+  a.count = count;
+  a.labels = labels;
+  a.Mo = num_observed;
+  a.Mq = num_queries;
+  a.M = num_problems;
+  a.T = points;
+  a.n = n;
+  for (int c = 0; c < 3; ++c) a.origin[c] = cells->origin[c], a.dims[c] = cells->dims[c];
+  a.cell = cell;
+  a.inv_cell = inv_cell;
+  a.C = (int)C;
+  a.L = L;
+  a.slots = (long long)num_observed * points;
+  a.max_distance = reach;
+  a.max_d2 = reach * reach;
+  a.start = workspace;                                   // Mo (C + 1) words hold the L + 1 starts
+  a.cursor = workspace + (long long)num_observed * (C + 1);
+  a.records = (int4*)(((uintptr_t)(a.cursor + L) + 15) & ~(uintptr_t)15);  // (the macro's 3 spare words)
+  a.index = index;
+  a.distance2 = distance2;
+  a.matched = (int*)matched;
+  a.found = found;
+  hipStream_t s = (hipStream_t)stream;
+  int rc;
+  if (build) {
+    const unsigned per_point = (unsigned)((a.slots + NJF_NN_THREADS - 1) / NJF_NN_THREADS);  // < 2^23
+    const int blocks = (int)((L + NJF_NN_SCAN_BLOCK - 1) / NJF_NN_SCAN_BLOCK);              // <= 2^21
+    hipError_t e = hipMemsetAsync(a.cursor, 0, (size_t)L * sizeof(int), s);
+    if (e != hipSuccess) return (int)e;
+    nn_points_kernel<false><<<per_point, NJF_NN_THREADS, 0, s>>>(a);
+    if ((rc = launch_status())) return rc;
+    nn_scan_sums_kernel<<<blocks, NJF_NN_THREADS, 0, s>>>(a);
+    if ((rc = launch_status())) return rc;
+    nn_scan_blocks_kernel<<<1, NJF_NN_THREADS, 0, s>>>(a, blocks);
+    if ((rc = launch_status())) return rc;
+    nn_scan_cells_kernel<<<blocks, NJF_NN_THREADS, 0, s>>>(a);
+    if ((rc = launch_status())) return rc;
+    nn_points_kernel<true><<<per_point, NJF_NN_THREADS, 0, s>>>(a);
+    if ((rc = launch_status())) return rc;
+  }
+  if (query) {
+    hipError_t e = hipMemsetAsync(found, 0, (size_t)num_problems * sizeof(int), s);
+    if (e != hipSuccess) return (int)e;
+    if (n > 0) {
+      if (phases & NJF_FIELD_NEAREST_WAVE) {
+        const dim3 grid((unsigned)(((long long)n + NJF_NN_THREADS / 64 - 1) / (NJF_NN_THREADS / 64)), (unsigned)num_problems);
+        nn_query_kernel<true><<<grid, NJF_NN_THREADS, 0, s>>>(a);
+      } else {
+        const dim3 grid((unsigned)(((long long)n + NJF_NN_THREADS - 1) / NJF_NN_THREADS), (unsigned)num_problems);
+        nn_query_kernel<false><<<grid, NJF_NN_THREADS, 0, s>>>(a);
+      }
+      if ((rc = launch_status())) return rc;
+    }
   }
   return NJF_OK;
 }

@@ -914,7 +914,7 @@ class FieldCommands:
         return self.cost.sqrt()
 
 
-def _box(name: str, what: str, v, m: int, a_dim: int, like: torch.Tensor):
+def _box(name: str, what: str, v, m: int, a_dim: int, like: torch.Tensor, of: str = "targets"):
     """``[M, A]`` fp32 on the device from None, a Python number, or an fp32 tensor ``[A]`` or ``[M, A]``."""
     if v is None:
         return None
@@ -923,8 +923,39 @@ def _box(name: str, what: str, v, m: int, a_dim: int, like: torch.Tensor):
     if not torch.is_tensor(v) or v.dtype != torch.float32 or tuple(v.shape) not in ((a_dim,), (m, a_dim)):
         raise ValueError(f"{name}: {what} must be fp32 [{a_dim}] or [{m}, {a_dim}]")
     if v.device != like.device:
-        raise ValueError(f"{name}: {what} must live on the device of targets")
+        raise ValueError(f"{name}: {what} must live on the device of {of}")
     return v.expand(m, a_dim).contiguous()
+
+
+def _check_solver(name: str, twists, xyz, labels, m: int, n: int, k: int, a_dim: int, like: torch.Tensor, of: str, joints, tree,
+                  weights, count, init, lower, upper, reg, iterations, damping):
+    """The checks of ``solve_commands`` that follow those of the twists, the points and the targets (``like``, called ``of`` in
+    the messages), shared with the registration; ``(parts_count, links, count, lower, upper)``."""
+    if weights is not None and (not torch.is_tensor(weights) or weights.dtype != torch.float32
+                                or tuple(weights.shape) not in ((n,), (m, n))):
+        raise ValueError(f"{name}: weights must be fp32 [{n}] or [{m}, {n}]")
+    if init is not None and (not torch.is_tensor(init) or init.dtype != torch.float32 or tuple(init.shape) != (m, a_dim)):
+        raise ValueError(f"{name}: init must be fp32 [{m}, {a_dim}]")
+    for what, v in (("reg", reg), ("damping", damping)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)):
+            raise ValueError(f"{name}: {what} must be a number")
+    if not reg >= 0.0:
+        raise ValueError(f"{name}: reg must be >= 0 (got {reg})")
+    if not damping > 0.0:
+        raise ValueError(f"{name}: damping must be > 0 (got {damping})")
+    if isinstance(iterations, bool) or not isinstance(iterations, int) or not 0 <= iterations <= hip.FIELD_COMMANDS_MAX_ITERATIONS:
+        raise ValueError(f"{name}: iterations must be an integer in [0, {hip.FIELD_COMMANDS_MAX_ITERATIONS}] (got {iterations})")
+    number = lambda v: isinstance(v, (int, float)) and not isinstance(v, bool)   # noqa: E731
+    if number(lower) and number(upper) and lower > upper:
+        raise ValueError(f"{name}: lower > upper ({lower} > {upper})")
+    lower, upper = _box(name, "lower", lower, m, a_dim, like, of), _box(name, "upper", upper, m, a_dim, like, of)
+    parts_count, same, links = _check_links(name, twists, joints, tree, k, a_dim, like)
+    count = _one_int32(name, "count", count, like)
+    same += [("xyz", xyz), ("labels", labels)] + [(what, t) for what, t in (("weights", weights), ("init", init)) if t is not None]
+    for what, t in same:
+        if t.device != like.device:
+            raise ValueError(f"{name}: {what} must live on the device of {of}")
+    return parts_count, links, count, lower, upper
 
 
 def solve_commands(twists: FieldTwists, xyz: torch.Tensor, labels: torch.Tensor, targets: torch.Tensor, *,
@@ -948,30 +979,8 @@ def solve_commands(twists: FieldTwists, xyz: torch.Tensor, labels: torch.Tensor,
     m = targets.shape[0]
     if not 1 <= m <= hip.FIELD_POSE_MAX_COMMANDS:
         raise ValueError(f"{name}: 1 to {hip.FIELD_POSE_MAX_COMMANDS} target sets (got {m})")
-    if weights is not None and (not torch.is_tensor(weights) or weights.dtype != torch.float32
-                                or tuple(weights.shape) not in ((n,), (m, n))):
-        raise ValueError(f"{name}: weights must be fp32 [{n}] or [{m}, {n}]")
-    if init is not None and (not torch.is_tensor(init) or init.dtype != torch.float32 or tuple(init.shape) != (m, a_dim)):
-        raise ValueError(f"{name}: init must be fp32 [{m}, {a_dim}]")
-    for what, v in (("reg", reg), ("damping", damping)):
-        if isinstance(v, bool) or not isinstance(v, (int, float)):
-            raise ValueError(f"{name}: {what} must be a number")
-    if not reg >= 0.0:
-        raise ValueError(f"{name}: reg must be >= 0 (got {reg})")
-    if not damping > 0.0:
-        raise ValueError(f"{name}: damping must be > 0 (got {damping})")
-    if isinstance(iterations, bool) or not isinstance(iterations, int) or not 0 <= iterations <= hip.FIELD_COMMANDS_MAX_ITERATIONS:
-        raise ValueError(f"{name}: iterations must be an integer in [0, {hip.FIELD_COMMANDS_MAX_ITERATIONS}] (got {iterations})")
-    number = lambda v: isinstance(v, (int, float)) and not isinstance(v, bool)   # noqa: E731
-    if number(lower) and number(upper) and lower > upper:
-        raise ValueError(f"{name}: lower > upper ({lower} > {upper})")
-    lower, upper = _box(name, "lower", lower, m, a_dim, targets), _box(name, "upper", upper, m, a_dim, targets)
-    parts_count, same, links = _check_links(name, twists, joints, tree, k, a_dim, targets)
-    count = _one_int32(name, "count", count, targets)
-    same += [("xyz", xyz), ("labels", labels)] + [(what, t) for what, t in (("weights", weights), ("init", init)) if t is not None]
-    for what, t in same:
-        if t.device != targets.device:
-            raise ValueError(f"{name}: {what} must live on the device of targets")
+    parts_count, links, count, lower, upper = _check_solver(name, twists, xyz, labels, m, n, k, a_dim, targets, "targets", joints,
+                                                            tree, weights, count, init, lower, upper, reg, iterations, damping)
     if targets.device.type != "cuda":
         raise ValueError(f"{name}: the tensors must live on the GPU; there is no CPU path")
     dev = targets.device
@@ -1003,6 +1012,222 @@ def cloud_commands(cloud: FieldPointCloud, labels: torch.Tensor, twists: FieldTw
                               init=init, lower=lower, upper=upper, reg=reg, iterations=iterations, damping=damping)
     except ValueError as err:
         raise ValueError(str(err).replace("solve_commands:", "cloud_commands:", 1)) from None
+
+
+# ---- registration to an unlabelled cloud: closest points on a cell list ------------------------------------
+def cell_grid(lower: Sequence[float], upper: Sequence[float], cell: float) -> FieldGrid:
+    """The cell lattice of ``nearest_points`` over the box ``lower`` .. ``upper``: origin = ``lower``, the three steps equal to
+    ``cell``, ``dims_c = max(1, ceil((upper_c - lower_c) / cell))`` cells per axis (at most 1,024).  Points outside the box are
+    still found: they land in the boundary cells."""
+    name = "cell_grid"
+    if isinstance(cell, bool) or not isinstance(cell, (int, float)) or not cell > 0.0 or not math.isfinite(cell):
+        raise ValueError(f"{name}: cell must be a finite number > 0 (got {cell})")
+    try:
+        lo, hi = tuple(float(v) for v in lower), tuple(float(v) for v in upper)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name}: lower and upper have three numbers each") from None
+    if len(lo) != 3 or len(hi) != 3 or not all(math.isfinite(v) for v in lo + hi):
+        raise ValueError(f"{name}: lower and upper have three finite numbers each")
+    if any(u < l for l, u in zip(lo, hi)):
+        raise ValueError(f"{name}: lower > upper ({lo} > {hi})")
+    dims = tuple(max(1, int(math.ceil((u - l) / cell))) for l, u in zip(lo, hi))
+    if max(dims) > hip.FIELD_NEAREST_MAX_DIM:
+        raise ValueError(f"{name}: at most {hip.FIELD_NEAREST_MAX_DIM} cells per axis (got {dims}); take a larger cell")
+    return FieldGrid(lo, (cell,) * 3, dims)
+
+
+@dataclass
+class FieldNearest:
+    """The closest valid observed point of every searched query row (``nearest_points``; include/njf_hip.h: njf_field_nearest),
+    per problem: the exact arg-min of ``(dx*dx + dy*dy) + dz*dz`` in fp32, ties to the lowest index, accepted within
+    ``max_distance``.  ``matched`` holds the observed point itself or three NaNs -- ``solve_commands``' "this row is free"."""
+
+    index: torch.Tensor       # [M, n] int32: the observed point's row, -1 = none
+    distance2: torch.Tensor   # [M, n] fp32: its squared distance, +inf = none
+    matched: torch.Tensor     # [M, n, 3] fp32: the point, or NaN
+    found: torch.Tensor       # [M] int32: the accepted rows
+
+
+def _check_nearest(name: str, observed, cells, max_distance, observed_count, count, labels, n: int, mq: int, like: torch.Tensor,
+                   of: str, m_other: int = 1):
+    """The checks of the observation, the lattice and the search that ``nearest_points`` and the registration share; ``like``
+    (called ``of`` in the messages) rules the device.  ``(observed [Mo, T, 3], M, observed_count, count)``."""
+    if not torch.is_tensor(observed) or observed.dtype != torch.float32 or observed.dim() not in (2, 3) or observed.shape[-1] != 3 \
+            or observed.shape[-2] < 1:
+        raise ValueError(f"{name}: observed must be fp32 [T, 3] or [Mo, T, 3] with T >= 1")
+    observed = observed.reshape(-1, *observed.shape[-2:]) if observed.dim() == 3 else observed[None]
+    mo, t = observed.shape[:2]
+    m = max(mo, mq, m_other)
+    if not 1 <= m <= hip.FIELD_POSE_MAX_COMMANDS or mo < 1 or mq < 1:
+        raise ValueError(f"{name}: 1 to {hip.FIELD_POSE_MAX_COMMANDS} problems (got {min(mo, mq, m)} and {m})")
+    if mo not in (1, m) or mq not in (1, m):
+        raise ValueError(f"{name}: observed and queries hold one set or one per problem (got {mo} and {mq} for {m} problems)")
+    if mo * t >= 2 ** 31:
+        raise ValueError(f"{name}: Mo * T must stay below 2**31")
+    if not isinstance(cells, FieldGrid):
+        raise ValueError(f"{name}: cells must be a FieldGrid (cell_grid)")
+    cell = cells.step[0]
+    if not cell > 0.0 or not math.isfinite(cell) or cells.step[1] != cell or cells.step[2] != cell or not 1.0 / cell < 2.0 ** 127:
+        raise ValueError(f"{name}: cells must have three equal steps > 0 (got {cells.step})")
+    if max(cells.dims) > hip.FIELD_NEAREST_MAX_DIM:
+        raise ValueError(f"{name}: at most {hip.FIELD_NEAREST_MAX_DIM} cells per axis (got {cells.dims})")
+    if mo * cells.num_nodes >= 2 ** 31:
+        raise ValueError(f"{name}: Mo * the number of cells must stay below 2**31")
+    if isinstance(max_distance, bool) or not isinstance(max_distance, (int, float)) or not max_distance > 0.0 \
+            or not math.isfinite(max_distance):
+        raise ValueError(f"{name}: max_distance must be a finite number > 0 (got {max_distance})")
+    with np.errstate(over="ignore"):
+        reach = float(np.float32(max_distance))          # the kernel's float
+    if not reach > 0.0:
+        raise ValueError(f"{name}: max_distance must be a finite number > 0 (got {max_distance})")
+    if not math.isfinite(reach) or not math.isfinite(reach / cell) or math.ceil(reach / cell) + 1 > hip.FIELD_NEAREST_MAX_RINGS:
+        raise ValueError(f"{name}: max_distance may span at most {hip.FIELD_NEAREST_MAX_RINGS - 1} cells (got {max_distance} for cells "
+                         f"of {cell}); take a larger cell")
+    if observed_count is not None and (not torch.is_tensor(observed_count) or observed_count.dtype != torch.int32
+                                       or tuple(observed_count.shape) != (mo,)):
+        raise ValueError(f"{name}: observed_count must be int32 [{mo}]")
+    count = _one_int32(name, "count", count, like)
+    if labels is not None and (not torch.is_tensor(labels) or labels.dtype != torch.int32 or tuple(labels.shape) != (n,)):
+        raise ValueError(f"{name}: labels must be int32 [{n}]")
+    for what, v in (("observed", observed), ("observed_count", observed_count), ("labels", labels)):
+        if v is not None and v.device != like.device:
+            raise ValueError(f"{name}: {what} must live on the device of {of}")
+    return observed, m, observed_count, count
+
+
+def _nearest_outputs(m: int, n: int, dev) -> FieldNearest:
+    return FieldNearest(index=torch.empty(m, n, dtype=torch.int32, device=dev), distance2=torch.empty(m, n, dtype=torch.float32, device=dev),
+                        matched=torch.empty(m, n, 3, dtype=torch.float32, device=dev), found=torch.empty(m, dtype=torch.int32, device=dev))
+
+
+def _nearest_launch(observed, queries, cells: FieldGrid, max_distance, m: int, near: Optional[FieldNearest], observed_count, count,
+                    labels, phase: int, workspace: torch.Tensor) -> None:
+    out = None if near is None else {f: getattr(near, f) for f in near.__dataclass_fields__}
+    hip.field_nearest(observed, queries, cells.c_grid(), max_distance, out, m, observed_count=observed_count, count=count,
+                      labels=labels, phase=phase, workspace=workspace)
+
+
+def nearest_points(queries: torch.Tensor, observed: torch.Tensor, cells: FieldGrid, max_distance: float, *,
+                   observed_count: Optional[torch.Tensor] = None, count: Optional[torch.Tensor] = None,
+                   labels: Optional[torch.Tensor] = None) -> FieldNearest:
+    """For every row of ``queries`` ``[n, 3]`` or ``[Mq, n, 3]`` (fp32) the closest point of the unlabelled cloud ``observed``
+    ``[T, 3]`` or ``[Mo, T, 3]`` (fp32) within ``max_distance``: M = max(Mq, Mo) problems, each of Mq and
+    Mo 1 or M.  A point is valid below ``observed_count`` (int32 ``[Mo]``; None = T) with finite coordinates; a row is searched
+    below ``count`` (one int32 on the device; None = n) with finite coordinates and, with ``labels`` (int32 ``[n]``), a label >=
+    0.  The result is the exact arg-min of ``(dx*dx + dy*dy) + dz*dz`` in fp32, ties to the lowest index; ``cells``
+    (``cell_grid``) only sets the cost: the points are sorted into its cells and a query walks the rings of cells around its
+    own, so it reads the records nearby instead of all T.  Integer atomics only, no host read: equal bytes from call to call,
+    capturable."""
+    name = "nearest_points"
+    if not torch.is_tensor(queries) or queries.dtype != torch.float32 or queries.dim() not in (2, 3) or queries.shape[-1] != 3:
+        raise ValueError(f"{name}: queries must be fp32 [n, 3] or [Mq, n, 3]")
+    queries = queries if queries.dim() == 3 else queries[None]
+    mq, n = queries.shape[:2]
+    observed, m, observed_count, count = _check_nearest(name, observed, cells, max_distance, observed_count, count, labels, n, mq,
+                                                        queries, "queries")
+    if queries.device.type != "cuda":
+        raise ValueError(f"{name}: the tensors must live on the GPU; there is no CPU path")
+    near = _nearest_outputs(m, n, queries.device)
+    workspace = torch.empty(hip.field_nearest_workspace(observed.shape[0], cells.num_nodes, observed.shape[1]), dtype=torch.int32,
+                            device=queries.device)
+    _nearest_launch(observed.contiguous(), queries.contiguous(), cells, max_distance, m, near,
+                    None if observed_count is None else observed_count.contiguous(), count,
+                    None if labels is None else labels.contiguous(), hip.FIELD_NEAREST_ALL, workspace)
+    return near
+
+
+@dataclass
+class FieldRegistration:
+    """The commands that bring the parts onto an unlabelled observation (``register_commands``): ``fit`` is the
+    ``FieldCommands`` of the last round, ``matches`` the ``FieldNearest`` it solved on; the histories hold every round's
+    commands, cost and number of matched rows.  The cost need not fall from round to round: the correspondences change."""
+
+    fit: FieldCommands
+    matches: FieldNearest
+    commands_history: torch.Tensor   # [R, M, A] fp32: the commands after every round
+    cost_history: torch.Tensor       # [R, M] float64
+    found_history: torch.Tensor      # [R, M] int32
+
+
+def register_commands(twists: FieldTwists, xyz: torch.Tensor, labels: torch.Tensor, observed: torch.Tensor, cells: FieldGrid,
+                      max_distance: float, *, joints: Optional[FieldJoints] = None, tree=None,
+                      observed_count: Optional[torch.Tensor] = None, count: Optional[torch.Tensor] = None,
+                      weights: Optional[torch.Tensor] = None, init: Optional[torch.Tensor] = None, lower=None, upper=None,
+                      reg: float = 0.0, rounds: int = 8, iterations: int = 3, damping: float = 1e-3) -> FieldRegistration:
+    """The command that explains an unlabelled observation of the body: closest-point registration of
+    the points ``xyz`` ``[n, 3]`` with part labels ``labels`` to the cloud ``observed`` ``[T, 3]`` or ``[Mo, T, 3]``.  The cell list
+    of ``observed`` is built once; then, ``rounds`` times from ``u_0 = clamp(init)``: the rows are posed at ``u_r`` (``part_poses``
+    and its points launch; rows of no part stay), ``nearest_points`` matches the posed rows of label >= 0 to observed points
+    within ``max_distance``, and ``solve_commands(xyz, targets=matched, init=u_r, iterations=iterations)`` gives ``u_{r+1}``.  The
+    targets are always targets for the un-posed ``xyz`` and the solver's pose is finite: no pose is ever composed with another.
+    M = max(Mo, rows of ``init``) problems; one observation with ``init`` ``[M, A]`` is a multi-start registration, of which the
+    caller takes ``fit.cost.argmin()``.  Every other argument is ``solve_commands``'.  No host read: capturable after one
+    eager call."""
+    name = "register_commands"
+    k, a_dim = _check_twists(name, twists)
+    n = _check_points(name, xyz, labels, None, a_dim)
+    if isinstance(rounds, bool) or not isinstance(rounds, int) or not 1 <= rounds <= 1000:
+        raise ValueError(f"{name}: rounds must be an integer in [1, 1000] (got {rounds})")
+    starts = init.shape[0] if torch.is_tensor(init) and init.dim() == 2 else 1
+    observed, m, observed_count, count = _check_nearest(name, observed, cells, max_distance, observed_count, count, None, n, 1, xyz,
+                                                        "xyz", m_other=max(starts, 1))
+    parts_count, links, count, lower_box, upper_box = _check_solver(name, twists, xyz, labels, m, n, k, a_dim, xyz, "xyz", joints, tree,
+                                                                    weights, count, init, lower, upper, reg, iterations, damping)
+    if xyz.device.type != "cuda":
+        raise ValueError(f"{name}: the tensors must live on the GPU; there is no CPU path")
+    dev = xyz.device
+    u = torch.zeros(m, a_dim, dtype=torch.float32, device=dev) if init is None else init
+    if lower_box is not None:
+        u = torch.maximum(u, lower_box)
+    if upper_box is not None:
+        u = torch.minimum(u, upper_box)
+    out = FieldRegistration(fit=None, matches=None, commands_history=torch.empty(rounds, m, a_dim, dtype=torch.float32, device=dev),
+                            cost_history=torch.empty(rounds, m, dtype=torch.float64, device=dev),
+                            found_history=torch.empty(rounds, m, dtype=torch.int32, device=dev))
+    labels_c = labels.contiguous()
+    observed_count = None if observed_count is None else observed_count.contiguous()
+    workspace = torch.empty(hip.field_nearest_workspace(observed.shape[0], cells.num_nodes, observed.shape[1]), dtype=torch.int32,
+                            device=dev)
+    _nearest_launch(observed.contiguous(), (1, n), cells, max_distance, m, None, observed_count, None, None, hip.FIELD_NEAREST_BUILD,
+                    workspace)
+    for r in range(rounds):
+        _, posed = _pose(name, twists, u, joints, tree, points=(xyz, labels, count, None))
+        near = _nearest_outputs(m, n, dev)
+        _nearest_launch(tuple(observed.shape[:2]), posed, cells, max_distance, m, near, observed_count, count, labels_c,
+                        hip.FIELD_NEAREST_QUERY, workspace)
+        fit = solve_commands(twists, xyz, labels, near.matched, joints=joints, tree=tree, weights=weights, count=count, init=u,
+                             lower=lower, upper=upper, reg=reg, iterations=iterations, damping=damping)
+        out.commands_history[r].copy_(fit.commands)
+        out.cost_history[r].copy_(fit.cost)
+        out.found_history[r].copy_(near.found)
+        out.fit, out.matches, u = fit, near, fit.commands
+    return out
+
+
+def cloud_registration(cloud: FieldPointCloud, labels: torch.Tensor, twists: FieldTwists, observed: torch.Tensor,
+                       max_distance: float, *, cells: Optional[FieldGrid] = None, joints: Optional[FieldJoints] = None, tree=None,
+                       observed_count: Optional[torch.Tensor] = None, weights: Optional[torch.Tensor] = None,
+                       init: Optional[torch.Tensor] = None, lower=None, upper=None, reg: float = 0.0, rounds: int = 8,
+                       iterations: int = 3, damping: float = 1e-3) -> FieldRegistration:
+    """``register_commands`` on the rows of an extracted cloud: ``cloud.xyz`` and ``cloud.count`` with ``labels`` ``[n]`` int32, the
+    per-row result of ``cloud_components`` -- the command that explains a second, unlabelled observation of the same body.
+    ``cells=None`` takes ``cell_grid`` over the bounds of ``cloud.grid`` with the largest of its steps as the cell."""
+    name = "cloud_registration"
+    if not isinstance(cloud, FieldPointCloud):
+        raise ValueError(f"{name}: cloud must be a FieldPointCloud")
+    try:
+        if cells is None:
+            grid = cloud.grid
+            if not isinstance(grid, FieldGrid):
+                raise ValueError("register_commands: cloud.grid must be a FieldGrid")
+            upper_corner = tuple(o + s * (d - 1) for o, s, d in zip(grid.origin, grid.step, grid.dims))
+            cells = cell_grid(tuple(min(o, u) for o, u in zip(grid.origin, upper_corner)),
+                              tuple(max(o, u) for o, u in zip(grid.origin, upper_corner)), max(abs(s) for s in grid.step))
+        return register_commands(twists, cloud.xyz, labels, observed, cells, max_distance, joints=joints, tree=tree,
+                                 observed_count=observed_count, count=cloud.count, weights=weights, init=init, lower=lower,
+                                 upper=upper, reg=reg, rounds=rounds, iterations=iterations, damping=damping)
+    except ValueError as err:
+        raise ValueError(str(err).replace("register_commands:", f"{name}:", 1).replace("cell_grid:", f"{name}:", 1)) from None
 
 
 # ---- coarse-to-fine band (DESIGN.md section 14) ----------------------------------------------------------------------------------

@@ -176,6 +176,8 @@ _SIGNATURES = {
     "njf_field_commands": ([_vp, _vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                             C.c_int, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp, C.c_double, C.c_int, C.c_double] + [_vp] * 11 +
                            [C.c_longlong, C.c_int, _vp], C.c_int),
+    "njf_field_nearest": ([_vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.POINTER(FieldGrid), C.c_double,
+                           _vp, _vp, _vp, _vp, _vp, C.c_longlong, C.c_int, _vp], C.c_int),
     "njf_pack_resnetfc_backward": ([C.POINTER(ResnetFcWeights), _vp, C.c_int, _vp], C.c_int),
     "njf_resnetfc_backward": ([_vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp], C.c_int),
     "njf_pack_transformer_backward": ([_vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, _vp], C.c_int),
@@ -1196,6 +1198,62 @@ def field_commands(parts: torch.Tensor, part_status: torch.Tensor, centroid: tor
             _double_ptr(out["weight"], "weight"), _int32_ptr(out["steps"], "steps"), _double_ptr(out["gradient"], "gradient"),
             _int32_ptr(out["status"], "status"), _int32_ptr(out["part_status"], "part_status"), _int32_ptr(out["depth"], "depth"),
             _double_ptr(out["moments"], "moments"), _double_ptr(workspace, "workspace"), int(workspace.numel()), int(phase))
+
+
+# ---- closest points of an unlabelled cloud against a cell list (include/njf_hip.h: njf_field_nearest) ------------------------
+FIELD_NEAREST_BUILD, FIELD_NEAREST_QUERY = 1, 2        # NJF_FIELD_NEAREST_BUILD (a memset, five launches), _QUERY (a memset, one)
+FIELD_NEAREST_PHASES = (FIELD_NEAREST_BUILD, FIELD_NEAREST_QUERY)
+FIELD_NEAREST_PHASE_NAMES = ("build", "query")
+FIELD_NEAREST_ALL = 3                                  # NJF_FIELD_NEAREST_ALL
+FIELD_NEAREST_WAVE = 4                                 # NJF_FIELD_NEAREST_WAVE: the query launch with a wave per query
+FIELD_NEAREST_MAX_RINGS = 64                           # NJF_FIELD_NEAREST_MAX_RINGS
+FIELD_NEAREST_MAX_DIM = 1024                           # NJF_FIELD_NEAREST_MAX_DIM
+
+
+def field_nearest_workspace(observed: int, cells: int, points: int) -> int:
+    """32-bit words of workspace njf_field_nearest needs: NJF_FIELD_NEAREST_WORKSPACE(Mo, C, T) -- Mo (C + 1) starts, Mo C
+    cursors, 4 Mo T record words and 3 words of alignment."""
+    return observed * (2 * cells + 1 + 4 * points) + 3
+
+
+def field_nearest(observed: Optional[torch.Tensor], queries: Optional[torch.Tensor], grid: FieldGrid, max_distance: float, out: dict,
+                  problems: int, observed_count=None, count=None, labels=None, phase: int = FIELD_NEAREST_ALL,
+                  workspace: Optional[torch.Tensor] = None) -> None:
+    """njf_field_nearest on ``observed`` [Mo, T, 3] and ``queries`` [Mq, n, 3] (fp32) for ``problems`` = M problems, Mo and Mq
+    each 1 or M, against the cell lattice ``grid``.  ``observed_count`` [Mo], ``count`` [1], ``labels`` [n]: int32 or None.
+    ``out`` maps index [M, n] (int32), distance2 [M, n], matched [M, n, 3] (fp32) and found [M] (int32) to tensors of their
+    shapes.  ``phase``: FIELD_NEAREST_BUILD reads ``observed`` and writes the workspace, FIELD_NEAREST_QUERY reads the workspace
+    and writes ``out``; a phase without the build takes the SHAPE ``(Mo, T)`` for ``observed``, one without the query the shape
+    ``(Mq, n)`` for ``queries`` and None for ``out``.  ``workspace``: int32, ``field_nearest_workspace`` elements."""
+    shape = lambda t: tuple(t.shape[:2]) if torch.is_tensor(t) else tuple(t)   # noqa: E731
+    if torch.is_tensor(observed) and (observed.dim() != 3 or observed.shape[2] != 3):
+        raise ValueError("njf_hip: field_nearest needs observed [Mo, T, 3]")
+    if torch.is_tensor(queries) and (queries.dim() != 3 or queries.shape[2] != 3):
+        raise ValueError("njf_hip: field_nearest needs queries [Mq, n, 3]")
+    (mo, t), (mq, n), m = shape(observed), shape(queries), int(problems)
+    build, query = bool(phase & FIELD_NEAREST_BUILD), bool(phase & FIELD_NEAREST_QUERY)
+    if (build and not torch.is_tensor(observed)) or (query and not torch.is_tensor(queries)):
+        raise ValueError("njf_hip: field_nearest needs the observed points to build and the queries to query")
+    if observed_count is not None and observed_count.numel() != mo:
+        raise ValueError("njf_hip: field_nearest needs observed_count [Mo]")
+    if count is not None and count.numel() != 1:
+        raise ValueError("njf_hip: field_nearest count must hold one int32")
+    if labels is not None and labels.numel() != n:
+        raise ValueError("njf_hip: field_nearest needs labels [n]")
+    if query:
+        for name, size in dict(index=m * n, distance2=m * n, matched=3 * m * n, found=m).items():
+            if out[name].numel() != size:
+                raise ValueError(f"njf_hip: field_nearest output {name} must hold {size} elements (got {out[name].numel()})")
+    cells = int(grid.dims[0]) * int(grid.dims[1]) * int(grid.dims[2])
+    if workspace is None:
+        like = observed if build else queries
+        workspace = torch.empty(field_nearest_workspace(mo, cells, t), dtype=torch.int32, device=like.device)
+    o = (lambda key, ptr: ptr(out[key], key) if query else None)   # noqa: E731
+    _launch("njf_field_nearest", load_library().njf_field_nearest, _ptr(observed, "observed") if build else None,
+            _int32_ptr(observed_count, "observed_count"), int(mo), int(t), _ptr(queries, "queries") if query else None,
+            _int32_ptr(count, "count"), _int32_ptr(labels, "labels"), int(mq), int(n), m, C.byref(grid), float(max_distance),
+            o("index", _int32_ptr), o("distance2", _ptr), o("matched", _ptr), o("found", _int32_ptr),
+            _int32_ptr(workspace, "workspace"), int(workspace.numel()), int(phase))
 
 
 def solve_action(mean_position, jacobian, projection, target_flow, visible_mask, init_action, iterations: int,
