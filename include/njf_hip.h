@@ -767,6 +767,59 @@ int njf_field_commands(const int* parts, const int* parts_count, int num_parts, 
                        int* steps, double* gradient, int* status, int* out_part_status, int* depth, double* moments,
                        double* workspace, long long workspace_doubles, int phases, void* stream);
 
+/* ---- inverse kinematics with a 3x3 information per target: pixel rays, planes, depth noise (ABI v20, additive; DESIGN.md
+ * section 20) ----------------------------------------------------------------------------------------------------------------------
+ * njf_field_commands with an anisotropic error per row: L_m(u) = (1/W_m) sum_i w_i z_mi^T Q_mi z_mi + (reg/A) |u|^2, z_mi =
+ * R_p(u) x_i + t_p(u) - y_mi, W_m = sum w_i, in double.  Q = I - d d^T holds a point to the ray of a pixel, Q = n n^T to a plane
+ * (point-to-plane registration), an inverse covariance weighs a depth camera's noise; Q = I is njf_field_commands' objective.
+ * Inputs: everything njf_field_commands takes, and information float, [n,6] (information_per_problem 0) or [M,n,6] (1): the
+ * symmetric Q of a row as [xx xy xz yy yz zz], widened to double.  Q is not tested for definiteness -- that is the caller's
+ * contract -- and the cost is clamped at 0 as before.
+ * COUNTED ROWS: njf_field_commands' rule, and all six information entries finite: a NaN in the information leaves the row out,
+ *        like a NaN target.
+ * MOMENTS [M,K,74] double per (problem, slot) about c = centroid[p]; x^ = (x~0, x~1, x~2, 1), x~ = x - c, y~ = y - c, b_a =
+ *        (Q_a0 y~0 + Q_a1 y~1) + Q_a2 y~2:
+ *        [0] s0 = sum w; [1 + 10 e + f] P[e][f] = sum (w Q_e) (x^_i x^_j), e over xx xy xz yy yz zz, f over the pairs i <= j in the
+ *        order 00 01 02 03 11 12 13 22 23 33; [61 + 4 a + j] B[a][j] = sum (w b_a) x^_j; [73] e = sum w ((y~0 b0 + y~1 b1) + y~2
+ *        b2).  Every term in double in exactly this parenthesisation, no contraction.  The launch has njf_field_commands' shape
+ *        -- workgroup (chunk, slot, tile of problems), the chunk's rows compacted in order, a wave per problem, lane l adding the
+ *        list entries l, l + 64, ... -- and the lanes are added by a REDUCE-SCATTER: with the partner at lane ^ 32 a lane exchanges
+ *        one half of its 74 sums and keeps the pair's sums of the other (lower half [0, ceil(L/2)) to the lane whose bit is
+ *        clear), then ^ 16 on the 37 it kept, and so on -- 37 + 19 + 10 + 5 + 3 + 2 = 76 cross-lane moves instead of 74 x 6 --
+ *        until every lane holds at most two finished sums, which it stores.  Each finished sum is the butterfly's tree over the
+ *        lanes (offsets 32, 16, ..., 1); the finishing launch adds the chunks in ascending order.  The order depends on (n, K, M)
+ *        alone, there are no floating-point atomics, two calls give equal bytes.  A slot whose pose status is not 0 has zeros.
+ *        NJF_FIELD_COMMANDS_METRIC_BUTTERFLY: the same sums by 74 butterflies, kept to be measured against.
+ * SOLVE  njf_field_commands' solver with the block that turns moments into shares replaced.  Slot p at pose (R, t) with derivative
+ *        twists (W_k, U_k): d = R c + t, G = (R | d - c) and D_k = ([W_k]x R | W_k x d + U_k), 3 x 4 each, <X, Y> = sum_{a,b,i,j}
+ *        X_ai Y_bj P[ab][ij].  The slot's shares: cost <G, G> - 2 sum G_ai B_ai + e, half-gradient <D_k, G> - sum D_k,ai B_ai,
+ *        Gauss-Newton matrix <D_k, D_l>.  The links, the chain walk with its index checks, the order in which the shares are
+ *        added, the Levenberg-Marquardt rule on the fp32 lattice with bounds and reg, and the status bits are
+ *        njf_field_commands', word for word.
+ * Outputs: those of njf_field_commands, moments being [M,K,74].
+ * workspace: NJF_FIELD_COMMANDS_METRIC_WORKSPACE(M, K, A, n) doubles: the chunks' partial moments [chunks,K,M,74], then the
+ * twists of the links and of the chains [M,2,K,A,6].
+ * `phases`: NJF_FIELD_COMMANDS_MOMENTS | NJF_FIELD_COMMANDS_SOLVE as in njf_field_commands (the solve phase READS moments) [|
+ * NJF_FIELD_COMMANDS_METRIC_BUTTERFLY, a modifier of the moments phase].  One stream, no host read (capture-safe).
+ * Returns, before the first launch: NJF_E_VALUE for everything njf_field_commands answers so, information_per_problem not 0 or
+ * 1, or unknown phases (the modifier without the moments phase included); NJF_E_SHAPE for n < 0 or a workspace that is too
+ * small; NJF_E_NULL for a missing pointer -- information, with the moments phase and n > 0, is one --, or joints without a tree
+ * or a tree without joints. */
+#define NJF_FIELD_COMMANDS_METRIC_MOMENTS_PER_PART 74
+#define NJF_FIELD_COMMANDS_METRIC_WORKSPACE(M, K, A, n) \
+  ((74LL * (((n) + NJF_FIELD_TWISTS_CHUNK - 1LL) / NJF_FIELD_TWISTS_CHUNK) + 12LL * (A)) * (M) * (K))
+#define NJF_FIELD_COMMANDS_METRIC_BUTTERFLY 4    /* modifier of _MOMENTS, not part of _ALL */
+int njf_field_commands_metric(const int* parts, const int* parts_count, int num_parts, const int* part_status,
+                              const double* centroid, const double* omega, const double* velocity, int action_dim,
+                              const int* part_a, const int* part_b, const int* joints_count, int max_joints, const double* anchor,
+                              const double* joint_omega, const double* joint_velocity, const int* parent, const int* joint_of,
+                              const float* xyz, const int* labels, const int* count, int n, const float* targets,
+                              const float* information, int information_per_problem, int num_problems, const float* weights,
+                              int weights_per_problem, const float* init, const float* lower, const float* upper, double reg,
+                              int iterations, double damping, float* commands, double* cost, double* initial_cost, double* weight,
+                              int* steps, double* gradient, int* status, int* out_part_status, int* depth, double* moments,
+                              double* workspace, long long workspace_doubles, int phases, void* stream);
+
 /* ---- closest points of an unlabelled cloud against a cell list (ABI v20, additive) -------------------------
  * For each of M problems and each row of a set of query points, the closest valid point of an observed cloud: the
  * correspondence step between the posed rows of a body and an observation of it (njf_field_commands takes `matched` as its

@@ -4009,6 +4009,8 @@ struct IkArgs {
   const float* targets;    // [M,n,3]
   const float* weights;    // null, [n] (weight_stride 0) or [M,n] (weight_stride n)
   long long weight_stride;
+  const float* information;   // the metric entry only: [n,6] (information_stride 0) or [M,n,6] (information_stride 6 n)
+  long long information_stride;
   const float *init, *lower, *upper;   // [M,A] or null
   double reg, damping;
   int iterations, chunks;
@@ -4097,7 +4099,135 @@ __global__ void __launch_bounds__(NJF_IK_THREADS) ik_moments_kernel(IkArgs a) {
   }
 }
 
+// ---- anisotropic targets: a 3 x 3 information per row (njf_field_commands_metric) -------------------------
+// z = R x + t - y is linear in the entries of (R | t), so sum w z^T Q z, its gradient and its Gauss-Newton matrix depend on
+// the rows of a part through 74 moments: s0, P[6][10] = sum (w Q_e) (x^_i x^_j), B[3][4] = sum (w b_a) x^_j, e = sum w y~.b,
+// x^ = (x~, 1), b = Q y~.  The launch has ik_moments_kernel's shape; what differs is how a wave finishes its 74 sums.
+#define NJF_IKM_MOMENTS NJF_FIELD_COMMANDS_METRIC_MOMENTS_PER_PART
+#define NJF_IKM_P 1    // P[e][f] at 1 + 10 e + f
+#define NJF_IKM_B 61   // B[a][j] at 61 + 4 a + j
+#define NJF_IKM_E 73
+
+// One step of the reduce-scatter: the L live sums of a lane are the halves lo = [0, ceil(L/2)) and hi = the rest.  A lane
+// whose bit `up` is clear keeps lo and hands hi to its partner, which keeps hi and hands lo back: ceil(L/2) cross-lane moves,
+// after which the lane holds the pair's sums of its half.  keep + received is own + partner's, the butterfly's v + shfl(v):
+// the sum a slot ends with is the butterfly's tree over the lanes (offsets 32, 16, ..., 1), bit for bit.
+template <int L>
+__device__ __forceinline__ void ikm_scatter_step(double* v, int offset, bool up) {
+  constexpr int lo = (L + 1) / 2;
+#pragma unroll
+  for (int i = 0; i < lo; ++i) {
+    const double high = lo + i < L ? v[lo + i] : 0.0;  // (L odd: hi is one short; that place holds a 0 nobody stores)
+    const double send = up ? v[i] : high, keep = up ? high : v[i];
+    v[i] = keep + __shfl_xor(send, offset);
+  }
+}
+// the moment that place j of a lane holds after the six steps 74 -> 37 -> 19 -> 10 -> 5 -> 3 -> 2, or -1 for a padding place
+__device__ __forceinline__ int ikm_scatter_index(int lane, int j) {
+  int at = j;
+  bool ok = true;
+  at += (lane & 1) ? 2 : 0, ok = ok && at < 3;
+  at += (lane & 2) ? 3 : 0, ok = ok && at < 5;
+  at += (lane & 4) ? 5 : 0, ok = ok && at < 10;
+  at += (lane & 8) ? 10 : 0, ok = ok && at < 19;
+  at += (lane & 16) ? 19 : 0, ok = ok && at < 37;
+  at += (lane & 32) ? 37 : 0, ok = ok && at < NJF_IKM_MOMENTS;
+  return ok ? at : -1;
+}
+
+template <bool BUTTERFLY>
+__global__ void __launch_bounds__(NJF_IK_THREADS) ikm_moments_kernel(IkArgs a) {
+  __shared__ int list[NJF_FIELD_TWISTS_CHUNK];
+  __shared__ int wave_count[NJF_TWIST_ITEMS][NJF_TWIST_THREADS / 64];
+  static_assert(NJF_IK_THREADS == NJF_TWIST_THREADS, "twist_compact is written for this workgroup size");
+  static_assert(NJF_IKM_MOMENTS == 74, "the reduce-scatter's halves are written out for 74 sums");
+  const PoseArgs& s = a.pose;
+  const int p = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (p >= counted_length(s.parts_count, s.K) || s.parts[p] < 0) return;  // (uniform; the finishing launch does not read it)
+  const int cnt = twist_compact(s.labels, s.parts[p], counted_length(s.count, s.n), list, wave_count);
+  const long long base = (long long)blockIdx.x * NJF_FIELD_TWISTS_CHUNK;
+  const double c0 = s.centroid[p * 3], c1 = s.centroid[p * 3 + 1], c2 = s.centroid[p * 3 + 2];
+  const int m0 = blockIdx.z * NJF_IK_PROBLEM_TILE, m1 = min(s.M, m0 + NJF_IK_PROBLEM_TILE);
+  for (int m = m0 + wave; m < m1; m += NJF_IK_THREADS / 64) {
+    const float* y = a.targets + (size_t)m * s.n * 3;
+    const float* wt = a.weights ? a.weights + (size_t)m * a.weight_stride : nullptr;
+    const float* qs = a.information + (size_t)m * a.information_stride;
+    double* out = a.partial + (((size_t)blockIdx.x * s.K + p) * s.M + m) * NJF_IKM_MOMENTS;  // p < K, m < M
+    if (cnt == 0) {  // (uniform) the sums of nothing
+      out[lane] = 0.0;
+      if (lane + 64 < NJF_IKM_MOMENTS) out[lane + 64] = 0.0;
+      continue;
+    }
+    double acc[NJF_IKM_MOMENTS];
+#pragma unroll
+    for (int k = 0; k < NJF_IKM_MOMENTS; ++k) acc[k] = 0.0;
+    for (int e = lane; e < cnt; e += 64) {
+      const long long i = base + list[e];  // a row below min(count, n)
+      const float w32 = wt ? wt[i] : 1.f;
+      const float y0 = y[i * 3], y1 = y[i * 3 + 1], y2 = y[i * 3 + 2];
+      float q32[6];
+      bool fine = w32 > 0.f && w32 < INFINITY && fabsf(y0) < INFINITY && fabsf(y1) < INFINITY && fabsf(y2) < INFINITY;
+#pragma unroll
+      for (int k = 0; k < 6; ++k) {
+        q32[k] = qs[i * 6 + k];
+        fine = fine && fabsf(q32[k]) < INFINITY;  // (a NaN in the information leaves the row out, like a NaN target)
+      }
+      if (fine) {
+        const double w = (double)w32;
+        const double xh[4] = {(double)s.xyz[i * 3] - c0, (double)s.xyz[i * 3 + 1] - c1, (double)s.xyz[i * 3 + 2] - c2, 1.0};
+        const double t[3] = {(double)y0 - c0, (double)y1 - c1, (double)y2 - c2};
+        const double q[6] = {(double)q32[0], (double)q32[1], (double)q32[2], (double)q32[3], (double)q32[4], (double)q32[5]};
+        double xx[10];  // x^_i x^_j, i <= j: 00 01 02 03 11 12 13 22 23 33
+        {
+          int f = 0;
+#pragma unroll
+          for (int r = 0; r < 4; ++r)
+#pragma unroll
+            for (int c = r; c < 4; ++c) xx[f++] = xh[r] * xh[c];
+        }
+        acc[0] += w;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) {
+          const double wq = w * q[k];
+#pragma unroll
+          for (int f = 0; f < 10; ++f) acc[NJF_IKM_P + 10 * k + f] += wq * xx[f];
+        }
+        const double b[3] = {(q[0] * t[0] + q[1] * t[1]) + q[2] * t[2], (q[1] * t[0] + q[3] * t[1]) + q[4] * t[2],
+                             (q[2] * t[0] + q[4] * t[1]) + q[5] * t[2]};
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+          const double wb = w * b[r];
+#pragma unroll
+          for (int c = 0; c < 4; ++c) acc[NJF_IKM_B + 4 * r + c] += wb * xh[c];
+        }
+        acc[NJF_IKM_E] += w * ((t[0] * b[0] + t[1] * b[1]) + t[2] * b[2]);
+      }
+    }
+    if (BUTTERFLY) {
+      double mine[2] = {0.0, 0.0};
+#pragma unroll
+      for (int k = 0; k < NJF_IKM_MOMENTS; ++k) {
+        const double v = twist_wave_sum(acc[k]);
+        if (lane == (k & 63)) mine[k >> 6] = v;
+      }
+      out[lane] = mine[0];
+      if (lane + 64 < NJF_IKM_MOMENTS) out[lane + 64] = mine[1];
+    } else {
+      ikm_scatter_step<74>(acc, 32, lane & 32);
+      ikm_scatter_step<37>(acc, 16, lane & 16);
+      ikm_scatter_step<19>(acc, 8, lane & 8);
+      ikm_scatter_step<10>(acc, 4, lane & 4);
+      ikm_scatter_step<5>(acc, 2, lane & 2);
+      ikm_scatter_step<3>(acc, 1, lane & 1);
+      const int k0 = ikm_scatter_index(lane, 0), k1 = ikm_scatter_index(lane, 1);  // every k < 74 is held by one (lane, place)
+      if (k0 >= 0) out[k0] = acc[0];
+      if (k1 >= 0) out[k1] = acc[1];
+    }
+  }
+}
+
 // moments[m][p] = the chunks' partials in ascending order, or zeros for a slot whose pose status is not 0; status and depth
+template <int NM>
 __global__ void __launch_bounds__(NJF_IK_THREADS) ik_finish_kernel(IkArgs a) {
   __shared__ int bits[NJF_FIELD_TWISTS_MAX_PARTS];
   __shared__ int result[2];
@@ -4121,13 +4251,13 @@ __global__ void __launch_bounds__(NJF_IK_THREADS) ik_finish_kernel(IkArgs a) {
   }
   __syncthreads();
   const bool live = result[0] == 0 && s.parts[p] >= 0;  // (status 0: p < active)
-  const int m0 = blockIdx.y * NJF_IK_FINISH_TILE, items = (min(s.M, m0 + NJF_IK_FINISH_TILE) - m0) * NJF_IK_MOMENTS;
+  const int m0 = blockIdx.y * NJF_IK_FINISH_TILE, items = (min(s.M, m0 + NJF_IK_FINISH_TILE) - m0) * NM;
   for (int e = tid; e < items; e += NJF_IK_THREADS) {
-    const int m = m0 + e / NJF_IK_MOMENTS, k = e % NJF_IK_MOMENTS;  // m < M
+    const int m = m0 + e / NM, k = e % NM;  // m < M
     double sum = 0.0;
     if (live)
-      for (int c = 0; c < a.chunks; ++c) sum += a.partial[(((size_t)c * s.K + p) * s.M + m) * NJF_IK_MOMENTS + k];
-    a.moments[((size_t)m * s.K + p) * NJF_IK_MOMENTS + k] = sum;
+      for (int c = 0; c < a.chunks; ++c) sum += a.partial[(((size_t)c * s.K + p) * s.M + m) * NM + k];
+    a.moments[((size_t)m * s.K + p) * NM + k] = sum;
   }
 }
 
@@ -4157,7 +4287,11 @@ __device__ __forceinline__ bool ik_entry_used(int e, int A) {  // does entry e b
 // G (into LDS) and derivative twists (into the workspace), walks up its parents composing both, turns its part's moments into
 // its share of cost, g and H, and a butterfly plus the four wave partials in wave order add the shares.  Then the A x A system
 // of the robust solve's Levenberg-Marquardt rule, in double; the candidate is evaluated in full and kept if it lowers L.
+// METRIC: the moments are the 74 of the anisotropic objective and the block that turns them into shares is the bilinear form
+// of section 20; the links, the chain, the reduction, the rule and the Gauss-Jordan are this one text.
+template <bool METRIC>
 __global__ void __launch_bounds__(NJF_IK_THREADS) ik_solve_kernel(IkArgs a) {
+  constexpr int NM = METRIC ? NJF_IKM_MOMENTS : NJF_IK_MOMENTS;
   __shared__ double G[NJF_FIELD_TWISTS_MAX_PARTS][12];
   __shared__ double red[NJF_IK_THREADS / 64][NJF_IK_ENTRIES];
   __shared__ double ev[NJF_IK_ENTRIES], cur[NJF_IK_ENTRIES];
@@ -4204,7 +4338,7 @@ __global__ void __launch_bounds__(NJF_IK_THREADS) ik_solve_kernel(IkArgs a) {
   // registers, and reads them back itself
   double* link_tw = a.link_twist + (size_t)m * 2 * K * A * 6;
   double* chain_tw = link_tw + (size_t)K * A * 6;
-  const double* mom = a.moments + ((size_t)m * K + tid) * NJF_IK_MOMENTS;
+  const double* mom = a.moments + ((size_t)m * K + tid) * NM;  // (read by counted threads only: tid < K)
 
   for (int it = 0;; ++it) {
     const float* pt = it == 0 ? u : cand;
@@ -4341,64 +4475,160 @@ __global__ void __launch_bounds__(NJF_IK_THREADS) ik_solve_kernel(IkArgs a) {
         const double v = twist_wave_sum(counted ? share : 0.0);
         if (lane == 0) red[wave][e] = v;
       };
-      double mo[NJF_IK_MOMENTS];
+      if constexpr (METRIC) {
+        // <X, Y> = sum X_ai Y_bj P[ab][ij]; G = (R | d - c), D_k = ([W_k]x R | W_k x d + U_k), 3 x 4 each, row-major.
+        // cost = <G, G> - 2 G.B + e, g_k = <D_k, G> - D_k.B, H_kl = <D_k, D_l>.  The moments are read where they are
+        // used: 74 of them and ten D_k do not fit in registers next to the chain.
+        const double* cp = s.centroid + (size_t)(tid < K ? tid : 0) * 3;
+        const double c3[3] = {cp[0], cp[1], cp[2]};
+        double d[3];
+        ik_matvec(T, c3, d);
 #pragma unroll
-      for (int k = 0; k < NJF_IK_MOMENTS; ++k) mo[k] = counted ? mom[k] : 0.0;
-      const double s0 = mo[0];
-      const double* s1 = mo + 1;
-      const double* t1 = mo + 10;
-      const double* C = mo + 13;
-      const double S2[9] = {mo[4], mo[5], mo[6], mo[5], mo[7], mo[8], mo[6], mo[8], mo[9]};
-      const double* cp = s.centroid + (size_t)(tid < K ? tid : 0) * 3;
-      const double c3[3] = {cp[0], cp[1], cp[2]};
-      double d[3], dt[3], rs1[3], k1[3];
-      ik_matvec(T, c3, d);
+        for (int c = 0; c < 3; ++c) d[c] += T[9 + c];
+        // PY = P Y: PY_ai = sum_bj P[ab][ij] Y_bj, the six blocks of P one after the other
+        auto apply = [&](const double* Y, double* PY) {
 #pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        d[c] += T[9 + c];
-        dt[c] = d[c] - c3[c];
-      }
-      ik_matvec(T, s1, rs1);
-      // M = R S2 R^T (symmetric), N = R C^T
-      double RS[9], Mx[9], Nx[9];
+          for (int e = 0; e < 12; ++e) PY[e] = 0.0;
 #pragma unroll
-      for (int r = 0; r < 3; ++r)
+          for (int r = 0; r < 3; ++r)
 #pragma unroll
-        for (int c = 0; c < 3; ++c) RS[r * 3 + c] = (T[r * 3] * S2[c] + T[r * 3 + 1] * S2[3 + c]) + T[r * 3 + 2] * S2[6 + c];
+            for (int c = r; c < 3; ++c) {
+              const int blk = r * 3 - r * (r - 1) / 2 + (c - r);  // xx xy xz yy yz zz
+              double Pe[10];
 #pragma unroll
-      for (int r = 0; r < 3; ++r)
+              for (int f = 0; f < 10; ++f) Pe[f] = mom[NJF_IKM_P + 10 * blk + f];
+#pragma unroll
+              for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                  const int lo = i < j ? i : j, hi = i < j ? j : i;
+                  const double pe = Pe[lo * 4 - lo * (lo - 1) / 2 + (hi - lo)];  // 00 01 02 03 11 12 13 22 23 33
+                  PY[r * 4 + i] += pe * Y[c * 4 + j];
+                  if (c != r) PY[c * 4 + i] += pe * Y[r * 4 + j];
+                }
+            }
+        };
+        const double* mine = chain_tw + (size_t)(tid < K ? tid : 0) * A * 6;
+        auto motion = [&](int ch, double* D) {  // D_ch, ch < A; read by counted threads only
+          const double W[3] = {mine[ch * 6], mine[ch * 6 + 1], mine[ch * 6 + 2]};
+          double Wxd[3];
+#pragma unroll
+          for (int c = 0; c < 3; ++c) {  // column c of [W]x R
+            const double col[3] = {T[c], T[3 + c], T[6 + c]};
+            double x[3];
+            ik_cross(W, col, x);
+            D[c] = x[0], D[4 + c] = x[1], D[8 + c] = x[2];
+          }
+          ik_cross(W, d, Wxd);
+#pragma unroll
+          for (int r = 0; r < 3; ++r) D[r * 4 + 3] = Wxd[r] + mine[ch * 6 + 3 + r];
+        };
+        double K1[12];  // P G - B
+        double cost = 0.0, s0 = 0.0;
+        if (counted) {
+          double Gm[12], PG[12];
+#pragma unroll
+          for (int r = 0; r < 3; ++r) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) Gm[r * 4 + c] = T[r * 3 + c];
+            Gm[r * 4 + 3] = d[r] - c3[r];
+          }
+          apply(Gm, PG);
+          double gg = 0.0, gb = 0.0;
+#pragma unroll
+          for (int e = 0; e < 12; ++e) {
+            const double be = mom[NJF_IKM_B + e];
+            gg += Gm[e] * PG[e];
+            gb += Gm[e] * be;
+            K1[e] = PG[e] - be;
+          }
+          cost = (gg - 2.0 * gb) + mom[NJF_IKM_E];
+          s0 = mom[0];
+        }
+        add(0, cost);
+        add(1, s0);
+        for (int l = 0; l < A; ++l) {
+          double PD[12];
+          double share = 0.0;
+          if (counted) {
+            double Dl[12];
+            motion(l, Dl);
+            apply(Dl, PD);
+#pragma unroll
+            for (int e = 0; e < 12; ++e) share += Dl[e] * K1[e];
+          }
+          add(NJF_IK_G + l, share);
+          for (int k = 0; k <= l; ++k) {
+            share = 0.0;
+            if (counted) {
+              double Dk[12];
+              motion(k, Dk);
+#pragma unroll
+              for (int e = 0; e < 12; ++e) share += Dk[e] * PD[e];
+            }
+            add(ik_triangle(k, l), share);
+          }
+        }
+      } else {
+        double mo[NJF_IK_MOMENTS];
+#pragma unroll
+        for (int k = 0; k < NJF_IK_MOMENTS; ++k) mo[k] = counted ? mom[k] : 0.0;
+        const double s0 = mo[0];
+        const double* s1 = mo + 1;
+        const double* t1 = mo + 10;
+        const double* C = mo + 13;
+        const double S2[9] = {mo[4], mo[5], mo[6], mo[5], mo[7], mo[8], mo[6], mo[8], mo[9]};
+        const double* cp = s.centroid + (size_t)(tid < K ? tid : 0) * 3;
+        const double c3[3] = {cp[0], cp[1], cp[2]};
+        double d[3], dt[3], rs1[3], k1[3];
+        ik_matvec(T, c3, d);
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-          Mx[r * 3 + c] = (RS[r * 3] * T[c * 3] + RS[r * 3 + 1] * T[c * 3 + 1]) + RS[r * 3 + 2] * T[c * 3 + 2];
-          Nx[r * 3 + c] = (T[r * 3] * C[c * 3] + T[r * 3 + 1] * C[c * 3 + 1]) + T[r * 3 + 2] * C[c * 3 + 2];
+          d[c] += T[9 + c];
+          dt[c] = d[c] - c3[c];
         }
-      const double trS = (mo[4] + mo[7]) + mo[9], trM = (Mx[0] + Mx[4]) + Mx[8], trN = (Nx[0] + Nx[4]) + Nx[8];
-      const double axial[3] = {Nx[5] - Nx[7], Nx[6] - Nx[2], Nx[1] - Nx[3]};  // tr([W]x N) = W . axial
-      add(0, ((trS + 2.0 * ik_dot(dt, rs1)) + s0 * ik_dot(dt, dt)) - 2.0 * trN - 2.0 * ik_dot(dt, t1) + mo[22]);
-      add(1, s0);
+        ik_matvec(T, s1, rs1);
+        // M = R S2 R^T (symmetric), N = R C^T
+        double RS[9], Mx[9], Nx[9];
 #pragma unroll
-      for (int c = 0; c < 3; ++c) k1[c] = (rs1[c] + s0 * dt[c]) - t1[c];
-      // beta_a = W_a x d + U_a; q_a = W_a x R s1.  tr(A_a S2 R^T) = tr([W_a]x M) is 0: M is symmetric
-      const double* mine = chain_tw + (size_t)(tid < K ? tid : 0) * A * 6;
-      auto twist = [&](int ch, double* W, double* beta) {  // ch < A
-        double Wxd[3];
+        for (int r = 0; r < 3; ++r)
 #pragma unroll
-        for (int c = 0; c < 3; ++c) W[c] = counted ? mine[ch * 6 + c] : 0.0;
-        ik_cross(W, d, Wxd);
+          for (int c = 0; c < 3; ++c) RS[r * 3 + c] = (T[r * 3] * S2[c] + T[r * 3 + 1] * S2[3 + c]) + T[r * 3 + 2] * S2[6 + c];
 #pragma unroll
-        for (int c = 0; c < 3; ++c) beta[c] = Wxd[c] + (counted ? mine[ch * 6 + 3 + c] : 0.0);
-      };
-      for (int i = 0; i < A; ++i) {
-        double Wi[3], bi[3], qi[3], MW[3];
-        twist(i, Wi, bi);
-        ik_cross(Wi, rs1, qi);
-        ik_matvec(Mx, Wi, MW);
-        add(NJF_IK_G + i, (ik_dot(qi, dt) - ik_dot(Wi, axial)) + ik_dot(bi, k1));
-        for (int j = i; j < A; ++j) {
-          double Wj[3], bj[3], qj[3];
-          twist(j, Wj, bj);
-          ik_cross(Wj, rs1, qj);
-          add(ik_triangle(i, j), ((ik_dot(Wi, Wj) * trM - ik_dot(Wj, MW)) + (ik_dot(bi, qj) + ik_dot(bj, qi))) + s0 * ik_dot(bi, bj));
+        for (int r = 0; r < 3; ++r)
+#pragma unroll
+          for (int c = 0; c < 3; ++c) {
+            Mx[r * 3 + c] = (RS[r * 3] * T[c * 3] + RS[r * 3 + 1] * T[c * 3 + 1]) + RS[r * 3 + 2] * T[c * 3 + 2];
+            Nx[r * 3 + c] = (T[r * 3] * C[c * 3] + T[r * 3 + 1] * C[c * 3 + 1]) + T[r * 3 + 2] * C[c * 3 + 2];
+          }
+        const double trS = (mo[4] + mo[7]) + mo[9], trM = (Mx[0] + Mx[4]) + Mx[8], trN = (Nx[0] + Nx[4]) + Nx[8];
+        const double axial[3] = {Nx[5] - Nx[7], Nx[6] - Nx[2], Nx[1] - Nx[3]};  // tr([W]x N) = W . axial
+        add(0, ((trS + 2.0 * ik_dot(dt, rs1)) + s0 * ik_dot(dt, dt)) - 2.0 * trN - 2.0 * ik_dot(dt, t1) + mo[22]);
+        add(1, s0);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) k1[c] = (rs1[c] + s0 * dt[c]) - t1[c];
+        // beta_a = W_a x d + U_a; q_a = W_a x R s1.  tr(A_a S2 R^T) = tr([W_a]x M) is 0: M is symmetric
+        const double* mine = chain_tw + (size_t)(tid < K ? tid : 0) * A * 6;
+        auto twist = [&](int ch, double* W, double* beta) {  // ch < A
+          double Wxd[3];
+#pragma unroll
+          for (int c = 0; c < 3; ++c) W[c] = counted ? mine[ch * 6 + c] : 0.0;
+          ik_cross(W, d, Wxd);
+#pragma unroll
+          for (int c = 0; c < 3; ++c) beta[c] = Wxd[c] + (counted ? mine[ch * 6 + 3 + c] : 0.0);
+        };
+        for (int i = 0; i < A; ++i) {
+          double Wi[3], bi[3], qi[3], MW[3];
+          twist(i, Wi, bi);
+          ik_cross(Wi, rs1, qi);
+          ik_matvec(Mx, Wi, MW);
+          add(NJF_IK_G + i, (ik_dot(qi, dt) - ik_dot(Wi, axial)) + ik_dot(bi, k1));
+          for (int j = i; j < A; ++j) {
+            double Wj[3], bj[3], qj[3];
+            twist(j, Wj, bj);
+            ik_cross(Wj, rs1, qj);
+            add(ik_triangle(i, j), ((ik_dot(Wi, Wj) * trM - ik_dot(Wj, MW)) + (ik_dot(bi, qj) + ik_dot(bj, qi))) + s0 * ik_dot(bi, bj));
+          }
         }
       }
     }
@@ -6924,31 +7154,36 @@ extern "C" int njf_field_pose(const int* parts, const int* parts_count, int num_
   return NJF_OK;
 }
 
-extern "C" int njf_field_commands(const int* parts, const int* parts_count, int num_parts, const int* part_status,
-                                  const double* centroid, const double* omega, const double* velocity, int action_dim,
-                                  const int* part_a, const int* part_b, const int* joints_count, int max_joints,
-                                  const double* anchor, const double* joint_omega, const double* joint_velocity, const int* parent,
-                                  const int* joint_of, const float* xyz, const int* labels, const int* count, int n,
-                                  const float* targets, int num_problems, const float* weights, int weights_per_problem,
-                                  const float* init, const float* lower, const float* upper, double reg, int iterations,
-                                  double damping, float* commands, double* cost, double* initial_cost, double* weight, int* steps,
-                                  double* gradient, int* status, int* out_part_status, int* depth, double* moments,
-                                  double* workspace, long long workspace_doubles, int phases, void* stream) {
+// njf_field_commands and njf_field_commands_metric: the checks and the three launches, `metric` choosing the 74-moment kernels
+static int ik_entry(bool metric, const float* information, int information_per_problem, const int* parts, const int* parts_count,
+                    int num_parts, const int* part_status, const double* centroid, const double* omega, const double* velocity,
+                    int action_dim, const int* part_a, const int* part_b, const int* joints_count, int max_joints,
+                    const double* anchor, const double* joint_omega, const double* joint_velocity, const int* parent,
+                    const int* joint_of, const float* xyz, const int* labels, const int* count, int n, const float* targets,
+                    int num_problems, const float* weights, int weights_per_problem, const float* init, const float* lower,
+                    const float* upper, double reg, int iterations, double damping, float* commands, double* cost,
+                    double* initial_cost, double* weight, int* steps, double* gradient, int* status, int* out_part_status,
+                    int* depth, double* moments, double* workspace, long long workspace_doubles, int phases, void* stream) {
   if (num_parts < 1 || num_parts > NJF_FIELD_TWISTS_MAX_PARTS) return NJF_E_VALUE;
   if (action_dim < 1 || action_dim > NJF_MAX_ACTION_DIM) return NJF_E_VALUE;
   if (num_problems < 1 || num_problems > NJF_FIELD_POSE_MAX_COMMANDS) return NJF_E_VALUE;
   const bool tree = part_a || part_b || joints_count || anchor || joint_omega || joint_velocity || parent || joint_of;
   if (tree && (max_joints < 1 || max_joints > NJF_FIELD_JOINTS_MAX)) return NJF_E_VALUE;
-  if (phases < 1 || phases > NJF_FIELD_COMMANDS_ALL) return NJF_E_VALUE;
+  const bool butterfly = metric && (phases & NJF_FIELD_COMMANDS_METRIC_BUTTERFLY);
+  if (butterfly) phases &= ~NJF_FIELD_COMMANDS_METRIC_BUTTERFLY;  // (a modifier of the moments phase)
+  if (phases < 1 || phases > NJF_FIELD_COMMANDS_ALL || (butterfly && !(phases & NJF_FIELD_COMMANDS_MOMENTS))) return NJF_E_VALUE;
+  if (metric && (information_per_problem < 0 || information_per_problem > 1)) return NJF_E_VALUE;
   if (iterations < 0 || iterations > NJF_FIELD_COMMANDS_MAX_ITERATIONS) return NJF_E_VALUE;
   if (!(damping > 0.0) || !(reg >= 0.0) || weights_per_problem < 0 || weights_per_problem > 1) return NJF_E_VALUE;
   if (n < 0) return NJF_E_SHAPE;
-  if (workspace_doubles < NJF_FIELD_COMMANDS_WORKSPACE(num_problems, num_parts, action_dim, n)) return NJF_E_SHAPE;
+  if (workspace_doubles < (metric ? NJF_FIELD_COMMANDS_METRIC_WORKSPACE(num_problems, num_parts, action_dim, n)
+                                  : NJF_FIELD_COMMANDS_WORKSPACE(num_problems, num_parts, action_dim, n)))
+    return NJF_E_SHAPE;
   if (!parts || !part_status || !centroid || !omega || !velocity || !moments || !out_part_status || !depth || !workspace)
     return NJF_E_NULL;
   if (tree && (!part_a || !part_b || !anchor || !joint_omega || !joint_velocity || !parent || !joint_of)) return NJF_E_NULL;
   const bool sums = phases & NJF_FIELD_COMMANDS_MOMENTS, solve = phases & NJF_FIELD_COMMANDS_SOLVE;
-  if (sums && n > 0 && (!xyz || !labels || !targets)) return NJF_E_NULL;
+  if (sums && n > 0 && (!xyz || !labels || !targets || (metric && !information))) return NJF_E_NULL;
   if (solve && (!commands || !cost || !initial_cost || !weight || !steps || !gradient || !status)) return NJF_E_NULL;
   IkArgs a;
   PoseArgs& p = a.pose;
@@ -6984,6 +7219,8 @@ extern "C" int njf_field_commands(const int* parts, const int* parts_count, int 
   a.targets = targets;
   a.weights = weights;
   a.weight_stride = weights_per_problem ? n : 0;
+  a.information = information;
+  a.information_stride = information_per_problem ? 6LL * n : 0;
   a.init = init;
   a.lower = lower;
   a.upper = upper;
@@ -6992,7 +7229,7 @@ extern "C" int njf_field_commands(const int* parts, const int* parts_count, int 
   a.iterations = iterations;
   a.chunks = (int)(((long long)n + NJF_FIELD_TWISTS_CHUNK - 1) / NJF_FIELD_TWISTS_CHUNK);
   a.partial = workspace;
-  a.link_twist = workspace + (size_t)NJF_IK_MOMENTS * a.chunks * num_problems * num_parts;  // [M][2][K][A][6]
+  a.link_twist = workspace + (size_t)(metric ? NJF_IKM_MOMENTS : NJF_IK_MOMENTS) * a.chunks * num_problems * num_parts;  // [M][2][K][A][6]
   a.moments = moments;
   a.commands = commands;
   a.cost = cost;
@@ -7008,18 +7245,58 @@ extern "C" int njf_field_commands(const int* parts, const int* parts_count, int 
   if (sums) {
     if (n > 0) {  // chunks <= 2^31 / 4096, K <= 256, tiles <= 4096
       const dim3 grid((unsigned)a.chunks, (unsigned)num_parts, (unsigned)((num_problems + NJF_IK_PROBLEM_TILE - 1) / NJF_IK_PROBLEM_TILE));
-      ik_moments_kernel<<<grid, NJF_IK_THREADS, 0, s>>>(a);
+      if (!metric) ik_moments_kernel<<<grid, NJF_IK_THREADS, 0, s>>>(a);
+      else if (butterfly) ikm_moments_kernel<true><<<grid, NJF_IK_THREADS, 0, s>>>(a);
+      else ikm_moments_kernel<false><<<grid, NJF_IK_THREADS, 0, s>>>(a);
       if ((rc = launch_status())) return rc;
     }
     const dim3 grid((unsigned)num_parts, (unsigned)((num_problems + NJF_IK_FINISH_TILE - 1) / NJF_IK_FINISH_TILE));
-    ik_finish_kernel<<<grid, NJF_IK_THREADS, 0, s>>>(a);
+    if (metric) ik_finish_kernel<NJF_IKM_MOMENTS><<<grid, NJF_IK_THREADS, 0, s>>>(a);
+    else ik_finish_kernel<NJF_IK_MOMENTS><<<grid, NJF_IK_THREADS, 0, s>>>(a);
     if ((rc = launch_status())) return rc;
   }
   if (solve) {
-    ik_solve_kernel<<<num_problems, NJF_IK_THREADS, 0, s>>>(a);
+    if (metric) ik_solve_kernel<true><<<num_problems, NJF_IK_THREADS, 0, s>>>(a);
+    else ik_solve_kernel<false><<<num_problems, NJF_IK_THREADS, 0, s>>>(a);
     if ((rc = launch_status())) return rc;
   }
   return NJF_OK;
+}
+
+extern "C" int njf_field_commands(const int* parts, const int* parts_count, int num_parts, const int* part_status,
+                                  const double* centroid, const double* omega, const double* velocity, int action_dim,
+                                  const int* part_a, const int* part_b, const int* joints_count, int max_joints,
+                                  const double* anchor, const double* joint_omega, const double* joint_velocity, const int* parent,
+                                  const int* joint_of, const float* xyz, const int* labels, const int* count, int n,
+                                  const float* targets, int num_problems, const float* weights, int weights_per_problem,
+                                  const float* init, const float* lower, const float* upper, double reg, int iterations,
+                                  double damping, float* commands, double* cost, double* initial_cost, double* weight, int* steps,
+                                  double* gradient, int* status, int* out_part_status, int* depth, double* moments,
+                                  double* workspace, long long workspace_doubles, int phases, void* stream) {
+  return ik_entry(false, nullptr, 0, parts, parts_count, num_parts, part_status, centroid, omega, velocity, action_dim, part_a, part_b,
+                  joints_count, max_joints, anchor, joint_omega, joint_velocity, parent, joint_of, xyz, labels, count, n, targets,
+                  num_problems, weights, weights_per_problem, init, lower, upper, reg, iterations, damping, commands, cost,
+                  initial_cost, weight, steps, gradient, status, out_part_status, depth, moments, workspace, workspace_doubles,
+                  phases, stream);
+}
+
+extern "C" int njf_field_commands_metric(const int* parts, const int* parts_count, int num_parts, const int* part_status,
+                                         const double* centroid, const double* omega, const double* velocity, int action_dim,
+                                         const int* part_a, const int* part_b, const int* joints_count, int max_joints,
+                                         const double* anchor, const double* joint_omega, const double* joint_velocity,
+                                         const int* parent, const int* joint_of, const float* xyz, const int* labels,
+                                         const int* count, int n, const float* targets, const float* information,
+                                         int information_per_problem, int num_problems, const float* weights,
+                                         int weights_per_problem, const float* init, const float* lower, const float* upper,
+                                         double reg, int iterations, double damping, float* commands, double* cost,
+                                         double* initial_cost, double* weight, int* steps, double* gradient, int* status,
+                                         int* out_part_status, int* depth, double* moments, double* workspace,
+                                         long long workspace_doubles, int phases, void* stream) {
+  return ik_entry(true, information, information_per_problem, parts, parts_count, num_parts, part_status, centroid, omega, velocity,
+                  action_dim, part_a, part_b, joints_count, max_joints, anchor, joint_omega, joint_velocity, parent, joint_of, xyz,
+                  labels, count, n, targets, num_problems, weights, weights_per_problem, init, lower, upper, reg, iterations, damping,
+                  commands, cost, initial_cost, weight, steps, gradient, status, out_part_status, depth, moments, workspace,
+                  workspace_doubles, phases, stream);
 }
 
 extern "C" int njf_field_nearest(const float* observed, const int* observed_count, int num_observed, int points,

@@ -23,7 +23,7 @@ from typing import Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import hip
+from . import geometry, hip
 from .decoder import ActionDecoderFlowMlp, ActionDecoderJacobian, PixelEncoding, _cameras, _map_of
 from .inference import jacobian_color_map as _cm
 
@@ -971,7 +971,13 @@ def solve_commands(twists: FieldTwists, xyz: torch.Tensor, labels: torch.Tensor,
     ``upper`` (a number, fp32 ``[A]`` or ``[M, A]``) box it, ``reg`` weighs ``|u|^2 / A``.  One pass over the rows forms 23 moments
     per problem and part; the ``iterations`` Levenberg-Marquardt rounds that follow never look at a row again.  In double,
     without atomics or a host read: equal bytes from call to call, capturable."""
-    name = "solve_commands"
+    return _solve("solve_commands", twists, xyz, labels, targets, None, False, joints, tree, weights, count, init, lower, upper, reg,
+                  iterations, damping)
+
+
+def _solve(name: str, twists, xyz, labels, targets, information, metric: bool, joints, tree, weights, count, init, lower, upper, reg,
+           iterations, damping):
+    """``solve_commands`` and, with ``metric``, ``solve_commands_metric``: the checks, the outputs and the launch."""
     k, a_dim = _check_twists(name, twists)
     n = _check_points(name, xyz, labels, None, a_dim)
     if not torch.is_tensor(targets) or targets.dtype != torch.float32 or targets.dim() != 3 or tuple(targets.shape[1:]) != (n, 3):
@@ -979,22 +985,32 @@ def solve_commands(twists: FieldTwists, xyz: torch.Tensor, labels: torch.Tensor,
     m = targets.shape[0]
     if not 1 <= m <= hip.FIELD_POSE_MAX_COMMANDS:
         raise ValueError(f"{name}: 1 to {hip.FIELD_POSE_MAX_COMMANDS} target sets (got {m})")
+    if metric:
+        if not torch.is_tensor(information) or information.dtype != torch.float32 \
+                or tuple(information.shape) not in ((n, 6), (m, n, 6)):
+            raise ValueError(f"{name}: information must be fp32 [{n}, 6] or [{m}, {n}, 6]")
+        if information.device != targets.device:
+            raise ValueError(f"{name}: information must live on the device of targets")
     parts_count, links, count, lower, upper = _check_solver(name, twists, xyz, labels, m, n, k, a_dim, targets, "targets", joints,
                                                             tree, weights, count, init, lower, upper, reg, iterations, damping)
     if targets.device.type != "cuda":
         raise ValueError(f"{name}: the tensors must live on the GPU; there is no CPU path")
     dev = targets.device
     i32, f64 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.float64, device=dev)
-    fit = FieldCommands(commands=torch.empty(m, a_dim, dtype=torch.float32, device=dev), cost=torch.empty(m, **f64),
-                        initial_cost=torch.empty(m, **f64), weight=torch.empty(m, **f64), steps=torch.empty(m, **i32),
-                        gradient=torch.empty(m, a_dim, **f64), status=torch.empty(m, **i32), part_status=torch.empty(k, **i32),
-                        depth=torch.empty(k, **i32), moments=torch.empty(m, k, hip.FIELD_COMMANDS_MOMENTS_PER_PART, **f64))
+    per_part = hip.FIELD_COMMANDS_METRIC_MOMENTS_PER_PART if metric else hip.FIELD_COMMANDS_MOMENTS_PER_PART
+    fit = (FieldMetricCommands if metric else FieldCommands)(
+        commands=torch.empty(m, a_dim, dtype=torch.float32, device=dev), cost=torch.empty(m, **f64),
+        initial_cost=torch.empty(m, **f64), weight=torch.empty(m, **f64), steps=torch.empty(m, **i32),
+        gradient=torch.empty(m, a_dim, **f64), status=torch.empty(m, **i32), part_status=torch.empty(k, **i32),
+        depth=torch.empty(k, **i32), moments=torch.empty(m, k, per_part, **f64))
     points = dict(xyz=xyz.contiguous(), labels=labels.contiguous(), count=count, targets=targets.contiguous())
-    hip.field_commands(twists.labels.contiguous(), twists.status.contiguous(), twists.centroid.contiguous(),
-                       twists.omega.contiguous(), twists.velocity.contiguous(), points, {f: getattr(fit, f) for f in fit.__dataclass_fields__},
-                       parts_count=parts_count, joints=links, weights=None if weights is None else weights.contiguous(),
-                       init=None if init is None else init.contiguous(), lower=lower, upper=upper, reg=reg,
-                       iterations=iterations, damping=damping)
+    if metric:
+        points["information"] = information.contiguous()
+    (hip.field_commands_metric if metric else hip.field_commands)(
+        twists.labels.contiguous(), twists.status.contiguous(), twists.centroid.contiguous(), twists.omega.contiguous(),
+        twists.velocity.contiguous(), points, {f: getattr(fit, f) for f in fit.__dataclass_fields__}, parts_count=parts_count,
+        joints=links, weights=None if weights is None else weights.contiguous(), init=None if init is None else init.contiguous(),
+        lower=lower, upper=upper, reg=reg, iterations=iterations, damping=damping)
     return fit
 
 
@@ -1228,6 +1244,225 @@ def cloud_registration(cloud: FieldPointCloud, labels: torch.Tensor, twists: Fie
                                  upper=upper, reg=reg, rounds=rounds, iterations=iterations, damping=damping)
     except ValueError as err:
         raise ValueError(str(err).replace("register_commands:", f"{name}:", 1).replace("cell_grid:", f"{name}:", 1)) from None
+
+
+# ---- commands from pixel rays and planes: a 3x3 information per target -------------------------------------
+@dataclass
+class FieldMetricCommands:
+    """``FieldCommands`` of the anisotropic objective (``solve_commands_metric``; include/njf_hip.h: njf_field_commands_metric):
+    ``cost`` is the weighted mean of ``z^T Q z``, ``z`` the residual of a row and ``Q`` its 3 x 3 information -- a squared
+    distance to a ray or a plane when ``Q`` is ``I - d d^T`` or ``n n^T``.  ``moments`` are the 74 weighted moments per problem
+    and part about the part's centroid: s0, P [6 x 10], B [3 x 4], e -- all the solver reads of the rows."""
+
+    commands: torch.Tensor       # [M, A] fp32
+    cost: torch.Tensor           # [M] float64: the weighted mean of z^T Q z at commands
+    initial_cost: torch.Tensor   # [M] float64: the same at the start
+    weight: torch.Tensor         # [M] float64: W_m, the sum of the counted rows' weights
+    steps: torch.Tensor          # [M] int32: accepted steps
+    gradient: torch.Tensor       # [M, A] float64: the half-gradient with the regulariser at commands
+    status: torch.Tensor         # [M] int32
+    part_status: torch.Tensor    # [K] int32
+    depth: torch.Tensor          # [K] int32
+    moments: torch.Tensor        # [M, K, 74] float64
+
+    def rms(self) -> torch.Tensor:
+        """``[M]`` float64: the root of the weighted mean of ``z^T Q z`` at ``commands``."""
+        return self.cost.sqrt()
+
+
+def solve_commands_metric(twists: FieldTwists, xyz: torch.Tensor, labels: torch.Tensor, targets: torch.Tensor,
+                          information: torch.Tensor, *, joints: Optional[FieldJoints] = None, tree=None,
+                          weights: Optional[torch.Tensor] = None, count: Optional[torch.Tensor] = None,
+                          init: Optional[torch.Tensor] = None, lower=None, upper=None, reg: float = 0.0, iterations: int = 20,
+                          damping: float = 1e-3) -> FieldMetricCommands:
+    """``solve_commands`` with an anisotropic error per row: row i of problem m costs ``w z^T Q z``, ``z``
+    its residual against ``targets[m, i]`` and ``Q`` the symmetric 3 x 3 ``information`` of the row, fp32 ``[n, 6]`` or ``[M, n,
+    6]`` as ``[xx xy xz yy yz zz]``.  ``ray_targets`` gives targets and information for 2-D keypoints in a calibrated camera (a
+    pixel holds a point to a ray), ``plane_information`` for point-to-plane matches, ``ray_information`` for a depth camera
+    whose noise is larger along the ray; the identity is ``solve_commands``' objective.  ``information`` is not tested for
+    definiteness: that is the caller's contract.  A row with a NaN in its information is left out, like one with a NaN
+    target; every other argument is ``solve_commands``'.  One pass over the rows forms 74 moments per problem and part; the
+    iterations never look at a row again.  In double, without atomics or a host read: equal bytes from call to call,
+    capturable."""
+    return _solve("solve_commands_metric", twists, xyz, labels, targets, information, True, joints, tree, weights, count, init, lower,
+                  upper, reg, iterations, damping)
+
+
+def cloud_commands_metric(cloud: FieldPointCloud, labels: torch.Tensor, twists: FieldTwists, targets: torch.Tensor,
+                          information: torch.Tensor, *, joints: Optional[FieldJoints] = None, tree=None,
+                          weights: Optional[torch.Tensor] = None, init: Optional[torch.Tensor] = None, lower=None, upper=None,
+                          reg: float = 0.0, iterations: int = 20, damping: float = 1e-3) -> FieldMetricCommands:
+    """``solve_commands_metric`` on the rows of an extracted cloud: ``cloud.xyz`` and ``cloud.count`` with ``labels`` ``[n]`` int32,
+    the per-row result of ``cloud_components``."""
+    if not isinstance(cloud, FieldPointCloud):
+        raise ValueError("cloud_commands_metric: cloud must be a FieldPointCloud")
+    try:
+        return solve_commands_metric(twists, cloud.xyz, labels, targets, information, joints=joints, tree=tree, weights=weights,
+                                     count=cloud.count, init=init, lower=lower, upper=upper, reg=reg, iterations=iterations,
+                                     damping=damping)
+    except ValueError as err:
+        raise ValueError(str(err).replace("solve_commands_metric:", "cloud_commands_metric:", 1)) from None
+
+
+INFORMATION_FLOOR = 2.0 ** -21   # the least weight in the free directions that keeps the fp32 matrices positive semi-definite
+
+
+def _outer_plus_identity(name: str, what: str, v, outer: float, identity: float) -> torch.Tensor:
+    """``outer u u^T + identity I`` packed ``[..., 6]``, ``u`` the normalised ``v`` ``[..., 3]`` (fp32); arithmetic on the device only."""
+    if not torch.is_tensor(v) or v.dtype != torch.float32 or v.dim() < 1 or v.shape[-1] != 3:
+        raise ValueError(f"{name}: {what} must be fp32 [..., 3]")
+    x, y, z = (v / torch.linalg.vector_norm(v, dim=-1, keepdim=True)).unbind(-1)
+    return torch.stack([outer * (x * x) + identity, outer * (x * y), outer * (x * z), outer * (y * y) + identity, outer * (y * z),
+                        outer * (z * z) + identity], dim=-1)
+
+
+def plane_information(normals: torch.Tensor) -> torch.Tensor:
+    """``n n^T`` packed ``[..., 6]`` (``[xx xy xz yy yz zz]``) for ``normals`` ``[..., 3]`` (fp32, normalised here): the information
+    of a point-to-plane match -- the residual counts along the normal only and the match may slide in the tangent plane.
+    Exactly: ``(1 - f) n n^T + f I`` with ``f = INFORMATION_FLOOR`` = 2^-21, for the reason given at ``ray_information``: the fp32
+    ``n n^T`` alone has eigenvalues of either sign near 3e-8 in the plane, where the residual of a slid match is large."""
+    return _outer_plus_identity("plane_information", "normals", normals, 1.0 - INFORMATION_FLOOR, INFORMATION_FLOOR)
+
+
+def ray_information(directions: torch.Tensor, along: float = 0.0) -> torch.Tensor:
+    """``I - (1 - along) d d^T`` packed ``[..., 6]`` for ``directions`` ``[..., 3]`` (fp32): weight 1 across the ray and ``along``
+    along it.  0 is a pixel ray (the depth is free); a depth camera whose noise along the ray is s times the noise across it
+    has ``along = 1 / s^2``; 1 is the identity.  ``along`` below ``INFORMATION_FLOOR`` = 2^-21 counts as that: in fp32 ``|d|^2`` is
+    1 only to a few 1e-7, so ``I - d d^T`` itself comes out indefinite along the ray in about every other row, and the residual
+    along the ray does not vanish at the solution (``ray_targets``' target is the foot of the UN-posed point).  The cost of a
+    good fit then falls below 0, where the solver clamps it and stops telling fits apart (on the planted chain: a command 9e-5
+    off).  The floor, with the directions normalised here once more, keeps every matrix positive semi-definite; what it
+    adds to the objective is a pull of weight 5e-7 along the ray."""
+    name = "ray_information"
+    if isinstance(along, bool) or not isinstance(along, (int, float)) or not 0.0 <= along <= 1.0:
+        raise ValueError(f"{name}: along must be a number in [0, 1] (got {along})")
+    return _outer_plus_identity(name, "directions", directions, -(1.0 - max(float(along), INFORMATION_FLOOR)), 1.0)
+
+
+def ray_targets(xyz: torch.Tensor, coordinates_xy: torch.Tensor, intrinsics: torch.Tensor, cam2world: torch.Tensor):
+    """``(targets [M, n, 3], information [M, n, 6])`` of ``solve_commands_metric`` for 2-D observations of the rows ``xyz`` ``[n,
+    3]`` (fp32): ``coordinates_xy`` ``[M, n, 2]`` are the pixels of the rows in the package's normalised convention (x right, y
+    down, in [0, 1]; ``geometry.get_pixel_coordinates``), ``intrinsics`` ``[M, 3, 3]`` normalised and ``cam2world`` ``[M, 4, 4]``
+    the camera of every problem.  The ray of a pixel is ``geometry.get_world_rays``' (origin o, unit direction d); the
+    information is ``ray_information(d)``, ``I - d d^T`` up to its floor, and the target the FOOT of ``xyz[i]`` on its ray, ``o + d (d . (x - o))``.  Any point of the ray
+    gives the same objective; the foot keeps the moments at the body's scale however far the camera is.  A row whose
+    coordinate is not finite gets a NaN target: it is free.  Several cameras of one problem: concatenate the rows -- ``xyz``
+    and ``labels`` repeated once per camera, each copy with its camera's targets and information.  Torch ops on the device
+    after the ray launch, no host read."""
+    name = "ray_targets"
+    if not torch.is_tensor(xyz) or xyz.dtype != torch.float32 or xyz.dim() != 2 or xyz.shape[1] != 3:
+        raise ValueError(f"{name}: xyz must be fp32 [n, 3]")
+    n = xyz.shape[0]
+    if not torch.is_tensor(coordinates_xy) or coordinates_xy.dtype != torch.float32 or coordinates_xy.dim() != 3 \
+            or tuple(coordinates_xy.shape[1:]) != (n, 2) or coordinates_xy.shape[0] < 1:
+        raise ValueError(f"{name}: coordinates_xy must be fp32 [M, {n}, 2]")
+    m = coordinates_xy.shape[0]
+    if not torch.is_tensor(intrinsics) or intrinsics.dtype != torch.float32 or tuple(intrinsics.shape) != (m, 3, 3):
+        raise ValueError(f"{name}: intrinsics must be fp32 [{m}, 3, 3]")
+    if not torch.is_tensor(cam2world) or cam2world.dtype != torch.float32 or tuple(cam2world.shape) != (m, 4, 4):
+        raise ValueError(f"{name}: cam2world must be fp32 [{m}, 4, 4]")
+    for what, t in (("coordinates_xy", coordinates_xy), ("intrinsics", intrinsics), ("cam2world", cam2world)):
+        if t.device != xyz.device:
+            raise ValueError(f"{name}: {what} must live on the device of xyz")
+    seen = torch.isfinite(coordinates_xy).all(dim=-1, keepdim=True)
+    origins, directions = geometry.get_world_rays(torch.where(seen, coordinates_xy, torch.full_like(coordinates_xy, 0.5)), intrinsics,
+                                                  cam2world)
+    directions = directions / torch.linalg.vector_norm(directions, dim=-1, keepdim=True)
+    along = ((xyz[None] - origins) * directions).sum(dim=-1, keepdim=True)
+    foot = origins + directions * along
+    return torch.where(seen, foot, torch.full_like(foot, float("nan"))), ray_information(directions)
+
+
+def register_commands_metric(twists: FieldTwists, xyz: torch.Tensor, labels: torch.Tensor, observed: torch.Tensor,
+                             observed_information: torch.Tensor, cells: FieldGrid, max_distance: float, *,
+                             joints: Optional[FieldJoints] = None, tree=None, observed_count: Optional[torch.Tensor] = None,
+                             count: Optional[torch.Tensor] = None, weights: Optional[torch.Tensor] = None,
+                             init: Optional[torch.Tensor] = None, lower=None, upper=None, reg: float = 0.0, rounds: int = 8,
+                             iterations: int = 3, damping: float = 1e-3) -> FieldRegistration:
+    """``register_commands`` with an information per observed point: ``observed_information`` fp32 ``[T,
+    6]`` or ``[Mo, T, 6]`` holds the symmetric 3 x 3 of every point of ``observed`` -- ``plane_information`` of the cloud's
+    normals makes it point-to-plane registration, in which a match may slide along the surface.  The loop is
+    ``register_commands``' with one more step per round: after ``nearest_points``, ``information[m, i] =
+    observed_information[mo, max(index[m, i], 0)]`` (a torch gather; a row without a match is free through its NaN target), and
+    ``solve_commands_metric`` takes the place of ``solve_commands``.  The correspondences stay the Euclidean arg-min.  Returns a
+    ``FieldRegistration`` whose ``fit`` is a ``FieldMetricCommands``.  No host read: capturable after one eager call."""
+    name = "register_commands_metric"
+    k, a_dim = _check_twists(name, twists)
+    n = _check_points(name, xyz, labels, None, a_dim)
+    if isinstance(rounds, bool) or not isinstance(rounds, int) or not 1 <= rounds <= 1000:
+        raise ValueError(f"{name}: rounds must be an integer in [1, 1000] (got {rounds})")
+    starts = init.shape[0] if torch.is_tensor(init) and init.dim() == 2 else 1
+    observed, m, observed_count, count = _check_nearest(name, observed, cells, max_distance, observed_count, count, None, n, 1, xyz,
+                                                        "xyz", m_other=max(starts, 1))
+    mo, t = observed.shape[:2]
+    if not torch.is_tensor(observed_information) or observed_information.dtype != torch.float32 \
+            or tuple(observed_information.shape) not in ((t, 6), (mo, t, 6)):
+        raise ValueError(f"{name}: observed_information must be fp32 [{t}, 6] or [{mo}, {t}, 6]")
+    if observed_information.device != xyz.device:
+        raise ValueError(f"{name}: observed_information must live on the device of xyz")
+    parts_count, links, count, lower_box, upper_box = _check_solver(name, twists, xyz, labels, m, n, k, a_dim, xyz, "xyz", joints, tree,
+                                                                    weights, count, init, lower, upper, reg, iterations, damping)
+    if xyz.device.type != "cuda":
+        raise ValueError(f"{name}: the tensors must live on the GPU; there is no CPU path")
+    dev = xyz.device
+    u = torch.zeros(m, a_dim, dtype=torch.float32, device=dev) if init is None else init
+    if lower_box is not None:
+        u = torch.maximum(u, lower_box)
+    if upper_box is not None:
+        u = torch.minimum(u, upper_box)
+    out = FieldRegistration(fit=None, matches=None, commands_history=torch.empty(rounds, m, a_dim, dtype=torch.float32, device=dev),
+                            cost_history=torch.empty(rounds, m, dtype=torch.float64, device=dev),
+                            found_history=torch.empty(rounds, m, dtype=torch.int32, device=dev))
+    labels_c = labels.contiguous()
+    observed_count = None if observed_count is None else observed_count.contiguous()
+    source = observed_information.reshape(-1, t, 6).expand(m, t, 6)          # [T, 6] or Mo = 1: one table for every problem
+    workspace = torch.empty(hip.field_nearest_workspace(mo, cells.num_nodes, t), dtype=torch.int32, device=dev)
+    _nearest_launch(observed.contiguous(), (1, n), cells, max_distance, m, None, observed_count, None, None, hip.FIELD_NEAREST_BUILD,
+                    workspace)
+    for r in range(rounds):
+        _, posed = _pose(name, twists, u, joints, tree, points=(xyz, labels, count, None))
+        near = _nearest_outputs(m, n, dev)
+        _nearest_launch((mo, t), posed, cells, max_distance, m, near, observed_count, count, labels_c, hip.FIELD_NEAREST_QUERY,
+                        workspace)
+        information = torch.gather(source, 1, near.index.clamp_min(0).long()[:, :, None].expand(m, n, 6))
+        fit = solve_commands_metric(twists, xyz, labels, near.matched, information, joints=joints, tree=tree, weights=weights,
+                                    count=count, init=u, lower=lower, upper=upper, reg=reg, iterations=iterations, damping=damping)
+        out.commands_history[r].copy_(fit.commands)
+        out.cost_history[r].copy_(fit.cost)
+        out.found_history[r].copy_(near.found)
+        out.fit, out.matches, u = fit, near, fit.commands
+    return out
+
+
+def cloud_registration_metric(cloud: FieldPointCloud, labels: torch.Tensor, twists: FieldTwists, observed: torch.Tensor,
+                              observed_information: torch.Tensor, max_distance: float, *, cells: Optional[FieldGrid] = None,
+                              joints: Optional[FieldJoints] = None, tree=None, observed_count: Optional[torch.Tensor] = None,
+                              weights: Optional[torch.Tensor] = None, init: Optional[torch.Tensor] = None, lower=None, upper=None,
+                              reg: float = 0.0, rounds: int = 8, iterations: int = 3, damping: float = 1e-3) -> FieldRegistration:
+    """``register_commands_metric`` on the rows of an extracted cloud, as ``cloud_registration`` is ``register_commands`` on
+    them; ``cells=None`` takes ``cell_grid`` over the bounds of ``cloud.grid`` with the largest of its steps as the cell."""
+    name = "cloud_registration_metric"
+    if not isinstance(cloud, FieldPointCloud):
+        raise ValueError(f"{name}: cloud must be a FieldPointCloud")
+    try:
+        if cells is None:
+            cells = _cloud_cells(cloud, "register_commands_metric")
+        return register_commands_metric(twists, cloud.xyz, labels, observed, observed_information, cells, max_distance,
+                                        joints=joints, tree=tree, observed_count=observed_count, count=cloud.count, weights=weights,
+                                        init=init, lower=lower, upper=upper, reg=reg, rounds=rounds, iterations=iterations,
+                                        damping=damping)
+    except ValueError as err:
+        raise ValueError(str(err).replace("register_commands_metric:", f"{name}:", 1).replace("cell_grid:", f"{name}:", 1)) from None
+
+
+def _cloud_cells(cloud: FieldPointCloud, name: str) -> FieldGrid:
+    """``cell_grid`` over the bounds of ``cloud.grid`` with the largest of its steps as the cell."""
+    grid = cloud.grid
+    if not isinstance(grid, FieldGrid):
+        raise ValueError(f"{name}: cloud.grid must be a FieldGrid")
+    upper_corner = tuple(o + s * (d - 1) for o, s, d in zip(grid.origin, grid.step, grid.dims))
+    return cell_grid(tuple(min(o, u) for o, u in zip(grid.origin, upper_corner)),
+                     tuple(max(o, u) for o, u in zip(grid.origin, upper_corner)), max(abs(s) for s in grid.step))
 
 
 # ---- coarse-to-fine band (DESIGN.md section 14) ----------------------------------------------------------------------------------

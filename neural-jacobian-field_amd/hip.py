@@ -176,6 +176,9 @@ _SIGNATURES = {
     "njf_field_commands": ([_vp, _vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                             C.c_int, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp, C.c_double, C.c_int, C.c_double] + [_vp] * 11 +
                            [C.c_longlong, C.c_int, _vp], C.c_int),
+    "njf_field_commands_metric": ([_vp, _vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                   _vp, C.c_int, _vp, _vp, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, _vp, C.c_double, C.c_int,
+                                   C.c_double] + [_vp] * 11 + [C.c_longlong, C.c_int, _vp], C.c_int),
     "njf_field_nearest": ([_vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.POINTER(FieldGrid), C.c_double,
                            _vp, _vp, _vp, _vp, _vp, C.c_longlong, C.c_int, _vp], C.c_int),
     "njf_pack_resnetfc_backward": ([C.POINTER(ResnetFcWeights), _vp, C.c_int, _vp], C.c_int),
@@ -1147,57 +1150,97 @@ def field_commands(parts: torch.Tensor, part_status: torch.Tensor, centroid: tor
     [K] (int32) to tensors of their shapes.  ``phase``: FIELD_COMMANDS_MOMENTS writes moments, part_status and depth;
     FIELD_COMMANDS_SOLVE READS moments and writes everything else, part_status and depth (the same values) included; ``workspace``: float64, ``field_commands_workspace``
     elements."""
+    _field_commands("field_commands", False, parts, part_status, centroid, omega, velocity, points, out, parts_count, joints, weights, init,
+                    lower, upper, reg, iterations, damping, phase, workspace)
+
+
+def _field_commands(entry, metric, parts, part_status, centroid, omega, velocity, points, out, parts_count, joints, weights, init, lower,
+                    upper, reg, iterations, damping, phase, workspace) -> None:
+    """``field_commands`` and ``field_commands_metric``: the shape checks and the call."""
+    per_part = FIELD_COMMANDS_METRIC_MOMENTS_PER_PART if metric else FIELD_COMMANDS_MOMENTS_PER_PART
+    information = points.get("information") if metric else None
     k = parts.numel()
     targets = points["targets"]
     if targets.dim() != 3 or targets.shape[2] != 3:
-        raise ValueError("njf_hip: field_commands needs targets [M, n, 3]")
+        raise ValueError(f"njf_hip: {entry} needs targets [M, n, 3]")
     m, n = targets.shape[:2]
     if omega.dim() != 3 or omega.shape[0] != k or omega.shape[2] != 3 or velocity.shape != omega.shape:
-        raise ValueError("njf_hip: field_commands needs omega and velocity [K, A, 3]")
+        raise ValueError(f"njf_hip: {entry} needs omega and velocity [K, A, 3]")
     a = omega.shape[1]
     if part_status.numel() != k or centroid.numel() != 3 * k:
-        raise ValueError("njf_hip: field_commands needs one status and one centroid per part")
+        raise ValueError(f"njf_hip: {entry} needs one status and one centroid per part")
     if points["xyz"].numel() != 3 * n or points["labels"].numel() != n:
-        raise ValueError("njf_hip: field_commands needs xyz [n, 3] and labels [n]")
-    sizes = dict(commands=m * a, cost=m, initial_cost=m, weight=m, gradient=m * a, moments=m * k * FIELD_COMMANDS_MOMENTS_PER_PART,
+        raise ValueError(f"njf_hip: {entry} needs xyz [n, 3] and labels [n]")
+    sizes = dict(commands=m * a, cost=m, initial_cost=m, weight=m, gradient=m * a, moments=m * k * per_part,
                  steps=m, status=m, part_status=k, depth=k)
     for name, size in sizes.items():
         if out[name].numel() != size:
-            raise ValueError(f"njf_hip: field_commands output {name} must hold {size} elements (got {out[name].numel()})")
+            raise ValueError(f"njf_hip: {entry} output {name} must hold {size} elements (got {out[name].numel()})")
+    information_per_problem = 0
+    if metric:
+        if information is None or tuple(information.shape) not in ((n, 6), (m, n, 6)):
+            raise ValueError(f"njf_hip: {entry} needs information [n, 6] or [M, n, 6]")
+        information_per_problem = int(information.dim() == 3)
     per_problem = 0
     if weights is not None:
         if tuple(weights.shape) not in ((n,), (m, n)):
-            raise ValueError("njf_hip: field_commands needs weights [n] or [M, n]")
+            raise ValueError(f"njf_hip: {entry} needs weights [n] or [M, n]")
         per_problem = int(weights.dim() == 2)
     for name, t in (("init", init), ("lower", lower), ("upper", upper)):
         if t is not None and t.numel() != m * a:
-            raise ValueError(f"njf_hip: field_commands needs {name} [M, A]")
+            raise ValueError(f"njf_hip: {entry} needs {name} [M, A]")
     one = [("parts_count", parts_count), ("count", points.get("count"))]
     j = 0
     if joints is not None:
         j = joints["part_a"].numel()
         if joints["part_b"].numel() != j or joints["anchor"].numel() != 3 * j or joints["omega"].numel() != 3 * a * j or \
                 joints["velocity"].numel() != 3 * a * j or joints["parent"].numel() != k or joints["joint_of"].numel() != k:
-            raise ValueError("njf_hip: field_commands needs part_a, part_b [J], anchor [J, 3], omega, velocity [J, A, 3] of the "
+            raise ValueError(f"njf_hip: {entry} needs part_a, part_b [J], anchor [J, 3], omega, velocity [J, A, 3] of the "
                              "joints and parent, joint_of [K]")
         one.append(("joints count", joints.get("count")))
     for name, t in one:
         if t is not None and t.numel() != 1:
-            raise ValueError(f"njf_hip: field_commands {name} must hold one int32")
+            raise ValueError(f"njf_hip: {entry} {name} must hold one int32")
     if workspace is None:
-        workspace = torch.empty(field_commands_workspace(m, k, a, n), dtype=torch.float64, device=targets.device)
+        workspace = torch.empty((field_commands_metric_workspace if metric else field_commands_workspace)(m, k, a, n),
+                                dtype=torch.float64, device=targets.device)
     jt = (lambda key, ptr=_double_ptr: None if joints is None else ptr(joints.get(key), "joints " + key))   # noqa: E731
-    _launch("njf_field_commands", load_library().njf_field_commands, _int32_ptr(parts, "parts"),
+    rows = [_ptr(targets, "targets")] + ([_ptr(information, "information"), information_per_problem] if metric else [])
+    _launch("njf_" + entry, getattr(load_library(), "njf_" + entry), _int32_ptr(parts, "parts"),
             _int32_ptr(parts_count, "parts_count"), int(k), _int32_ptr(part_status, "part_status"), _double_ptr(centroid, "centroid"),
             _double_ptr(omega, "omega"), _double_ptr(velocity, "velocity"), int(a), jt("part_a", _int32_ptr), jt("part_b", _int32_ptr),
             jt("count", _int32_ptr), int(j), jt("anchor"), jt("omega"), jt("velocity"), jt("parent", _int32_ptr),
             jt("joint_of", _int32_ptr), _ptr(points["xyz"], "xyz"), _int32_ptr(points["labels"], "labels"),
-            _int32_ptr(points.get("count"), "count"), int(n), _ptr(targets, "targets"), int(m), _ptr(weights, "weights"), per_problem,
+            _int32_ptr(points.get("count"), "count"), int(n), *rows, int(m), _ptr(weights, "weights"), per_problem,
             _ptr(init, "init"), _ptr(lower, "lower"), _ptr(upper, "upper"), float(reg), int(iterations), float(damping),
             _ptr(out["commands"], "commands"), _double_ptr(out["cost"], "cost"), _double_ptr(out["initial_cost"], "initial_cost"),
             _double_ptr(out["weight"], "weight"), _int32_ptr(out["steps"], "steps"), _double_ptr(out["gradient"], "gradient"),
             _int32_ptr(out["status"], "status"), _int32_ptr(out["part_status"], "part_status"), _int32_ptr(out["depth"], "depth"),
             _double_ptr(out["moments"], "moments"), _double_ptr(workspace, "workspace"), int(workspace.numel()), int(phase))
+
+
+# ---- the same with a 3 x 3 information per target (include/njf_hip.h: njf_field_commands_metric) ------------------------------
+FIELD_COMMANDS_METRIC_MOMENTS_PER_PART = 74            # NJF_FIELD_COMMANDS_METRIC_MOMENTS_PER_PART
+FIELD_COMMANDS_METRIC_BUTTERFLY = 4                    # NJF_FIELD_COMMANDS_METRIC_BUTTERFLY: the moments by 74 butterflies
+
+
+def field_commands_metric_workspace(problems: int, parts: int, action_dim: int, rows: int) -> int:
+    """Doubles of workspace njf_field_commands_metric needs: NJF_FIELD_COMMANDS_METRIC_WORKSPACE(M, K, A, n) -- the chunks'
+    partial moments [chunks, K, M, 74] and the twists of the links and the chains [M, 2, K, A, 6]."""
+    chunks = (rows + FIELD_TWISTS_CHUNK - 1) // FIELD_TWISTS_CHUNK
+    return (FIELD_COMMANDS_METRIC_MOMENTS_PER_PART * chunks + 12 * action_dim) * problems * parts
+
+
+def field_commands_metric(parts: torch.Tensor, part_status: torch.Tensor, centroid: torch.Tensor, omega: torch.Tensor,
+                          velocity: torch.Tensor, points: dict, out: dict, parts_count=None, joints: Optional[dict] = None,
+                          weights: Optional[torch.Tensor] = None, init=None, lower=None, upper=None, reg: float = 0.0,
+                          iterations: int = 20, damping: float = 1e-3, phase: int = FIELD_COMMANDS_ALL,
+                          workspace: Optional[torch.Tensor] = None) -> None:
+    """njf_field_commands_metric: ``field_commands`` with ``points["information"]`` [n, 6] or [M, n, 6] (fp32), the symmetric
+    3 x 3 information of every target as [xx xy xz yy yz zz]; ``out["moments"]`` is [M, K, 74].  ``phase`` may add
+    FIELD_COMMANDS_METRIC_BUTTERFLY to the moments phase; ``workspace``: float64, ``field_commands_metric_workspace`` elements."""
+    _field_commands("field_commands_metric", True, parts, part_status, centroid, omega, velocity, points, out, parts_count, joints,
+                    weights, init, lower, upper, reg, iterations, damping, phase, workspace)
 
 
 # ---- closest points of an unlabelled cloud against a cell list (include/njf_hip.h: njf_field_nearest) ------------------------
