@@ -273,6 +273,26 @@ def test_relu_backward_step_equals_torch(dev, points, channels):
     assert torch.equal(colsum, colsum2)                                          # deterministic reduction order
 
 
+@pytest.mark.parametrize("points,channels", [(513, 64), (7, 128)])
+def test_relu_backward_step_at_the_edges_of_the_sign_test(dev, points, channels):
+    """njf_relu_backward on activations drawn from +0.0, -0.0, an fp32 denormal, the smallest normal fp32, a value that is zero as
+    fp16, and 1.0 (tests/resnetfc_backward_restatement.py: SIGN_EDGE_VALUES): the gate is the float64 decision act > 0, decided on
+    the host -- a closed gate gives exactly the residual (exactly 0 without one), an open gate residual + upstream in one rounding."""
+    import resnetfc_backward_restatement as R
+    from neural_jacobian_field_amd import hip
+    g = torch.Generator().manual_seed(channels + points)
+    values = torch.tensor(R.SIGN_EDGE_VALUES, dtype=torch.float32)
+    act = values[torch.randint(0, len(values), (points, channels), generator=g)]
+    gate = act.double() > 0                                                      # on the host, in float64
+    for k, v in enumerate(R.SIGN_EDGE_VALUES):
+        assert bool(gate[act.view(torch.int32) == values.view(torch.int32)[k]].all()) == (v > 0) and (act == values[k]).any()
+    up, res = torch.randn(points, channels, generator=g), torch.randn(points, channels, generator=g)
+    out, _ = hip.relu_backward(up.to(dev), act.to(dev), res.to(dev))
+    assert torch.equal(out.cpu(), torch.where(gate, res + up, res))
+    out2, _ = hip.relu_backward(up.to(dev), act.to(dev), None, want_colsum=False)
+    assert torch.equal(out2.cpu(), torch.where(gate, up, torch.zeros(())))
+
+
 def test_binding_error_behaviour(dev):
     from neural_jacobian_field_amd import hip
     z = torch.zeros(2, 300, device=dev)
