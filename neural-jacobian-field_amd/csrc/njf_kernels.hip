@@ -6049,24 +6049,50 @@ struct CompositeBwdArgs {
   float* g_color;        // [rays, S, 3] or NULL
 };
 
-__device__ __forceinline__ float wave_incl_scan(float v, int lane) {
+// The arithmetic is float64 on the fp32 inputs, rounded once at the store.  In fp32 the kernel met the 2e-5 of
+// test_composite_backward_equals_autograd, but not what tests/test_sampler_chain_gpu.py holds a ray's gradient to (a few ulps of
+// its largest element, norm-wise per ray), for three reasons it measured one after the other:
+//  * the depth in front of a sample taken as `inclusive scan - ds`: behind thin fog a dense sample kept 2^-24 (excl + ds) of error in
+//    excl, i.e. that much RELATIVE error in its weight -- the largest of the ray (1.5e-3 at ds = 1e5, and in g_sigma of everything in
+//    front of it).  It is the SHIFTED scan now, as in tile_weights;
+//  * the suffix sums taken as `tile sum - inclusive prefix`: 2^-24 of the tile's sum in every lane, 4 x the gradients behind a first
+//    sample with ds = 16 (they are exp(-excl) small).  They are scanned from the far end of the tile now;
+//  * dL/dds_k = G_k T_{k+1} - sum_{s>k} G_s w_s cancels (10 x where the next samples absorb most of the ray): an ulp each in ds, T, w
+//    and G left 8.4e-7 of a ray's gradient against the 6.6e-7 allowed, with nothing wrong in any single step.  Hence float64:
+//    3 exp + 1 expm1 per sample, in a kernel that took 0.02 % of a perception training step in fp32
+//    (profiles/r04_train_perception_kernel_stats.csv).
+__device__ __forceinline__ double wave_incl_scan(double v, int lane) {
 #pragma unroll
   for (int o = 1; o < 64; o <<= 1) {
-    const float t = __shfl_up(v, o, 64);
+    const double t = __shfl_up(v, o, 64);
     if (lane >= o) v += t;
   }
   return v;
 }
-__device__ __forceinline__ float wave_sum(float v) {
+// inclusive scan from the last lane towards this one
+__device__ __forceinline__ double wave_incl_suffix_scan(double v, int lane) {
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const double t = __shfl_down(v, o, 64);
+    if (lane + o < 64) v += t;
+  }
+  return v;
+}
+__device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
   for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
+}
+// the scan of the lanes in front of this one: the inclusive scan shifted by a lane (NOT `incl - v`, see above)
+__device__ __forceinline__ double shifted_scan(double incl, int lane) {
+  const double t = __shfl_up(incl, 1, 64);
+  return lane == 0 ? 0.0 : t;
 }
 
 #define NJF_COMPOSITE_MAX_TILES 16  // 1,024 samples per ray
 
 __global__ void __launch_bounds__(256) composite_backward_kernel(CompositeBwdArgs a) {
-  __shared__ float tile_start[4][NJF_COMPOSITE_MAX_TILES];  // per wave: optical depth in front of each 64-sample tile
+  __shared__ double tile_start[4][NJF_COMPOSITE_MAX_TILES];  // per wave: optical depth in front of each 64-sample tile
   const int ray = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const bool live = ray < a.rays;
@@ -6074,19 +6100,19 @@ __global__ void __launch_bounds__(256) composite_backward_kernel(CompositeBwdArg
   const size_t base = (size_t)min(ray, a.rays - 1) * S;
   // forward sweep: the optical depth in front of every tile (accumulated front to back, like the forward pass -- taking it
   // from the ray's total by subtraction loses 1e-4 of the transmittance on opaque rays), sum w and sum w t (depth)
-  float sum_w = 0.f, sum_wt = 0.f, carry = 0.f;
+  double sum_w = 0.0, sum_wt = 0.0, carry = 0.0;
   const bool need_depth = a.g_depth != nullptr;
   for (int t = 0; t < tiles; ++t) {
     const int s = t * 64 + lane;
     const bool valid = s < S;
     const float delta = valid ? a.deltas[base + s] : 0.f;
-    const float ds = (valid && delta > 0.f) ? delta * a.sigma[base + s] : 0.f;
-    const float incl = wave_incl_scan(ds, lane);
+    const double ds = (valid && delta > 0.f) ? (double)delta * (double)a.sigma[base + s] : 0.0;
+    const double incl = wave_incl_scan(ds, lane);
     if (lane == 0) tile_start[wv][t] = carry;
     if (need_depth) {
-      const float w = alpha_of(ds) * expf(-(carry + incl - ds));
-      sum_w += valid ? w : 0.f;
-      sum_wt += valid ? w * a.steps[base + s] : 0.f;
+      const double w = -expm1(-ds) * exp(-(carry + shifted_scan(incl, lane)));
+      sum_w += valid ? w : 0.0;
+      sum_wt += valid ? w * (double)a.steps[base + s] : 0.0;
     }
     carry += __shfl(incl, 63, 64);
   }
@@ -6096,45 +6122,43 @@ __global__ void __launch_bounds__(256) composite_backward_kernel(CompositeBwdArg
   }
   __syncthreads();  // tile_start written by lane 0 of each wave, read by all of its lanes (uniform trip counts: S is per launch)
   if (!live) return;
-  const float denom = sum_w + 1e-10f;
-  const float depth = sum_wt / denom;
-  const float gd = need_depth ? a.g_depth[ray] / denom : 0.f;
-  float gr[3] = {0.f, 0.f, 0.f};
+  const double denom = sum_w + 1e-10;
+  const double depth = sum_wt / denom;
+  const double gd = need_depth ? (double)a.g_depth[ray] / denom : 0.0;
+  double gr[3] = {0.0, 0.0, 0.0};
   if (a.g_rgb) {
     gr[0] = a.g_rgb[3 * (size_t)ray];
     gr[1] = a.g_rgb[3 * (size_t)ray + 1];
     gr[2] = a.g_rgb[3 * (size_t)ray + 2];
   }
-  float behind = 0.f;   // sum of G_s w_s over the tiles already visited (samples further along the ray)
+  double behind = 0.0;   // sum of G_s w_s over the tiles already visited (samples further along the ray)
   for (int t = tiles - 1; t >= 0; --t) {
     const int s = t * 64 + lane;
     const bool valid = s < S;
     const float delta = valid ? a.deltas[base + s] : 0.f;
-    const float ds = (valid && delta > 0.f) ? delta * a.sigma[base + s] : 0.f;
-    const float incl = wave_incl_scan(ds, lane);
-    const float before = tile_start[wv][t];             // optical depth in front of this tile
-    const float t_next = expf(-(before + incl));        // T_{s+1}
-    const float w = alpha_of(ds) * expf(-(before + incl - ds));
-    float G = a.g_w ? (valid ? a.g_w[base + s] : 0.f) : 0.f;
-    float c[3] = {0.f, 0.f, 0.f};
+    const double ds = (valid && delta > 0.f) ? (double)delta * (double)a.sigma[base + s] : 0.0;
+    const double incl = wave_incl_scan(ds, lane);
+    const double before = tile_start[wv][t];            // optical depth in front of this tile
+    const double t_next = exp(-(before + incl));        // T_{s+1}
+    const double w = -expm1(-ds) * exp(-(before + shifted_scan(incl, lane)));
+    double G = a.g_w ? (valid ? (double)a.g_w[base + s] : 0.0) : 0.0;
     if (a.color && valid) {
-      c[0] = a.color[3 * (base + s)];
-      c[1] = a.color[3 * (base + s) + 1];
-      c[2] = a.color[3 * (base + s) + 2];
-      G += gr[0] * c[0] + gr[1] * c[1] + gr[2] * c[2];
+      G += gr[0] * (double)a.color[3 * (base + s)] + gr[1] * (double)a.color[3 * (base + s) + 1] +
+           gr[2] * (double)a.color[3 * (base + s) + 2];
     }
-    if (need_depth && valid) G += gd * (a.steps[base + s] - depth);
-    const float gw = valid ? G * w : 0.f;
-    // exclusive suffix sum inside the tile = tile sum - inclusive prefix sum
-    const float pre = wave_incl_scan(gw, lane);
-    const float tile_gw = __shfl(pre, 63, 64);
-    const float suffix = behind + (tile_gw - pre);
+    if (need_depth && valid) G += gd * ((double)a.steps[base + s] - depth);
+    const double gw = valid ? G * w : 0.0;
+    // exclusive suffix sum inside the tile, scanned from the far end
+    const double post = wave_incl_suffix_scan(gw, lane);
+    const double tile_gw = __shfl(post, 0, 64);
+    const double after = __shfl_down(post, 1, 64);
+    const double suffix = behind + (lane == 63 ? 0.0 : after);
     if (valid) {
-      a.g_sigma[base + s] = delta > 0.f ? delta * (G * t_next - suffix) : 0.f;
+      a.g_sigma[base + s] = delta > 0.f ? (float)((double)delta * (G * t_next - suffix)) : 0.f;
       if (a.g_color) {
-        a.g_color[3 * (base + s)] = w * gr[0];
-        a.g_color[3 * (base + s) + 1] = w * gr[1];
-        a.g_color[3 * (base + s) + 2] = w * gr[2];
+        a.g_color[3 * (base + s)] = (float)(w * gr[0]);
+        a.g_color[3 * (base + s) + 1] = (float)(w * gr[1]);
+        a.g_color[3 * (base + s) + 2] = (float)(w * gr[2]);
       }
     }
     behind += tile_gw;
