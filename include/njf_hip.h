@@ -874,6 +874,68 @@ int njf_field_nearest(const float* observed, const int* observed_count, int num_
                       double max_distance, int* index, float* distance2, float* matched, int* found, int* workspace,
                       long long workspace_words, int phases, void* stream);
 
+/* ---- surface normals of an observed cloud from exact moments on the cell list (ABI v20, additive) -----------
+ * For each of M problems and each row of a set of query points: the normal, the neighbour count and the surface variation of the
+ * observed points within `radius`, from their covariance -- what plane_information needs of a cloud that comes with points alone.
+ * The neighbourhood sums are integers, so that the order in which the cell list is read cannot change a byte of any output.
+ * Inputs, all on the device: observed [Mo,T,3] float; observed_count int32 [Mo] or NULL (= T); queries [Mq,n,3] float; count
+ * int32 [1] or NULL (= n); viewpoint [Mv,3] float or NULL.  Mo, Mq and Mv are each 1 or M.  `cells`: njf_field_nearest's
+ * lattice, under the same rules.  `radius` is used as (float)radius; `min_neighbours` >= 3.
+ * VALID POINT j of problem m: j < min(observed_count[m], T) and three finite coordinates.
+ * SEARCHED ROW i: i < min(*count, n) and three finite coordinates.
+ * NEIGHBOUR of a searched row q: a valid point p with d2 = (ex*ex + ey*ey) + ez*ez <= (float)radius * (float)radius, e_c = p_c -
+ *        q_c, all in float, in exactly this order, no contraction.  A query that is a point of the cloud is its own neighbour.
+ * CELLS  visited: the Chebyshev rings 0 .. R around the query's cell (njf_field_nearest's CELLS), clipped to the lattice, R the
+ *        smallest r >= 1 with ((float)r - 1/128) * cell > (float)radius in float: njf_field_nearest's second stop test, exact by
+ *        its argument (the clamp is 1-Lipschitz, the slack of cell / 128 covers the rounding).  Every cell index is checked
+ *        against [0, Mo * C) and every range against [0, Mo * T) before use.
+ * MOMENTS scale = 262144.0 / (double)(float)radius (2^18 / radius, one double division); k_c = rint((double)e_c * scale), a double
+ *        product rounded to the nearest integer, ties to even; d2 <= r2 gives |k_c| <= 2^18 + 1.  Ten int64 sums over the
+ *        neighbours of a row: S0 = sum 1; S1[3] = sum k; S2[6] = sum k_a k_b as [xx xy xz yy yz zz]; moments [M,n,10] int64 holds
+ *        (S0, S1, S2), zeros for a row that is not searched.  |S2| < (2^18 + 1)^2 T < 2^63 for T < 2^26.  Integer addition is
+ *        associative: the sums are the same bytes in any visiting order, and in both kernel forms.
+ *        NJF_FIELD_NORMALS_WAVE: one wave per (m, i) instead of one lane, the lanes sharing a range's records.
+ * FINISH one lane per (m, i), in double, no contraction; reads the moments of the rows i < min(*count, n) and nothing else,
+ *        except the query and the viewpoint of a row whose normal it orients.
+ *        N = S0; with N < min_neighbours there is no normal.  mean_a = (double)S1_a / (double)N; C_ab = (double)S2_ab / (double)N
+ *        - mean_a * mean_b.  Eigen-decomposition by cyclic Jacobi rotations on the pairs (p,q) = (0,1), (0,2), (1,2), exactly
+ *        8 sweeps; a pair with C_pq == 0 is skipped and there is no other exit.  One rotation, o the third axis: theta = (C_qq -
+ *        C_pp) / (2 C_pq); t = sgn(theta) / (|theta| + sqrt(theta * theta + 1)), sgn(0) = 1; c = 1 / sqrt(t * t + 1); s = t * c;
+ *        C_pp -= t C_pq; C_qq += t C_pq; C_pq = 0; (C_op, C_oq) <- (c C_op - s C_oq, s C_op + c C_oq); every row k of V (the
+ *        identity at first): (V_kp, V_kq) <- (c V_kp - s V_kq, s V_kp + c V_kq).  lambda = the diagonal, sorted ascending (ties
+ *        in the order of the axes) and clamped at 0; with (lambda0 + lambda1) + lambda2 == 0 -- all neighbours coincide -- there
+ *        is no normal.  Otherwise the normal is the column of V that belongs to lambda0, divided by its length.
+ * SIGN   with a viewpoint v of three finite coordinates: flipped iff (n_x (v_x - q_x) + n_y (v_y - q_y)) + n_z (v_z - q_z) < 0, in
+ *        double from the float inputs.  Otherwise (NULL, or not finite): flipped iff the component of largest magnitude, ties
+ *        to the lowest axis, is negative.
+ * Outputs, every row i < n written: normal [M,n,3] float (three NaNs where there is no normal); neighbours [M,n] int32 = S0 (0
+ *        for a row that is not searched); variation [M,n] float = lambda0 / ((lambda0 + lambda1) + lambda2), 0 on a plane and 1/3
+ *        for an isotropic neighbourhood (NaN where there is no normal); eigenvalues [M,n,3] double or NULL = lambda / (scale *
+ *        scale), ascending, in the cloud's units (NaN where there is no normal).
+ * workspace: njf_field_nearest's, NJF_FIELD_NORMALS_WORKSPACE(Mo, C, T) = NJF_FIELD_NEAREST_WORKSPACE(Mo, C, T) words in its
+ * documented layout; one that njf_field_nearest's build phase wrote for the same observed and cells is taken as it is.
+ * `phases`: NJF_FIELD_NORMALS_BUILD (njf_field_nearest's build: reads observed, writes the workspace) | NJF_FIELD_NORMALS_MOMENTS
+ * (reads the workspace and the queries, writes moments) [| NJF_FIELD_NORMALS_WAVE] | NJF_FIELD_NORMALS_FINISH (reads moments, writes
+ * the outputs).  One stream, no host read (capture-safe), no atomics beyond the build's integer ones.
+ * Returns, before the first launch: NJF_E_VALUE for everything njf_field_nearest answers so (radius in max_distance's place), Mv
+ * not 1 or M with a viewpoint, min_neighbours < 3, or unknown phases (the modifier without the moments phase included);
+ * NJF_E_SHAPE for n < 0, T < 1, T >= 2^26, Mo * T >= 2^31 or, with the build or the moments phase, a workspace that is too small;
+ * NJF_E_NULL for a missing pointer: cells; the workspace with the build or the moments phase; observed with the build; with n >
+ * 0, queries and moments with the moments or the finish phase, normal, neighbours and variation with the finish phase. */
+#define NJF_FIELD_NORMALS_WORKSPACE(Mo, C, T) NJF_FIELD_NEAREST_WORKSPACE(Mo, C, T)
+#define NJF_FIELD_NORMALS_MOMENTS_PER_ROW 10
+#define NJF_FIELD_NORMALS_SWEEPS 8
+#define NJF_FIELD_NORMALS_BUILD 1    /* phases */
+#define NJF_FIELD_NORMALS_MOMENTS 2
+#define NJF_FIELD_NORMALS_FINISH 4
+#define NJF_FIELD_NORMALS_ALL 7
+#define NJF_FIELD_NORMALS_WAVE 8     /* with MOMENTS: a wave per row */
+int njf_field_normals(const float* observed, const int* observed_count, int num_observed, int points, const float* queries,
+                      const int* count, int num_queries, int n, int num_problems, const NjfFieldGrid* cells, double radius,
+                      int min_neighbours, const float* viewpoint, int num_viewpoints, long long* moments, float* normal,
+                      int* neighbours, float* variation, double* eigenvalues, int* workspace, long long workspace_words,
+                      int phases, void* stream);
+
 /* ---- stand-alone sampler / compositing ops (API parity with the un-fused reference calls) -- */
 /* RaySamples.get_weights (ray_samplers.py:77-101): deltas, densities [N,S] -> weights [N,S]. */
 int njf_alpha_weights(const float* deltas, const float* densities, int rays, int samples, float* weights, void* stream);

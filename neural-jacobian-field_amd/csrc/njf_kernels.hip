@@ -4943,6 +4943,227 @@ __global__ void __launch_bounds__(NJF_NN_THREADS) nn_query_kernel(NnArgs a) {
   if (lane == 0 && accepted) atomicAdd(&a.found[m], accepted);
 }
 
+// ---- surface normals from integer moments on the cell list (njf_field_normals) -----------------------------
+// Every searched row reads the records of the Chebyshev rings 0 .. R around its cell -- njf_field_nearest's list and its
+// walk, without the best-so-far test -- and adds ten int64 sums over the points within the radius: the count, the offsets
+// e = p - q quantised to k = rint(e * 2^18 / radius), and the six products k_a k_b.  The order inside a cell depends on
+// scheduling; integer sums do not.  A second launch turns the sums into a covariance and takes its eigenvectors in double.
+struct NrmArgs {
+  const float* queries;    // [Mq,n,3]
+  const int* count;        // [1] or null
+  const float* viewpoint;  // [Mv,3] or null
+  int Mo, Mq, Mv, M, T, n;
+  float origin[3];
+  float cell, inv_cell;
+  int dims[3];
+  int C;
+  long long L, slots;      // Mo * C, Mo * T
+  float r2;                // (float)radius * (float)radius
+  int rings;               // R
+  double scale;            // 2^18 / (double)(float)radius
+  int min_neighbours;
+  const int* start;        // njf_field_nearest's workspace
+  const int4* records;
+  long long* moments;      // [M,n,10]
+  float* normal;           // [M,n,3]
+  int* neighbours;         // [M,n]
+  float* variation;        // [M,n]
+  double* eigenvalues;     // [M,n,3] or null
+};
+
+// the records of the cells c0 .. c1 (one problem, consecutive along z) against the query; |k| <= 2^18 + 1, so k is an int and
+// every product one 32 x 32 -> 64-bit multiply-add
+template <bool WAVE>
+__device__ __forceinline__ void nrm_visit(const NrmArgs& a, long long c0, long long c1, int lane, float qx, float qy, float qz,
+                                          long long (&sum)[10]) {
+  if (c0 < 0 || c1 >= a.L || c0 > c1) return;
+  long long lo = a.start[c0], hi = a.start[c1 + 1];
+  lo = min(max(lo, 0LL), a.slots);
+  hi = min(min(max(hi, lo), a.slots), lo + a.T);
+  for (long long s = lo + (WAVE ? lane : 0); s < hi; s += WAVE ? 64 : 1) {
+    const int4 rec = a.records[s];
+    const float ex = __int_as_float(rec.x) - qx, ey = __int_as_float(rec.y) - qy, ez = __int_as_float(rec.z) - qz;
+    if ((ex * ex + ey * ey) + ez * ez <= a.r2) {
+      const int kx = (int)rint((double)ex * a.scale), ky = (int)rint((double)ey * a.scale), kz = (int)rint((double)ez * a.scale);
+      sum[0] += 1;
+      sum[1] += kx;
+      sum[2] += ky;
+      sum[3] += kz;
+      sum[4] += (long long)kx * kx;
+      sum[5] += (long long)kx * ky;
+      sum[6] += (long long)kx * kz;
+      sum[7] += (long long)ky * ky;
+      sum[8] += (long long)ky * kz;
+      sum[9] += (long long)kz * kz;
+    }
+  }
+}
+
+// WAVE false: one lane per (problem, row); true: one wave per (problem, row), the lanes share a range's records and add their
+// sums at the end, as pairs of 32-bit halves
+template <bool WAVE>
+__global__ void __launch_bounds__(NJF_NN_THREADS) nrm_moments_kernel(NrmArgs a) {
+  const int lane = threadIdx.x & 63;
+  const int m = blockIdx.y;
+  const long long i = WAVE ? (long long)blockIdx.x * (NJF_NN_THREADS / 64) + (threadIdx.x >> 6)
+                           : (long long)blockIdx.x * NJF_NN_THREADS + threadIdx.x;
+  const bool live = i < a.n;
+  bool searched = live && i < counted_length(a.count, a.n);  // (rows from the count on are not read)
+  float qx = 0.f, qy = 0.f, qz = 0.f;
+  if (searched) {
+    const float* q = a.queries + ((long long)(a.Mq == 1 ? 0 : m) * a.n + i) * 3;
+    qx = q[0], qy = q[1], qz = q[2];
+    searched = nn_finite(qx, qy, qz);
+  }
+  long long sum[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  if (searched) {
+    const long long cells = (long long)(a.Mo == 1 ? 0 : m) * a.C;
+    const int dx = a.dims[0], dy = a.dims[1], dz = a.dims[2];
+    const int cx = nn_cell_axis(qx, a.origin[0], a.inv_cell, dx), cy = nn_cell_axis(qy, a.origin[1], a.inv_cell, dy),
+              cz = nn_cell_axis(qz, a.origin[2], a.inv_cell, dz);
+    for (int r = 0; r <= a.rings; ++r) {
+      // no cell at this distance, nor at a larger one
+      if (cx - r < 0 && cx + r >= dx && cy - r < 0 && cy + r >= dy && cz - r < 0 && cz + r >= dz) break;
+      const int x0 = max(cx - r, 0), x1 = min(cx + r, dx - 1), y0 = max(cy - r, 0), y1 = min(cy + r, dy - 1);
+      const int z0 = max(cz - r, 0), z1 = min(cz + r, dz - 1);
+      for (int x = x0; x <= x1; ++x)
+        for (int y = y0; y <= y1; ++y) {
+          const long long column = cells + ((long long)x * dy + y) * dz;
+          if (x == cx - r || x == cx + r || y == cy - r || y == cy + r) {  // a face of the ring: the whole column
+            nrm_visit<WAVE>(a, column + z0, column + z1, lane, qx, qy, qz, sum);
+          } else {  // (r >= 1) inside: the two ends
+            if (cz - r >= 0) nrm_visit<WAVE>(a, column + cz - r, column + cz - r, lane, qx, qy, qz, sum);
+            if (cz + r < dz) nrm_visit<WAVE>(a, column + cz + r, column + cz + r, lane, qx, qy, qz, sum);
+          }
+        }
+    }
+  }
+  if (WAVE)
+    for (int o = 32; o > 0; o >>= 1)
+#pragma unroll
+      for (int e = 0; e < 10; ++e) {
+        const unsigned low = (unsigned)__shfl_xor((int)(unsigned)sum[e], o, 64);
+        const int high = __shfl_xor((int)(sum[e] >> 32), o, 64);
+        sum[e] += (long long)(((unsigned long long)(unsigned)high << 32) | low);
+      }
+  if (live && (!WAVE || lane == 0)) {
+    long long* out = a.moments + ((long long)m * a.n + i) * 10;
+#pragma unroll
+    for (int e = 0; e < 10; ++e) out[e] = sum[e];
+  }
+}
+
+// one Jacobi rotation on the pair (p, q) of a symmetric 3 x 3, o the third axis: zeroes a_pq; vp, vq the columns p, q of V
+__device__ __forceinline__ void nrm_rotate(double& app, double& aqq, double& apq, double& aop, double& aoq, double (&vp)[3],
+                                           double (&vq)[3]) {
+  if (apq == 0.0) return;
+  const double theta = (aqq - app) / (2.0 * apq);
+  const double t = (theta < 0.0 ? -1.0 : 1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+  const double c = 1.0 / sqrt(t * t + 1.0), sn = t * c;
+  app = app - t * apq;
+  aqq = aqq + t * apq;
+  apq = 0.0;
+  const double op = aop, oq = aoq;
+  aop = c * op - sn * oq;
+  aoq = sn * op + c * oq;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const double p = vp[k], q = vq[k];
+    vp[k] = c * p - sn * q;
+    vq[k] = sn * p + c * q;
+  }
+}
+
+// one lane per (problem, row): the ten sums -> neighbours, normal, variation, eigenvalues.  Reads the moments only, and the
+// query and the viewpoint of a row that has a normal to orient.
+__global__ void __launch_bounds__(NJF_NN_THREADS) nrm_finish_kernel(NrmArgs a) {
+  const int m = blockIdx.y;
+  const long long i = (long long)blockIdx.x * NJF_NN_THREADS + threadIdx.x;
+  if (i >= a.n) return;
+  const long long row = (long long)m * a.n + i;
+  const double nan = __longlong_as_double(0x7ff8000000000000LL);
+  long long N = 0;
+  double lam[3] = {nan, nan, nan}, nrm[3] = {nan, nan, nan};
+  bool have = false;
+  if (i < counted_length(a.count, a.n)) {  // (rows from the count on are not read)
+    const long long* s = a.moments + row * 10;
+    N = s[0];
+    if (N >= a.min_neighbours) {
+      const double inv = (double)N;
+      const double mx = (double)s[1] / inv, my = (double)s[2] / inv, mz = (double)s[3] / inv;
+      // the covariance, rotated towards a diagonal; V0, V1, V2: the columns of the rotations' product, the eigenvectors
+      double a00 = (double)s[4] / inv - mx * mx, a01 = (double)s[5] / inv - mx * my, a02 = (double)s[6] / inv - mx * mz;
+      double a11 = (double)s[7] / inv - my * my, a12 = (double)s[8] / inv - my * mz, a22 = (double)s[9] / inv - mz * mz;
+      double V0[3] = {1.0, 0.0, 0.0}, V1[3] = {0.0, 1.0, 0.0}, V2[3] = {0.0, 0.0, 1.0};
+#pragma unroll 1
+      for (int sweep = 0; sweep < NJF_FIELD_NORMALS_SWEEPS; ++sweep) {
+        nrm_rotate(a00, a11, a01, a02, a12, V0, V1);
+        nrm_rotate(a00, a22, a02, a01, a12, V0, V2);
+        nrm_rotate(a11, a22, a12, a01, a02, V1, V2);
+      }
+      // ascending, ties in the order of the axes; the eigenvector of the smallest
+      double l0 = a00, l1 = a11, l2 = a22;
+      double v0 = V0[0], v1 = V0[1], v2 = V0[2];
+      if (l1 < l0) {
+        const double t = l0;
+        l0 = l1, l1 = t;
+        v0 = V1[0], v1 = V1[1], v2 = V1[2];
+      }
+      if (l2 < l0) {
+        const double t = l0;
+        l0 = l2, l2 = t;
+        v0 = V2[0], v1 = V2[1], v2 = V2[2];
+      }
+      if (l2 < l1) {
+        const double t = l1;
+        l1 = l2, l2 = t;
+      }
+      l0 = fmax(l0, 0.0), l1 = fmax(l1, 0.0), l2 = fmax(l2, 0.0);
+      const double total = (l0 + l1) + l2;
+      if (total > 0.0) {
+        have = true;
+        const double len = sqrt((v0 * v0 + v1 * v1) + v2 * v2);
+        v0 = v0 / len, v1 = v1 / len, v2 = v2 / len;
+        bool flip;
+        bool seen = false;
+        double toward = 0.0;
+        if (a.viewpoint) {
+          const float* v = a.viewpoint + (long long)(a.Mv == 1 ? 0 : m) * 3;
+          const float vx = v[0], vy = v[1], vz = v[2];
+          if (nn_finite(vx, vy, vz)) {
+            const float* q = a.queries + ((long long)(a.Mq == 1 ? 0 : m) * a.n + i) * 3;
+            seen = true;
+            toward = (v0 * ((double)vx - (double)q[0]) + v1 * ((double)vy - (double)q[1])) + v2 * ((double)vz - (double)q[2]);
+          }
+        }
+        if (seen) {
+          flip = toward < 0.0;
+        } else {  // the component of largest magnitude is positive, ties to the lowest axis
+          double big = v0;
+          if (fabs(v1) > fabs(big)) big = v1;
+          if (fabs(v2) > fabs(big)) big = v2;
+          flip = big < 0.0;
+        }
+        if (flip) v0 = -v0, v1 = -v1, v2 = -v2;
+        nrm[0] = v0, nrm[1] = v1, nrm[2] = v2;
+        const double s2 = a.scale * a.scale;
+        lam[0] = l0 / s2, lam[1] = l1 / s2, lam[2] = l2 / s2;
+        a.variation[row] = (float)(l0 / total);
+      }
+    }
+  }
+  a.neighbours[row] = (int)N;
+  if (!have) a.variation[row] = (float)nan;
+  a.normal[row * 3] = (float)nrm[0];
+  a.normal[row * 3 + 1] = (float)nrm[1];
+  a.normal[row * 3 + 2] = (float)nrm[2];
+  if (a.eigenvalues) {
+    a.eigenvalues[row * 3] = lam[0];
+    a.eigenvalues[row * 3 + 1] = lam[1];
+    a.eigenvalues[row * 3 + 2] = lam[2];
+  }
+}
+
 // =============================================================================================
 // inverse dynamics: Levenberg-Marquardt on the linearised flow, one workgroup per batch element
 // =============================================================================================
@@ -7410,6 +7631,97 @@ extern "C" int njf_field_nearest(const float* observed, const int* observed_coun
       }
       if ((rc = launch_status())) return rc;
     }
+  }
+  return NJF_OK;
+}
+
+extern "C" int njf_field_normals(const float* observed, const int* observed_count, int num_observed, int points,
+                                 const float* queries, const int* count, int num_queries, int n, int num_problems,
+                                 const NjfFieldGrid* cells, double radius, int min_neighbours, const float* viewpoint,
+                                 int num_viewpoints, long long* moments, float* normal, int* neighbours, float* variation,
+                                 double* eigenvalues, int* workspace, long long workspace_words, int phases, void* stream) {
+  if (num_problems < 1 || num_problems > NJF_FIELD_POSE_MAX_COMMANDS) return NJF_E_VALUE;
+  if ((num_observed != 1 && num_observed != num_problems) || (num_queries != 1 && num_queries != num_problems)) return NJF_E_VALUE;
+  if (viewpoint && num_viewpoints != 1 && num_viewpoints != num_problems) return NJF_E_VALUE;
+  if (phases < 1 || phases > (NJF_FIELD_NORMALS_ALL | NJF_FIELD_NORMALS_WAVE) || !(phases & NJF_FIELD_NORMALS_ALL) ||
+      ((phases & NJF_FIELD_NORMALS_WAVE) && !(phases & NJF_FIELD_NORMALS_MOMENTS)))
+    return NJF_E_VALUE;
+  if (min_neighbours < 3) return NJF_E_VALUE;
+  if (!cells) return NJF_E_NULL;
+  const float cell = cells->step[0], inv_cell = 1.0f / cell, reach = (float)radius;
+  if (!(cell > 0.0f) || cells->step[1] != cell || cells->step[2] != cell || !(inv_cell > 0.0f) || !(cell < INFINITY) ||
+      !(inv_cell < INFINITY))
+    return NJF_E_VALUE;
+  long long C = 1;
+  for (int c = 0; c < 3; ++c) {
+    if (cells->dims[c] < 1 || cells->dims[c] > NJF_FIELD_NEAREST_MAX_DIM) return NJF_E_VALUE;
+    if (!(fabsf(cells->origin[c]) < INFINITY)) return NJF_E_VALUE;
+    C *= cells->dims[c];
+  }
+  if (!(radius > 0.0) || !(reach > 0.0f) || !(reach < INFINITY)) return NJF_E_VALUE;
+  if (ceil((double)reach / (double)cell) + 1.0 > (double)NJF_FIELD_NEAREST_MAX_RINGS) return NJF_E_VALUE;
+  const long long L = (long long)num_observed * C;
+  if (L >= (1LL << 31)) return NJF_E_VALUE;
+  if (n < 0 || points < 1 || points >= (1 << 26) || (long long)num_observed * points >= (1LL << 31)) return NJF_E_SHAPE;
+  const bool build = phases & NJF_FIELD_NORMALS_BUILD, sums = phases & NJF_FIELD_NORMALS_MOMENTS,
+             finish = phases & NJF_FIELD_NORMALS_FINISH;
+  if ((build || sums) && workspace_words < NJF_FIELD_NEAREST_WORKSPACE(num_observed, C, points)) return NJF_E_SHAPE;
+  if (((build || sums) && !workspace) || (build && !observed)) return NJF_E_NULL;
+  if (n > 0 && (((sums || finish) && (!queries || !moments)) || (finish && (!normal || !neighbours || !variation))))
+    return NJF_E_NULL;
+  int rc;
+  if (build && (rc = njf_field_nearest(observed, observed_count, num_observed, points, nullptr, nullptr, nullptr, num_queries, n,
+                                       num_problems, cells, radius, nullptr, nullptr, nullptr, nullptr, workspace,
+                                       workspace_words, NJF_FIELD_NEAREST_BUILD, stream)))
+    return rc;
+  if (n == 0 || !(sums || finish)) return NJF_OK;
+  NrmArgs a;
+  a.queries = queries;
+  a.count = count;
+  a.viewpoint = viewpoint;
+  a.Mo = num_observed;
+  a.Mq = num_queries;
+  a.Mv = num_viewpoints;
+  a.M = num_problems;
+  a.T = points;
+  a.n = n;
+  for (int c = 0; c < 3; ++c) a.origin[c] = cells->origin[c], a.dims[c] = cells->dims[c];
+  a.cell = cell;
+  a.inv_cell = inv_cell;
+  a.C = (int)C;
+  a.L = L;
+  a.slots = (long long)num_observed * points;
+  a.r2 = reach * reach;
+  a.rings = 1;  // the smallest r >= 1 whose rings beyond it hold nothing within the radius: njf_field_nearest's second stop test
+  while (a.rings < NJF_FIELD_NEAREST_MAX_RINGS && !(((float)a.rings - 0.0078125f) * cell > reach)) ++a.rings;
+  a.scale = 262144.0 / (double)reach;
+  a.min_neighbours = min_neighbours;
+  a.start = workspace;                                   // njf_field_nearest's layout
+  a.records = nullptr;
+  if (workspace) {
+    const int* cursor = workspace + (long long)num_observed * (C + 1);
+    a.records = (const int4*)(((uintptr_t)(cursor + L) + 15) & ~(uintptr_t)15);
+  }
+  a.moments = moments;
+  a.normal = normal;
+  a.neighbours = neighbours;
+  a.variation = variation;
+  a.eigenvalues = eigenvalues;
+  hipStream_t s = (hipStream_t)stream;
+  if (sums) {
+    if (phases & NJF_FIELD_NORMALS_WAVE) {
+      const dim3 grid((unsigned)(((long long)n + NJF_NN_THREADS / 64 - 1) / (NJF_NN_THREADS / 64)), (unsigned)num_problems);
+      nrm_moments_kernel<true><<<grid, NJF_NN_THREADS, 0, s>>>(a);
+    } else {
+      const dim3 grid((unsigned)(((long long)n + NJF_NN_THREADS - 1) / NJF_NN_THREADS), (unsigned)num_problems);
+      nrm_moments_kernel<false><<<grid, NJF_NN_THREADS, 0, s>>>(a);
+    }
+    if ((rc = launch_status())) return rc;
+  }
+  if (finish) {
+    const dim3 grid((unsigned)(((long long)n + NJF_NN_THREADS - 1) / NJF_NN_THREADS), (unsigned)num_problems);
+    nrm_finish_kernel<<<grid, NJF_NN_THREADS, 0, s>>>(a);
+    if ((rc = launch_status())) return rc;
   }
   return NJF_OK;
 }

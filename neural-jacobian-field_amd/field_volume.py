@@ -1152,6 +1152,99 @@ def nearest_points(queries: torch.Tensor, observed: torch.Tensor, cells: FieldGr
     return near
 
 
+# ---- surface normals of an observed cloud: exact moments on the cell list ---------------------------------
+@dataclass
+class FieldNormals:
+    """The normal, the neighbour count and the surface variation of every searched query row (``point_normals``;
+    include/njf_hip.h: njf_field_normals), per problem, from the covariance of the valid observed points within the radius.
+    ``moments`` holds the ten integer sums the rest is computed from: ``S0`` (the count), ``S1[3]`` and ``S2[6]`` (``[xx xy xz
+    yy yz zz]``) of the offsets quantised to ``radius / 2^18``."""
+
+    normal: torch.Tensor                  # [M, n, 3] fp32: the unit normal, or NaN
+    neighbours: torch.Tensor              # [M, n] int32: the points within the radius, 0 for a row that is not searched
+    variation: torch.Tensor               # [M, n] fp32: lambda0 / (lambda0 + lambda1 + lambda2) -- 0 on a plane, 1/3 isotropic --, or NaN
+    moments: torch.Tensor                 # [M, n, 10] int64
+    eigenvalues: Optional[torch.Tensor]   # [M, n, 3] float64, ascending, in the cloud's units (``eigenvalues=True``), or None
+
+    def information(self, max_variation: Optional[float] = None) -> torch.Tensor:
+        """``plane_information(normal)`` ``[M, n, 6]`` (fp32, with its floor): what ``register_commands_metric`` takes as
+        ``observed_information`` when the rows are the observed points.  A row without a normal gives six NaNs, which
+        ``solve_commands_metric`` reads as "this row is free"; so does, with ``max_variation``, a row whose ``variation``
+        exceeds it (an edge, a corner, a thin or noisy neighbourhood).  Torch ops on the device, no host read."""
+        name = "FieldNormals.information"
+        if max_variation is not None and (isinstance(max_variation, bool) or not isinstance(max_variation, (int, float))
+                                          or not max_variation >= 0.0):
+            raise ValueError(f"{name}: max_variation must be a number >= 0 or None (got {max_variation})")
+        info = plane_information(self.normal)
+        if max_variation is not None:
+            info = torch.where((self.variation <= float(max_variation))[..., None], info, torch.full_like(info, float("nan")))
+        return info
+
+
+def point_normals(queries: Optional[torch.Tensor], observed: torch.Tensor, cells: FieldGrid, radius: float, *,
+                  observed_count: Optional[torch.Tensor] = None, count: Optional[torch.Tensor] = None,
+                  viewpoint: Optional[torch.Tensor] = None, min_neighbours: int = 3, eigenvalues: bool = False) -> FieldNormals:
+    """For every row of ``queries`` ``[n, 3]`` or ``[Mq, n, 3]`` (fp32; None = the observed points themselves) the surface
+    normal of the unlabelled cloud ``observed`` ``[T, 3]`` or ``[Mo, T, 3]`` (fp32) around it: the
+    eigenvector of the smallest eigenvalue of the covariance of the valid points within ``radius``, M = max(Mq, Mo, Mv)
+    problems, each of Mq, Mo and Mv 1 or M.  A point is valid below ``observed_count`` (int32 ``[Mo]``; None = T) with finite
+    coordinates; a row is searched below ``count`` (one int32 on the device; None = n) with finite coordinates; a neighbour
+    has ``(ex*ex + ey*ey) + ez*ez <= radius * radius`` in fp32.  A row with fewer than ``min_neighbours`` (>= 3) neighbours, or
+    whose neighbours all coincide, has no normal: NaN, which ``information()`` hands on as a free row.  With ``viewpoint``
+    (fp32 ``[3]`` or ``[Mv, 3]``) a normal points to the half-space of the viewpoint; without, its largest component is
+    positive.  ``cells`` (``cell_grid``) only sets the cost, as for ``nearest_points``, whose cell list this reads: a row visits
+    the cells within ``radius`` of its own.  The neighbourhood sums are integers (offsets quantised to ``radius / 2^18``), so
+    the order in which the list is read cannot matter: integer atomics only (the build's), no host read, equal bytes from call
+    to call, capturable."""
+    name = "point_normals"
+    if queries is not None and (not torch.is_tensor(queries) or queries.dtype != torch.float32 or queries.dim() not in (2, 3)
+                                or queries.shape[-1] != 3):
+        raise ValueError(f"{name}: queries must be fp32 [n, 3] or [Mq, n, 3], or None")
+    if viewpoint is not None and (not torch.is_tensor(viewpoint) or viewpoint.dtype != torch.float32 or viewpoint.dim() not in (1, 2)
+                                  or viewpoint.shape[-1] != 3 or viewpoint.shape[0] < 1):
+        raise ValueError(f"{name}: viewpoint must be fp32 [3] or [Mv, 3]")
+    viewpoint = viewpoint if viewpoint is None or viewpoint.dim() == 2 else viewpoint[None]
+    mv = 1 if viewpoint is None else viewpoint.shape[0]
+    if queries is not None:
+        queries = queries if queries.dim() == 3 else queries[None]
+    like, of = (observed, "observed") if queries is None else (queries, "queries")
+    mq, n = (1, 0) if queries is None else queries.shape[:2]
+    try:
+        observed, m, observed_count, count = _check_nearest(name, observed, cells, radius, observed_count, count, None, n, mq, like, of,
+                                                            m_other=mv)
+    except ValueError as err:
+        raise ValueError(str(err).replace("max_distance", "radius")) from None
+    if queries is None:
+        queries = observed
+        mq, n = queries.shape[:2]
+    if mv not in (1, m):
+        raise ValueError(f"{name}: viewpoint holds one point or one per problem (got {mv} for {m} problems)")
+    if observed.shape[1] >= hip.FIELD_NORMALS_MAX_POINTS:
+        raise ValueError(f"{name}: T must stay below 2**26")
+    if isinstance(min_neighbours, bool) or not isinstance(min_neighbours, int) or not 3 <= min_neighbours < 2 ** 31:
+        raise ValueError(f"{name}: min_neighbours must be an integer >= 3 (got {min_neighbours})")
+    if not isinstance(eigenvalues, bool):
+        raise ValueError(f"{name}: eigenvalues must be True or False (got {eigenvalues})")
+    if viewpoint is not None and viewpoint.device != like.device:
+        raise ValueError(f"{name}: viewpoint must live on the device of {of}")
+    if queries.device.type != "cuda":
+        raise ValueError(f"{name}: the tensors must live on the GPU; there is no CPU path")
+    dev = queries.device
+    out = FieldNormals(normal=torch.empty(m, n, 3, dtype=torch.float32, device=dev),
+                       neighbours=torch.empty(m, n, dtype=torch.int32, device=dev),
+                       variation=torch.empty(m, n, dtype=torch.float32, device=dev),
+                       moments=torch.empty(m, n, hip.FIELD_NORMALS_MOMENTS_PER_ROW, dtype=torch.int64, device=dev),
+                       eigenvalues=torch.empty(m, n, 3, dtype=torch.float64, device=dev) if eigenvalues else None)
+    workspace = torch.empty(hip.field_normals_workspace(observed.shape[0], cells.num_nodes, observed.shape[1]), dtype=torch.int32,
+                            device=dev)
+    hip.field_normals(observed.contiguous(), queries.contiguous(), cells.c_grid(), radius,
+                      {f: getattr(out, f) for f in out.__dataclass_fields__}, m,
+                      observed_count=None if observed_count is None else observed_count.contiguous(), count=count,
+                      viewpoint=None if viewpoint is None else viewpoint.contiguous(), min_neighbours=min_neighbours,
+                      phase=hip.FIELD_NORMALS_ALL, workspace=workspace)
+    return out
+
+
 @dataclass
 class FieldRegistration:
     """The commands that bring the parts onto an unlabelled observation (``register_commands``): ``fit`` is the

@@ -181,6 +181,8 @@ _SIGNATURES = {
                                    C.c_double] + [_vp] * 11 + [C.c_longlong, C.c_int, _vp], C.c_int),
     "njf_field_nearest": ([_vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.POINTER(FieldGrid), C.c_double,
                            _vp, _vp, _vp, _vp, _vp, C.c_longlong, C.c_int, _vp], C.c_int),
+    "njf_field_normals": ([_vp, _vp, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, C.POINTER(FieldGrid), C.c_double, C.c_int,
+                           _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_longlong, C.c_int, _vp], C.c_int),
     "njf_pack_resnetfc_backward": ([C.POINTER(ResnetFcWeights), _vp, C.c_int, _vp], C.c_int),
     "njf_resnetfc_backward": ([_vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp], C.c_int),
     "njf_pack_transformer_backward": ([_vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, _vp], C.c_int),
@@ -1297,6 +1299,65 @@ def field_nearest(observed: Optional[torch.Tensor], queries: Optional[torch.Tens
             _int32_ptr(count, "count"), _int32_ptr(labels, "labels"), int(mq), int(n), m, C.byref(grid), float(max_distance),
             o("index", _int32_ptr), o("distance2", _ptr), o("matched", _ptr), o("found", _int32_ptr),
             _int32_ptr(workspace, "workspace"), int(workspace.numel()), int(phase))
+
+
+# ---- surface normals of an observed cloud from integer moments on the cell list (include/njf_hip.h: njf_field_normals) --------
+FIELD_NORMALS_BUILD, FIELD_NORMALS_MOMENTS, FIELD_NORMALS_FINISH = 1, 2, 4   # NJF_FIELD_NORMALS_BUILD (nearest's), _MOMENTS, _FINISH
+FIELD_NORMALS_PHASES = (FIELD_NORMALS_BUILD, FIELD_NORMALS_MOMENTS, FIELD_NORMALS_FINISH)
+FIELD_NORMALS_PHASE_NAMES = ("build", "moments", "finish")
+FIELD_NORMALS_ALL = 7                                  # NJF_FIELD_NORMALS_ALL
+FIELD_NORMALS_WAVE = 8                                 # NJF_FIELD_NORMALS_WAVE: the moments launch with a wave per row
+FIELD_NORMALS_MOMENTS_PER_ROW = 10                     # NJF_FIELD_NORMALS_MOMENTS_PER_ROW: S0, S1[3], S2[6]
+FIELD_NORMALS_SWEEPS = 8                               # NJF_FIELD_NORMALS_SWEEPS
+FIELD_NORMALS_MAX_POINTS = 2 ** 26                     # T below this: the int64 second moments cannot overflow
+field_normals_workspace = field_nearest_workspace      # NJF_FIELD_NORMALS_WORKSPACE: the cell list is njf_field_nearest's
+
+
+def field_normals(observed: Optional[torch.Tensor], queries: Optional[torch.Tensor], grid: FieldGrid, radius: float, out: dict,
+                  problems: int, observed_count=None, count=None, viewpoint=None, min_neighbours: int = 3,
+                  phase: int = FIELD_NORMALS_ALL, workspace: Optional[torch.Tensor] = None) -> None:
+    """njf_field_normals on ``observed`` [Mo, T, 3] and ``queries`` [Mq, n, 3] (fp32) for ``problems`` = M problems, Mo and Mq
+    each 1 or M, against the cell lattice ``grid``.  ``observed_count`` [Mo], ``count`` [1]: int32 or None; ``viewpoint`` [Mv,
+    3] fp32 or None, Mv 1 or M.  ``out`` maps moments [M, n, 10] (int64), normal [M, n, 3], variation [M, n] (fp32), neighbours
+    [M, n] (int32) and -- optionally -- eigenvalues [M, n, 3] (float64) to tensors of their shapes.  ``phase``:
+    FIELD_NORMALS_BUILD reads ``observed`` and writes the workspace (njf_field_nearest's build), FIELD_NORMALS_MOMENTS reads the
+    workspace and the queries and writes ``out["moments"]`` [+ FIELD_NORMALS_WAVE], FIELD_NORMALS_FINISH reads the moments and
+    writes the other outputs; a phase without the build takes the SHAPE ``(Mo, T)`` for ``observed``.  ``workspace``: int32,
+    ``field_normals_workspace`` elements, not needed by the finish alone."""
+    shape = lambda t: tuple(t.shape[:2]) if torch.is_tensor(t) else tuple(t)   # noqa: E731
+    if torch.is_tensor(observed) and (observed.dim() != 3 or observed.shape[2] != 3):
+        raise ValueError("njf_hip: field_normals needs observed [Mo, T, 3]")
+    if torch.is_tensor(queries) and (queries.dim() != 3 or queries.shape[2] != 3):
+        raise ValueError("njf_hip: field_normals needs queries [Mq, n, 3]")
+    (mo, t), (mq, n), m = shape(observed), shape(queries), int(problems)
+    build, sums, finish = (bool(phase & p) for p in FIELD_NORMALS_PHASES)
+    if (build and not torch.is_tensor(observed)) or ((sums or finish) and not torch.is_tensor(queries)):
+        raise ValueError("njf_hip: field_normals needs the observed points to build and the queries for the moments and the finish")
+    if observed_count is not None and observed_count.numel() != mo:
+        raise ValueError("njf_hip: field_normals needs observed_count [Mo]")
+    if count is not None and count.numel() != 1:
+        raise ValueError("njf_hip: field_normals count must hold one int32")
+    if viewpoint is not None and (viewpoint.dim() != 2 or viewpoint.shape[1] != 3):
+        raise ValueError("njf_hip: field_normals needs viewpoint [Mv, 3]")
+    sizes = dict(moments=10 * m * n) if sums or finish else {}
+    if finish:
+        sizes.update(normal=3 * m * n, neighbours=m * n, variation=m * n)
+        if out.get("eigenvalues") is not None:
+            sizes.update(eigenvalues=3 * m * n)
+    for name, size in sizes.items():
+        if out[name].numel() != size:
+            raise ValueError(f"njf_hip: field_normals output {name} must hold {size} elements (got {out[name].numel()})")
+    cells = int(grid.dims[0]) * int(grid.dims[1]) * int(grid.dims[2])
+    if workspace is None and (build or sums):
+        like = observed if build else queries
+        workspace = torch.empty(field_normals_workspace(mo, cells, t), dtype=torch.int32, device=like.device)
+    o = (lambda key, ptr, *dtype: ptr(out[key], key, *dtype) if key in sizes else None)   # noqa: E731
+    _launch("njf_field_normals", load_library().njf_field_normals, _ptr(observed, "observed") if build else None,
+            _int32_ptr(observed_count, "observed_count"), int(mo), int(t), _ptr(queries, "queries") if sums or finish else None,
+            _int32_ptr(count, "count"), int(mq), int(n), m, C.byref(grid), float(radius), int(min_neighbours),
+            _ptr(viewpoint, "viewpoint"), 0 if viewpoint is None else int(viewpoint.shape[0]), o("moments", _ptr, torch.int64),
+            o("normal", _ptr), o("neighbours", _int32_ptr), o("variation", _ptr), o("eigenvalues", _double_ptr),
+            _int32_ptr(workspace, "workspace"), 0 if workspace is None else int(workspace.numel()), int(phase))
 
 
 def solve_action(mean_position, jacobian, projection, target_flow, visible_mask, init_action, iterations: int,
