@@ -936,6 +936,82 @@ int njf_field_normals(const float* observed, const int* observed_count, int num_
                       int* neighbours, float* variation, double* eigenvalues, int* workspace, long long workspace_words,
                       int phases, void* stream);
 
+/* ---- a depth frame to world points (ABI v20, additive) -------------------------------------------------------
+ * The back-projection of B depth images through the package's cameras: the observed cloud that njf_field_nearest, njf_field_normals
+ * and njf_field_voxels take, with the invalid and the "flying" pixels of a real sensor taken out.
+ * Inputs, all on the device: depth [B,H,W] float; k_inv [B,3,3] float, the INVERSE of the normalised intrinsics; c2w [B,4,4] float.
+ * PIXEL  r = row * W + col has the centre x = ((float)col + 0.5f) / (float)W, y = ((float)row + 0.5f) / (float)H (row-major,
+ *        get_pixel_coordinates' grid).
+ * RAY    njf_generate_rays' of that centre, bit for bit -- the same fma chains, sqrtf and divisions: origin o = the translation of
+ *        c2w, unit direction d, and cz, the camera-space z of the unit direction.
+ * POINT  t = depth for NJF_FIELD_DEPTH_RAY (a distance along the unit ray: the package's own rendered depth), t = depth / cz, an
+ *        IEEE division, for NJF_FIELD_DEPTH_Z (what depth cameras report).  p_c = o_c + d_c * t: one float multiply and one float
+ *        add per component, no contraction.
+ * VALID  a pixel of depth d is valid when d is finite and near < d <= far, compared in float: near = 0 drops the zeros that sensors
+ *        write for "no return".  With max_jump > 0 a valid pixel is dropped as well when one of its 4-neighbours inside the image
+ *        has a valid depth dn with fabsf(d - dn) > max_jump * fminf(d, dn) (a float product).  Invalid neighbours do not count; the
+ *        rule is symmetric, so both sides of a depth edge go; it reads the input only.  max_jump = 0: no such test.
+ * Outputs: points [B,H*W,3] float -- read as [B / V, V*H*W, 3], the V = views_per_scene consecutive views of a scene are one
+ *        cloud; EVERY row is written, a pixel that gives no point gets three NaNs, which the cell-list build skips.  kept [B / V]
+ *        int32: the pixels that gave a point, counted with integer atomics.
+ * One memset (kept) and one launch, one lane per pixel; one stream, no host read (capture-safe).
+ * Returns, before the launch: NJF_E_NULL for a missing pointer; NJF_E_SHAPE for B, H or W < 1, B*H*W >= 2^31, V < 1 or B % V != 0;
+ * NJF_E_VALUE for an unknown kind, near not in [0, inf), far not > near (NaN included), max_jump negative or not finite. */
+#define NJF_FIELD_DEPTH_RAY 0        /* kind */
+#define NJF_FIELD_DEPTH_Z 1
+int njf_field_depth_points(const float* depth, int batch, int height, int width, const float* k_inv, const float* c2w, int kind,
+                           float near, float far, float max_jump, int views_per_scene, float* points, int* kept, void* stream);
+
+/* ---- one centroid per occupied cell of a cloud (ABI v20, additive) ---------------------------------------------
+ * For each of M clouds: the points that fall into one cell of a lattice are replaced by their centroid -- the standard thinning of
+ * a cloud that is much denser than its cells, which also averages sensor noise.  The sums are integers, so that the order in
+ * which the cell list is read cannot change a byte of any output.
+ * Inputs, all on the device: points [M,T,3] float; points_count int32 [M] or NULL (= T).  `cells`: njf_field_nearest's lattice,
+ * under the same rules: origin = its lower corner, three equal steps `cell` > 0, dims = cells per axis, inv_cell = 1.0f / cell.
+ * VALID POINT j of problem m: j < min(points_count[m], T) and three finite coordinates.
+ * INSIDE a valid point is inside when 0 <= floorf(t_c) < dims_c on all three axes, t_c = (p_c - origin_c) * inv_cell in float,
+ *        njf_field_nearest's cell coordinate: its unclamped cell is the cell the build stores it in.  The other valid points,
+ *        which the build puts into boundary cells, are not reduced; they are counted in outside [M].
+ * SUMS   an inside point adds q_c = (long long)rintf((t_c - floorf(t_c)) * 1048576.0f), in [0, 2^20], to three int64 sums S_c of its
+ *        cell, and 1 to the cell's count k.  Integer addition is associative: the same bytes in any order, and in both forms.
+ * KEPT   a cell with k >= min_points, 1 <= min_points.  Its centroid is (float)(origin_c + (cell_index_c + S_c / (k * 2^20)) * cell)
+ *        in double with exactly this association: (double)S_c / ((double)k * 1048576.0), plus (double)cell_index_c, times
+ *        (double)cell, plus (double)origin_c, no contraction.
+ * ORDER  the kept cells of a problem in ascending cell index (cx*dy + cy)*dz + cz.
+ * Outputs: out_points [M,capacity,3] float; weight [M,capacity] int32 = k; cell_index [M,capacity] int32; sums [M,capacity,3] int64;
+ *        count [M] int32 = the TRUE number of kept cells, which may exceed capacity (the rows beyond it are dropped); outside [M]
+ *        int32.  Rows from min(count, capacity) on are written too: NaN, 0, -1, 0 -- out_points is a valid `observed` of
+ *        njf_field_nearest with or without count as its observed_count.  capacity = min(T, C) cannot overflow.
+ * BUILD  njf_field_nearest's build (a memset, five launches) on the same workspace.
+ * REDUCE a memset (outside) and one launch, one lane per (problem, cell), which reads the cell's range of 16-byte records and writes
+ *        the cell's sums, its count and its kept flag into the workspace; outside with integer atomics.  Every range is clamped
+ *        to [0, M * T) and to T records before use: on a workspace that was never built it reads nothing outside it.
+ *        NJF_FIELD_VOXELS_WAVE: one wave per (problem, cell), the lanes sharing the records.
+ * COMPACT four launches: the exclusive scan of the kept flags over the M * C cells -- the build's three scan launches on a second
+ *        starts array -- and the ordered scatter, which also writes the fill rows and count.  The scan clears the flags (they
+ *        live in the build's cursors, which nothing reads after the build): every COMPACT needs a REDUCE of its own before it.
+ *        A row index is checked against [0, capacity) before it is written.
+ * workspace: NJF_FIELD_VOXELS_WORKSPACE(M, C, T) 32-bit words, C = dims[0]*dims[1]*dims[2]: njf_field_nearest's, in its layout, and
+ * behind its records 3 M C int64 sums, M C counts and M C + 1 second starts.  The starts and the records stay as the build wrote
+ * them: the same workspace still answers njf_field_nearest's query phase, and one that njf_field_nearest's build wrote (in a
+ * buffer of this size) is taken as it is.
+ * `phases`: NJF_FIELD_VOXELS_BUILD | NJF_FIELD_VOXELS_REDUCE [| NJF_FIELD_VOXELS_WAVE] | NJF_FIELD_VOXELS_COMPACT.  One stream, no
+ * host read (capture-safe), integer atomics only.
+ * Returns, before the first launch: NJF_E_VALUE for M outside [1, NJF_FIELD_POSE_MAX_COMMANDS], a lattice njf_field_nearest
+ * refuses, M * C >= 2^31, min_points < 1 or unknown phases (the modifier without the reduce phase included); NJF_E_SHAPE for T <
+ * 1, M * T >= 2^31, capacity < 1, M * capacity >= 2^31 or a workspace that is too small; NJF_E_NULL for a missing pointer: cells;
+ * the workspace; points with the build; outside with the reduce; the other five outputs with the compact phase. */
+#define NJF_FIELD_VOXELS_WORKSPACE(M, C, T) (NJF_FIELD_NEAREST_WORKSPACE(M, C, T) + 8LL * (M) * (C) + 1LL)
+#define NJF_FIELD_VOXELS_QUANTUM 1048576   /* 2^20 steps per cell */
+#define NJF_FIELD_VOXELS_BUILD 1     /* phases */
+#define NJF_FIELD_VOXELS_REDUCE 2
+#define NJF_FIELD_VOXELS_COMPACT 4
+#define NJF_FIELD_VOXELS_ALL 7
+#define NJF_FIELD_VOXELS_WAVE 8      /* with REDUCE: a wave per cell */
+int njf_field_voxels(const float* points, const int* points_count, int num_problems, int num_points, const NjfFieldGrid* cells,
+                     int min_points, int capacity, float* out_points, int* weight, int* cell_index, long long* sums, int* count,
+                     int* outside, int* workspace, long long workspace_words, int phases, void* stream);
+
 /* ---- stand-alone sampler / compositing ops (API parity with the un-fused reference calls) -- */
 /* RaySamples.get_weights (ray_samplers.py:77-101): deltas, densities [N,S] -> weights [N,S]. */
 int njf_alpha_weights(const float* deltas, const float* densities, int rays, int samples, float* weights, void* stream);

@@ -1177,6 +1177,118 @@ extern "C" int njf_generate_rays(const float* coords, int height, int width, con
   return launch_status();
 }
 
+// ---- a depth frame to world points (njf_field_depth_points) -------------------------------------------------
+// One lane per pixel: the validity of its depth and of its four neighbours, raygen_kernel's ray of the pixel centre -- the same
+// expressions in the same order, restated here so that raygen_kernel is not touched --, t from the depth, and the point o + d t
+// as one multiply and one add per component.  Every row is written; `kept` is counted with integer atomics.
+struct DepthArgs {
+  const float* depth;  // [B,H,W]
+  const float* k_inv;  // [B,3,3]
+  const float* c2w;    // [B,4,4]
+  int batch, height, width, views;
+  long long rays;      // H * W
+  long long total;     // B * H * W < 2^31
+  int kind;
+  float near, far, max_jump;
+  float* points;       // [B,H*W,3]
+  int* kept;           // [B / views]
+};
+
+__device__ __forceinline__ bool depth_valid(float d, float near, float far) {
+  return fabsf(d) < INFINITY && d > near && d <= far;  // (NaN compares false)
+}
+
+// a valid neighbour across a depth edge: the rule is symmetric in (d, dn)
+__device__ __forceinline__ bool depth_jump(float d, float dn, const DepthArgs& a) {
+  return depth_valid(dn, a.near, a.far) && fabsf(d - dn) > a.max_jump * fminf(d, dn);
+}
+
+__global__ void __launch_bounds__(256) depth_points_kernel(DepthArgs a) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  const bool live = i < a.total;
+  const int b = live ? (int)(i / a.rays) : 0;
+  const int scene = live ? b / a.views : -1;
+  bool ok = false;
+  if (live) {
+    const int r = (int)(i - (long long)b * a.rays);
+    const int row = r / a.width, col = r - row * a.width;
+    const float* img = a.depth + (long long)b * a.rays;
+    const float d = img[r];
+    ok = depth_valid(d, a.near, a.far);
+    if (ok && a.max_jump > 0.0f) {
+      if (row > 0 && depth_jump(d, img[r - a.width], a)) ok = false;
+      if (row + 1 < a.height && depth_jump(d, img[r + a.width], a)) ok = false;
+      if (col > 0 && depth_jump(d, img[r - 1], a)) ok = false;
+      if (col + 1 < a.width && depth_jump(d, img[r + 1], a)) ok = false;
+    }
+    float px = __int_as_float(0x7fc00000), py = px, pz = px;
+    if (ok) {
+      const float x = ((float)col + 0.5f) / (float)a.width;
+      const float y = ((float)row + 0.5f) / (float)a.height;
+      const float* ki = a.k_inv + b * 9;
+      float cx = fmaf(ki[2], 1.0f, fmaf(ki[1], y, ki[0] * x));
+      float cy = fmaf(ki[5], 1.0f, fmaf(ki[4], y, ki[3] * x));
+      float cz = fmaf(ki[8], 1.0f, fmaf(ki[7], y, ki[6] * x));
+      cx *= 1.0f;
+      const float nrm = sqrtf(cx * cx + cy * cy + cz * cz);
+      cx /= nrm;
+      cy /= nrm;
+      cz /= nrm;
+      const float* m = a.c2w + b * 16;
+      const float dx = fmaf(m[3], 0.0f, fmaf(m[2], cz, fmaf(m[1], cy, m[0] * cx)));
+      const float dy = fmaf(m[7], 0.0f, fmaf(m[6], cz, fmaf(m[5], cy, m[4] * cx)));
+      const float dz = fmaf(m[11], 0.0f, fmaf(m[10], cz, fmaf(m[9], cy, m[8] * cx)));
+      const float t = a.kind == NJF_FIELD_DEPTH_Z ? d / cz : d;
+      px = m[3] + dx * t;
+      py = m[7] + dy * t;
+      pz = m[11] + dz * t;
+    }
+    a.points[3 * i + 0] = px;
+    a.points[3 * i + 1] = py;
+    a.points[3 * i + 2] = pz;
+  }
+  // one atomic per wave where its pixels belong to one scene (lane 0 is live whenever any lane is)
+  const int first = __shfl(scene, 0, 64);
+  if (__all(!ok || scene == first)) {
+    const int n = __popcll(__ballot(ok));
+    if ((threadIdx.x & 63) == 0 && n) atomicAdd(&a.kept[first], n);
+  } else if (ok) {
+    atomicAdd(&a.kept[scene], 1);
+  }
+}
+
+extern "C" int njf_field_depth_points(const float* depth, int batch, int height, int width, const float* k_inv, const float* c2w,
+                                      int kind, float near, float far, float max_jump, int views_per_scene, float* points,
+                                      int* kept, void* stream) {
+  if (!depth || !k_inv || !c2w || !points || !kept) return NJF_E_NULL;
+  if (batch < 1 || height < 1 || width < 1 || (long long)batch * height * width >= (1LL << 31)) return NJF_E_SHAPE;
+  if (views_per_scene < 1 || batch % views_per_scene) return NJF_E_SHAPE;
+  if (kind != NJF_FIELD_DEPTH_RAY && kind != NJF_FIELD_DEPTH_Z) return NJF_E_VALUE;
+  if (!(near >= 0.0f) || !(near < INFINITY) || !(far > near)) return NJF_E_VALUE;
+  if (!(max_jump >= 0.0f) || !(max_jump < INFINITY)) return NJF_E_VALUE;
+  DepthArgs a;
+  a.depth = depth;
+  a.k_inv = k_inv;
+  a.c2w = c2w;
+  a.batch = batch;
+  a.height = height;
+  a.width = width;
+  a.views = views_per_scene;
+  a.rays = (long long)height * width;
+  a.total = a.rays * batch;
+  a.kind = kind;
+  a.near = near;
+  a.far = far;
+  a.max_jump = max_jump;
+  a.points = points;
+  a.kept = kept;
+  hipStream_t s = (hipStream_t)stream;
+  hipError_t e = hipMemsetAsync(kept, 0, (size_t)(batch / views_per_scene) * sizeof(int), s);
+  if (e != hipSuccess) return (int)e;
+  depth_points_kernel<<<(unsigned)((a.total + 255) / 256), 256, 0, s>>>(a);
+  return launch_status();
+}
+
 // =============================================================================================
 // shared pieces of the fused ray kernels
 // =============================================================================================
@@ -5164,6 +5276,120 @@ __global__ void __launch_bounds__(NJF_NN_THREADS) nrm_finish_kernel(NrmArgs a) {
   }
 }
 
+// ---- one centroid per occupied cell (njf_field_voxels) ---------------------------------------------------------
+// REDUCE reads the records of every cell of njf_field_nearest's list and adds, over the points whose unclamped cell is this
+// cell, the fractional cell coordinates quantised to 2^-20 cells: three int64 sums and a count per cell.  The order inside a
+// cell depends on scheduling; integer sums do not.  COMPACT scans the kept flags with the nn_scan_* kernels, pointed at a
+// second starts array, and scatters the kept cells in ascending cell index.
+struct VoxArgs {
+  int M, T, C;
+  float origin[3];
+  float cell, inv_cell;
+  int dims[3];
+  long long L, slots;      // M * C, M * T
+  int min_points, capacity;
+  const int* start;        // njf_field_nearest's workspace
+  const int4* records;
+  int* flag;               // [L]: njf_field_nearest's cursors, free after its build; the scan clears them again
+  long long* cell_sums;    // [L,3]
+  int* cell_k;             // [L]
+  const int* kept_start;   // [L + 1]: the exclusive scan of the flags
+  float* points;           // [M,capacity,3]
+  int* weight;             // [M,capacity]
+  int* cell_index;         // [M,capacity]
+  long long* sums;         // [M,capacity,3]
+  int* count;              // [M]
+  int* outside;            // [M]
+};
+
+__device__ __forceinline__ long long vox_shfl_xor(long long v, int o) {
+  const unsigned low = (unsigned)__shfl_xor((int)(unsigned)v, o, 64);
+  const int high = __shfl_xor((int)(v >> 32), o, 64);
+  return (long long)(((unsigned long long)(unsigned)high << 32) | low);
+}
+
+// WAVE false: one lane per (problem, cell); true: one wave per (problem, cell), the lanes share the cell's records
+template <bool WAVE>
+__global__ void __launch_bounds__(NJF_NN_THREADS) vox_reduce_kernel(VoxArgs a) {
+  const int lane = threadIdx.x & 63;
+  const long long c = WAVE ? (long long)blockIdx.x * (NJF_NN_THREADS / 64) + (threadIdx.x >> 6)
+                           : (long long)blockIdx.x * NJF_NN_THREADS + threadIdx.x;
+  if (c >= a.L) return;  // (a whole wave in the wave form)
+  long long lo = a.start[c], hi = a.start[c + 1];
+  lo = min(max(lo, 0LL), a.slots);
+  hi = min(min(max(hi, lo), a.slots), lo + a.T);
+  long long sx = 0, sy = 0, sz = 0;
+  int k = 0, out = 0;
+  for (long long s = lo + (WAVE ? lane : 0); s < hi; s += WAVE ? 64 : 1) {
+    const int4 rec = a.records[s];
+    const float tx = (__int_as_float(rec.x) - a.origin[0]) * a.inv_cell, ty = (__int_as_float(rec.y) - a.origin[1]) * a.inv_cell,
+                tz = (__int_as_float(rec.z) - a.origin[2]) * a.inv_cell;
+    const float fx = floorf(tx), fy = floorf(ty), fz = floorf(tz);
+    if (fx >= 0.0f && fx < (float)a.dims[0] && fy >= 0.0f && fy < (float)a.dims[1] && fz >= 0.0f && fz < (float)a.dims[2]) {
+      sx += (long long)rintf((tx - fx) * 1048576.0f);
+      sy += (long long)rintf((ty - fy) * 1048576.0f);
+      sz += (long long)rintf((tz - fz) * 1048576.0f);
+      ++k;
+    } else {
+      ++out;
+    }
+  }
+  if (WAVE)
+    for (int o = 32; o > 0; o >>= 1) {
+      sx += vox_shfl_xor(sx, o);
+      sy += vox_shfl_xor(sy, o);
+      sz += vox_shfl_xor(sz, o);
+      k += __shfl_xor(k, o, 64);
+      out += __shfl_xor(out, o, 64);
+    }
+  if (!WAVE || lane == 0) {
+    a.cell_sums[c * 3] = sx;
+    a.cell_sums[c * 3 + 1] = sy;
+    a.cell_sums[c * 3 + 2] = sz;
+    a.cell_k[c] = k;
+    a.flag[c] = k >= a.min_points ? 1 : 0;
+    if (out) atomicAdd(&a.outside[(int)(c / a.C)], out);
+  }
+}
+
+// thread e < L: the kept cell e to its row; thread e < M * capacity: the fill of a row from the count on
+__global__ void __launch_bounds__(NJF_NN_THREADS) vox_scatter_kernel(VoxArgs a) {
+  const long long e = (long long)blockIdx.x * NJF_NN_THREADS + threadIdx.x;
+  if (e < a.L) {
+    const int m = (int)(e / a.C), ci = (int)(e - (long long)m * a.C);
+    const long long base = a.kept_start[(long long)m * a.C];
+    const long long row = (long long)a.kept_start[e] - base;
+    if (ci == 0) a.count[m] = (int)((long long)a.kept_start[(long long)(m + 1) * a.C] - base);
+    if (a.kept_start[e + 1] > a.kept_start[e] && row >= 0 && row < a.capacity) {
+      const long long r = (long long)m * a.capacity + row;
+      const int k = a.cell_k[e];
+      const int cz = ci % a.dims[2], cy = (ci / a.dims[2]) % a.dims[1], cx = ci / (a.dims[2] * a.dims[1]);
+      const int axis[3] = {cx, cy, cz};
+      const double per = (double)k * 1048576.0;
+#pragma unroll
+      for (int d = 0; d < 3; ++d) {
+        const long long s = a.cell_sums[e * 3 + d];
+        a.sums[r * 3 + d] = s;
+        a.points[r * 3 + d] = (float)((double)a.origin[d] + ((double)axis[d] + (double)s / per) * (double)a.cell);
+      }
+      a.weight[r] = k;
+      a.cell_index[r] = ci;
+    }
+  }
+  if (e < (long long)a.M * a.capacity) {
+    const int m = (int)(e / a.capacity);
+    const long long row = e - (long long)m * a.capacity;
+    const long long kept = (long long)a.kept_start[(long long)(m + 1) * a.C] - a.kept_start[(long long)m * a.C];
+    if (row >= kept) {
+      const float nan = __int_as_float(0x7fc00000);
+      a.points[e * 3] = nan, a.points[e * 3 + 1] = nan, a.points[e * 3 + 2] = nan;
+      a.sums[e * 3] = 0, a.sums[e * 3 + 1] = 0, a.sums[e * 3 + 2] = 0;
+      a.weight[e] = 0;
+      a.cell_index[e] = -1;
+    }
+  }
+}
+
 // =============================================================================================
 // inverse dynamics: Levenberg-Marquardt on the linearised flow, one workgroup per batch element
 // =============================================================================================
@@ -7721,6 +7947,97 @@ extern "C" int njf_field_normals(const float* observed, const int* observed_coun
   if (finish) {
     const dim3 grid((unsigned)(((long long)n + NJF_NN_THREADS - 1) / NJF_NN_THREADS), (unsigned)num_problems);
     nrm_finish_kernel<<<grid, NJF_NN_THREADS, 0, s>>>(a);
+    if ((rc = launch_status())) return rc;
+  }
+  return NJF_OK;
+}
+
+extern "C" int njf_field_voxels(const float* points, const int* points_count, int num_problems, int num_points,
+                                const NjfFieldGrid* cells, int min_points, int capacity, float* out_points, int* weight,
+                                int* cell_index, long long* sums, int* count, int* outside, int* workspace,
+                                long long workspace_words, int phases, void* stream) {
+  if (num_problems < 1 || num_problems > NJF_FIELD_POSE_MAX_COMMANDS) return NJF_E_VALUE;
+  if (phases < 1 || phases > (NJF_FIELD_VOXELS_ALL | NJF_FIELD_VOXELS_WAVE) || !(phases & NJF_FIELD_VOXELS_ALL) ||
+      ((phases & NJF_FIELD_VOXELS_WAVE) && !(phases & NJF_FIELD_VOXELS_REDUCE)))
+    return NJF_E_VALUE;
+  if (min_points < 1) return NJF_E_VALUE;
+  if (!cells) return NJF_E_NULL;
+  const float cell = cells->step[0], inv_cell = 1.0f / cell;
+  if (!(cell > 0.0f) || cells->step[1] != cell || cells->step[2] != cell || !(inv_cell > 0.0f) || !(cell < INFINITY) ||
+      !(inv_cell < INFINITY))
+    return NJF_E_VALUE;
+  long long C = 1;
+  for (int c = 0; c < 3; ++c) {
+    if (cells->dims[c] < 1 || cells->dims[c] > NJF_FIELD_NEAREST_MAX_DIM) return NJF_E_VALUE;
+    if (!(fabsf(cells->origin[c]) < INFINITY)) return NJF_E_VALUE;
+    C *= cells->dims[c];
+  }
+  const long long L = (long long)num_problems * C;
+  if (L >= (1LL << 31)) return NJF_E_VALUE;
+  if (num_points < 1 || (long long)num_problems * num_points >= (1LL << 31)) return NJF_E_SHAPE;
+  if (capacity < 1 || (long long)num_problems * capacity >= (1LL << 31)) return NJF_E_SHAPE;
+  if (workspace_words < NJF_FIELD_VOXELS_WORKSPACE(num_problems, C, num_points)) return NJF_E_SHAPE;
+  const bool build = phases & NJF_FIELD_VOXELS_BUILD, reduce = phases & NJF_FIELD_VOXELS_REDUCE,
+             compact = phases & NJF_FIELD_VOXELS_COMPACT;
+  if (!workspace || (build && !points) || (reduce && !outside) ||
+      (compact && (!out_points || !weight || !cell_index || !sums || !count)))
+    return NJF_E_NULL;
+  hipStream_t s = (hipStream_t)stream;
+  int rc;
+  // one cell is a max_distance that njf_field_nearest admits for every lattice; its build does not read it
+  if (build && (rc = njf_field_nearest(points, points_count, num_problems, num_points, nullptr, nullptr, nullptr, 1, 0, num_problems,
+                                       cells, (double)cell, nullptr, nullptr, nullptr, nullptr, workspace, workspace_words,
+                                       NJF_FIELD_NEAREST_BUILD, stream)))
+    return rc;
+  VoxArgs a;
+  a.M = num_problems;
+  a.T = num_points;
+  a.C = (int)C;
+  for (int c = 0; c < 3; ++c) a.origin[c] = cells->origin[c], a.dims[c] = cells->dims[c];
+  a.cell = cell;
+  a.inv_cell = inv_cell;
+  a.L = L;
+  a.slots = (long long)num_problems * num_points;
+  a.min_points = min_points;
+  a.capacity = capacity;
+  a.start = workspace;                                   // njf_field_nearest's layout ...
+  int* cursor = workspace + (long long)num_problems * (C + 1);
+  int4* records = (int4*)(((uintptr_t)(cursor + L) + 15) & ~(uintptr_t)15);
+  a.records = records;
+  a.flag = cursor;
+  a.cell_sums = (long long*)(records + a.slots);        // ... and behind it 3 L int64 sums, L counts, L + 1 second starts
+  a.cell_k = (int*)(a.cell_sums + 3 * L);
+  int* kept_start = a.cell_k + L;
+  a.kept_start = kept_start;
+  a.points = out_points;
+  a.weight = weight;
+  a.cell_index = cell_index;
+  a.sums = sums;
+  a.count = count;
+  a.outside = outside;
+  if (reduce) {
+    hipError_t e = hipMemsetAsync(outside, 0, (size_t)num_problems * sizeof(int), s);
+    if (e != hipSuccess) return (int)e;
+    if (phases & NJF_FIELD_VOXELS_WAVE)
+      vox_reduce_kernel<true><<<(unsigned)((L + NJF_NN_THREADS / 64 - 1) / (NJF_NN_THREADS / 64)), NJF_NN_THREADS, 0, s>>>(a);
+    else
+      vox_reduce_kernel<false><<<(unsigned)((L + NJF_NN_THREADS - 1) / NJF_NN_THREADS), NJF_NN_THREADS, 0, s>>>(a);
+    if ((rc = launch_status())) return rc;
+  }
+  if (compact) {
+    NnArgs scan{};                                       // the three scan launches read cursor, L and write start: nothing else
+    scan.L = L;
+    scan.start = kept_start;
+    scan.cursor = cursor;
+    const int blocks = (int)((L + NJF_NN_SCAN_BLOCK - 1) / NJF_NN_SCAN_BLOCK);
+    nn_scan_sums_kernel<<<blocks, NJF_NN_THREADS, 0, s>>>(scan);
+    if ((rc = launch_status())) return rc;
+    nn_scan_blocks_kernel<<<1, NJF_NN_THREADS, 0, s>>>(scan, blocks);
+    if ((rc = launch_status())) return rc;
+    nn_scan_cells_kernel<<<blocks, NJF_NN_THREADS, 0, s>>>(scan);
+    if ((rc = launch_status())) return rc;
+    const long long threads = L > (long long)num_problems * capacity ? L : (long long)num_problems * capacity;
+    vox_scatter_kernel<<<(unsigned)((threads + NJF_NN_THREADS - 1) / NJF_NN_THREADS), NJF_NN_THREADS, 0, s>>>(a);
     if ((rc = launch_status())) return rc;
   }
   return NJF_OK;

@@ -1064,13 +1064,12 @@ class FieldNearest:
     found: torch.Tensor       # [M] int32: the accepted rows
 
 
-def _check_nearest(name: str, observed, cells, max_distance, observed_count, count, labels, n: int, mq: int, like: torch.Tensor,
-                   of: str, m_other: int = 1):
-    """The checks of the observation, the lattice and the search that ``nearest_points`` and the registration share; ``like``
-    (called ``of`` in the messages) rules the device.  ``(observed [Mo, T, 3], M, observed_count, count)``."""
+def _check_cloud_cells(name: str, observed, cells, mq: int = 1, m_other: int = 1, what: str = "observed"):
+    """The checks of a cloud and of the lattice it is sorted into, shared by everything that builds the cell list
+    (``_check_nearest``, ``voxel_reduce``).  ``(observed [Mo, T, 3], M)``."""
     if not torch.is_tensor(observed) or observed.dtype != torch.float32 or observed.dim() not in (2, 3) or observed.shape[-1] != 3 \
             or observed.shape[-2] < 1:
-        raise ValueError(f"{name}: observed must be fp32 [T, 3] or [Mo, T, 3] with T >= 1")
+        raise ValueError(f"{name}: {what} must be fp32 [T, 3] or [Mo, T, 3] with T >= 1")
     observed = observed.reshape(-1, *observed.shape[-2:]) if observed.dim() == 3 else observed[None]
     mo, t = observed.shape[:2]
     m = max(mo, mq, m_other)
@@ -1089,6 +1088,20 @@ def _check_nearest(name: str, observed, cells, max_distance, observed_count, cou
         raise ValueError(f"{name}: at most {hip.FIELD_NEAREST_MAX_DIM} cells per axis (got {cells.dims})")
     if mo * cells.num_nodes >= 2 ** 31:
         raise ValueError(f"{name}: Mo * the number of cells must stay below 2**31")
+    return observed, m
+
+
+def _check_cloud_count(name: str, what: str, count, mo: int) -> None:
+    if count is not None and (not torch.is_tensor(count) or count.dtype != torch.int32 or tuple(count.shape) != (mo,)):
+        raise ValueError(f"{name}: {what} must be int32 [{mo}]")
+
+
+def _check_nearest(name: str, observed, cells, max_distance, observed_count, count, labels, n: int, mq: int, like: torch.Tensor,
+                   of: str, m_other: int = 1):
+    """The checks of the observation, the lattice and the search that ``nearest_points`` and the registration share; ``like``
+    (called ``of`` in the messages) rules the device.  ``(observed [Mo, T, 3], M, observed_count, count)``."""
+    observed, m = _check_cloud_cells(name, observed, cells, mq, m_other)
+    mo, cell = observed.shape[0], cells.step[0]
     if isinstance(max_distance, bool) or not isinstance(max_distance, (int, float)) or not max_distance > 0.0 \
             or not math.isfinite(max_distance):
         raise ValueError(f"{name}: max_distance must be a finite number > 0 (got {max_distance})")
@@ -1099,9 +1112,7 @@ def _check_nearest(name: str, observed, cells, max_distance, observed_count, cou
     if not math.isfinite(reach) or not math.isfinite(reach / cell) or math.ceil(reach / cell) + 1 > hip.FIELD_NEAREST_MAX_RINGS:
         raise ValueError(f"{name}: max_distance may span at most {hip.FIELD_NEAREST_MAX_RINGS - 1} cells (got {max_distance} for cells "
                          f"of {cell}); take a larger cell")
-    if observed_count is not None and (not torch.is_tensor(observed_count) or observed_count.dtype != torch.int32
-                                       or tuple(observed_count.shape) != (mo,)):
-        raise ValueError(f"{name}: observed_count must be int32 [{mo}]")
+    _check_cloud_count(name, "observed_count", observed_count, mo)
     count = _one_int32(name, "count", count, like)
     if labels is not None and (not torch.is_tensor(labels) or labels.dtype != torch.int32 or tuple(labels.shape) != (n,)):
         raise ValueError(f"{name}: labels must be int32 [{n}]")
@@ -1242,6 +1253,123 @@ def point_normals(queries: Optional[torch.Tensor], observed: torch.Tensor, cells
                       observed_count=None if observed_count is None else observed_count.contiguous(), count=count,
                       viewpoint=None if viewpoint is None else viewpoint.contiguous(), min_neighbours=min_neighbours,
                       phase=hip.FIELD_NORMALS_ALL, workspace=workspace)
+    return out
+
+
+# ---- observed clouds from depth images: back-projection and voxel centroids -------------------------------
+@dataclass
+class FieldDepthPoints:
+    """The world points of depth frames (``depth_points``; include/njf_hip.h: njf_field_depth_points): one row per pixel,
+    row-major, the views of a scene one after the other; a pixel that gives no point holds three NaNs, which
+    ``nearest_points``, ``point_normals`` and ``voxel_reduce`` skip."""
+
+    points: torch.Tensor      # [B / V, V*H*W, 3] fp32
+    kept: torch.Tensor        # [B / V] int32: the pixels that gave a point
+
+
+def depth_points(depth: torch.Tensor, intrinsics: torch.Tensor, cam2world: torch.Tensor, *, kind: str = "z", near: float = 0.0,
+                 far: float = math.inf, max_jump: Optional[float] = None, views_per_scene: int = 1) -> FieldDepthPoints:
+    """The back-projection of the depth frames ``depth`` ``[B, H, W]`` (fp32) through the cameras ``intrinsics`` ``[B, 3, 3]``
+    (normalised) and ``cam2world`` ``[B, 4, 4]``.  The pixel grid is ``geometry.get_pixel_coordinates``'
+    (row-major, pixel centres) and the ray of a pixel ``geometry.full_frame_rays``', bit for bit: origin o, unit direction d,
+    camera-space cz.  ``kind="ray"``: the depth is a distance along the unit ray (``Model.forward``'s rendered depth), t =
+    depth; ``kind="z"``: it is the camera-space z that depth cameras report, t = depth / cz.  The point is ``o + d * t`` in fp32,
+    equal to that torch expression byte for byte.  A pixel is valid when its depth is finite and ``near < depth <= far`` in
+    fp32 (``near = 0`` drops a sensor's zeros); with ``max_jump`` (a relative threshold > 0) a valid pixel is dropped as well
+    when a 4-neighbour inside the image has a valid depth ``dn`` with ``|depth - dn| > max_jump * min(depth, dn)``: both sides
+    of a depth edge go, and with them the "flying" pixels between them.  The ``views_per_scene`` = V consecutive views of a
+    scene become one cloud.  Every row is written, NaN where there is no point; no host read, capturable."""
+    name = "depth_points"
+    if not torch.is_tensor(depth) or depth.dtype != torch.float32 or depth.dim() != 3 or min(depth.shape) < 1:
+        raise ValueError(f"{name}: depth must be fp32 [B, H, W] with B, H, W >= 1")
+    b, h, w = depth.shape
+    if not torch.is_tensor(intrinsics) or intrinsics.dtype != torch.float32 or tuple(intrinsics.shape) != (b, 3, 3):
+        raise ValueError(f"{name}: intrinsics must be fp32 [{b}, 3, 3]")
+    if not torch.is_tensor(cam2world) or cam2world.dtype != torch.float32 or tuple(cam2world.shape) != (b, 4, 4):
+        raise ValueError(f"{name}: cam2world must be fp32 [{b}, 4, 4]")
+    if kind not in hip.FIELD_DEPTH_KINDS:
+        raise ValueError(f"{name}: kind must be one of {sorted(hip.FIELD_DEPTH_KINDS)} (got {kind!r})")
+    for what, v in (("near", near), ("far", far)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or math.isnan(v):
+            raise ValueError(f"{name}: {what} must be a number (got {v})")
+    with np.errstate(over="ignore"):
+        near32, far32 = float(np.float32(near)), float(np.float32(far))     # the kernel's floats
+    if not 0.0 <= near32 < math.inf or not far32 > near32:
+        raise ValueError(f"{name}: 0 <= near < far, near finite (got {near} and {far})")
+    jump32 = 0.0                                                             # the kernel's "no such test"
+    if max_jump is not None:
+        if isinstance(max_jump, bool) or not isinstance(max_jump, (int, float)):
+            raise ValueError(f"{name}: max_jump must be a finite number > 0 or None (got {max_jump})")
+        with np.errstate(over="ignore"):
+            jump32 = float(np.float32(max_jump))
+        if not 0.0 < jump32 < math.inf:
+            raise ValueError(f"{name}: max_jump must be a finite number > 0 or None (got {max_jump})")
+    if isinstance(views_per_scene, bool) or not isinstance(views_per_scene, int) or views_per_scene < 1:
+        raise ValueError(f"{name}: views_per_scene must be an integer >= 1 (got {views_per_scene})")
+    if b % views_per_scene:
+        raise ValueError(f"{name}: the batch ({b}) must be a multiple of views_per_scene ({views_per_scene})")
+    if b * h * w >= 2 ** 31:
+        raise ValueError(f"{name}: B * H * W must stay below 2**31")
+    for what, t in (("intrinsics", intrinsics), ("cam2world", cam2world)):
+        if t.device != depth.device:
+            raise ValueError(f"{name}: {what} must live on the device of depth")
+    if depth.device.type != "cuda":
+        raise ValueError(f"{name}: the tensors must live on the GPU; there is no CPU path")
+    scenes = b // views_per_scene
+    out = FieldDepthPoints(points=torch.empty(scenes, views_per_scene * h * w, 3, dtype=torch.float32, device=depth.device),
+                           kept=torch.empty(scenes, dtype=torch.int32, device=depth.device))
+    hip.field_depth_points(depth.contiguous(), hip.inverse(intrinsics).contiguous(), cam2world.contiguous(),
+                           hip.FIELD_DEPTH_KINDS[kind], near32, far32, jump32, views_per_scene, out.points, out.kept)
+    return out
+
+
+@dataclass
+class FieldVoxels:
+    """One centroid per kept cell of a lattice (``voxel_reduce``; include/njf_hip.h: njf_field_voxels), per problem, in
+    ascending cell index.  ``points`` is a valid ``observed`` with or without ``observed_count=count``: the rows from the count
+    on hold NaN (and weight 0, cell -1, sums 0)."""
+
+    points: torch.Tensor      # [M, capacity, 3] fp32: the centroids
+    weight: torch.Tensor      # [M, capacity] int32: the points of the cell
+    cell: torch.Tensor        # [M, capacity] int32: its index (cx * dims_y + cy) * dims_z + cz
+    sums: torch.Tensor        # [M, capacity, 3] int64: the fractional cell coordinates of its points in steps of 2^-20 cells, summed
+    count: torch.Tensor       # [M] int32: the TRUE number of kept cells; may exceed the capacity
+    outside: torch.Tensor     # [M] int32: the valid points outside the lattice, which are not reduced
+
+
+def voxel_reduce(points: torch.Tensor, cells: FieldGrid, *, count: Optional[torch.Tensor] = None, min_points: int = 1,
+                 capacity: Optional[int] = None) -> FieldVoxels:
+    """The cloud ``points`` ``[T, 3]`` or ``[M, T, 3]`` (fp32) thinned to one centroid per occupied cell of ``cells``
+    (``cell_grid``), per problem.  A point is valid below ``count`` (int32 ``[M]``; None = T) with finite
+    coordinates, and inside when its unclamped cell ``floor((p - origin) / cell)`` lies in the lattice; valid points outside are
+    not reduced but counted in ``outside``.  A cell is kept with at least ``min_points`` points (more than 1 removes speckle);
+    its centroid is the mean of the points' cell coordinates quantised to 2^-20 cells -- exact integer sums, so the order in
+    which the cell list is read cannot matter: equal bytes from call to call, capturable, integer atomics only.  The kept cells
+    come in ascending cell index; ``capacity`` (None = min(T, C), which cannot overflow) bounds the rows, ``count`` stays true
+    beyond it, and the rows behind the kept ones are NaN: ``points`` goes into ``nearest_points``, ``point_normals`` and the
+    registration as it is."""
+    name = "voxel_reduce"
+    points, m = _check_cloud_cells(name, points, cells, what="points")
+    t = points.shape[1]
+    _check_cloud_count(name, "count", count, m)
+    if isinstance(min_points, bool) or not isinstance(min_points, int) or not 1 <= min_points < 2 ** 31:
+        raise ValueError(f"{name}: min_points must be an integer in [1, 2**31) (got {min_points})")
+    if capacity is None:
+        capacity = min(t, cells.num_nodes)
+    elif isinstance(capacity, bool) or not isinstance(capacity, int) or capacity < 1 or m * capacity >= 2 ** 31:
+        raise ValueError(f"{name}: capacity must be an integer >= 1 with M * capacity below 2**31, or None (got {capacity})")
+    if count is not None and count.device != points.device:
+        raise ValueError(f"{name}: count must live on the device of points")
+    if points.device.type != "cuda":
+        raise ValueError(f"{name}: the tensors must live on the GPU; there is no CPU path")
+    dev = points.device
+    out = FieldVoxels(points=torch.empty(m, capacity, 3, dtype=torch.float32, device=dev),
+                      weight=torch.empty(m, capacity, dtype=torch.int32, device=dev),
+                      cell=torch.empty(m, capacity, dtype=torch.int32, device=dev),
+                      sums=torch.empty(m, capacity, 3, dtype=torch.int64, device=dev),
+                      count=torch.empty(m, dtype=torch.int32, device=dev), outside=torch.empty(m, dtype=torch.int32, device=dev))
+    hip.field_voxels(points.contiguous(), cells.c_grid(), {f: getattr(out, f) for f in out.__dataclass_fields__},
+                     points_count=None if count is None else count.contiguous(), min_points=min_points, phase=hip.FIELD_VOXELS_ALL)
     return out
 
 

@@ -183,6 +183,10 @@ _SIGNATURES = {
                            _vp, _vp, _vp, _vp, _vp, C.c_longlong, C.c_int, _vp], C.c_int),
     "njf_field_normals": ([_vp, _vp, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, C.POINTER(FieldGrid), C.c_double, C.c_int,
                            _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_longlong, C.c_int, _vp], C.c_int),
+    "njf_field_depth_points": ([_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int, _vp, _vp,
+                                _vp], C.c_int),
+    "njf_field_voxels": ([_vp, _vp, C.c_int, C.c_int, C.POINTER(FieldGrid), C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                          C.c_longlong, C.c_int, _vp], C.c_int),
     "njf_pack_resnetfc_backward": ([C.POINTER(ResnetFcWeights), _vp, C.c_int, _vp], C.c_int),
     "njf_resnetfc_backward": ([_vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp], C.c_int),
     "njf_pack_transformer_backward": ([_vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, _vp], C.c_int),
@@ -1358,6 +1362,77 @@ def field_normals(observed: Optional[torch.Tensor], queries: Optional[torch.Tens
             _ptr(viewpoint, "viewpoint"), 0 if viewpoint is None else int(viewpoint.shape[0]), o("moments", _ptr, torch.int64),
             o("normal", _ptr), o("neighbours", _int32_ptr), o("variation", _ptr), o("eigenvalues", _double_ptr),
             _int32_ptr(workspace, "workspace"), 0 if workspace is None else int(workspace.numel()), int(phase))
+
+
+# ---- a depth frame to world points (include/njf_hip.h: njf_field_depth_points) -------------------------------------------------------
+FIELD_DEPTH_RAY, FIELD_DEPTH_Z = 0, 1                  # NJF_FIELD_DEPTH_RAY (t = depth), NJF_FIELD_DEPTH_Z (t = depth / cz)
+FIELD_DEPTH_KINDS = {"ray": FIELD_DEPTH_RAY, "z": FIELD_DEPTH_Z}
+
+
+def field_depth_points(depth: torch.Tensor, k_inv: torch.Tensor, c2w: torch.Tensor, kind: int, near: float, far: float,
+                       max_jump: float, views_per_scene: int, points: torch.Tensor, kept: torch.Tensor) -> None:
+    """njf_field_depth_points on ``depth`` [B, H, W], ``k_inv`` [B, 3, 3] (the INVERSE intrinsics) and ``c2w`` [B, 4, 4] (fp32):
+    ``points`` [B / V, V*H*W, 3] (fp32) and ``kept`` [B / V] (int32), every row written.  ``max_jump`` 0 = no flying-pixel test."""
+    if depth.dim() != 3:
+        raise ValueError("njf_hip: field_depth_points needs depth [B, H, W]")
+    b, h, w = (int(v) for v in depth.shape)
+    views = int(views_per_scene)
+    if views < 1 or b % views:
+        raise ValueError(f"njf_hip: field_depth_points needs B a multiple of views_per_scene (got {b} and {views_per_scene})")
+    for name, t, size in (("k_inv", k_inv, 9 * b), ("c2w", c2w, 16 * b), ("points", points, 3 * b * h * w), ("kept", kept, b // views)):
+        if t.numel() != size:
+            raise ValueError(f"njf_hip: field_depth_points {name} must hold {size} elements (got {t.numel()})")
+    _launch("njf_field_depth_points", load_library().njf_field_depth_points, _ptr(depth, "depth"), b, h, w, _ptr(k_inv, "k_inv"),
+            _ptr(c2w, "c2w"), int(kind), float(near), float(far), float(max_jump), views, _ptr(points, "points"),
+            _int32_ptr(kept, "kept"))
+
+
+# ---- one centroid per occupied cell of a cloud (include/njf_hip.h: njf_field_voxels) --------------------------------------------------
+FIELD_VOXELS_BUILD, FIELD_VOXELS_REDUCE, FIELD_VOXELS_COMPACT = 1, 2, 4   # NJF_FIELD_VOXELS_BUILD (nearest's), _REDUCE, _COMPACT
+FIELD_VOXELS_PHASES = (FIELD_VOXELS_BUILD, FIELD_VOXELS_REDUCE, FIELD_VOXELS_COMPACT)
+FIELD_VOXELS_PHASE_NAMES = ("build", "reduce", "compact")
+FIELD_VOXELS_ALL = 7                                   # NJF_FIELD_VOXELS_ALL
+FIELD_VOXELS_WAVE = 8                                  # NJF_FIELD_VOXELS_WAVE: the reduce launch with a wave per cell
+FIELD_VOXELS_QUANTUM = 2 ** 20                         # NJF_FIELD_VOXELS_QUANTUM: steps per cell of the integer sums
+
+
+def field_voxels_workspace(problems: int, cells: int, points: int) -> int:
+    """32-bit words of workspace njf_field_voxels needs: NJF_FIELD_VOXELS_WORKSPACE(M, C, T) -- njf_field_nearest's and, behind
+    it, 3 M C int64 sums, M C counts and M C + 1 second starts."""
+    return field_nearest_workspace(problems, cells, points) + 8 * problems * cells + 1
+
+
+def field_voxels(points, grid: FieldGrid, out: dict, points_count=None, min_points: int = 1, phase: int = FIELD_VOXELS_ALL,
+                 workspace: Optional[torch.Tensor] = None) -> None:
+    """njf_field_voxels on ``points`` [M, T, 3] (fp32) against the cell lattice ``grid``; ``points_count`` [M]: int32 or None.
+    ``out`` maps points [M, capacity, 3] (fp32), weight, cell [M, capacity] (int32), sums [M, capacity, 3] (int64), count and
+    outside [M] (int32) to tensors of their shapes; the capacity is read off ``out["weight"]``.  ``phase``: FIELD_VOXELS_BUILD
+    reads ``points`` and writes the workspace (njf_field_nearest's build), FIELD_VOXELS_REDUCE [+ FIELD_VOXELS_WAVE] reads the
+    cell list and writes the per-cell sums and ``out["outside"]``, FIELD_VOXELS_COMPACT writes the other outputs; a phase
+    without the build takes the SHAPE ``(M, T)`` for ``points``.  ``workspace``: int32, ``field_voxels_workspace`` elements."""
+    if torch.is_tensor(points) and (points.dim() != 3 or points.shape[2] != 3):
+        raise ValueError("njf_hip: field_voxels needs points [M, T, 3]")
+    m, t = (int(v) for v in (points.shape[:2] if torch.is_tensor(points) else points))
+    build = bool(phase & FIELD_VOXELS_BUILD)
+    if build and not torch.is_tensor(points):
+        raise ValueError("njf_hip: field_voxels needs the points to build")
+    if points_count is not None and points_count.numel() != m:
+        raise ValueError("njf_hip: field_voxels needs points_count [M]")
+    if out["weight"].dim() != 2 or out["weight"].shape[0] != m or out["weight"].shape[1] < 1:
+        raise ValueError("njf_hip: field_voxels needs weight [M, capacity] with capacity >= 1")
+    capacity = int(out["weight"].shape[1])
+    for name, size in dict(points=3 * m * capacity, weight=m * capacity, cell=m * capacity, sums=3 * m * capacity, count=m,
+                           outside=m).items():
+        if out[name].numel() != size:
+            raise ValueError(f"njf_hip: field_voxels output {name} must hold {size} elements (got {out[name].numel()})")
+    cells = int(grid.dims[0]) * int(grid.dims[1]) * int(grid.dims[2])
+    if workspace is None:
+        workspace = torch.empty(field_voxels_workspace(m, cells, t), dtype=torch.int32, device=out["weight"].device)
+    _launch("njf_field_voxels", load_library().njf_field_voxels, _ptr(points, "points") if build else None,
+            _int32_ptr(points_count, "points_count"), m, t, C.byref(grid), int(min_points), capacity, _ptr(out["points"], "points"),
+            _int32_ptr(out["weight"], "weight"), _int32_ptr(out["cell"], "cell"), _ptr(out["sums"], "sums", torch.int64),
+            _int32_ptr(out["count"], "count"), _int32_ptr(out["outside"], "outside"), _int32_ptr(workspace, "workspace"),
+            int(workspace.numel()), int(phase))
 
 
 def solve_action(mean_position, jacobian, projection, target_flow, visible_mask, init_action, iterations: int,
