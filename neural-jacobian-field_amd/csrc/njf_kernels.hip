@@ -4835,23 +4835,28 @@ __global__ void __launch_bounds__(NJF_IK_THREADS) ik_solve_kernel(IkArgs a) {
 #define NJF_NN_THREADS 256
 #define NJF_NN_SCAN_BLOCK 1024
 #define NJF_NN_SCAN_ITEMS (NJF_NN_SCAN_BLOCK / NJF_NN_THREADS)
-struct NnArgs {
-  const float* observed;      // [Mo,T,3]
-  const int* observed_count;  // [Mo] or null
-  const float* queries;       // [Mq,n,3]
-  const int* count;           // [1] or null
-  const int* labels;          // [n] or null
-  int Mo, Mq, M, T, n;
+// The list itself (DESIGN.md section 23 holds its invariants): made by cell_list_make, written by cell_list_build, read by
+// the query, the moments and the voxel kernels through cell_records and cell_ring.
+struct CellList {
   float origin[3];
   float cell, inv_cell;
   int dims[3];
-  int C;                      // cells per problem
-  long long L;                // Mo * C < 2^31
-  long long slots;            // Mo * T < 2^31
+  int C;            // cells per problem
+  int Mo, T;        // clouds (1: one list for every problem), slots per cloud
+  long long L;      // Mo * C < 2^31
+  long long slots;  // Mo * T < 2^31
+  int* start;       // [L + 1]: the first record of every (cloud, cell), the total at the end
+  int* cursor;      // [L]: counts, then (zero after the scan) the fill's slot counters; free for a consumer after the build
+  int4* records;    // [slots]: (x, y, z as their bits, j)
+};
+
+struct NnArgs {
+  CellList list;
+  const float* queries;       // [Mq,n,3]
+  const int* count;           // [1] or null
+  const int* labels;          // [n] or null
+  int Mq, M, n;
   float max_distance, max_d2;
-  int* start;                 // [L + 1]: the first record of every (problem, cell), the total at the end
-  int* cursor;                // [L]: counts, then (after the scan) the fill's slot counters
-  int4* records;              // [slots]: (x, y, z as their bits, j)
   int* index;                 // [M,n]
   float* distance2;           // [M,n]
   int* matched;               // [M,n,3] (the bits of the floats)
@@ -4867,55 +4872,62 @@ __device__ __forceinline__ int nn_cell_axis(float p, float origin, float inv_cel
   return (int)fminf(fmaxf(f, 0.0f), (float)(dim - 1));  // dim <= 1024: exact
 }
 
+// the cell of a point: every axis clamped into the lattice
+__device__ __forceinline__ void nn_cell(const CellList& l, float x, float y, float z, int& cx, int& cy, int& cz) {
+  cx = nn_cell_axis(x, l.origin[0], l.inv_cell, l.dims[0]);
+  cy = nn_cell_axis(y, l.origin[1], l.inv_cell, l.dims[1]);
+  cz = nn_cell_axis(z, l.origin[2], l.inv_cell, l.dims[2]);
+}
+
 // FILL false: count the valid points per (problem, cell); true: write their records
 template <bool FILL>
-__global__ void __launch_bounds__(NJF_NN_THREADS) nn_points_kernel(NnArgs a) {
+__global__ void __launch_bounds__(NJF_NN_THREADS) nn_points_kernel(CellList l, const float* observed, const int* observed_count) {
   const long long e = (long long)blockIdx.x * NJF_NN_THREADS + threadIdx.x;
-  if (e >= a.slots) return;
-  const int mo = (int)(e / a.T), j = (int)(e % a.T);
-  if (j >= counted_length(a.observed_count ? a.observed_count + mo : nullptr, a.T)) return;
-  const float* p = a.observed + e * 3;
+  if (e >= l.slots) return;
+  const int mo = (int)(e / l.T), j = (int)(e % l.T);
+  if (j >= counted_length(observed_count ? observed_count + mo : nullptr, l.T)) return;
+  const float* p = observed + e * 3;
   const float x = p[0], y = p[1], z = p[2];
   if (!nn_finite(x, y, z)) return;
-  const int cx = nn_cell_axis(x, a.origin[0], a.inv_cell, a.dims[0]), cy = nn_cell_axis(y, a.origin[1], a.inv_cell, a.dims[1]),
-            cz = nn_cell_axis(z, a.origin[2], a.inv_cell, a.dims[2]);
-  const long long c = (long long)mo * a.C + ((long long)cx * a.dims[1] + cy) * a.dims[2] + cz;
-  if (c < 0 || c >= a.L) return;
+  int cx, cy, cz;
+  nn_cell(l, x, y, z, cx, cy, cz);
+  const long long c = (long long)mo * l.C + ((long long)cx * l.dims[1] + cy) * l.dims[2] + cz;
+  if (c < 0 || c >= l.L) return;
   if (!FILL) {
-    atomicAdd(&a.cursor[c], 1);
+    atomicAdd(&l.cursor[c], 1);
   } else {
-    const long long s = (long long)a.start[c] + atomicAdd(&a.cursor[c], 1);
-    if (s >= 0 && s < a.slots) a.records[s] = make_int4(__float_as_int(x), __float_as_int(y), __float_as_int(z), j);
+    const long long s = (long long)l.start[c] + atomicAdd(&l.cursor[c], 1);
+    if (s >= 0 && s < l.slots) l.records[s] = make_int4(__float_as_int(x), __float_as_int(y), __float_as_int(z), j);
   }
 }
 
 // workgroup b: the sum of the counts [b * 1024, (b + 1) * 1024) to start[b * 1024]
-__global__ void __launch_bounds__(NJF_NN_THREADS) nn_scan_sums_kernel(NnArgs a) {
+__global__ void __launch_bounds__(NJF_NN_THREADS) nn_scan_sums_kernel(const int* counts, int* start, long long L) {
   __shared__ int wave_sum[NJF_NN_THREADS / 64];
   const long long base = (long long)blockIdx.x * NJF_NN_SCAN_BLOCK + threadIdx.x * NJF_NN_SCAN_ITEMS;
   int v = 0;
 #pragma unroll
   for (int e = 0; e < NJF_NN_SCAN_ITEMS; ++e)
-    if (base + e < a.L) v += a.cursor[base + e];
+    if (base + e < L) v += counts[base + e];
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = v;
   __syncthreads();
   if (threadIdx.x == 0) {
     int s = 0;
     for (int w = 0; w < NJF_NN_THREADS / 64; ++w) s += wave_sum[w];
-    a.start[(long long)blockIdx.x * NJF_NN_SCAN_BLOCK] = s;
+    start[(long long)blockIdx.x * NJF_NN_SCAN_BLOCK] = s;
   }
 }
 
 // one workgroup: the block sums at start[b * 1024] -> their exclusive prefix sums in place, the total to start[L]
 // (select_scan_kernel's scheme on a strided array)
-__global__ void __launch_bounds__(NJF_NN_THREADS) nn_scan_blocks_kernel(NnArgs a, int blocks) {
+__global__ void __launch_bounds__(NJF_NN_THREADS) nn_scan_blocks_kernel(int* start, long long L, int blocks) {
   __shared__ int part[NJF_NN_THREADS];
   const int t = threadIdx.x;
   const int per = (blocks + NJF_NN_THREADS - 1) / NJF_NN_THREADS;  // a contiguous run per thread
   const int lo = min(t * per, blocks), hi = min(lo + per, blocks);
   int s = 0;
-  for (int i = lo; i < hi; ++i) s += a.start[(long long)i * NJF_NN_SCAN_BLOCK];
+  for (int i = lo; i < hi; ++i) s += start[(long long)i * NJF_NN_SCAN_BLOCK];
   part[t] = s;
   __syncthreads();
   if (t == 0) {
@@ -4925,26 +4937,26 @@ __global__ void __launch_bounds__(NJF_NN_THREADS) nn_scan_blocks_kernel(NnArgs a
       part[i] = run;
       run += c;
     }
-    a.start[a.L] = run;
+    start[L] = run;
   }
   __syncthreads();
   int run = part[t];
   for (int i = lo; i < hi; ++i) {
-    const int c = a.start[(long long)i * NJF_NN_SCAN_BLOCK];
-    a.start[(long long)i * NJF_NN_SCAN_BLOCK] = run;
+    const int c = start[(long long)i * NJF_NN_SCAN_BLOCK];
+    start[(long long)i * NJF_NN_SCAN_BLOCK] = run;
     run += c;
   }
 }
 
 // workgroup b: start[c] for its 1024 cells from the block's offset and the counts, which are cleared for the fill
-__global__ void __launch_bounds__(NJF_NN_THREADS) nn_scan_cells_kernel(NnArgs a) {
+__global__ void __launch_bounds__(NJF_NN_THREADS) nn_scan_cells_kernel(int* counts, int* start, long long L) {
   __shared__ int wave_sum[NJF_NN_THREADS / 64];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const long long base = (long long)blockIdx.x * NJF_NN_SCAN_BLOCK + threadIdx.x * NJF_NN_SCAN_ITEMS;
   int c[NJF_NN_SCAN_ITEMS], mine = 0;
 #pragma unroll
   for (int e = 0; e < NJF_NN_SCAN_ITEMS; ++e) {
-    c[e] = base + e < a.L ? a.cursor[base + e] : 0;
+    c[e] = base + e < L ? counts[base + e] : 0;
     mine += c[e];
   }
   int incl = mine;
@@ -4953,17 +4965,78 @@ __global__ void __launch_bounds__(NJF_NN_THREADS) nn_scan_cells_kernel(NnArgs a)
     if (lane >= o) incl += t;
   }
   if (lane == 63) wave_sum[wave] = incl;
-  const int offset = a.start[(long long)blockIdx.x * NJF_NN_SCAN_BLOCK];  // (read by all before thread 0 overwrites it)
+  const int offset = start[(long long)blockIdx.x * NJF_NN_SCAN_BLOCK];  // (read by all before thread 0 overwrites it)
   __syncthreads();
   int run = offset + incl - mine;
   for (int w = 0; w < wave; ++w) run += wave_sum[w];
 #pragma unroll
   for (int e = 0; e < NJF_NN_SCAN_ITEMS; ++e)
-    if (base + e < a.L) {
-      a.start[base + e] = run;
-      a.cursor[base + e] = 0;
+    if (base + e < L) {
+      start[base + e] = run;
+      counts[base + e] = 0;
       run += c[e];
     }
+}
+
+// The readers.  WAVE false: one lane per row (a query, or a cell); true: one wave per row, the lanes share a range's records.
+// f(rec) for the records of the cells c0 .. c1 (one problem, consecutive along z): the one place that reads start and records
+template <bool WAVE, class F>
+__device__ __forceinline__ void cell_records(const CellList& l, long long c0, long long c1, int lane, F&& f) {
+  if (c0 < 0 || c1 >= l.L || c0 > c1) return;
+  long long lo = l.start[c0], hi = l.start[c1 + 1];
+  lo = min(max(lo, 0LL), l.slots);
+  hi = min(min(max(hi, lo), l.slots), lo + l.T);
+  for (long long s = lo + (WAVE ? lane : 0); s < hi; s += WAVE ? 64 : 1) f(l.records[s]);
+}
+
+// f(rec) for the records of the Chebyshev ring r around the cell (cx, cy, cz) of the problem whose cells begin at `cells`;
+// false, and nothing read: no cell at this distance, nor at a larger one
+template <bool WAVE, class F>
+__device__ __forceinline__ bool cell_ring(const CellList& l, long long cells, int cx, int cy, int cz, int r, int lane, F&& f) {
+  const int dx = l.dims[0], dy = l.dims[1], dz = l.dims[2];
+  if (cx - r < 0 && cx + r >= dx && cy - r < 0 && cy + r >= dy && cz - r < 0 && cz + r >= dz) return false;
+  const int x0 = max(cx - r, 0), x1 = min(cx + r, dx - 1), y0 = max(cy - r, 0), y1 = min(cy + r, dy - 1);
+  const int z0 = max(cz - r, 0), z1 = min(cz + r, dz - 1);
+  for (int x = x0; x <= x1; ++x)
+    for (int y = y0; y <= y1; ++y) {
+      const long long column = cells + ((long long)x * dy + y) * dz;
+      if (x == cx - r || x == cx + r || y == cy - r || y == cy + r) {  // a face of the ring: the whole column
+        cell_records<WAVE>(l, column + z0, column + z1, lane, f);
+      } else {  // (r >= 1) inside: the two ends
+        if (cz - r >= 0) cell_records<WAVE>(l, column + cz - r, column + cz - r, lane, f);
+        if (cz + r < dz) cell_records<WAVE>(l, column + cz + r, column + cz + r, lane, f);
+      }
+    }
+  return true;
+}
+
+// the row of a thread (WAVE: of its wave) among the n queries of problem m, and its query
+struct CellQuery {
+  long long i;
+  bool live;      // i < n
+  bool searched;  // below the count and finite (rows from the count on are not read)
+  float x, y, z;
+};
+
+template <bool WAVE>
+__device__ __forceinline__ CellQuery cell_query(const float* queries, const int* count, int Mq, int n, int m) {
+  CellQuery q{WAVE ? (long long)blockIdx.x * (NJF_NN_THREADS / 64) + (threadIdx.x >> 6)
+                   : (long long)blockIdx.x * NJF_NN_THREADS + threadIdx.x,
+              false, false, 0.f, 0.f, 0.f};
+  q.live = q.i < n;
+  q.searched = q.live && q.i < counted_length(count, n);
+  if (q.searched) {
+    const float* p = queries + ((long long)(Mq == 1 ? 0 : m) * n + q.i) * 3;
+    q.x = p[0], q.y = p[1], q.z = p[2];
+    q.searched = nn_finite(q.x, q.y, q.z);
+  }
+  return q;
+}
+
+__device__ __forceinline__ long long shfl_xor_i64(long long v, int o) {  // as a pair of 32-bit halves
+  const unsigned low = (unsigned)__shfl_xor((int)(unsigned)v, o, 64);
+  const int high = __shfl_xor((int)(v >> 32), o, 64);
+  return (long long)(((unsigned long long)(unsigned)high << 32) | low);
 }
 
 struct NnBest {
@@ -4975,65 +5048,31 @@ __device__ __forceinline__ void nn_take(NnBest& b, float d2, int j, int x, int y
   if (d2 < b.d2 || (d2 == b.d2 && j < b.j)) b = NnBest{d2, j, x, y, z};
 }
 
-// the records of the cells c0 .. c1 (one problem, consecutive along z) against the query
-template <bool WAVE>
-__device__ __forceinline__ void nn_visit(const NnArgs& a, long long c0, long long c1, int lane, float qx, float qy, float qz,
-                                         NnBest& b) {
-  if (c0 < 0 || c1 >= a.L || c0 > c1) return;
-  long long lo = a.start[c0], hi = a.start[c1 + 1];
-  lo = min(max(lo, 0LL), a.slots);
-  hi = min(min(max(hi, lo), a.slots), lo + a.T);
-  for (long long s = lo + (WAVE ? lane : 0); s < hi; s += WAVE ? 64 : 1) {
-    const int4 rec = a.records[s];
-    const float dx = qx - __int_as_float(rec.x), dy = qy - __int_as_float(rec.y), dz = qz - __int_as_float(rec.z);
-    nn_take(b, (dx * dx + dy * dy) + dz * dz, rec.w, rec.x, rec.y, rec.z);
-  }
-}
-
-// WAVE false: one lane per (problem, row); true: one wave per (problem, row), the lanes share a range's records and agree on
-// the best after every ring
+// the lanes of the wave form agree on the best after every ring
 template <bool WAVE>
 __global__ void __launch_bounds__(NJF_NN_THREADS) nn_query_kernel(NnArgs a) {
   const int lane = threadIdx.x & 63;
   const int m = blockIdx.y;
-  const long long i = WAVE ? (long long)blockIdx.x * (NJF_NN_THREADS / 64) + (threadIdx.x >> 6)
-                           : (long long)blockIdx.x * NJF_NN_THREADS + threadIdx.x;
-  const bool live = i < a.n;
-  bool searched = live && i < counted_length(a.count, a.n);  // (rows from the count on are not read)
-  if (searched && a.labels) searched = a.labels[i] >= 0;
-  float qx = 0.f, qy = 0.f, qz = 0.f;
-  if (searched) {
-    const float* q = a.queries + ((long long)(a.Mq == 1 ? 0 : m) * a.n + i) * 3;
-    qx = q[0], qy = q[1], qz = q[2];
-    searched = nn_finite(qx, qy, qz);
-  }
+  CellQuery q = cell_query<WAVE>(a.queries, a.count, a.Mq, a.n, m);
+  if (q.searched && a.labels) q.searched = a.labels[q.i] >= 0;
+  const long long i = q.i;
+  const bool live = q.live, searched = q.searched;
   NnBest b{INFINITY, 0x7fffffff, 0, 0, 0};
   if (searched) {
-    const long long cells = (long long)(a.Mo == 1 ? 0 : m) * a.C;
-    const int dx = a.dims[0], dy = a.dims[1], dz = a.dims[2];
-    const int cx = nn_cell_axis(qx, a.origin[0], a.inv_cell, dx), cy = nn_cell_axis(qy, a.origin[1], a.inv_cell, dy),
-              cz = nn_cell_axis(qz, a.origin[2], a.inv_cell, dz);
+    int cx, cy, cz;
+    nn_cell(a.list, q.x, q.y, q.z, cx, cy, cz);
+    const auto visit = [&](const int4 rec) {
+      const float dx = q.x - __int_as_float(rec.x), dy = q.y - __int_as_float(rec.y), dz = q.z - __int_as_float(rec.z);
+      nn_take(b, (dx * dx + dy * dy) + dz * dz, rec.w, rec.x, rec.y, rec.z);
+    };
     // the centre cell and at most NJF_FIELD_NEAREST_MAX_RINGS rings: with ceil(max_distance / cell) + 1 <= MAX_RINGS the
     // second test below ends the search by itself, after ring MAX_RINGS at the latest
     for (int r = 0; r <= NJF_FIELD_NEAREST_MAX_RINGS; ++r) {
       if (r >= 2) {  // rings 0 .. r - 1 are done: what is left is (r - 1) cells away or more, up to rounding
-        const float lim = ((float)(r - 1) - 0.0078125f) * a.cell;
+        const float lim = ((float)(r - 1) - 0.0078125f) * a.list.cell;
         if (b.d2 < lim * lim || lim > a.max_distance) break;
       }
-      // no cell at this distance, nor at a larger one
-      if (cx - r < 0 && cx + r >= dx && cy - r < 0 && cy + r >= dy && cz - r < 0 && cz + r >= dz) break;
-      const int x0 = max(cx - r, 0), x1 = min(cx + r, dx - 1), y0 = max(cy - r, 0), y1 = min(cy + r, dy - 1);
-      const int z0 = max(cz - r, 0), z1 = min(cz + r, dz - 1);
-      for (int x = x0; x <= x1; ++x)
-        for (int y = y0; y <= y1; ++y) {
-          const long long column = cells + ((long long)x * dy + y) * dz;
-          if (x == cx - r || x == cx + r || y == cy - r || y == cy + r) {  // a face of the ring: the whole column
-            nn_visit<WAVE>(a, column + z0, column + z1, lane, qx, qy, qz, b);
-          } else {  // (r >= 1) inside: the two ends
-            if (cz - r >= 0) nn_visit<WAVE>(a, column + cz - r, column + cz - r, lane, qx, qy, qz, b);
-            if (cz + r < dz) nn_visit<WAVE>(a, column + cz + r, column + cz + r, lane, qx, qy, qz, b);
-          }
-        }
+      if (!cell_ring<WAVE>(a.list, (long long)(a.list.Mo == 1 ? 0 : m) * a.list.C, cx, cy, cz, r, lane, visit)) break;
       if (WAVE)
         for (int o = 32; o > 0; o >>= 1)
           nn_take(b, __shfl_xor(b.d2, o, 64), __shfl_xor(b.j, o, 64), __shfl_xor(b.x, o, 64), __shfl_xor(b.y, o, 64),
@@ -5056,26 +5095,20 @@ __global__ void __launch_bounds__(NJF_NN_THREADS) nn_query_kernel(NnArgs a) {
 }
 
 // ---- surface normals from integer moments on the cell list (njf_field_normals) -----------------------------
-// Every searched row reads the records of the Chebyshev rings 0 .. R around its cell -- njf_field_nearest's list and its
-// walk, without the best-so-far test -- and adds ten int64 sums over the points within the radius: the count, the offsets
+// Every searched row reads the records of the Chebyshev rings 0 .. R around its cell -- the cell list and cell_ring's walk,
+// without the best-so-far test -- and adds ten int64 sums over the points within the radius: the count, the offsets
 // e = p - q quantised to k = rint(e * 2^18 / radius), and the six products k_a k_b.  The order inside a cell depends on
 // scheduling; integer sums do not.  A second launch turns the sums into a covariance and takes its eigenvectors in double.
 struct NrmArgs {
+  CellList list;           // (the finish reads none of it)
   const float* queries;    // [Mq,n,3]
   const int* count;        // [1] or null
   const float* viewpoint;  // [Mv,3] or null
-  int Mo, Mq, Mv, M, T, n;
-  float origin[3];
-  float cell, inv_cell;
-  int dims[3];
-  int C;
-  long long L, slots;      // Mo * C, Mo * T
+  int Mq, Mv, M, n;
   float r2;                // (float)radius * (float)radius
   int rings;               // R
   double scale;            // 2^18 / (double)(float)radius
   int min_neighbours;
-  const int* start;        // njf_field_nearest's workspace
-  const int4* records;
   long long* moments;      // [M,n,10]
   float* normal;           // [M,n,3]
   int* neighbours;         // [M,n]
@@ -5083,81 +5116,43 @@ struct NrmArgs {
   double* eigenvalues;     // [M,n,3] or null
 };
 
-// the records of the cells c0 .. c1 (one problem, consecutive along z) against the query; |k| <= 2^18 + 1, so k is an int and
-// every product one 32 x 32 -> 64-bit multiply-add
+// the lanes of the wave form add their sums at the end.  At most 7 waves per SIMD: the lane form fits 8 (64 VGPRs) and is then
+// 4 to 8 % SLOWER from M = 16 on (section 23's measurement) -- more waves miss more often in the scattered 16-byte record loads
 template <bool WAVE>
-__device__ __forceinline__ void nrm_visit(const NrmArgs& a, long long c0, long long c1, int lane, float qx, float qy, float qz,
-                                          long long (&sum)[10]) {
-  if (c0 < 0 || c1 >= a.L || c0 > c1) return;
-  long long lo = a.start[c0], hi = a.start[c1 + 1];
-  lo = min(max(lo, 0LL), a.slots);
-  hi = min(min(max(hi, lo), a.slots), lo + a.T);
-  for (long long s = lo + (WAVE ? lane : 0); s < hi; s += WAVE ? 64 : 1) {
-    const int4 rec = a.records[s];
-    const float ex = __int_as_float(rec.x) - qx, ey = __int_as_float(rec.y) - qy, ez = __int_as_float(rec.z) - qz;
-    if ((ex * ex + ey * ey) + ez * ez <= a.r2) {
-      const int kx = (int)rint((double)ex * a.scale), ky = (int)rint((double)ey * a.scale), kz = (int)rint((double)ez * a.scale);
-      sum[0] += 1;
-      sum[1] += kx;
-      sum[2] += ky;
-      sum[3] += kz;
-      sum[4] += (long long)kx * kx;
-      sum[5] += (long long)kx * ky;
-      sum[6] += (long long)kx * kz;
-      sum[7] += (long long)ky * ky;
-      sum[8] += (long long)ky * kz;
-      sum[9] += (long long)kz * kz;
-    }
-  }
-}
-
-// WAVE false: one lane per (problem, row); true: one wave per (problem, row), the lanes share a range's records and add their
-// sums at the end, as pairs of 32-bit halves
-template <bool WAVE>
-__global__ void __launch_bounds__(NJF_NN_THREADS) nrm_moments_kernel(NrmArgs a) {
+__global__ void __launch_bounds__(NJF_NN_THREADS) __attribute__((amdgpu_waves_per_eu(1, 7))) nrm_moments_kernel(NrmArgs a) {
   const int lane = threadIdx.x & 63;
   const int m = blockIdx.y;
-  const long long i = WAVE ? (long long)blockIdx.x * (NJF_NN_THREADS / 64) + (threadIdx.x >> 6)
-                           : (long long)blockIdx.x * NJF_NN_THREADS + threadIdx.x;
-  const bool live = i < a.n;
-  bool searched = live && i < counted_length(a.count, a.n);  // (rows from the count on are not read)
-  float qx = 0.f, qy = 0.f, qz = 0.f;
-  if (searched) {
-    const float* q = a.queries + ((long long)(a.Mq == 1 ? 0 : m) * a.n + i) * 3;
-    qx = q[0], qy = q[1], qz = q[2];
-    searched = nn_finite(qx, qy, qz);
-  }
+  const CellQuery q = cell_query<WAVE>(a.queries, a.count, a.Mq, a.n, m);
+  const long long i = q.i;
+  const bool live = q.live;
   long long sum[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  if (searched) {
-    const long long cells = (long long)(a.Mo == 1 ? 0 : m) * a.C;
-    const int dx = a.dims[0], dy = a.dims[1], dz = a.dims[2];
-    const int cx = nn_cell_axis(qx, a.origin[0], a.inv_cell, dx), cy = nn_cell_axis(qy, a.origin[1], a.inv_cell, dy),
-              cz = nn_cell_axis(qz, a.origin[2], a.inv_cell, dz);
-    for (int r = 0; r <= a.rings; ++r) {
-      // no cell at this distance, nor at a larger one
-      if (cx - r < 0 && cx + r >= dx && cy - r < 0 && cy + r >= dy && cz - r < 0 && cz + r >= dz) break;
-      const int x0 = max(cx - r, 0), x1 = min(cx + r, dx - 1), y0 = max(cy - r, 0), y1 = min(cy + r, dy - 1);
-      const int z0 = max(cz - r, 0), z1 = min(cz + r, dz - 1);
-      for (int x = x0; x <= x1; ++x)
-        for (int y = y0; y <= y1; ++y) {
-          const long long column = cells + ((long long)x * dy + y) * dz;
-          if (x == cx - r || x == cx + r || y == cy - r || y == cy + r) {  // a face of the ring: the whole column
-            nrm_visit<WAVE>(a, column + z0, column + z1, lane, qx, qy, qz, sum);
-          } else {  // (r >= 1) inside: the two ends
-            if (cz - r >= 0) nrm_visit<WAVE>(a, column + cz - r, column + cz - r, lane, qx, qy, qz, sum);
-            if (cz + r < dz) nrm_visit<WAVE>(a, column + cz + r, column + cz + r, lane, qx, qy, qz, sum);
-          }
-        }
-    }
+  if (q.searched) {
+    int cx, cy, cz;
+    nn_cell(a.list, q.x, q.y, q.z, cx, cy, cz);
+    // |k| <= 2^18 + 1, so k is an int and every product one 32 x 32 -> 64-bit multiply-add
+    const auto visit = [&](const int4 rec) {
+      const float ex = __int_as_float(rec.x) - q.x, ey = __int_as_float(rec.y) - q.y, ez = __int_as_float(rec.z) - q.z;
+      if ((ex * ex + ey * ey) + ez * ez <= a.r2) {
+        const int kx = (int)rint((double)ex * a.scale), ky = (int)rint((double)ey * a.scale), kz = (int)rint((double)ez * a.scale);
+        sum[0] += 1;
+        sum[1] += kx;
+        sum[2] += ky;
+        sum[3] += kz;
+        sum[4] += (long long)kx * kx;
+        sum[5] += (long long)kx * ky;
+        sum[6] += (long long)kx * kz;
+        sum[7] += (long long)ky * ky;
+        sum[8] += (long long)ky * kz;
+        sum[9] += (long long)kz * kz;
+      }
+    };
+    for (int r = 0; r <= a.rings; ++r)
+      if (!cell_ring<WAVE>(a.list, (long long)(a.list.Mo == 1 ? 0 : m) * a.list.C, cx, cy, cz, r, lane, visit)) break;
   }
   if (WAVE)
     for (int o = 32; o > 0; o >>= 1)
 #pragma unroll
-      for (int e = 0; e < 10; ++e) {
-        const unsigned low = (unsigned)__shfl_xor((int)(unsigned)sum[e], o, 64);
-        const int high = __shfl_xor((int)(sum[e] >> 32), o, 64);
-        sum[e] += (long long)(((unsigned long long)(unsigned)high << 32) | low);
-      }
+      for (int e = 0; e < 10; ++e) sum[e] += shfl_xor_i64(sum[e], o);
   if (live && (!WAVE || lane == 0)) {
     long long* out = a.moments + ((long long)m * a.n + i) * 10;
 #pragma unroll
@@ -5277,20 +5272,13 @@ __global__ void __launch_bounds__(NJF_NN_THREADS) nrm_finish_kernel(NrmArgs a) {
 }
 
 // ---- one centroid per occupied cell (njf_field_voxels) ---------------------------------------------------------
-// REDUCE reads the records of every cell of njf_field_nearest's list and adds, over the points whose unclamped cell is this
+// REDUCE reads the records of every cell of the cell list and adds, over the points whose unclamped cell is this
 // cell, the fractional cell coordinates quantised to 2^-20 cells: three int64 sums and a count per cell.  The order inside a
-// cell depends on scheduling; integer sums do not.  COMPACT scans the kept flags with the nn_scan_* kernels, pointed at a
-// second starts array, and scatters the kept cells in ascending cell index.
+// cell depends on scheduling; integer sums do not.  COMPACT scans the kept flags (exclusive_scan_1024) into a second starts
+// array and scatters the kept cells in ascending cell index.
 struct VoxArgs {
-  int M, T, C;
-  float origin[3];
-  float cell, inv_cell;
-  int dims[3];
-  long long L, slots;      // M * C, M * T
+  CellList list;           // one cloud per problem; REDUCE parks the kept flags in its cursors, COMPACT's scan clears them again
   int min_points, capacity;
-  const int* start;        // njf_field_nearest's workspace
-  const int4* records;
-  int* flag;               // [L]: njf_field_nearest's cursors, free after its build; the scan clears them again
   long long* cell_sums;    // [L,3]
   int* cell_k;             // [L]
   const int* kept_start;   // [L + 1]: the exclusive scan of the flags
@@ -5302,43 +5290,34 @@ struct VoxArgs {
   int* outside;            // [M]
 };
 
-__device__ __forceinline__ long long vox_shfl_xor(long long v, int o) {
-  const unsigned low = (unsigned)__shfl_xor((int)(unsigned)v, o, 64);
-  const int high = __shfl_xor((int)(v >> 32), o, 64);
-  return (long long)(((unsigned long long)(unsigned)high << 32) | low);
-}
-
-// WAVE false: one lane per (problem, cell); true: one wave per (problem, cell), the lanes share the cell's records
+// one lane, or one wave, per (problem, cell)
 template <bool WAVE>
 __global__ void __launch_bounds__(NJF_NN_THREADS) vox_reduce_kernel(VoxArgs a) {
+  const CellList& l = a.list;
   const int lane = threadIdx.x & 63;
   const long long c = WAVE ? (long long)blockIdx.x * (NJF_NN_THREADS / 64) + (threadIdx.x >> 6)
                            : (long long)blockIdx.x * NJF_NN_THREADS + threadIdx.x;
-  if (c >= a.L) return;  // (a whole wave in the wave form)
-  long long lo = a.start[c], hi = a.start[c + 1];
-  lo = min(max(lo, 0LL), a.slots);
-  hi = min(min(max(hi, lo), a.slots), lo + a.T);
+  if (c >= l.L) return;  // (a whole wave in the wave form)
   long long sx = 0, sy = 0, sz = 0;
   int k = 0, out = 0;
-  for (long long s = lo + (WAVE ? lane : 0); s < hi; s += WAVE ? 64 : 1) {
-    const int4 rec = a.records[s];
-    const float tx = (__int_as_float(rec.x) - a.origin[0]) * a.inv_cell, ty = (__int_as_float(rec.y) - a.origin[1]) * a.inv_cell,
-                tz = (__int_as_float(rec.z) - a.origin[2]) * a.inv_cell;
+  cell_records<WAVE>(l, c, c, lane, [&](const int4 rec) {
+    const float tx = (__int_as_float(rec.x) - l.origin[0]) * l.inv_cell, ty = (__int_as_float(rec.y) - l.origin[1]) * l.inv_cell,
+                tz = (__int_as_float(rec.z) - l.origin[2]) * l.inv_cell;
     const float fx = floorf(tx), fy = floorf(ty), fz = floorf(tz);
-    if (fx >= 0.0f && fx < (float)a.dims[0] && fy >= 0.0f && fy < (float)a.dims[1] && fz >= 0.0f && fz < (float)a.dims[2]) {
+    const bool inside =
+        fx >= 0.0f && fx < (float)l.dims[0] && fy >= 0.0f && fy < (float)l.dims[1] && fz >= 0.0f && fz < (float)l.dims[2];
+    if (inside) {
       sx += (long long)rintf((tx - fx) * 1048576.0f);
       sy += (long long)rintf((ty - fy) * 1048576.0f);
       sz += (long long)rintf((tz - fz) * 1048576.0f);
-      ++k;
-    } else {
-      ++out;
     }
-  }
+    k += inside, out += !inside;  // (not ++ in the two branches: through the captures that becomes a store to a selected address)
+  });
   if (WAVE)
     for (int o = 32; o > 0; o >>= 1) {
-      sx += vox_shfl_xor(sx, o);
-      sy += vox_shfl_xor(sy, o);
-      sz += vox_shfl_xor(sz, o);
+      sx += shfl_xor_i64(sx, o);
+      sy += shfl_xor_i64(sy, o);
+      sz += shfl_xor_i64(sz, o);
       k += __shfl_xor(k, o, 64);
       out += __shfl_xor(out, o, 64);
     }
@@ -5347,39 +5326,40 @@ __global__ void __launch_bounds__(NJF_NN_THREADS) vox_reduce_kernel(VoxArgs a) {
     a.cell_sums[c * 3 + 1] = sy;
     a.cell_sums[c * 3 + 2] = sz;
     a.cell_k[c] = k;
-    a.flag[c] = k >= a.min_points ? 1 : 0;
-    if (out) atomicAdd(&a.outside[(int)(c / a.C)], out);
+    l.cursor[c] = k >= a.min_points ? 1 : 0;
+    if (out) atomicAdd(&a.outside[(int)(c / l.C)], out);
   }
 }
 
 // thread e < L: the kept cell e to its row; thread e < M * capacity: the fill of a row from the count on
 __global__ void __launch_bounds__(NJF_NN_THREADS) vox_scatter_kernel(VoxArgs a) {
+  const CellList& l = a.list;
   const long long e = (long long)blockIdx.x * NJF_NN_THREADS + threadIdx.x;
-  if (e < a.L) {
-    const int m = (int)(e / a.C), ci = (int)(e - (long long)m * a.C);
-    const long long base = a.kept_start[(long long)m * a.C];
+  if (e < l.L) {
+    const int m = (int)(e / l.C), ci = (int)(e - (long long)m * l.C);
+    const long long base = a.kept_start[(long long)m * l.C];
     const long long row = (long long)a.kept_start[e] - base;
-    if (ci == 0) a.count[m] = (int)((long long)a.kept_start[(long long)(m + 1) * a.C] - base);
+    if (ci == 0) a.count[m] = (int)((long long)a.kept_start[(long long)(m + 1) * l.C] - base);
     if (a.kept_start[e + 1] > a.kept_start[e] && row >= 0 && row < a.capacity) {
       const long long r = (long long)m * a.capacity + row;
       const int k = a.cell_k[e];
-      const int cz = ci % a.dims[2], cy = (ci / a.dims[2]) % a.dims[1], cx = ci / (a.dims[2] * a.dims[1]);
+      const int cz = ci % l.dims[2], cy = (ci / l.dims[2]) % l.dims[1], cx = ci / (l.dims[2] * l.dims[1]);
       const int axis[3] = {cx, cy, cz};
       const double per = (double)k * 1048576.0;
 #pragma unroll
       for (int d = 0; d < 3; ++d) {
         const long long s = a.cell_sums[e * 3 + d];
         a.sums[r * 3 + d] = s;
-        a.points[r * 3 + d] = (float)((double)a.origin[d] + ((double)axis[d] + (double)s / per) * (double)a.cell);
+        a.points[r * 3 + d] = (float)((double)l.origin[d] + ((double)axis[d] + (double)s / per) * (double)l.cell);
       }
       a.weight[r] = k;
       a.cell_index[r] = ci;
     }
   }
-  if (e < (long long)a.M * a.capacity) {
+  if (e < (long long)l.Mo * a.capacity) {
     const int m = (int)(e / a.capacity);
     const long long row = e - (long long)m * a.capacity;
-    const long long kept = (long long)a.kept_start[(long long)(m + 1) * a.C] - a.kept_start[(long long)m * a.C];
+    const long long kept = (long long)a.kept_start[(long long)(m + 1) * l.C] - a.kept_start[(long long)m * l.C];
     if (row >= kept) {
       const float nan = __int_as_float(0x7fc00000);
       a.points[e * 3] = nan, a.points[e * 3 + 1] = nan, a.points[e * 3 + 2] = nan;
@@ -7770,6 +7750,70 @@ extern "C" int njf_field_commands_metric(const int* parts, const int* parts_coun
                   workspace_doubles, phases, stream);
 }
 
+// The cell list of njf_field_nearest, njf_field_normals and njf_field_voxels.  The lattice checks, all
+// NJF_E_VALUE, and the layout of the workspace: Mo (C + 1) words hold the L + 1 starts, L cursors, then the records on the next
+// 16 bytes (the macro's 3 spare words).  The caller checks `points`, the workspace's length and its pointer afterwards, in
+// its own order: until then `slots` may be anything, and a null workspace leaves the three pointers null.
+static int cell_list_make(const NjfFieldGrid* cells, int num_observed, int points, int* workspace, CellList* out) {
+  const float cell = cells->step[0], inv_cell = 1.0f / cell;
+  if (!(cell > 0.0f) || cells->step[1] != cell || cells->step[2] != cell || !(inv_cell > 0.0f) || !(cell < INFINITY) ||
+      !(inv_cell < INFINITY))
+    return NJF_E_VALUE;
+  long long C = 1;
+  for (int c = 0; c < 3; ++c) {
+    if (cells->dims[c] < 1 || cells->dims[c] > NJF_FIELD_NEAREST_MAX_DIM) return NJF_E_VALUE;
+    if (!(fabsf(cells->origin[c]) < INFINITY)) return NJF_E_VALUE;
+    C *= cells->dims[c];
+  }
+  const long long L = (long long)num_observed * C;
+  if (L >= (1LL << 31)) return NJF_E_VALUE;
+  for (int c = 0; c < 3; ++c) out->origin[c] = cells->origin[c], out->dims[c] = cells->dims[c];
+  out->cell = cell;
+  out->inv_cell = inv_cell;
+  out->C = (int)C;
+  out->Mo = num_observed;
+  out->T = points;
+  out->L = L;
+  out->slots = (long long)num_observed * points;
+  out->start = workspace;
+  out->cursor = workspace ? workspace + (long long)num_observed * (C + 1) : nullptr;
+  out->records = workspace ? (int4*)(((uintptr_t)(out->cursor + L) + 15) & ~(uintptr_t)15) : nullptr;
+  return NJF_OK;
+}
+
+// the reach of a walk (max_distance, radius) as a float: positive, finite, within NJF_FIELD_NEAREST_MAX_RINGS rings
+static int cell_list_reach(const CellList& list, double distance, float* reach) {
+  *reach = (float)distance;
+  if (!(distance > 0.0) || !(*reach > 0.0f) || !(*reach < INFINITY)) return NJF_E_VALUE;
+  if (ceil((double)*reach / (double)list.cell) + 1.0 > (double)NJF_FIELD_NEAREST_MAX_RINGS) return NJF_E_VALUE;
+  return NJF_OK;
+}
+
+// start[0 .. L]: the exclusive prefix sums of counts[0 .. L), the total at the end; clears the counts
+static int exclusive_scan_1024(int* counts, int* start, long long L, hipStream_t s) {
+  const int blocks = (int)((L + NJF_NN_SCAN_BLOCK - 1) / NJF_NN_SCAN_BLOCK);  // <= 2^21
+  int rc;
+  nn_scan_sums_kernel<<<blocks, NJF_NN_THREADS, 0, s>>>(counts, start, L);
+  if ((rc = launch_status())) return rc;
+  nn_scan_blocks_kernel<<<1, NJF_NN_THREADS, 0, s>>>(start, L, blocks);
+  if ((rc = launch_status())) return rc;
+  nn_scan_cells_kernel<<<blocks, NJF_NN_THREADS, 0, s>>>(counts, start, L);
+  return launch_status();
+}
+
+// a memset and five launches -- count, the scan, fill: the only writer of start and records, and it clears the cursors first
+static int cell_list_build(const CellList& list, const float* observed, const int* observed_count, hipStream_t s) {
+  const unsigned per_point = (unsigned)((list.slots + NJF_NN_THREADS - 1) / NJF_NN_THREADS);  // < 2^23
+  int rc;
+  hipError_t e = hipMemsetAsync(list.cursor, 0, (size_t)list.L * sizeof(int), s);
+  if (e != hipSuccess) return (int)e;
+  nn_points_kernel<false><<<per_point, NJF_NN_THREADS, 0, s>>>(list, observed, observed_count);
+  if ((rc = launch_status())) return rc;
+  if ((rc = exclusive_scan_1024(list.cursor, list.start, list.L, s))) return rc;
+  nn_points_kernel<true><<<per_point, NJF_NN_THREADS, 0, s>>>(list, observed, observed_count);
+  return launch_status();
+}
+
 extern "C" int njf_field_nearest(const float* observed, const int* observed_count, int num_observed, int points,
                                  const float* queries, const int* count, const int* labels, int num_queries, int n,
                                  int num_problems, const NjfFieldGrid* cells, double max_distance, int* index, float* distance2,
@@ -7781,69 +7825,28 @@ extern "C" int njf_field_nearest(const float* observed, const int* observed_coun
       ((phases & NJF_FIELD_NEAREST_WAVE) && !(phases & NJF_FIELD_NEAREST_QUERY)))
     return NJF_E_VALUE;
   if (!cells) return NJF_E_NULL;
-  const float cell = cells->step[0], inv_cell = 1.0f / cell, reach = (float)max_distance;
-  if (!(cell > 0.0f) || cells->step[1] != cell || cells->step[2] != cell || !(inv_cell > 0.0f) || !(cell < INFINITY) ||
-      !(inv_cell < INFINITY))
-    return NJF_E_VALUE;
-  long long C = 1;
-  for (int c = 0; c < 3; ++c) {
-    if (cells->dims[c] < 1 || cells->dims[c] > NJF_FIELD_NEAREST_MAX_DIM) return NJF_E_VALUE;
-    if (!(fabsf(cells->origin[c]) < INFINITY)) return NJF_E_VALUE;
-    C *= cells->dims[c];
-  }
-  if (!(max_distance > 0.0) || !(reach > 0.0f) || !(reach < INFINITY)) return NJF_E_VALUE;
-  if (ceil((double)reach / (double)cell) + 1.0 > (double)NJF_FIELD_NEAREST_MAX_RINGS) return NJF_E_VALUE;
-  const long long L = (long long)num_observed * C;
-  if (L >= (1LL << 31)) return NJF_E_VALUE;
-  if (n < 0 || points < 1 || (long long)num_observed * points >= (1LL << 31)) return NJF_E_SHAPE;
-  if (workspace_words < NJF_FIELD_NEAREST_WORKSPACE(num_observed, C, points)) return NJF_E_SHAPE;
+  NnArgs a;
+  int rc;
+  if ((rc = cell_list_make(cells, num_observed, points, workspace, &a.list))) return rc;
+  if ((rc = cell_list_reach(a.list, max_distance, &a.max_distance))) return rc;
+  if (n < 0 || points < 1 || a.list.slots >= (1LL << 31)) return NJF_E_SHAPE;
+  if (workspace_words < NJF_FIELD_NEAREST_WORKSPACE(num_observed, a.list.C, points)) return NJF_E_SHAPE;
   const bool build = phases & NJF_FIELD_NEAREST_BUILD, query = phases & NJF_FIELD_NEAREST_QUERY;
   if (!workspace || (build && !observed) || (query && (!found || (n > 0 && (!queries || !index || !distance2 || !matched)))))
     return NJF_E_NULL;
-  NnArgs a;
-  a.observed = observed;
-  a.observed_count = observed_count;
   a.queries = queries;
   a.count = count;
   a.labels = labels;
-  a.Mo = num_observed;
   a.Mq = num_queries;
   a.M = num_problems;
-  a.T = points;
   a.n = n;
-  for (int c = 0; c < 3; ++c) a.origin[c] = cells->origin[c], a.dims[c] = cells->dims[c];
-  a.cell = cell;
-  a.inv_cell = inv_cell;
-  a.C = (int)C;
-  a.L = L;
-  a.slots = (long long)num_observed * points;
-  a.max_distance = reach;
-  a.max_d2 = reach * reach;
-  a.start = workspace;                                   // Mo (C + 1) words hold the L + 1 starts
-  a.cursor = workspace + (long long)num_observed * (C + 1);
-  a.records = (int4*)(((uintptr_t)(a.cursor + L) + 15) & ~(uintptr_t)15);  // (the macro's 3 spare words)
+  a.max_d2 = a.max_distance * a.max_distance;
   a.index = index;
   a.distance2 = distance2;
   a.matched = (int*)matched;
   a.found = found;
   hipStream_t s = (hipStream_t)stream;
-  int rc;
-  if (build) {
-    const unsigned per_point = (unsigned)((a.slots + NJF_NN_THREADS - 1) / NJF_NN_THREADS);  // < 2^23
-    const int blocks = (int)((L + NJF_NN_SCAN_BLOCK - 1) / NJF_NN_SCAN_BLOCK);              // <= 2^21
-    hipError_t e = hipMemsetAsync(a.cursor, 0, (size_t)L * sizeof(int), s);
-    if (e != hipSuccess) return (int)e;
-    nn_points_kernel<false><<<per_point, NJF_NN_THREADS, 0, s>>>(a);
-    if ((rc = launch_status())) return rc;
-    nn_scan_sums_kernel<<<blocks, NJF_NN_THREADS, 0, s>>>(a);
-    if ((rc = launch_status())) return rc;
-    nn_scan_blocks_kernel<<<1, NJF_NN_THREADS, 0, s>>>(a, blocks);
-    if ((rc = launch_status())) return rc;
-    nn_scan_cells_kernel<<<blocks, NJF_NN_THREADS, 0, s>>>(a);
-    if ((rc = launch_status())) return rc;
-    nn_points_kernel<true><<<per_point, NJF_NN_THREADS, 0, s>>>(a);
-    if ((rc = launch_status())) return rc;
-  }
+  if (build && (rc = cell_list_build(a.list, observed, observed_count, s))) return rc;
   if (query) {
     hipError_t e = hipMemsetAsync(found, 0, (size_t)num_problems * sizeof(int), s);
     if (e != hipSuccess) return (int)e;
@@ -7874,66 +7877,38 @@ extern "C" int njf_field_normals(const float* observed, const int* observed_coun
     return NJF_E_VALUE;
   if (min_neighbours < 3) return NJF_E_VALUE;
   if (!cells) return NJF_E_NULL;
-  const float cell = cells->step[0], inv_cell = 1.0f / cell, reach = (float)radius;
-  if (!(cell > 0.0f) || cells->step[1] != cell || cells->step[2] != cell || !(inv_cell > 0.0f) || !(cell < INFINITY) ||
-      !(inv_cell < INFINITY))
-    return NJF_E_VALUE;
-  long long C = 1;
-  for (int c = 0; c < 3; ++c) {
-    if (cells->dims[c] < 1 || cells->dims[c] > NJF_FIELD_NEAREST_MAX_DIM) return NJF_E_VALUE;
-    if (!(fabsf(cells->origin[c]) < INFINITY)) return NJF_E_VALUE;
-    C *= cells->dims[c];
-  }
-  if (!(radius > 0.0) || !(reach > 0.0f) || !(reach < INFINITY)) return NJF_E_VALUE;
-  if (ceil((double)reach / (double)cell) + 1.0 > (double)NJF_FIELD_NEAREST_MAX_RINGS) return NJF_E_VALUE;
-  const long long L = (long long)num_observed * C;
-  if (L >= (1LL << 31)) return NJF_E_VALUE;
-  if (n < 0 || points < 1 || points >= (1 << 26) || (long long)num_observed * points >= (1LL << 31)) return NJF_E_SHAPE;
+  NrmArgs a;
+  float reach;
+  int rc;
+  if ((rc = cell_list_make(cells, num_observed, points, workspace, &a.list))) return rc;
+  if ((rc = cell_list_reach(a.list, radius, &reach))) return rc;
+  if (n < 0 || points < 1 || points >= (1 << 26) || a.list.slots >= (1LL << 31)) return NJF_E_SHAPE;
   const bool build = phases & NJF_FIELD_NORMALS_BUILD, sums = phases & NJF_FIELD_NORMALS_MOMENTS,
              finish = phases & NJF_FIELD_NORMALS_FINISH;
-  if ((build || sums) && workspace_words < NJF_FIELD_NEAREST_WORKSPACE(num_observed, C, points)) return NJF_E_SHAPE;
+  if ((build || sums) && workspace_words < NJF_FIELD_NEAREST_WORKSPACE(num_observed, a.list.C, points)) return NJF_E_SHAPE;
   if (((build || sums) && !workspace) || (build && !observed)) return NJF_E_NULL;
   if (n > 0 && (((sums || finish) && (!queries || !moments)) || (finish && (!normal || !neighbours || !variation))))
     return NJF_E_NULL;
-  int rc;
-  if (build && (rc = njf_field_nearest(observed, observed_count, num_observed, points, nullptr, nullptr, nullptr, num_queries, n,
-                                       num_problems, cells, radius, nullptr, nullptr, nullptr, nullptr, workspace,
-                                       workspace_words, NJF_FIELD_NEAREST_BUILD, stream)))
-    return rc;
+  hipStream_t s = (hipStream_t)stream;
+  if (build && (rc = cell_list_build(a.list, observed, observed_count, s))) return rc;
   if (n == 0 || !(sums || finish)) return NJF_OK;
-  NrmArgs a;
   a.queries = queries;
   a.count = count;
   a.viewpoint = viewpoint;
-  a.Mo = num_observed;
   a.Mq = num_queries;
   a.Mv = num_viewpoints;
   a.M = num_problems;
-  a.T = points;
   a.n = n;
-  for (int c = 0; c < 3; ++c) a.origin[c] = cells->origin[c], a.dims[c] = cells->dims[c];
-  a.cell = cell;
-  a.inv_cell = inv_cell;
-  a.C = (int)C;
-  a.L = L;
-  a.slots = (long long)num_observed * points;
   a.r2 = reach * reach;
-  a.rings = 1;  // the smallest r >= 1 whose rings beyond it hold nothing within the radius: njf_field_nearest's second stop test
-  while (a.rings < NJF_FIELD_NEAREST_MAX_RINGS && !(((float)a.rings - 0.0078125f) * cell > reach)) ++a.rings;
+  a.rings = 1;  // the smallest r >= 1 whose rings beyond it hold nothing within the radius: nn_query_kernel's second stop test
+  while (a.rings < NJF_FIELD_NEAREST_MAX_RINGS && !(((float)a.rings - 0.0078125f) * a.list.cell > reach)) ++a.rings;
   a.scale = 262144.0 / (double)reach;
   a.min_neighbours = min_neighbours;
-  a.start = workspace;                                   // njf_field_nearest's layout
-  a.records = nullptr;
-  if (workspace) {
-    const int* cursor = workspace + (long long)num_observed * (C + 1);
-    a.records = (const int4*)(((uintptr_t)(cursor + L) + 15) & ~(uintptr_t)15);
-  }
   a.moments = moments;
   a.normal = normal;
   a.neighbours = neighbours;
   a.variation = variation;
   a.eigenvalues = eigenvalues;
-  hipStream_t s = (hipStream_t)stream;
   if (sums) {
     if (phases & NJF_FIELD_NORMALS_WAVE) {
       const dim3 grid((unsigned)(((long long)n + NJF_NN_THREADS / 64 - 1) / (NJF_NN_THREADS / 64)), (unsigned)num_problems);
@@ -7962,50 +7937,23 @@ extern "C" int njf_field_voxels(const float* points, const int* points_count, in
     return NJF_E_VALUE;
   if (min_points < 1) return NJF_E_VALUE;
   if (!cells) return NJF_E_NULL;
-  const float cell = cells->step[0], inv_cell = 1.0f / cell;
-  if (!(cell > 0.0f) || cells->step[1] != cell || cells->step[2] != cell || !(inv_cell > 0.0f) || !(cell < INFINITY) ||
-      !(inv_cell < INFINITY))
-    return NJF_E_VALUE;
-  long long C = 1;
-  for (int c = 0; c < 3; ++c) {
-    if (cells->dims[c] < 1 || cells->dims[c] > NJF_FIELD_NEAREST_MAX_DIM) return NJF_E_VALUE;
-    if (!(fabsf(cells->origin[c]) < INFINITY)) return NJF_E_VALUE;
-    C *= cells->dims[c];
-  }
-  const long long L = (long long)num_problems * C;
-  if (L >= (1LL << 31)) return NJF_E_VALUE;
-  if (num_points < 1 || (long long)num_problems * num_points >= (1LL << 31)) return NJF_E_SHAPE;
+  VoxArgs a;
+  int rc;
+  if ((rc = cell_list_make(cells, num_problems, num_points, workspace, &a.list))) return rc;
+  const long long L = a.list.L;
+  if (num_points < 1 || a.list.slots >= (1LL << 31)) return NJF_E_SHAPE;
   if (capacity < 1 || (long long)num_problems * capacity >= (1LL << 31)) return NJF_E_SHAPE;
-  if (workspace_words < NJF_FIELD_VOXELS_WORKSPACE(num_problems, C, num_points)) return NJF_E_SHAPE;
+  if (workspace_words < NJF_FIELD_VOXELS_WORKSPACE(num_problems, a.list.C, num_points)) return NJF_E_SHAPE;
   const bool build = phases & NJF_FIELD_VOXELS_BUILD, reduce = phases & NJF_FIELD_VOXELS_REDUCE,
              compact = phases & NJF_FIELD_VOXELS_COMPACT;
   if (!workspace || (build && !points) || (reduce && !outside) ||
       (compact && (!out_points || !weight || !cell_index || !sums || !count)))
     return NJF_E_NULL;
   hipStream_t s = (hipStream_t)stream;
-  int rc;
-  // one cell is a max_distance that njf_field_nearest admits for every lattice; its build does not read it
-  if (build && (rc = njf_field_nearest(points, points_count, num_problems, num_points, nullptr, nullptr, nullptr, 1, 0, num_problems,
-                                       cells, (double)cell, nullptr, nullptr, nullptr, nullptr, workspace, workspace_words,
-                                       NJF_FIELD_NEAREST_BUILD, stream)))
-    return rc;
-  VoxArgs a;
-  a.M = num_problems;
-  a.T = num_points;
-  a.C = (int)C;
-  for (int c = 0; c < 3; ++c) a.origin[c] = cells->origin[c], a.dims[c] = cells->dims[c];
-  a.cell = cell;
-  a.inv_cell = inv_cell;
-  a.L = L;
-  a.slots = (long long)num_problems * num_points;
+  if (build && (rc = cell_list_build(a.list, points, points_count, s))) return rc;
   a.min_points = min_points;
   a.capacity = capacity;
-  a.start = workspace;                                   // njf_field_nearest's layout ...
-  int* cursor = workspace + (long long)num_problems * (C + 1);
-  int4* records = (int4*)(((uintptr_t)(cursor + L) + 15) & ~(uintptr_t)15);
-  a.records = records;
-  a.flag = cursor;
-  a.cell_sums = (long long*)(records + a.slots);        // ... and behind it 3 L int64 sums, L counts, L + 1 second starts
+  a.cell_sums = (long long*)(a.list.records + a.list.slots);  // behind the list: 3 L int64 sums, L counts, L + 1 second starts
   a.cell_k = (int*)(a.cell_sums + 3 * L);
   int* kept_start = a.cell_k + L;
   a.kept_start = kept_start;
@@ -8025,17 +7973,7 @@ extern "C" int njf_field_voxels(const float* points, const int* points_count, in
     if ((rc = launch_status())) return rc;
   }
   if (compact) {
-    NnArgs scan{};                                       // the three scan launches read cursor, L and write start: nothing else
-    scan.L = L;
-    scan.start = kept_start;
-    scan.cursor = cursor;
-    const int blocks = (int)((L + NJF_NN_SCAN_BLOCK - 1) / NJF_NN_SCAN_BLOCK);
-    nn_scan_sums_kernel<<<blocks, NJF_NN_THREADS, 0, s>>>(scan);
-    if ((rc = launch_status())) return rc;
-    nn_scan_blocks_kernel<<<1, NJF_NN_THREADS, 0, s>>>(scan, blocks);
-    if ((rc = launch_status())) return rc;
-    nn_scan_cells_kernel<<<blocks, NJF_NN_THREADS, 0, s>>>(scan);
-    if ((rc = launch_status())) return rc;
+    if ((rc = exclusive_scan_1024(a.list.cursor, kept_start, L, s))) return rc;
     const long long threads = L > (long long)num_problems * capacity ? L : (long long)num_problems * capacity;
     vox_scatter_kernel<<<(unsigned)((threads + NJF_NN_THREADS - 1) / NJF_NN_THREADS), NJF_NN_THREADS, 0, s>>>(a);
     if ((rc = launch_status())) return rc;

@@ -1097,20 +1097,21 @@ def _check_cloud_count(name: str, what: str, count, mo: int) -> None:
 
 
 def _check_nearest(name: str, observed, cells, max_distance, observed_count, count, labels, n: int, mq: int, like: torch.Tensor,
-                   of: str, m_other: int = 1):
-    """The checks of the observation, the lattice and the search that ``nearest_points`` and the registration share; ``like``
-    (called ``of`` in the messages) rules the device.  ``(observed [Mo, T, 3], M, observed_count, count)``."""
+                   of: str, m_other: int = 1, reach_name: str = "max_distance"):
+    """The checks of the observation, the lattice and the search that ``nearest_points``, ``point_normals`` and the registration
+    share; ``like`` (called ``of`` in the messages) rules the device, ``reach_name`` is what the caller calls ``max_distance``.
+    ``(observed [Mo, T, 3], M, observed_count, count)``."""
     observed, m = _check_cloud_cells(name, observed, cells, mq, m_other)
     mo, cell = observed.shape[0], cells.step[0]
     if isinstance(max_distance, bool) or not isinstance(max_distance, (int, float)) or not max_distance > 0.0 \
             or not math.isfinite(max_distance):
-        raise ValueError(f"{name}: max_distance must be a finite number > 0 (got {max_distance})")
+        raise ValueError(f"{name}: {reach_name} must be a finite number > 0 (got {max_distance})")
     with np.errstate(over="ignore"):
         reach = float(np.float32(max_distance))          # the kernel's float
     if not reach > 0.0:
-        raise ValueError(f"{name}: max_distance must be a finite number > 0 (got {max_distance})")
+        raise ValueError(f"{name}: {reach_name} must be a finite number > 0 (got {max_distance})")
     if not math.isfinite(reach) or not math.isfinite(reach / cell) or math.ceil(reach / cell) + 1 > hip.FIELD_NEAREST_MAX_RINGS:
-        raise ValueError(f"{name}: max_distance may span at most {hip.FIELD_NEAREST_MAX_RINGS - 1} cells (got {max_distance} for cells "
+        raise ValueError(f"{name}: {reach_name} may span at most {hip.FIELD_NEAREST_MAX_RINGS - 1} cells (got {max_distance} for cells "
                          f"of {cell}); take a larger cell")
     _check_cloud_count(name, "observed_count", observed_count, mo)
     count = _one_int32(name, "count", count, like)
@@ -1220,11 +1221,8 @@ def point_normals(queries: Optional[torch.Tensor], observed: torch.Tensor, cells
         queries = queries if queries.dim() == 3 else queries[None]
     like, of = (observed, "observed") if queries is None else (queries, "queries")
     mq, n = (1, 0) if queries is None else queries.shape[:2]
-    try:
-        observed, m, observed_count, count = _check_nearest(name, observed, cells, radius, observed_count, count, None, n, mq, like, of,
-                                                            m_other=mv)
-    except ValueError as err:
-        raise ValueError(str(err).replace("max_distance", "radius")) from None
+    observed, m, observed_count, count = _check_nearest(name, observed, cells, radius, observed_count, count, None, n, mq, like, of,
+                                                        m_other=mv, reach_name="radius")
     if queries is None:
         queries = observed
         mq, n = queries.shape[:2]

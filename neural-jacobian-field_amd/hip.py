@@ -1265,6 +1265,27 @@ def field_nearest_workspace(observed: int, cells: int, points: int) -> int:
     return observed * (2 * cells + 1 + 4 * points) + 3
 
 
+def _cloud_shape(op: str, name: str, layout: str, cloud) -> tuple:
+    """(M, T) of ``cloud``: a tensor [M, T, 3], or the shape tuple that stands for it in a phase that does not read it."""
+    if not torch.is_tensor(cloud):
+        return tuple(int(v) for v in cloud)
+    if cloud.dim() != 3 or cloud.shape[2] != 3:
+        raise ValueError(f"njf_hip: {op} needs {name} [{layout}, 3]")
+    return int(cloud.shape[0]), int(cloud.shape[1])
+
+
+def _check_output_sizes(op: str, out: dict, sizes: dict) -> None:
+    for name, size in sizes.items():
+        if out[name].numel() != size:
+            raise ValueError(f"njf_hip: {op} output {name} must hold {size} elements (got {out[name].numel()})")
+
+
+def _cell_list_workspace(words, grid: FieldGrid, clouds: int, points: int, device) -> torch.Tensor:
+    """A fresh workspace of ``words(clouds, cells of the grid, points)`` int32 elements."""
+    cells = int(grid.dims[0]) * int(grid.dims[1]) * int(grid.dims[2])
+    return torch.empty(words(clouds, cells, points), dtype=torch.int32, device=device)
+
+
 def field_nearest(observed: Optional[torch.Tensor], queries: Optional[torch.Tensor], grid: FieldGrid, max_distance: float, out: dict,
                   problems: int, observed_count=None, count=None, labels=None, phase: int = FIELD_NEAREST_ALL,
                   workspace: Optional[torch.Tensor] = None) -> None:
@@ -1274,12 +1295,8 @@ def field_nearest(observed: Optional[torch.Tensor], queries: Optional[torch.Tens
     shapes.  ``phase``: FIELD_NEAREST_BUILD reads ``observed`` and writes the workspace, FIELD_NEAREST_QUERY reads the workspace
     and writes ``out``; a phase without the build takes the SHAPE ``(Mo, T)`` for ``observed``, one without the query the shape
     ``(Mq, n)`` for ``queries`` and None for ``out``.  ``workspace``: int32, ``field_nearest_workspace`` elements."""
-    shape = lambda t: tuple(t.shape[:2]) if torch.is_tensor(t) else tuple(t)   # noqa: E731
-    if torch.is_tensor(observed) and (observed.dim() != 3 or observed.shape[2] != 3):
-        raise ValueError("njf_hip: field_nearest needs observed [Mo, T, 3]")
-    if torch.is_tensor(queries) and (queries.dim() != 3 or queries.shape[2] != 3):
-        raise ValueError("njf_hip: field_nearest needs queries [Mq, n, 3]")
-    (mo, t), (mq, n), m = shape(observed), shape(queries), int(problems)
+    mo, t = _cloud_shape("field_nearest", "observed", "Mo, T", observed)
+    (mq, n), m = _cloud_shape("field_nearest", "queries", "Mq, n", queries), int(problems)
     build, query = bool(phase & FIELD_NEAREST_BUILD), bool(phase & FIELD_NEAREST_QUERY)
     if (build and not torch.is_tensor(observed)) or (query and not torch.is_tensor(queries)):
         raise ValueError("njf_hip: field_nearest needs the observed points to build and the queries to query")
@@ -1290,17 +1307,13 @@ def field_nearest(observed: Optional[torch.Tensor], queries: Optional[torch.Tens
     if labels is not None and labels.numel() != n:
         raise ValueError("njf_hip: field_nearest needs labels [n]")
     if query:
-        for name, size in dict(index=m * n, distance2=m * n, matched=3 * m * n, found=m).items():
-            if out[name].numel() != size:
-                raise ValueError(f"njf_hip: field_nearest output {name} must hold {size} elements (got {out[name].numel()})")
-    cells = int(grid.dims[0]) * int(grid.dims[1]) * int(grid.dims[2])
+        _check_output_sizes("field_nearest", out, dict(index=m * n, distance2=m * n, matched=3 * m * n, found=m))
     if workspace is None:
-        like = observed if build else queries
-        workspace = torch.empty(field_nearest_workspace(mo, cells, t), dtype=torch.int32, device=like.device)
+        workspace = _cell_list_workspace(field_nearest_workspace, grid, mo, t, (observed if build else queries).device)
     o = (lambda key, ptr: ptr(out[key], key) if query else None)   # noqa: E731
     _launch("njf_field_nearest", load_library().njf_field_nearest, _ptr(observed, "observed") if build else None,
-            _int32_ptr(observed_count, "observed_count"), int(mo), int(t), _ptr(queries, "queries") if query else None,
-            _int32_ptr(count, "count"), _int32_ptr(labels, "labels"), int(mq), int(n), m, C.byref(grid), float(max_distance),
+            _int32_ptr(observed_count, "observed_count"), mo, t, _ptr(queries, "queries") if query else None,
+            _int32_ptr(count, "count"), _int32_ptr(labels, "labels"), mq, n, m, C.byref(grid), float(max_distance),
             o("index", _int32_ptr), o("distance2", _ptr), o("matched", _ptr), o("found", _int32_ptr),
             _int32_ptr(workspace, "workspace"), int(workspace.numel()), int(phase))
 
@@ -1328,12 +1341,8 @@ def field_normals(observed: Optional[torch.Tensor], queries: Optional[torch.Tens
     workspace and the queries and writes ``out["moments"]`` [+ FIELD_NORMALS_WAVE], FIELD_NORMALS_FINISH reads the moments and
     writes the other outputs; a phase without the build takes the SHAPE ``(Mo, T)`` for ``observed``.  ``workspace``: int32,
     ``field_normals_workspace`` elements, not needed by the finish alone."""
-    shape = lambda t: tuple(t.shape[:2]) if torch.is_tensor(t) else tuple(t)   # noqa: E731
-    if torch.is_tensor(observed) and (observed.dim() != 3 or observed.shape[2] != 3):
-        raise ValueError("njf_hip: field_normals needs observed [Mo, T, 3]")
-    if torch.is_tensor(queries) and (queries.dim() != 3 or queries.shape[2] != 3):
-        raise ValueError("njf_hip: field_normals needs queries [Mq, n, 3]")
-    (mo, t), (mq, n), m = shape(observed), shape(queries), int(problems)
+    mo, t = _cloud_shape("field_normals", "observed", "Mo, T", observed)
+    (mq, n), m = _cloud_shape("field_normals", "queries", "Mq, n", queries), int(problems)
     build, sums, finish = (bool(phase & p) for p in FIELD_NORMALS_PHASES)
     if (build and not torch.is_tensor(observed)) or ((sums or finish) and not torch.is_tensor(queries)):
         raise ValueError("njf_hip: field_normals needs the observed points to build and the queries for the moments and the finish")
@@ -1348,17 +1357,13 @@ def field_normals(observed: Optional[torch.Tensor], queries: Optional[torch.Tens
         sizes.update(normal=3 * m * n, neighbours=m * n, variation=m * n)
         if out.get("eigenvalues") is not None:
             sizes.update(eigenvalues=3 * m * n)
-    for name, size in sizes.items():
-        if out[name].numel() != size:
-            raise ValueError(f"njf_hip: field_normals output {name} must hold {size} elements (got {out[name].numel()})")
-    cells = int(grid.dims[0]) * int(grid.dims[1]) * int(grid.dims[2])
+    _check_output_sizes("field_normals", out, sizes)
     if workspace is None and (build or sums):
-        like = observed if build else queries
-        workspace = torch.empty(field_normals_workspace(mo, cells, t), dtype=torch.int32, device=like.device)
+        workspace = _cell_list_workspace(field_normals_workspace, grid, mo, t, (observed if build else queries).device)
     o = (lambda key, ptr, *dtype: ptr(out[key], key, *dtype) if key in sizes else None)   # noqa: E731
     _launch("njf_field_normals", load_library().njf_field_normals, _ptr(observed, "observed") if build else None,
-            _int32_ptr(observed_count, "observed_count"), int(mo), int(t), _ptr(queries, "queries") if sums or finish else None,
-            _int32_ptr(count, "count"), int(mq), int(n), m, C.byref(grid), float(radius), int(min_neighbours),
+            _int32_ptr(observed_count, "observed_count"), mo, t, _ptr(queries, "queries") if sums or finish else None,
+            _int32_ptr(count, "count"), mq, n, m, C.byref(grid), float(radius), int(min_neighbours),
             _ptr(viewpoint, "viewpoint"), 0 if viewpoint is None else int(viewpoint.shape[0]), o("moments", _ptr, torch.int64),
             o("normal", _ptr), o("neighbours", _int32_ptr), o("variation", _ptr), o("eigenvalues", _double_ptr),
             _int32_ptr(workspace, "workspace"), 0 if workspace is None else int(workspace.numel()), int(phase))
@@ -1410,9 +1415,7 @@ def field_voxels(points, grid: FieldGrid, out: dict, points_count=None, min_poin
     reads ``points`` and writes the workspace (njf_field_nearest's build), FIELD_VOXELS_REDUCE [+ FIELD_VOXELS_WAVE] reads the
     cell list and writes the per-cell sums and ``out["outside"]``, FIELD_VOXELS_COMPACT writes the other outputs; a phase
     without the build takes the SHAPE ``(M, T)`` for ``points``.  ``workspace``: int32, ``field_voxels_workspace`` elements."""
-    if torch.is_tensor(points) and (points.dim() != 3 or points.shape[2] != 3):
-        raise ValueError("njf_hip: field_voxels needs points [M, T, 3]")
-    m, t = (int(v) for v in (points.shape[:2] if torch.is_tensor(points) else points))
+    m, t = _cloud_shape("field_voxels", "points", "M, T", points)
     build = bool(phase & FIELD_VOXELS_BUILD)
     if build and not torch.is_tensor(points):
         raise ValueError("njf_hip: field_voxels needs the points to build")
@@ -1421,13 +1424,10 @@ def field_voxels(points, grid: FieldGrid, out: dict, points_count=None, min_poin
     if out["weight"].dim() != 2 or out["weight"].shape[0] != m or out["weight"].shape[1] < 1:
         raise ValueError("njf_hip: field_voxels needs weight [M, capacity] with capacity >= 1")
     capacity = int(out["weight"].shape[1])
-    for name, size in dict(points=3 * m * capacity, weight=m * capacity, cell=m * capacity, sums=3 * m * capacity, count=m,
-                           outside=m).items():
-        if out[name].numel() != size:
-            raise ValueError(f"njf_hip: field_voxels output {name} must hold {size} elements (got {out[name].numel()})")
-    cells = int(grid.dims[0]) * int(grid.dims[1]) * int(grid.dims[2])
+    _check_output_sizes("field_voxels", out, dict(points=3 * m * capacity, weight=m * capacity, cell=m * capacity,
+                                                  sums=3 * m * capacity, count=m, outside=m))
     if workspace is None:
-        workspace = torch.empty(field_voxels_workspace(m, cells, t), dtype=torch.int32, device=out["weight"].device)
+        workspace = _cell_list_workspace(field_voxels_workspace, grid, m, t, out["weight"].device)
     _launch("njf_field_voxels", load_library().njf_field_voxels, _ptr(points, "points") if build else None,
             _int32_ptr(points_count, "points_count"), m, t, C.byref(grid), int(min_points), capacity, _ptr(out["points"], "points"),
             _int32_ptr(out["weight"], "weight"), _int32_ptr(out["cell"], "cell"), _ptr(out["sums"], "sums", torch.int64),

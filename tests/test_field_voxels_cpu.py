@@ -300,6 +300,39 @@ def test_the_shared_checks_still_speak_for_their_callers():
         nearest_points(q, torch.zeros(5, 3), cells, 0.1, observed_count=torch.ones(2, dtype=torch.int32))
 
 
+def test_the_three_entries_refuse_the_same_lattices(lib):
+    """One cell list stands behind njf_field_nearest, njf_field_normals and njf_field_voxels: a lattice
+    that one of them refuses, all three refuse, with NJF_E_VALUE, whatever else the call holds."""
+    from neural_jacobian_field_amd import hip
+    P = 0x1000                                   # never dereferenced: every call below fails its checks
+    entries = (
+        (lib.njf_field_nearest,
+         ("observed", "observed_count", "clouds", "points", "queries", "count", "labels", "clouds", "n", "clouds", "cells", 0.5, "index",
+          "distance2", "matched", "found", "workspace", "words", 3)),
+        (lib.njf_field_normals,
+         ("observed", "observed_count", "clouds", "points", "queries", "count", "clouds", "n", "clouds", "cells", 0.5, 3, "viewpoint",
+          "clouds", "moments", "normal", "neighbours", "variation", "eigenvalues", "workspace", "words", 7)),
+        (lib.njf_field_voxels,
+         ("observed", "observed_count", "clouds", "points", "cells", 1, 720, "out_points", "weight", "cell_index", "sums", "count",
+          "outside", "workspace", "words", 7)))
+
+    def codes(origin=(0.0, 0.0, 0.0), step=(0.25, 0.25, 0.25), dims=(8, 9, 10), clouds=5, **kw):
+        values = dict(clouds=clouds, points=5000, n=300, words=2 ** 62, cells=hip.make_field_grid(origin, step, dims))
+        values.update(kw)
+        return [entry(*[values.get(a, P) if isinstance(a, str) else a for a in args], None) for entry, args in entries]
+
+    assert codes(workspace=None) == [E_NULL] * 3                 # the lattice of the table is good: only the workspace is missing
+    nan, inf = float("nan"), float("inf")
+    bad = [dict(step=s) for s in ((0.25, 0.25, 0.5), (0.25, 0.5, 0.25), (0.0,) * 3, (-0.25,) * 3, (nan,) * 3, (inf,) * 3, (1e-45,) * 3)]
+    bad += [dict(dims=d) for d in ((0, 9, 10), (8, -1, 10), (8, 9, 1025), (1025, 9, 10))]
+    bad += [dict(origin=o) for o in ((nan, 0.0, 0.0), (0.0, nan, 0.0), (0.0, 0.0, inf))]
+    bad += [dict(dims=(1024, 1024, 1024), clouds=2)]             # Mo * C = 2^31
+    for lattice in bad:
+        assert codes(**lattice) == [E_VALUE] * 3, lattice
+        assert codes(**lattice, workspace=None, points=0) == [E_VALUE] * 3, lattice   # (judged before the shapes and the pointers)
+    assert codes(dims=(1024, 1024, 1023), clouds=2, workspace=None) == [E_NULL] * 3   # the largest list: 2^31 - 2^21 cells
+
+
 # ---- (vi) the C ABI ----------------------------------------------------------------------------------------------------------------------
 def test_the_symbols_are_declared_exported_and_bound(lib):
     from neural_jacobian_field_amd import hip

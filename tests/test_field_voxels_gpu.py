@@ -202,6 +202,81 @@ def test_the_phases_one_by_one_and_on_a_workspace_that_nearest_points_built(dev)
         assert int(near.found.sum()) > 100
 
 
+def _one_list_case():
+    """The smallest case that crosses every edge the three readers share: C = 1,287 cells and L = 2,574 --
+    three scan blocks, the last one partial, the boundary between the problems inside the second --, counts (1500, 777), 100
+    points of problem 0 in one cell (the wave form strides it twice), NaN rows, points beyond every face; 193 queries (no
+    multiple of 64) with the eight corners of the box, rows far outside it and a NaN row; a reach of 2.3 cells (three rings,
+    clipped at the faces)."""
+    rng = np.random.default_rng(23)
+    cells = _cells((0.2, -0.4, 1.0), 0.07, (9, 11, 13))
+    origin, cell, dims = np.float32(cells.origin), np.float32(cells.step[0]), np.asarray(cells.dims)
+    pts = _cloud(rng, 2, 1500, cells, outside=0.1)
+    pts[0, 100:200] = origin + (np.float32([4, 5, 6]) + rng.uniform(0, 1, (100, 3)).astype(np.float32) * np.float32(0.999)) * cell
+    pts[1, 40:44, 2], pts[0, 900] = np.nan, np.inf
+    queries = _cloud(rng, 2, 193, cells, outside=0.05, dirty=False)
+    corners = np.float32([[x, y, z] for x in (0, dims[0]) for y in (0, dims[1]) for z in (0, dims[2])])
+    queries[:, :8] = origin + corners * cell
+    queries[:, 8:12] = origin + np.float32([[-5, 3, 3], [4, 17, 6], [4, 5, -6], [15, 17, 19]]) * cell      # beyond the reach of the box
+    queries[:, 12, 1] = np.nan
+    queries[1, 13:] += np.float32(0.01)
+    return cells, pts, np.int32([1500, 777]), queries, float(np.float32(2.3) * cell), 6
+
+
+def test_one_list_feeds_the_three_readers(dev):
+    """One build, then njf_field_nearest's query, njf_field_normals' moments and finish and njf_field_voxels' reduce and compact
+    on that workspace, each in the lane and in the wave form: every output equals its restatement byte for byte, and the two
+    forms equal each other in every byte.  One output cannot: the float64 eigenvalues are a Jacobi iteration's and the
+    restatement's are ``eigh``'s, 1e-15 of the largest apart (752 of the 1,125 differ in a last bit); they are held to
+    test_field_normals_gpu's bound on the rows with a normal and to the bytes (NaN) on the others.  The fp32 normals and
+    variations round both to the same floats here.  The voxels run last: their reduce parks its flags in the cursors, and
+    their scan clears them."""
+    import field_nearest_restatement as NN
+    import test_field_normals_gpu as TN
+    from neural_jacobian_field_amd import hip
+    cells, pts, count, queries, reach, min_neighbours = _one_list_case()
+    origin, cell, dims = cells.origin, cells.step[0], cells.dims
+    NN.check_lattice(origin, cell, dims, reach)
+    near = NN.rings(pts, queries, origin, cell, dims, reach, observed_count=count)
+    moments, _ = NS.ring_moments(pts, queries, origin, cell, dims, reach, observed_count=count)
+    normals = NS.finish(moments, queries, reach, min_neighbours)
+    vox = S.voxels(pts, origin, cell, dims, count, 2, cells.num_nodes)
+    planted = (4 * dims[1] + 5) * dims[2] + 6
+    assert vox["weight"][0][vox["cell"][0] == planted].tolist()[0] > 64 and NS.ring_count(cell, reach) == 3
+    assert near["rings"].max() >= 3 and ((near["index"] < 0) & (near["rings"] >= 0)).any()          # a searched row without a match
+    assert (normals["neighbours"] < min_neighbours).any() and normals["has"].sum() > 300 and vox["outside"].min() > 50
+    m, t, n = 2, pts.shape[1], queries.shape[1]
+    p, c, q, grid = _t(dev, pts), _t(dev, count), _t(dev, queries), cells.c_grid()
+    workspace = torch.full((hip.field_voxels_workspace(m, cells.num_nodes, t),), 0x5a5a5a5a, dtype=torch.int32, device=dev)
+    hip.field_nearest(p, (m, n), grid, reach, None, m, observed_count=c, phase=hip.FIELD_NEAREST_BUILD, workspace=workspace)
+    got = []
+    for wave in (False, True):
+        out = dict(index=torch.empty(m, n, dtype=torch.int32, device=dev), distance2=torch.empty(m, n, device=dev),
+                   matched=torch.empty(m, n, 3, device=dev), found=torch.empty(m, dtype=torch.int32, device=dev))
+        hip.field_nearest((m, t), q, grid, reach, out, m, observed_count=c, workspace=workspace,
+                          phase=hip.FIELD_NEAREST_QUERY | (hip.FIELD_NEAREST_WAVE if wave else 0))
+        for f in out:
+            assert _np(out[f]).tobytes() == near[f].tobytes(), ("nearest", f, wave)
+        nrm = TN._raw(dev, (m, t), q, cells, reach, hip.FIELD_NORMALS_MOMENTS | hip.FIELD_NORMALS_FINISH |
+                      (hip.FIELD_NORMALS_WAVE if wave else 0), m, fill=0x5a, workspace=workspace, observed_count=c,
+                      min_neighbours=min_neighbours)
+        assert _np(nrm["moments"]).tobytes() == moments.tobytes() and _np(nrm["neighbours"]).tobytes() == normals["neighbours"].tobytes()
+        for f in ("normal", "variation", "eigenvalues"):
+            g, w = _np(nrm[f]), normals[f]
+            rows = ~normals["has"] if f == "eigenvalues" else np.ones_like(normals["has"])
+            print(f"normals {f}, wave {wave}: {int((g != w)[normals['has']].sum())} of {w[normals['has']].size} values differ from eigh's")
+            assert g.dtype == w.dtype and g[rows].tobytes() == w[rows].tobytes(), ("normals", f, wave)
+        TN._against_eigh(nrm, normals, reach, f"one list, wave {wave}")
+        out.update({"normals " + f: v for f, v in nrm.items()})
+        red = _raw(dev, (m, t), cells, hip.FIELD_VOXELS_REDUCE | hip.FIELD_VOXELS_COMPACT | (hip.FIELD_VOXELS_WAVE if wave else 0),
+                   cells.num_nodes, fill=0xa5, workspace=workspace, points_count=c, min_points=2)
+        _same(red, vox, f"one list, wave {wave}")
+        out.update({"voxels " + f: v for f, v in red.items()})
+        got.append(out)
+    for f in got[0]:
+        assert torch.equal(_bytes(got[0][f]), _bytes(got[1][f])), (f, "the two forms differ")
+
+
 # ---- 4. determinism -----------------------------------------------------------------------------------------------------------------------------
 def test_calls_and_a_captured_replay_give_equal_bytes(dev):
     from neural_jacobian_field_amd.field_volume import voxel_reduce
