@@ -1012,6 +1012,60 @@ int njf_field_voxels(const float* points, const int* points_count, int num_probl
                      int min_points, int capacity, float* out_points, int* weight, int* cell_index, long long* sums, int* count,
                      int* outside, int* workspace, long long workspace_words, int phases, void* stream);
 
+/* ---- which posed rows a depth camera sees: a z-buffer of points (ABI v20, additive) -----------------------------
+ * For each of M problems and V cameras: the rows of a point set splatted into a depth image -- the inverse of
+ * njf_field_depth_points with NJF_FIELD_DEPTH_Z --, and per row whether it is the nearest thing in its own pixel.  `culled` goes into
+ * njf_field_nearest's QUERY phase as its queries: a hidden row is a row that is not searched.
+ * Inputs, all on the device: points [Mq,n,3] float, Mq = 1 or M; count int32 [1] or NULL (= n); labels int32 [n] or NULL; k [V,3,3]
+ * float, the normalised intrinsics (NOT their inverse; the third row is not read and taken as 0 0 1); w2c [V,4,4] float, world to
+ * camera (its fourth row is not read).  The cameras are shared by the M problems.
+ * READ ROW i: i < min(*count, n), three finite coordinates, and labels[i] >= 0 when labels are given (njf_field_nearest's SEARCHED
+ *        ROW).  A row that is not read is not splatted, not visible, and gets the fill values below.
+ * PROJECTION of a read row p in view v, in float, nothing contracted beyond the fmaf written here:
+ *        xc = fmaf(w[2], p.z, fmaf(w[1], p.y, fmaf(w[0], p.x, w[3]))), yc and zc likewise from w[4..7] and w[8..11], w = w2c[v]
+ *        row-major; PROJECTABLE when zc is finite and zc > near.  s = xc / zc, t = yc / zc (IEEE divisions);
+ *        pu = fmaf(k[1], t, fmaf(k[0], s, k[2])), pv = fmaf(k[4], t, fmaf(k[3], s, k[5])); col = floorf(pu * (float)W), row =
+ *        floorf(pv * (float)H) (get_pixel_coordinates' grid: pixel (row, col) covers [col, col + 1) / W x [row, row + 1) / H).
+ *        INSIDE when projectable and 0 <= col < W and 0 <= row < H, compared as floats before any conversion to int.
+ * SPLAT  a projectable row writes the key (bits(zc) << 32) | i, a 64-bit unsigned minimum, into the pixels (row + dr, col + dc),
+ *        |dr|, |dc| <= footprint, that lie in the image -- also where its own pixel does not.  The key image starts as all ones.
+ *        zc > 0 is finite, so its bits order as the float does: a pixel's winner is the smallest zc, ties to the LOWEST row i, in
+ *        any order of the atomics.  By default a plain load of the key precedes the atomic, which is skipped where the pixel
+ *        already holds a key that is not larger; the minimum is monotone, so this cannot change a byte.
+ *        NJF_FIELD_VISIBLE_DIRECT: every atomic is issued.
+ * RESOLVE a workgroup per 2,048 pixels of one image, eight per lane, and one count atomic per workgroup: depth [M,V,H,W] float =
+ *        the winner's zc, 0 for an empty pixel (njf_field_depth_points drops it with near = 0); index [M,V,H,W] int32 = the
+ *        winner's row, -1 for an empty pixel; covered [M,V] int32 = the pixels with a winner.
+ * TEST   one lane per (m, i), one count atomic per workgroup.  A lane projects again (the same expressions: the same bits) and
+ *        reads `depth`: row i is VISIBLE in view v iff it is inside and zc - zmin <= tolerance * zmin, zmin = depth at its own
+ *        pixel: a float subtraction, a float product and a comparison, no contraction.  seen [M,n] int32: bit v set iff visible
+ *        in view v; culled [M,n,3] float: the point itself, bit for bit, if seen != 0, else three NaNs; visible [M] int32: the
+ *        rows with seen != 0; pixel [M,V,n] int32: row * W + col of the row's own pixel, -1 when not inside (or not read); z
+ *        [M,V,n] float: zc, NaN when the row is not read.
+ * Every element of every output of a phase is written by it.  Integer atomics only (the minimum and the three counts).
+ * workspace: NJF_FIELD_VISIBLE_WORKSPACE(M, V, H, W) 32-bit words of the caller's: the M V H W keys of 8 bytes and one word that brings
+ * them to an 8-byte boundary.
+ * `phases`: NJF_FIELD_VISIBLE_SPLAT (a memset and one launch: reads points, writes the workspace) [| NJF_FIELD_VISIBLE_DIRECT] |
+ * NJF_FIELD_VISIBLE_RESOLVE (a memset and one launch: reads the workspace, writes depth, index, covered) | NJF_FIELD_VISIBLE_TEST (a
+ * memset and one launch: reads points and depth, writes the other five outputs).  One stream, no host read (capture-safe).
+ * Returns, before the first launch: NJF_E_NULL for a missing pointer a requested phase needs (k and w2c: always); NJF_E_VALUE for
+ * unknown phases (the modifier without the splat included), M outside [1, NJF_FIELD_POSE_MAX_COMMANDS], Mq not 1 or M, V outside
+ * [1, NJF_FIELD_VISIBLE_MAX_VIEWS], a footprint outside [0, NJF_FIELD_VISIBLE_MAX_FOOTPRINT], near or tolerance negative or not
+ * finite; NJF_E_SHAPE for n < 0, H or W < 1, M * V * H * W >= 2^31, M * V * n >= 2^31 or, with the splat or the resolve, a workspace
+ * that is too small. */
+#define NJF_FIELD_VISIBLE_MAX_VIEWS 32
+#define NJF_FIELD_VISIBLE_MAX_FOOTPRINT 4
+#define NJF_FIELD_VISIBLE_WORKSPACE(M, V, H, W) (2LL * (M) * (V) * (H) * (W) + 1LL)
+#define NJF_FIELD_VISIBLE_SPLAT 1    /* phases */
+#define NJF_FIELD_VISIBLE_RESOLVE 2
+#define NJF_FIELD_VISIBLE_TEST 4
+#define NJF_FIELD_VISIBLE_ALL 7
+#define NJF_FIELD_VISIBLE_DIRECT 8   /* with SPLAT: no load before the atomic */
+int njf_field_visible(const float* points, const int* count, const int* labels, int num_queries, int n, int num_problems,
+                      const float* k, const float* w2c, int views, int height, int width, int footprint, float near,
+                      float tolerance, float* depth, int* index, int* covered, int* seen, float* culled, int* visible, int* pixel,
+                      float* z, int* workspace, long long workspace_words, int phases, void* stream);
+
 /* ---- stand-alone sampler / compositing ops (API parity with the un-fused reference calls) -- */
 /* RaySamples.get_weights (ray_samplers.py:77-101): deltas, densities [N,S] -> weights [N,S]. */
 int njf_alpha_weights(const float* deltas, const float* densities, int rays, int samples, float* weights, void* stream);

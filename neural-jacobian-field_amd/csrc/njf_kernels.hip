@@ -7981,6 +7981,240 @@ extern "C" int njf_field_voxels(const float* points, const int* points_count, in
   return NJF_OK;
 }
 
+// ---- which rows a depth camera sees: a z-buffer of points (njf_field_visible) ---------------------------------
+// The key image holds (bits(z) << 32) | row per pixel, cleared to all ones; z > near >= 0 is finite, so the bits order as the
+// floats do and a 64-bit unsigned minimum picks the smallest z, ties to the lowest row, in any order of arrival.  The splat and the
+// test project through the one function below, so a row's own pixel is the same in both.
+struct VisArgs {
+  const float* points;  // [Mq,n,3]
+  const int* count;     // [1] or NULL
+  const int* labels;    // [n] or NULL
+  const float* k;       // [V,3,3]
+  const float* w2c;     // [V,4,4]
+  int Mq, M, V, n, H, W, f;
+  long long pixels;     // H * W
+  long long total;      // M * V * H * W < 2^31
+  unsigned chunks;      // workgroups of the resolve per image
+  float near, tolerance;
+  unsigned long long* keys;  // [M,V,H,W]
+  float* depth;         // [M,V,H,W]
+  int* index;           // [M,V,H,W]
+  int* covered;         // [M,V]
+  int* seen;            // [M,n]
+  float* culled;        // [M,n,3]
+  int* visible;         // [M]
+  int* pixel;           // [M,V,n]
+  float* z;             // [M,V,n]
+};
+
+struct VisPixel {
+  float z, col, row;  // the camera-space z and floor(u W), floor(v H), still floats
+  bool projectable;   // z finite and > near
+  bool inside;        // projectable and 0 <= col < W, 0 <= row < H
+};
+
+// the READ ROW of njf_field_nearest: below the count, finite, and of a label >= 0
+__device__ __forceinline__ bool vis_read(const VisArgs& a, int m, long long i, float& x, float& y, float& z) {
+  if (i >= counted_length(a.count, a.n)) return false;
+  const float* p = a.points + ((long long)(a.Mq == 1 ? 0 : m) * a.n + i) * 3;
+  x = p[0], y = p[1], z = p[2];
+  if (!nn_finite(x, y, z)) return false;
+  return !a.labels || a.labels[i] >= 0;
+}
+
+__device__ __forceinline__ VisPixel vis_project(const VisArgs& a, int v, float x, float y, float z) {
+  const float* w = a.w2c + v * 16;
+  const float* k = a.k + v * 9;
+  const float xc = fmaf(w[2], z, fmaf(w[1], y, fmaf(w[0], x, w[3])));
+  const float yc = fmaf(w[6], z, fmaf(w[5], y, fmaf(w[4], x, w[7])));
+  const float zc = fmaf(w[10], z, fmaf(w[9], y, fmaf(w[8], x, w[11])));
+  VisPixel p;
+  p.z = zc;
+  p.projectable = fabsf(zc) < INFINITY && zc > a.near;
+  const float s = xc / zc, t = yc / zc;
+  const float pu = fmaf(k[1], t, fmaf(k[0], s, k[2]));
+  const float pv = fmaf(k[4], t, fmaf(k[3], s, k[5]));
+  p.col = floorf(pu * (float)a.W);
+  p.row = floorf(pv * (float)a.H);
+  p.inside = p.projectable && p.col >= 0.0f && p.col < (float)a.W && p.row >= 0.0f && p.row < (float)a.H;  // (NaN: false)
+  return p;
+}
+
+// one lane per (m, v, i).  PRE: a plain load of the key first, the atomic only where the key could still fall -- the minimum is
+// monotone, so a stale load can only ask for an atomic that changes nothing.
+template <bool PRE>
+__global__ void __launch_bounds__(256) vis_splat_kernel(VisArgs a) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  const int v = blockIdx.y, m = blockIdx.z;
+  if (i >= a.n) return;
+  float x, y, z;
+  if (!vis_read(a, m, i, x, y, z)) return;
+  const VisPixel p = vis_project(a, v, x, y, z);
+  const float f = (float)a.f;
+  // a footprint pixel inside the image: judged in float, before any conversion (NaN and infinities compare false)
+  if (!p.projectable || !(p.col >= -f && p.col < (float)a.W + f && p.row >= -f && p.row < (float)a.H + f)) return;
+  const int col = (int)p.col, row = (int)p.row;  // |col| <= W + 4, |row| <= H + 4: exact
+  const unsigned long long key = ((unsigned long long)__float_as_uint(p.z) << 32) | (unsigned)i;
+  unsigned long long* image = a.keys + ((long long)m * a.V + v) * a.pixels;
+  const int r0 = max(row - a.f, 0), r1 = min(row + a.f, a.H - 1), c0 = max(col - a.f, 0), c1 = min(col + a.f, a.W - 1);
+  for (int r = r0; r <= r1; ++r)
+    for (int c = c0; c <= c1; ++c) {
+      unsigned long long* slot = image + (long long)r * a.W + c;
+      if (PRE && *slot <= key) continue;
+      atomicMin(slot, key);
+    }
+}
+
+// A workgroup covers NJF_VIS_RESOLVE_PIXELS consecutive pixels of ONE image, eight per lane, and adds its winners to the image's
+// count with one atomic: the counts of all images lie in one or two cache lines, where the atomics of a wave per 64 pixels
+// queued behind each other.
+#define NJF_VIS_RESOLVE_PIXELS 2048
+__global__ void __launch_bounds__(256) vis_resolve_kernel(VisArgs a) {
+  __shared__ int block_won;
+  const unsigned image = blockIdx.x / a.chunks;  // < M * V
+  const long long first = (long long)(blockIdx.x - image * a.chunks) * NJF_VIS_RESOLVE_PIXELS;
+  if (threadIdx.x == 0) block_won = 0;
+  __syncthreads();
+  int n = 0;
+  for (int j = 0; j < NJF_VIS_RESOLVE_PIXELS / 256; ++j) {
+    const long long r = first + j * 256 + threadIdx.x;
+    bool won = false;
+    if (r < a.pixels) {
+      const long long p = (long long)image * a.pixels + r;  // < M * V * H * W
+      const unsigned long long key = a.keys[p];
+      won = key != ~0ull;
+      a.depth[p] = won ? __uint_as_float((unsigned)(key >> 32)) : 0.0f;
+      a.index[p] = won ? (int)(unsigned)key : -1;
+    }
+    n += __popcll(__ballot(won));
+  }
+  if ((threadIdx.x & 63) == 0 && n) atomicAdd(&block_won, n);
+  __syncthreads();
+  if (threadIdx.x == 0 && block_won) atomicAdd(&a.covered[image], block_won);
+}
+
+// one lane per (m, i)
+__global__ void __launch_bounds__(256) vis_test_kernel(VisArgs a) {
+  __shared__ int block_seen;
+  if (threadIdx.x == 0) block_seen = 0;
+  __syncthreads();
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  const int m = blockIdx.y;
+  const bool live = i < a.n;
+  unsigned seen = 0;
+  if (live) {
+    float x = 0.f, y = 0.f, z = 0.f;
+    const bool read = vis_read(a, m, i, x, y, z);
+    for (int v = 0; v < a.V; ++v) {
+      int own = -1;
+      float zc = __int_as_float(0x7fc00000);
+      if (read) {
+        const VisPixel p = vis_project(a, v, x, y, z);
+        zc = p.z;
+        if (p.inside) {
+          own = (int)p.row * a.W + (int)p.col;
+          const float zmin = a.depth[((long long)m * a.V + v) * a.pixels + own];
+          if (__fsub_rn(p.z, zmin) <= __fmul_rn(a.tolerance, zmin)) seen |= 1u << v;
+        }
+      }
+      const long long o = ((long long)m * a.V + v) * a.n + i;
+      a.pixel[o] = own;
+      a.z[o] = zc;
+    }
+    const float nan = __int_as_float(0x7fc00000);
+    float* c = a.culled + ((long long)m * a.n + i) * 3;
+    c[0] = seen ? x : nan;
+    c[1] = seen ? y : nan;
+    c[2] = seen ? z : nan;
+    a.seen[(long long)m * a.n + i] = (int)seen;
+  }
+  const int n = __popcll(__ballot(seen != 0));  // a workgroup lies in one problem: one atomic for its four waves
+  if ((threadIdx.x & 63) == 0 && n) atomicAdd(&block_seen, n);
+  __syncthreads();
+  if (threadIdx.x == 0 && block_seen) atomicAdd(&a.visible[m], block_seen);
+}
+
+extern "C" int njf_field_visible(const float* points, const int* count, const int* labels, int num_queries, int n,
+                                 int num_problems, const float* k, const float* w2c, int views, int height, int width,
+                                 int footprint, float near, float tolerance, float* depth, int* index, int* covered, int* seen,
+                                 float* culled, int* visible, int* pixel, float* z, int* workspace, long long workspace_words,
+                                 int phases, void* stream) {
+  const bool known = phases >= 1 && phases <= (NJF_FIELD_VISIBLE_ALL | NJF_FIELD_VISIBLE_DIRECT) && (phases & NJF_FIELD_VISIBLE_ALL) &&
+                     (!(phases & NJF_FIELD_VISIBLE_DIRECT) || (phases & NJF_FIELD_VISIBLE_SPLAT));
+  const bool splat = known && (phases & NJF_FIELD_VISIBLE_SPLAT), resolve = known && (phases & NJF_FIELD_VISIBLE_RESOLVE),
+             test = known && (phases & NJF_FIELD_VISIBLE_TEST);
+  if (!k || !w2c || ((splat || test) && !points) || ((splat || resolve) && !workspace) ||
+      ((resolve || test) && !depth) || (resolve && (!index || !covered)) ||
+      (test && (!seen || !culled || !visible || !pixel || !z)))
+    return NJF_E_NULL;
+  if (!known) return NJF_E_VALUE;
+  if (num_problems < 1 || num_problems > NJF_FIELD_POSE_MAX_COMMANDS) return NJF_E_VALUE;
+  if (num_queries != 1 && num_queries != num_problems) return NJF_E_VALUE;
+  if (views < 1 || views > NJF_FIELD_VISIBLE_MAX_VIEWS) return NJF_E_VALUE;
+  if (footprint < 0 || footprint > NJF_FIELD_VISIBLE_MAX_FOOTPRINT) return NJF_E_VALUE;
+  if (!(near >= 0.0f) || !(near < INFINITY) || !(tolerance >= 0.0f) || !(tolerance < INFINITY)) return NJF_E_VALUE;
+  if (n < 0 || height < 1 || width < 1) return NJF_E_SHAPE;
+  const long long images = (long long)num_problems * views;
+  if ((long long)height * width >= (1LL << 31) || images * height * width >= (1LL << 31) || images * n >= (1LL << 31))
+    return NJF_E_SHAPE;
+  if ((splat || resolve) && workspace_words < NJF_FIELD_VISIBLE_WORKSPACE(num_problems, views, height, width)) return NJF_E_SHAPE;
+  VisArgs a;
+  a.points = points;
+  a.count = count;
+  a.labels = labels;
+  a.k = k;
+  a.w2c = w2c;
+  a.Mq = num_queries;
+  a.M = num_problems;
+  a.V = views;
+  a.n = n;
+  a.H = height;
+  a.W = width;
+  a.f = footprint;
+  a.pixels = (long long)height * width;
+  a.total = images * a.pixels;
+  a.chunks = (unsigned)((a.pixels + NJF_VIS_RESOLVE_PIXELS - 1) / NJF_VIS_RESOLVE_PIXELS);
+  a.near = near;
+  a.tolerance = tolerance;
+  a.keys = (unsigned long long*)(((uintptr_t)workspace + 7) & ~(uintptr_t)7);  // the spare word of the workspace pays for this
+  a.depth = depth;
+  a.index = index;
+  a.covered = covered;
+  a.seen = seen;
+  a.culled = culled;
+  a.visible = visible;
+  a.pixel = pixel;
+  a.z = z;
+  hipStream_t s = (hipStream_t)stream;
+  hipError_t e;
+  int rc;
+  const unsigned row_blocks = (unsigned)(((long long)n + 255) / 256);
+  if (splat) {
+    if ((e = hipMemsetAsync(a.keys, 0xff, (size_t)a.total * sizeof(unsigned long long), s)) != hipSuccess) return (int)e;
+    if (n > 0) {
+      const dim3 grid(row_blocks, (unsigned)views, (unsigned)num_problems);
+      if (phases & NJF_FIELD_VISIBLE_DIRECT)
+        vis_splat_kernel<false><<<grid, 256, 0, s>>>(a);
+      else
+        vis_splat_kernel<true><<<grid, 256, 0, s>>>(a);
+      if ((rc = launch_status())) return rc;
+    }
+  }
+  if (resolve) {
+    if ((e = hipMemsetAsync(covered, 0, (size_t)images * sizeof(int), s)) != hipSuccess) return (int)e;
+    vis_resolve_kernel<<<(unsigned)(images * a.chunks), 256, 0, s>>>(a);  // <= total / 2048 + images < 2^31
+    if ((rc = launch_status())) return rc;
+  }
+  if (test) {
+    if ((e = hipMemsetAsync(visible, 0, (size_t)num_problems * sizeof(int), s)) != hipSuccess) return (int)e;
+    if (n > 0) {
+      vis_test_kernel<<<dim3(row_blocks, (unsigned)num_problems), 256, 0, s>>>(a);
+      if ((rc = launch_status())) return rc;
+    }
+  }
+  return NJF_OK;
+}
+
 extern "C" int njf_resnetfc_backward(const float* d_out, int d_out_dim, const float* activations, const float* w_backward,
                                      int points, float* deltas, float* colsum_partial, const unsigned* masks, int precision,
                                      const float* d_out_absmax, void* deltas16, void* stream) {

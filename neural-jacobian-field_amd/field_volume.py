@@ -1371,6 +1371,128 @@ def voxel_reduce(points: torch.Tensor, cells: FieldGrid, *, count: Optional[torc
     return out
 
 
+# ---- which posed rows a depth camera sees: a z-buffer of points -------------------------------------------
+@dataclass
+class FieldView:
+    """The depth cameras that look at a body (``visible_rows``; ``visible_from`` of ``register_commands_visible``): ``intrinsics`` ``[V, 3,
+    3]`` (normalised, as ``depth_points`` takes them) and ``cam2world`` ``[V, 4, 4]`` (fp32), images of ``height`` x ``width``.  A
+    row is splatted over the ``(2 footprint + 1)^2`` pixels around its own (0 to 4); it is visible when its camera-space z lies
+    within ``tolerance * zmin`` of the smallest z in its own pixel and beyond ``near``.  A footprint of 0 lets the far side of a
+    body show through the gaps between rows that lie a pixel or more apart."""
+
+    intrinsics: torch.Tensor
+    cam2world: torch.Tensor
+    height: int
+    width: int
+    footprint: int = 1
+    tolerance: float = 0.01
+    near: float = 0.0
+
+
+@dataclass
+class FieldVisibility:
+    """What the cameras of a ``FieldView`` see of a point set (``visible_rows``; include/njf_hip.h: njf_field_visible), per
+    problem.  ``depth[m]`` ``[V, H, W]`` is the depth image each camera would report and a valid ``depth`` of
+    ``depth_points(kind="z")`` with the same cameras: an empty pixel holds 0, which ``near=0`` drops.  ``culled`` is a valid
+    ``queries`` of ``nearest_points``: a hidden row holds NaN and is not searched."""
+
+    seen: torch.Tensor        # [M, n] int32: bit v set iff the row is visible in view v
+    culled: torch.Tensor      # [M, n, 3] fp32: the point itself where seen != 0, else NaN
+    visible: torch.Tensor     # [M] int32: the rows with seen != 0
+    depth: torch.Tensor       # [M, V, H, W] fp32: the smallest camera-space z splatted into the pixel, 0 = none
+    index: torch.Tensor       # [M, V, H, W] int32: the row that gave it (ties to the lowest), -1 = none
+    covered: torch.Tensor     # [M, V] int32: the pixels with a depth
+    pixel: torch.Tensor       # [M, V, n] int32: row * W + col of the row's own pixel, -1 = outside the image, behind it, or not read
+    z: torch.Tensor           # [M, V, n] fp32: the row's camera-space z, NaN for a row that is not read
+
+
+def _check_view(name: str, view, like: torch.Tensor, of: str, m: int, n: int):
+    """The checks of a ``FieldView`` against ``m`` problems of ``n`` rows on the device of ``like`` (called ``of``);
+    ``(V, near, tolerance)`` with the two numbers as the kernel's floats."""
+    if not isinstance(view, FieldView):
+        raise ValueError(f"{name}: the view must be a FieldView")
+    k, c2w = view.intrinsics, view.cam2world
+    if not torch.is_tensor(k) or k.dtype != torch.float32 or k.dim() != 3 or tuple(k.shape[1:]) != (3, 3) \
+            or not 1 <= k.shape[0] <= hip.FIELD_VISIBLE_MAX_VIEWS:
+        raise ValueError(f"{name}: intrinsics must be fp32 [V, 3, 3] with 1 <= V <= {hip.FIELD_VISIBLE_MAX_VIEWS}")
+    v = k.shape[0]
+    if not torch.is_tensor(c2w) or c2w.dtype != torch.float32 or tuple(c2w.shape) != (v, 4, 4):
+        raise ValueError(f"{name}: cam2world must be fp32 [{v}, 4, 4]")
+    for what, value in (("height", view.height), ("width", view.width)):
+        if isinstance(value, bool) or not isinstance(value, int) or value < 1:
+            raise ValueError(f"{name}: {what} must be an integer >= 1 (got {value})")
+    f = view.footprint
+    if isinstance(f, bool) or not isinstance(f, int) or not 0 <= f <= hip.FIELD_VISIBLE_MAX_FOOTPRINT:
+        raise ValueError(f"{name}: footprint must be an integer in [0, {hip.FIELD_VISIBLE_MAX_FOOTPRINT}] (got {f})")
+    floats = []
+    for what, value in (("near", view.near), ("tolerance", view.tolerance)):
+        if isinstance(value, bool) or not isinstance(value, (int, float)) or math.isnan(value):
+            raise ValueError(f"{name}: {what} must be a finite number >= 0 (got {value})")
+        with np.errstate(over="ignore"):
+            value32 = float(np.float32(value))                  # the kernel's float
+        if not 0.0 <= value32 < math.inf:
+            raise ValueError(f"{name}: {what} must be a finite number >= 0 (got {value})")
+        floats.append(value32)
+    if m * v * view.height * view.width >= 2 ** 31:
+        raise ValueError(f"{name}: M * V * height * width must stay below 2**31")
+    if m * v * n >= 2 ** 31:
+        raise ValueError(f"{name}: M * V * n must stay below 2**31")
+    for what, t in (("intrinsics", k), ("cam2world", c2w)):
+        if t.device != like.device:
+            raise ValueError(f"{name}: {what} must live on the device of {of}")
+    return v, floats[0], floats[1]
+
+
+class _Visibility:
+    """The launches of ``visible_rows`` for ``m`` problems of ``n`` rows: the world-to-camera matrices (``hip.inverse``) and the
+    workspace are made once, ``__call__`` takes the points ``[Mq, n, 3]`` of one round."""
+
+    def __init__(self, view: FieldView, v: int, near: float, tolerance: float, m: int, n: int, dev):
+        self.k, self.w2c = view.intrinsics.contiguous(), hip.inverse(view.cam2world).contiguous()
+        self.shape, self.m, self.n, self.dev = (v, view.height, view.width), m, n, dev
+        self.kw = dict(footprint=view.footprint, near=near, tolerance=tolerance, phase=hip.field_visible_default_phase())
+        self.workspace = torch.empty(hip.field_visible_workspace(m, v, view.height, view.width), dtype=torch.int32, device=dev)
+
+    def __call__(self, points: torch.Tensor, count, labels) -> FieldVisibility:
+        (v, h, w), m, n = self.shape, self.m, self.n
+        i32, f32 = dict(dtype=torch.int32, device=self.dev), dict(dtype=torch.float32, device=self.dev)
+        out = FieldVisibility(seen=torch.empty(m, n, **i32), culled=torch.empty(m, n, 3, **f32), visible=torch.empty(m, **i32),
+                              depth=torch.empty(m, v, h, w, **f32), index=torch.empty(m, v, h, w, **i32),
+                              covered=torch.empty(m, v, **i32), pixel=torch.empty(m, v, n, **i32), z=torch.empty(m, v, n, **f32))
+        hip.field_visible(points, self.k, self.w2c, h, w, {f: getattr(out, f) for f in out.__dataclass_fields__}, m, count=count,
+                          labels=labels, workspace=self.workspace, **self.kw)
+        return out
+
+
+def visible_rows(points: torch.Tensor, view: FieldView, *, labels: Optional[torch.Tensor] = None,
+                 count: Optional[torch.Tensor] = None) -> FieldVisibility:
+    """Which rows of ``points`` ``[n, 3]`` or ``[M, n, 3]`` (fp32) the depth cameras of ``view`` see, and
+    the depth images they would report.  A row is read below ``count`` (one int32 on the device; None = n) with finite
+    coordinates and, with ``labels`` (int32 ``[n]``), a label >= 0 -- ``nearest_points``' searched row.  Every read row in front
+    of a camera (z > ``view.near``) is projected by the pinhole model of ``depth_points`` and written over its footprint into a
+    z-buffer that keeps the smallest z per pixel, ties to the lowest row; a row is visible in a view when it falls into the
+    image and ``z - zmin <= tolerance * zmin`` at its own pixel.  ``FieldVisibility.depth[m]`` is a valid ``depth`` for
+    ``depth_points(kind="z")`` with the same cameras; ``culled`` goes into ``nearest_points`` as its queries.  The z-buffer is a
+    64-bit integer minimum, so the order of the atomics cannot matter: equal bytes from call to call, no host read, capturable."""
+    name = "visible_rows"
+    if not torch.is_tensor(points) or points.dtype != torch.float32 or points.dim() not in (2, 3) or points.shape[-1] != 3:
+        raise ValueError(f"{name}: points must be fp32 [n, 3] or [M, n, 3]")
+    points = points if points.dim() == 3 else points[None]
+    m, n = points.shape[:2]
+    if not 1 <= m <= hip.FIELD_POSE_MAX_COMMANDS:
+        raise ValueError(f"{name}: 1 to {hip.FIELD_POSE_MAX_COMMANDS} problems (got {m})")
+    v, near, tolerance = _check_view(name, view, points, "points", m, n)
+    count = _one_int32(name, "count", count, points)
+    if labels is not None and (not torch.is_tensor(labels) or labels.dtype != torch.int32 or tuple(labels.shape) != (n,)):
+        raise ValueError(f"{name}: labels must be int32 [{n}]")
+    if labels is not None and labels.device != points.device:
+        raise ValueError(f"{name}: labels must live on the device of points")
+    if points.device.type != "cuda":
+        raise ValueError(f"{name}: the tensors must live on the GPU; there is no CPU path")
+    run = _Visibility(view, v, near, tolerance, m, n, points.device)
+    return run(points.contiguous(), count, None if labels is None else labels.contiguous())
+
+
 @dataclass
 class FieldRegistration:
     """The commands that bring the parts onto an unlabelled observation (``register_commands``): ``fit`` is the
@@ -1382,6 +1504,23 @@ class FieldRegistration:
     commands_history: torch.Tensor   # [R, M, A] fp32: the commands after every round
     cost_history: torch.Tensor       # [R, M] float64
     found_history: torch.Tensor      # [R, M] int32
+
+
+@dataclass
+class FieldVisibleRegistration(FieldRegistration):
+    """``FieldRegistration`` of a registration that culls the posed rows by what the cameras see (``register_commands_visible``):
+    ``visible_history`` holds the rows seen in every round; ``found_history`` stays the matched rows."""
+
+    visible_history: torch.Tensor    # [R, M] int32
+
+
+def _registration_outputs(cull, rounds: int, m: int, a_dim: int, dev) -> FieldRegistration:
+    histories = dict(fit=None, matches=None, commands_history=torch.empty(rounds, m, a_dim, dtype=torch.float32, device=dev),
+                     cost_history=torch.empty(rounds, m, dtype=torch.float64, device=dev),
+                     found_history=torch.empty(rounds, m, dtype=torch.int32, device=dev))
+    if cull is None:
+        return FieldRegistration(**histories)
+    return FieldVisibleRegistration(**histories, visible_history=torch.empty(rounds, m, dtype=torch.int32, device=dev))
 
 
 def register_commands(twists: FieldTwists, xyz: torch.Tensor, labels: torch.Tensor, observed: torch.Tensor, cells: FieldGrid,
@@ -1398,7 +1537,14 @@ def register_commands(twists: FieldTwists, xyz: torch.Tensor, labels: torch.Tens
     M = max(Mo, rows of ``init``) problems; one observation with ``init`` ``[M, A]`` is a multi-start registration, of which the
     caller takes ``fit.cost.argmin()``.  Every other argument is ``solve_commands``'.  No host read: capturable after one
     eager call."""
-    name = "register_commands"
+    return _register("register_commands", None, twists, xyz, labels, observed, cells, max_distance, joints, tree, observed_count, count,
+                     weights, init, lower, upper, reg, rounds, iterations, damping)
+
+
+def _register(name: str, visible_from, twists, xyz, labels, observed, cells, max_distance, joints, tree, observed_count, count, weights,
+              init, lower, upper, reg, rounds, iterations, damping):
+    """``register_commands`` under the caller's ``name``; with ``visible_from`` (a ``FieldView``) every round culls the posed rows
+    before the closest-point query and the result is a ``FieldVisibleRegistration``."""
     k, a_dim = _check_twists(name, twists)
     n = _check_points(name, xyz, labels, None, a_dim)
     if isinstance(rounds, bool) or not isinstance(rounds, int) or not 1 <= rounds <= 1000:
@@ -1408,6 +1554,7 @@ def register_commands(twists: FieldTwists, xyz: torch.Tensor, labels: torch.Tens
                                                         "xyz", m_other=max(starts, 1))
     parts_count, links, count, lower_box, upper_box = _check_solver(name, twists, xyz, labels, m, n, k, a_dim, xyz, "xyz", joints, tree,
                                                                     weights, count, init, lower, upper, reg, iterations, damping)
+    cull = None if visible_from is None else _check_view(name, visible_from, xyz, "xyz", m, n)
     if xyz.device.type != "cuda":
         raise ValueError(f"{name}: the tensors must live on the GPU; there is no CPU path")
     dev = xyz.device
@@ -1416,17 +1563,21 @@ def register_commands(twists: FieldTwists, xyz: torch.Tensor, labels: torch.Tens
         u = torch.maximum(u, lower_box)
     if upper_box is not None:
         u = torch.minimum(u, upper_box)
-    out = FieldRegistration(fit=None, matches=None, commands_history=torch.empty(rounds, m, a_dim, dtype=torch.float32, device=dev),
-                            cost_history=torch.empty(rounds, m, dtype=torch.float64, device=dev),
-                            found_history=torch.empty(rounds, m, dtype=torch.int32, device=dev))
+    out = _registration_outputs(cull, rounds, m, a_dim, dev)
     labels_c = labels.contiguous()
     observed_count = None if observed_count is None else observed_count.contiguous()
+    if cull is not None:
+        cull = _Visibility(visible_from, *cull, m, n, dev)
     workspace = torch.empty(hip.field_nearest_workspace(observed.shape[0], cells.num_nodes, observed.shape[1]), dtype=torch.int32,
                             device=dev)
     _nearest_launch(observed.contiguous(), (1, n), cells, max_distance, m, None, observed_count, None, None, hip.FIELD_NEAREST_BUILD,
                     workspace)
     for r in range(rounds):
         _, posed = _pose(name, twists, u, joints, tree, points=(xyz, labels, count, None))
+        if cull is not None:
+            seen = cull(posed, count, labels_c)
+            out.visible_history[r].copy_(seen.visible)
+            posed = seen.culled
         near = _nearest_outputs(m, n, dev)
         _nearest_launch(tuple(observed.shape[:2]), posed, cells, max_distance, m, near, observed_count, count, labels_c,
                         hip.FIELD_NEAREST_QUERY, workspace)
@@ -1605,7 +1756,13 @@ def register_commands_metric(twists: FieldTwists, xyz: torch.Tensor, labels: tor
     observed_information[mo, max(index[m, i], 0)]`` (a torch gather; a row without a match is free through its NaN target), and
     ``solve_commands_metric`` takes the place of ``solve_commands``.  The correspondences stay the Euclidean arg-min.  Returns a
     ``FieldRegistration`` whose ``fit`` is a ``FieldMetricCommands``.  No host read: capturable after one eager call."""
-    name = "register_commands_metric"
+    return _register_metric("register_commands_metric", None, twists, xyz, labels, observed, observed_information, cells, max_distance,
+                            joints, tree, observed_count, count, weights, init, lower, upper, reg, rounds, iterations, damping)
+
+
+def _register_metric(name: str, visible_from, twists, xyz, labels, observed, observed_information, cells, max_distance, joints, tree,
+                     observed_count, count, weights, init, lower, upper, reg, rounds, iterations, damping):
+    """``register_commands_metric`` under the caller's ``name``, with ``_register``'s ``visible_from``."""
     k, a_dim = _check_twists(name, twists)
     n = _check_points(name, xyz, labels, None, a_dim)
     if isinstance(rounds, bool) or not isinstance(rounds, int) or not 1 <= rounds <= 1000:
@@ -1621,6 +1778,7 @@ def register_commands_metric(twists: FieldTwists, xyz: torch.Tensor, labels: tor
         raise ValueError(f"{name}: observed_information must live on the device of xyz")
     parts_count, links, count, lower_box, upper_box = _check_solver(name, twists, xyz, labels, m, n, k, a_dim, xyz, "xyz", joints, tree,
                                                                     weights, count, init, lower, upper, reg, iterations, damping)
+    cull = None if visible_from is None else _check_view(name, visible_from, xyz, "xyz", m, n)
     if xyz.device.type != "cuda":
         raise ValueError(f"{name}: the tensors must live on the GPU; there is no CPU path")
     dev = xyz.device
@@ -1629,17 +1787,21 @@ def register_commands_metric(twists: FieldTwists, xyz: torch.Tensor, labels: tor
         u = torch.maximum(u, lower_box)
     if upper_box is not None:
         u = torch.minimum(u, upper_box)
-    out = FieldRegistration(fit=None, matches=None, commands_history=torch.empty(rounds, m, a_dim, dtype=torch.float32, device=dev),
-                            cost_history=torch.empty(rounds, m, dtype=torch.float64, device=dev),
-                            found_history=torch.empty(rounds, m, dtype=torch.int32, device=dev))
+    out = _registration_outputs(cull, rounds, m, a_dim, dev)
     labels_c = labels.contiguous()
     observed_count = None if observed_count is None else observed_count.contiguous()
+    if cull is not None:
+        cull = _Visibility(visible_from, *cull, m, n, dev)
     source = observed_information.reshape(-1, t, 6).expand(m, t, 6)          # [T, 6] or Mo = 1: one table for every problem
     workspace = torch.empty(hip.field_nearest_workspace(mo, cells.num_nodes, t), dtype=torch.int32, device=dev)
     _nearest_launch(observed.contiguous(), (1, n), cells, max_distance, m, None, observed_count, None, None, hip.FIELD_NEAREST_BUILD,
                     workspace)
     for r in range(rounds):
         _, posed = _pose(name, twists, u, joints, tree, points=(xyz, labels, count, None))
+        if cull is not None:
+            seen = cull(posed, count, labels_c)
+            out.visible_history[r].copy_(seen.visible)
+            posed = seen.culled
         near = _nearest_outputs(m, n, dev)
         _nearest_launch((mo, t), posed, cells, max_distance, m, near, observed_count, count, labels_c, hip.FIELD_NEAREST_QUERY,
                         workspace)
@@ -1672,6 +1834,51 @@ def cloud_registration_metric(cloud: FieldPointCloud, labels: torch.Tensor, twis
                                         damping=damping)
     except ValueError as err:
         raise ValueError(str(err).replace("register_commands_metric:", f"{name}:", 1).replace("cell_grid:", f"{name}:", 1)) from None
+
+
+def register_commands_visible(twists: FieldTwists, xyz: torch.Tensor, labels: torch.Tensor, observed: torch.Tensor, cells: FieldGrid,
+                              max_distance: float, visible_from: FieldView, *, observed_information: Optional[torch.Tensor] = None,
+                              joints: Optional[FieldJoints] = None, tree=None, observed_count: Optional[torch.Tensor] = None,
+                              count: Optional[torch.Tensor] = None, weights: Optional[torch.Tensor] = None,
+                              init: Optional[torch.Tensor] = None, lower=None, upper=None, reg: float = 0.0, rounds: int = 8,
+                              iterations: int = 3, damping: float = 1e-3) -> FieldVisibleRegistration:
+    """``register_commands`` to an observation that depth cameras made: ``visible_from`` is the ``FieldView``
+    of those cameras, and every round goes pose, ``visible_rows`` of the posed rows (with the query's labels and count),
+    ``nearest_points`` on its ``culled`` rows instead of the posed rows, solve -- a row the cameras do not see at ``u_r`` is free
+    in that round, so the WHOLE body can be registered to a depth image, which shows one side of it.  With
+    ``observed_information`` (``register_commands_metric``'s, fp32 ``[T, 6]`` or ``[Mo, T, 6]``) the loop is
+    ``register_commands_metric``'s.  Every other argument is ``register_commands``'; the result adds ``visible_history``, the rows
+    seen in every round.  The workspace of the z-buffer is allocated once; no host read: capturable after one eager call."""
+    name = "register_commands_visible"
+    if not isinstance(visible_from, FieldView):
+        raise ValueError(f"{name}: the view must be a FieldView")
+    if observed_information is None:
+        return _register(name, visible_from, twists, xyz, labels, observed, cells, max_distance, joints, tree, observed_count, count,
+                         weights, init, lower, upper, reg, rounds, iterations, damping)
+    return _register_metric(name, visible_from, twists, xyz, labels, observed, observed_information, cells, max_distance, joints, tree,
+                            observed_count, count, weights, init, lower, upper, reg, rounds, iterations, damping)
+
+
+def cloud_registration_visible(cloud: FieldPointCloud, labels: torch.Tensor, twists: FieldTwists, observed: torch.Tensor,
+                               max_distance: float, visible_from: FieldView, *, observed_information: Optional[torch.Tensor] = None,
+                               cells: Optional[FieldGrid] = None, joints: Optional[FieldJoints] = None, tree=None,
+                               observed_count: Optional[torch.Tensor] = None, weights: Optional[torch.Tensor] = None,
+                               init: Optional[torch.Tensor] = None, lower=None, upper=None, reg: float = 0.0, rounds: int = 8,
+                               iterations: int = 3, damping: float = 1e-3) -> FieldVisibleRegistration:
+    """``register_commands_visible`` on the rows of an extracted cloud, as ``cloud_registration`` is ``register_commands`` on them;
+    ``cells=None`` takes ``cell_grid`` over the bounds of ``cloud.grid`` with the largest of its steps as the cell."""
+    name = "cloud_registration_visible"
+    if not isinstance(cloud, FieldPointCloud):
+        raise ValueError(f"{name}: cloud must be a FieldPointCloud")
+    try:
+        if cells is None:
+            cells = _cloud_cells(cloud, "register_commands_visible")
+        return register_commands_visible(twists, cloud.xyz, labels, observed, cells, max_distance, visible_from,
+                                         observed_information=observed_information, joints=joints, tree=tree,
+                                         observed_count=observed_count, count=cloud.count, weights=weights, init=init, lower=lower,
+                                         upper=upper, reg=reg, rounds=rounds, iterations=iterations, damping=damping)
+    except ValueError as err:
+        raise ValueError(str(err).replace("register_commands_visible:", f"{name}:", 1).replace("cell_grid:", f"{name}:", 1)) from None
 
 
 def _cloud_cells(cloud: FieldPointCloud, name: str) -> FieldGrid:

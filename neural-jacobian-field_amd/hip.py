@@ -187,6 +187,8 @@ _SIGNATURES = {
                                 _vp], C.c_int),
     "njf_field_voxels": ([_vp, _vp, C.c_int, C.c_int, C.POINTER(FieldGrid), C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                           C.c_longlong, C.c_int, _vp], C.c_int),
+    "njf_field_visible": ([_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
+                           C.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_longlong, C.c_int, _vp], C.c_int),
     "njf_pack_resnetfc_backward": ([C.POINTER(ResnetFcWeights), _vp, C.c_int, _vp], C.c_int),
     "njf_resnetfc_backward": ([_vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp], C.c_int),
     "njf_pack_transformer_backward": ([_vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, _vp], C.c_int),
@@ -1433,6 +1435,68 @@ def field_voxels(points, grid: FieldGrid, out: dict, points_count=None, min_poin
             _int32_ptr(out["weight"], "weight"), _int32_ptr(out["cell"], "cell"), _ptr(out["sums"], "sums", torch.int64),
             _int32_ptr(out["count"], "count"), _int32_ptr(out["outside"], "outside"), _int32_ptr(workspace, "workspace"),
             int(workspace.numel()), int(phase))
+
+
+# ---- which posed rows a depth camera sees: a z-buffer of points (include/njf_hip.h: njf_field_visible) -------------------------------
+FIELD_VISIBLE_SPLAT, FIELD_VISIBLE_RESOLVE, FIELD_VISIBLE_TEST = 1, 2, 4   # NJF_FIELD_VISIBLE_SPLAT, _RESOLVE, _TEST: a memset, a launch
+FIELD_VISIBLE_PHASES = (FIELD_VISIBLE_SPLAT, FIELD_VISIBLE_RESOLVE, FIELD_VISIBLE_TEST)
+FIELD_VISIBLE_PHASE_NAMES = ("splat", "resolve", "test")
+FIELD_VISIBLE_ALL = 7                                  # NJF_FIELD_VISIBLE_ALL
+FIELD_VISIBLE_DIRECT = 8                               # NJF_FIELD_VISIBLE_DIRECT: the splat without the load before the atomic
+FIELD_VISIBLE_MAX_VIEWS = 32                           # NJF_FIELD_VISIBLE_MAX_VIEWS: one bit of `seen` per view
+FIELD_VISIBLE_MAX_FOOTPRINT = 4                        # NJF_FIELD_VISIBLE_MAX_FOOTPRINT
+FIELD_VISIBLE_OUTPUTS = (("depth", torch.float32), ("index", torch.int32), ("covered", torch.int32), ("seen", torch.int32),
+                         ("culled", torch.float32), ("visible", torch.int32), ("pixel", torch.int32), ("z", torch.float32))
+
+
+def field_visible_workspace(m: int, v: int, h: int, w: int) -> int:
+    """32-bit words of workspace njf_field_visible needs: NJF_FIELD_VISIBLE_WORKSPACE(M, V, H, W) -- M V H W keys of 8 bytes and
+    one word of alignment."""
+    return 2 * m * v * h * w + 1
+
+
+def field_visible_default_phase() -> int:
+    """FIELD_VISIBLE_ALL in the default form of the splat; ``NJF_FIELD_VISIBLE_DIRECT=1`` in the environment selects the form
+    without the load before the atomic (equal bytes: DESIGN.md section 24 holds the measurement)."""
+    return FIELD_VISIBLE_ALL | (FIELD_VISIBLE_DIRECT if os.environ.get("NJF_FIELD_VISIBLE_DIRECT", "0") == "1" else 0)
+
+
+def field_visible(points: torch.Tensor, k: torch.Tensor, w2c: torch.Tensor, height: int, width: int, out: dict, problems: int,
+                  count=None, labels=None, footprint: int = 1, near: float = 0.0, tolerance: float = 0.01,
+                  phase: int = FIELD_VISIBLE_ALL, workspace: Optional[torch.Tensor] = None) -> None:
+    """njf_field_visible on ``points`` [Mq, n, 3] (fp32) for ``problems`` = M problems, Mq 1 or M, through the cameras ``k`` [V, 3,
+    3] (normalised intrinsics) and ``w2c`` [V, 4, 4] (fp32) into images of ``height`` x ``width``.  ``count`` [1], ``labels`` [n]:
+    int32 or None.  ``out`` maps depth, index [M, V, H, W], covered [M, V], seen [M, n], culled [M, n, 3], visible [M], pixel and z
+    [M, V, n] (FIELD_VISIBLE_OUTPUTS holds the element types) to tensors of their shapes.  ``phase``: FIELD_VISIBLE_SPLAT [+
+    FIELD_VISIBLE_DIRECT] reads the points and writes the workspace, FIELD_VISIBLE_RESOLVE writes depth, index and covered from
+    it, FIELD_VISIBLE_TEST reads the points and ``out["depth"]`` and writes the other five.  ``workspace``: int32,
+    ``field_visible_workspace`` elements."""
+    mq, n = _cloud_shape("field_visible", "points", "Mq, n", points)
+    m, h, w = int(problems), int(height), int(width)
+    if k.dim() != 3 or tuple(k.shape[1:]) != (3, 3) or w2c.dim() != 3 or tuple(w2c.shape) != (k.shape[0], 4, 4):
+        raise ValueError("njf_hip: field_visible needs k [V, 3, 3] and w2c [V, 4, 4]")
+    v = int(k.shape[0])
+    if count is not None and count.numel() != 1:
+        raise ValueError("njf_hip: field_visible count must hold one int32")
+    if labels is not None and labels.numel() != n:
+        raise ValueError("njf_hip: field_visible needs labels [n]")
+    splat, resolve, test = (bool(phase & p) for p in FIELD_VISIBLE_PHASES)
+    sizes = {}
+    if resolve or test:
+        sizes.update(depth=m * v * h * w)
+    if resolve:
+        sizes.update(index=m * v * h * w, covered=m * v)
+    if test:
+        sizes.update(seen=m * n, culled=3 * m * n, visible=m, pixel=m * v * n, z=m * v * n)
+    _check_output_sizes("field_visible", out, sizes)
+    if workspace is None and (splat or resolve):
+        workspace = torch.empty(field_visible_workspace(m, v, h, w), dtype=torch.int32, device=points.device)
+    o = (lambda key, ptr: ptr(out[key], key) if key in sizes else None)   # noqa: E731
+    _launch("njf_field_visible", load_library().njf_field_visible, _ptr(points, "points"), _int32_ptr(count, "count"),
+            _int32_ptr(labels, "labels"), mq, n, m, _ptr(k, "k"), _ptr(w2c, "w2c"), v, h, w, int(footprint), float(near),
+            float(tolerance), o("depth", _ptr), o("index", _int32_ptr), o("covered", _int32_ptr), o("seen", _int32_ptr),
+            o("culled", _ptr), o("visible", _int32_ptr), o("pixel", _int32_ptr), o("z", _ptr),
+            _int32_ptr(workspace, "workspace"), 0 if workspace is None else int(workspace.numel()), int(phase))
 
 
 def solve_action(mean_position, jacobian, projection, target_flow, visible_mask, init_action, iterations: int,
