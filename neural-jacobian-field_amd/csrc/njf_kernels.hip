@@ -2250,14 +2250,138 @@ __global__ void __launch_bounds__(256) field_xyz_kernel(FieldList l, float* __re
   xyz[3 * (size_t)i + 2] = pz;
 }
 
+// ---- workgroup sums, ranks and offsets -------------------------------------------------------------
+// What the field entries share when they count, rank or compact the entries of a workgroup.  A thread holds ITEMS entries:
+// item `it` of thread tid is entry it * blockDim.x + tid, so the order inside a workgroup is item-major, then wave, then lane
+// -- ascending index.  Integer arithmetic, no atomics, every order fixed by (ITEMS, WAVES) alone: what comes out of these
+// is a function of the inputs, never of scheduling.  Every thread of the workgroup calls (barriers inside); `lds` is free
+// again after a barrier of the caller.
+//
+// the butterfly 32, 16, ..., 1: every lane ends with the wave's sum.  The offset order is part of the contract -- the double
+// sums of the twists, the commands and the compositing backward are compared bit for bit (a + b == b + a bit for bit, so
+// every lane holds the same bits).
+template <class T>
+__device__ __forceinline__ T wave_sum(T v) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// the workgroup's sum of the per-wave totals `n` (wave-uniform: a ballot + popcount count stays on the scalar unit)
+template <int WAVES>
+__device__ __forceinline__ int block_sum_waves(int n, int (&lds)[WAVES]) {
+  if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = n;
+  __syncthreads();
+  int s = 0;
+#pragma unroll
+  for (int w = 0; w < WAVES; ++w) s += lds[w];
+  return s;
+}
+
+// the workgroup's sum of `v`
+template <int WAVES>
+__device__ __forceinline__ int block_sum(int v, int (&lds)[WAVES]) {
+  return block_sum_waves(wave_sum(v), lds);
+}
+
+// bit `it` of `flags`: item `it` is kept.  f(it, rank) for every kept item, `it` ascending, with rank = base + the kept
+// entries of the workgroup in front of the item (its place in the ordered output); returns the workgroup's number of kept
+// entries.  (A callback, not rank[ITEMS]: with the 16 items of a twist chunk the array cost 50 VGPRs and three waves per SIMD.)
+template <int ITEMS, int WAVES, class F>
+__device__ __forceinline__ int block_flag_ranks(unsigned flags, int base, int (&lds)[ITEMS][WAVES], F&& f) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int it = 0; it < ITEMS; ++it) {
+    const unsigned long long m = __ballot((flags >> it) & 1u);
+    if (lane == 0) lds[it][wave] = __popcll(m);
+  }
+  __syncthreads();
+  int run = base;
+#pragma unroll
+  for (int it = 0; it < ITEMS; ++it) {
+    int off = run;
+#pragma unroll
+    for (int w = 0; w < WAVES; ++w) {
+      const int c = lds[it][w];
+      if (w < wave) off += c;
+      run += c;
+    }
+    const unsigned long long m = __ballot((flags >> it) & 1u);  // (again: cheaper than ITEMS masks across the barrier)
+    if ((flags >> it) & 1u) f(it, off + __popcll(m & ((1ull << lane) - 1ull)));
+  }
+  return run - base;
+}
+
+// the same for integer counts: rank[it] = base + the sum of c over the workgroup's entries in front of item `it`
+template <int ITEMS, int WAVES>
+__device__ __forceinline__ void block_count_ranks(const int (&c)[ITEMS], int base, int (&rank)[ITEMS], int (&lds)[ITEMS][WAVES]) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int before[ITEMS];
+#pragma unroll
+  for (int it = 0; it < ITEMS; ++it) {
+    int v = c[it];
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const int o = __shfl_up(v, d, 64);
+      if (lane >= d) v += o;
+    }
+    before[it] = v - c[it];
+    if (lane == 63) lds[it][wave] = v;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int it = 0; it < ITEMS; ++it) {
+    int r = base;
+    for (int w = 0; w < wave; ++w) r += lds[it][w];
+    rank[it] = r + before[it];
+    for (int w = 0; w < WAVES; ++w) base += lds[it][w];
+  }
+}
+
+// the workgroup of the kernels over blocks of 1,024 consecutive entries (selection, mesh, fusion, band)
+#define NJF_BLOCK_THREADS 256
+#define NJF_BLOCK_WAVES (NJF_BLOCK_THREADS / 64)
+#define NJF_BLOCK_ITEMS (NJF_FIELD_SELECT_BLOCK / NJF_BLOCK_THREADS)
+static_assert(NJF_BLOCK_ITEMS * NJF_BLOCK_THREADS == NJF_FIELD_SELECT_BLOCK && NJF_BLOCK_ITEMS <= 8 &&
+                  NJF_FIELD_MESH_BLOCK == NJF_FIELD_SELECT_BLOCK && NJF_FIELD_BAND_BLOCK == NJF_FIELD_SELECT_BLOCK,
+              "one block of entries");
+
+// one workgroup: the per-workgroup sums at sums[b * STRIDE], b < blocks -> their exclusive prefix sums in place, the
+// grand total to *total.  A contiguous run of sums per thread, thread 0 scans the 256 run sums.  (STRIDE at compile time:
+// with a run-time stride the strided loads lost their unrolling, 1 to 2 % of the cell list's build.)
+template <long long STRIDE>
+__global__ void __launch_bounds__(NJF_BLOCK_THREADS) block_offsets_kernel(int* sums, int blocks, int* total) {
+  constexpr long long stride = STRIDE;
+  __shared__ int part[NJF_BLOCK_THREADS];
+  const int t = threadIdx.x;
+  const int per = (blocks + NJF_BLOCK_THREADS - 1) / NJF_BLOCK_THREADS;
+  const int lo = min(t * per, blocks), hi = min(lo + per, blocks);
+  int s = 0;
+  for (int i = lo; i < hi; ++i) s += sums[i * stride];
+  part[t] = s;
+  __syncthreads();
+  if (t == 0) {
+    int run = 0;
+    for (int i = 0; i < NJF_BLOCK_THREADS; ++i) {
+      const int c = part[i];
+      part[i] = run;
+      run += c;
+    }
+    *total = run;
+  }
+  __syncthreads();
+  int run = part[t];
+  for (int i = lo; i < hi; ++i) {
+    const int c = sums[i * stride];
+    sums[i * stride] = run;
+    run += c;
+  }
+}
+
 // ---- ordered selection --------------------------------------------------------------------
 // keep(entry i) = (values == null || values[i] >= threshold) && (no cameras || the node projects inside the context image
-// with positive camera depth).  Three launches: per-workgroup counts (ballot + popcount), a one-workgroup exclusive scan of
-// the counts, a scatter that re-evaluates the predicate and writes the survivors' global indices in input order.  Integer
-// arithmetic only, no atomics: the output bytes do not depend on scheduling.
-#define NJF_SELECT_THREADS 256
-#define NJF_SELECT_ITEMS (NJF_FIELD_SELECT_BLOCK / NJF_SELECT_THREADS)
-static_assert(NJF_SELECT_ITEMS * NJF_SELECT_THREADS == NJF_FIELD_SELECT_BLOCK && NJF_SELECT_ITEMS <= 8, "selection block");
+// with positive camera depth).  Three launches: per-workgroup counts, block_offsets_kernel, a scatter that re-evaluates the
+// predicate and writes the survivors' global indices in input order (block_flag_ranks).
 struct SelectArgs {
   FieldList list;
   const float* values;  // [entries] or null
@@ -2289,12 +2413,12 @@ __device__ __forceinline__ bool field_in_view(const SelectArgs& a, int gi) {
   return point_in_view(cam, px, py, pz);
 }
 
-// bit `it` of the result: keep entry block*NJF_FIELD_SELECT_BLOCK + it*NJF_SELECT_THREADS + tid
+// bit `it` of the result: keep entry block*NJF_FIELD_SELECT_BLOCK + it*NJF_BLOCK_THREADS + tid
 __device__ __forceinline__ unsigned select_flags(const SelectArgs& a, int entries) {
   unsigned flags = 0;
 #pragma unroll
-  for (int it = 0; it < NJF_SELECT_ITEMS; ++it) {
-    const long long i = (long long)blockIdx.x * NJF_FIELD_SELECT_BLOCK + it * NJF_SELECT_THREADS + threadIdx.x;
+  for (int it = 0; it < NJF_BLOCK_ITEMS; ++it) {
+    const long long i = (long long)blockIdx.x * NJF_FIELD_SELECT_BLOCK + it * NJF_BLOCK_THREADS + threadIdx.x;
     bool keep = i < entries;
     if (keep && a.values) keep = a.values[i] >= a.threshold;
     if (keep && a.w2c) keep = field_in_view(a, field_global_index(a.list, (int)i));
@@ -2303,78 +2427,23 @@ __device__ __forceinline__ unsigned select_flags(const SelectArgs& a, int entrie
   return flags;
 }
 
-__global__ void __launch_bounds__(NJF_SELECT_THREADS) select_count_kernel(SelectArgs a) {
-  __shared__ int wave_count[NJF_SELECT_THREADS / 64];
+__global__ void __launch_bounds__(NJF_BLOCK_THREADS) select_count_kernel(SelectArgs a) {
+  __shared__ int wave_count[NJF_BLOCK_WAVES];
   const unsigned flags = select_flags(a, field_entries(a.list));
   int n = 0;
 #pragma unroll
-  for (int it = 0; it < NJF_SELECT_ITEMS; ++it) n += __popcll(__ballot((flags >> it) & 1u));  // wave-uniform
-  if ((threadIdx.x & 63) == 0) wave_count[threadIdx.x >> 6] = n;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int s = 0;
-    for (int w = 0; w < NJF_SELECT_THREADS / 64; ++w) s += wave_count[w];
-    a.block_counts[blockIdx.x] = s;
-  }
+  for (int it = 0; it < NJF_BLOCK_ITEMS; ++it) n += __popcll(__ballot((flags >> it) & 1u));  // wave-uniform
+  const int s = block_sum_waves(n, wave_count);
+  if (threadIdx.x == 0) a.block_counts[blockIdx.x] = s;
 }
 
-// one workgroup: block_counts -> exclusive prefix sums in place, the total to out_count
-__global__ void __launch_bounds__(NJF_SELECT_THREADS) select_scan_kernel(int* __restrict__ block_counts, int blocks,
-                                                                         int* __restrict__ out_count) {
-  __shared__ int part[NJF_SELECT_THREADS];
-  const int t = threadIdx.x;
-  const int per = (blocks + NJF_SELECT_THREADS - 1) / NJF_SELECT_THREADS;  // a contiguous run per thread
-  const int lo = min(t * per, blocks), hi = min(lo + per, blocks);
-  int s = 0;
-  for (int i = lo; i < hi; ++i) s += block_counts[i];
-  part[t] = s;
-  __syncthreads();
-  if (t == 0) {
-    int run = 0;
-    for (int i = 0; i < NJF_SELECT_THREADS; ++i) {
-      const int c = part[i];
-      part[i] = run;
-      run += c;
-    }
-    *out_count = run;
-  }
-  __syncthreads();
-  int run = part[t];
-  for (int i = lo; i < hi; ++i) {
-    const int c = block_counts[i];
-    block_counts[i] = run;
-    run += c;
-  }
-}
-
-__global__ void __launch_bounds__(NJF_SELECT_THREADS) select_scatter_kernel(SelectArgs a) {
-  constexpr int WAVES = NJF_SELECT_THREADS / 64;
-  __shared__ int wave_count[NJF_SELECT_ITEMS][WAVES];
+__global__ void __launch_bounds__(NJF_BLOCK_THREADS) select_scatter_kernel(SelectArgs a) {
+  __shared__ int wave_count[NJF_BLOCK_ITEMS][NJF_BLOCK_WAVES];
   const unsigned flags = select_flags(a, field_entries(a.list));
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int before[NJF_SELECT_ITEMS];  // kept entries of this wave in front of this lane, per item
-#pragma unroll
-  for (int it = 0; it < NJF_SELECT_ITEMS; ++it) {
-    const unsigned long long m = __ballot((flags >> it) & 1u);
-    before[it] = __popcll(m & ((1ull << lane) - 1ull));
-    if (lane == 0) wave_count[it][wave] = __popcll(m);
-  }
-  __syncthreads();
-  int base = a.block_counts[blockIdx.x];  // exclusive offset of this workgroup
-#pragma unroll
-  for (int it = 0; it < NJF_SELECT_ITEMS; ++it) {
-    // input order inside a workgroup: item-major, then wave, then lane
-    int rank = base;
-    for (int w = 0; w < wave; ++w) rank += wave_count[it][w];
-    if ((flags >> it) & 1u) {
-      rank += before[it];
-      if (rank < a.out_capacity) {
-        const int i = blockIdx.x * NJF_FIELD_SELECT_BLOCK + it * NJF_SELECT_THREADS + threadIdx.x;
-        a.out_indices[rank] = field_global_index(a.list, i);
-      }
-    }
-    for (int w = 0; w < WAVES; ++w) base += wave_count[it][w];
-  }
+  block_flag_ranks(flags, a.block_counts[blockIdx.x], wave_count, [&](int it, int rank) {
+    const int i = blockIdx.x * NJF_FIELD_SELECT_BLOCK + it * NJF_BLOCK_THREADS + threadIdx.x;
+    if (rank < a.out_capacity) a.out_indices[rank] = field_global_index(a.list, i);
+  });
 }
 
 // ---- isosurface mesh of a scalar on the grid: marching tetrahedra on the Kuhn cut ------------------------------------------
@@ -2384,12 +2453,8 @@ __global__ void __launch_bounds__(NJF_SELECT_THREADS) select_scatter_kernel(Sele
 // tetrahedron edge is (lower node) + one of the seven directions k = 0..6 below; the lower node OWNS the edge.  One vertex
 // per edge whose ends are both valid and differ in `inside`, in ascending (owner, k); triangles per cell in ascending global
 // cell index, tetrahedra in the order above.  Six launches (mask + count, scan, vertex emit; count, scan, triangle emit),
-// integer arithmetic apart from the interpolation, no atomics: the output bytes do not depend on scheduling.
-#define NJF_MESH_THREADS 256
-#define NJF_MESH_ITEMS (NJF_FIELD_MESH_BLOCK / NJF_MESH_THREADS)
-#define NJF_MESH_WAVES (NJF_MESH_THREADS / 64)
+// integer arithmetic apart from the interpolation; sums, ranks and offsets by the workgroup primitives above.
 #define NJF_MESH_VALID 0x80u  // bit 7 of a node's mask byte: the node is valid; bits 0..6: edge k carries a vertex
-static_assert(NJF_MESH_ITEMS * NJF_MESH_THREADS == NJF_FIELD_MESH_BLOCK && NJF_MESH_ITEMS <= 8, "mesh block");
 struct MeshArgs {
   SelectArgs sel;              // list: the identity over B*N; values, threshold; w2c / k: frustum part of `valid` (or null)
   const unsigned char* valid;  // [B*N] or null
@@ -2419,52 +2484,14 @@ __device__ __forceinline__ bool mesh_node_valid(const MeshArgs& a, int gi) {
   return a.sel.w2c ? field_in_view(a.sel, gi) : true;
 }
 
-// sum of `v` over the workgroup (every thread calls), valid in thread 0
-__device__ __forceinline__ int mesh_block_sum(int v, int* wave_part) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-  if ((threadIdx.x & 63) == 0) wave_part[threadIdx.x >> 6] = v;
-  __syncthreads();
-  int s = 0;
-  for (int w = 0; w < NJF_MESH_WAVES; ++w) s += wave_part[w];
-  return s;
-}
-
-// rank[it] = base + (sum of c over the workgroup's entries in front of this thread's item `it`); entry order inside a
-// workgroup is item-major, then wave, then lane, which is ascending index (every thread calls)
-__device__ __forceinline__ void mesh_block_ranks(const int (&c)[NJF_MESH_ITEMS], int base, int (&rank)[NJF_MESH_ITEMS],
-                                                 int (*wave_sum)[NJF_MESH_WAVES]) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int before[NJF_MESH_ITEMS];
-#pragma unroll
-  for (int it = 0; it < NJF_MESH_ITEMS; ++it) {
-    int v = c[it];
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int o = __shfl_up(v, d, 64);
-      if (lane >= d) v += o;
-    }
-    before[it] = v - c[it];
-    if (lane == 63) wave_sum[it][wave] = v;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int it = 0; it < NJF_MESH_ITEMS; ++it) {
-    int r = base;
-    for (int w = 0; w < wave; ++w) r += wave_sum[it][w];
-    rank[it] = r + before[it];
-    for (int w = 0; w < NJF_MESH_WAVES; ++w) base += wave_sum[it][w];
-  }
-}
-
 // launch 1: the mask byte of every node and the number of vertices per workgroup
-__global__ void __launch_bounds__(NJF_MESH_THREADS) mesh_mask_kernel(MeshArgs a) {
-  __shared__ int wave_part[NJF_MESH_WAVES];
+__global__ void __launch_bounds__(NJF_BLOCK_THREADS) mesh_mask_kernel(MeshArgs a) {
+  __shared__ int wave_part[NJF_BLOCK_WAVES];
   const NjfFieldGrid& g = a.sel.list.grid;
   int n_vertices = 0;
 #pragma unroll
-  for (int it = 0; it < NJF_MESH_ITEMS; ++it) {
-    const long long i = (long long)blockIdx.x * NJF_FIELD_MESH_BLOCK + it * NJF_MESH_THREADS + threadIdx.x;
+  for (int it = 0; it < NJF_BLOCK_ITEMS; ++it) {
+    const long long i = (long long)blockIdx.x * NJF_FIELD_MESH_BLOCK + it * NJF_BLOCK_THREADS + threadIdx.x;
     if (i >= a.sel.list.total) continue;
     const int gi = (int)i;
     const int n = gi % a.sel.list.nodes;
@@ -2486,26 +2513,26 @@ __global__ void __launch_bounds__(NJF_MESH_THREADS) mesh_mask_kernel(MeshArgs a)
     a.mask[gi] = (unsigned char)m;
     n_vertices += __popc(m & 0x7fu);
   }
-  const int s = mesh_block_sum(n_vertices, wave_part);
+  const int s = block_sum(n_vertices, wave_part);
   if (threadIdx.x == 0) a.block_counts[blockIdx.x] = s;
 }
 
 // launch 3: per-node exclusive offsets (all nodes) and the vertex rows of ranks below the capacity
-__global__ void __launch_bounds__(NJF_MESH_THREADS) mesh_vertex_kernel(MeshArgs a) {
-  __shared__ int wave_sum[NJF_MESH_ITEMS][NJF_MESH_WAVES];
+__global__ void __launch_bounds__(NJF_BLOCK_THREADS) mesh_vertex_kernel(MeshArgs a) {
+  __shared__ int wave_part[NJF_BLOCK_ITEMS][NJF_BLOCK_WAVES];
   const NjfFieldGrid& g = a.sel.list.grid;
-  int c[NJF_MESH_ITEMS], rank[NJF_MESH_ITEMS];
-  unsigned m[NJF_MESH_ITEMS];
+  int c[NJF_BLOCK_ITEMS], rank[NJF_BLOCK_ITEMS];
+  unsigned m[NJF_BLOCK_ITEMS];
 #pragma unroll
-  for (int it = 0; it < NJF_MESH_ITEMS; ++it) {
-    const long long i = (long long)blockIdx.x * NJF_FIELD_MESH_BLOCK + it * NJF_MESH_THREADS + threadIdx.x;
+  for (int it = 0; it < NJF_BLOCK_ITEMS; ++it) {
+    const long long i = (long long)blockIdx.x * NJF_FIELD_MESH_BLOCK + it * NJF_BLOCK_THREADS + threadIdx.x;
     m[it] = i < a.sel.list.total ? (a.mask[i] & 0x7fu) : 0u;
     c[it] = __popc(m[it]);
   }
-  mesh_block_ranks(c, a.block_counts[blockIdx.x], rank, wave_sum);
+  block_count_ranks(c, a.block_counts[blockIdx.x], rank, wave_part);
 #pragma unroll
-  for (int it = 0; it < NJF_MESH_ITEMS; ++it) {
-    const long long i = (long long)blockIdx.x * NJF_FIELD_MESH_BLOCK + it * NJF_MESH_THREADS + threadIdx.x;
+  for (int it = 0; it < NJF_BLOCK_ITEMS; ++it) {
+    const long long i = (long long)blockIdx.x * NJF_FIELD_MESH_BLOCK + it * NJF_BLOCK_THREADS + threadIdx.x;
     if (i >= a.sel.list.total) continue;
     const int gi = (int)i;
     a.offset[gi] = rank[it];
@@ -2617,32 +2644,32 @@ __device__ __forceinline__ int mesh_cell_triangles(const MeshArgs& a, int gc, F&
 }
 
 // launch 4: the number of triangles per workgroup of cells
-__global__ void __launch_bounds__(NJF_MESH_THREADS) mesh_triangle_count_kernel(MeshArgs a) {
-  __shared__ int wave_part[NJF_MESH_WAVES];
+__global__ void __launch_bounds__(NJF_BLOCK_THREADS) mesh_triangle_count_kernel(MeshArgs a) {
+  __shared__ int wave_part[NJF_BLOCK_WAVES];
   int n = 0;
 #pragma unroll
-  for (int it = 0; it < NJF_MESH_ITEMS; ++it) {
-    const long long i = (long long)blockIdx.x * NJF_FIELD_MESH_BLOCK + it * NJF_MESH_THREADS + threadIdx.x;
+  for (int it = 0; it < NJF_BLOCK_ITEMS; ++it) {
+    const long long i = (long long)blockIdx.x * NJF_FIELD_MESH_BLOCK + it * NJF_BLOCK_THREADS + threadIdx.x;
     if (i < a.total_cells) n += mesh_cell_triangles<true>(a, (int)i, [](int, int, int) {});
   }
-  const int s = mesh_block_sum(n, wave_part);
+  const int s = block_sum(n, wave_part);
   if (threadIdx.x == 0) a.block_counts[blockIdx.x] = s;
 }
 
 // launch 6: the triangle rows of ranks below the capacity
-__global__ void __launch_bounds__(NJF_MESH_THREADS) mesh_triangle_kernel(MeshArgs a) {
-  __shared__ int wave_sum[NJF_MESH_ITEMS][NJF_MESH_WAVES];
-  int c[NJF_MESH_ITEMS], rank[NJF_MESH_ITEMS];
+__global__ void __launch_bounds__(NJF_BLOCK_THREADS) mesh_triangle_kernel(MeshArgs a) {
+  __shared__ int wave_part[NJF_BLOCK_ITEMS][NJF_BLOCK_WAVES];
+  int c[NJF_BLOCK_ITEMS], rank[NJF_BLOCK_ITEMS];
 #pragma unroll
-  for (int it = 0; it < NJF_MESH_ITEMS; ++it) {
-    const long long i = (long long)blockIdx.x * NJF_FIELD_MESH_BLOCK + it * NJF_MESH_THREADS + threadIdx.x;
+  for (int it = 0; it < NJF_BLOCK_ITEMS; ++it) {
+    const long long i = (long long)blockIdx.x * NJF_FIELD_MESH_BLOCK + it * NJF_BLOCK_THREADS + threadIdx.x;
     c[it] = i < a.total_cells ? mesh_cell_triangles<true>(a, (int)i, [](int, int, int) {}) : 0;
   }
-  mesh_block_ranks(c, a.block_counts[blockIdx.x], rank, wave_sum);
+  block_count_ranks(c, a.block_counts[blockIdx.x], rank, wave_part);
 #pragma unroll
-  for (int it = 0; it < NJF_MESH_ITEMS; ++it) {
+  for (int it = 0; it < NJF_BLOCK_ITEMS; ++it) {
     if (c[it] == 0 || rank[it] >= a.max_triangles) continue;
-    const int gc = blockIdx.x * NJF_FIELD_MESH_BLOCK + it * NJF_MESH_THREADS + threadIdx.x;
+    const int gc = blockIdx.x * NJF_FIELD_MESH_BLOCK + it * NJF_BLOCK_THREADS + threadIdx.x;
     int r = rank[it];
     mesh_cell_triangles<false>(a, gc, [&](int v0, int v1, int v2) {
       if (r < a.max_triangles) {
@@ -2659,10 +2686,7 @@ __global__ void __launch_bounds__(NJF_MESH_THREADS) mesh_triangle_kernel(MeshArg
 // ---- fusion of the fields of several context views ------------------------------------------------
 // The B context images are G = B / V scenes of V consecutive views (batch element b = g*V + v) on one grid.  s_v = the frustum
 // predicate of the selection (point_in_view) for view v, all ones without cameras; c = the number of views that see a node.
-#define NJF_FUSE_THREADS 256
-#define NJF_FUSE_ITEMS (NJF_FIELD_SELECT_BLOCK / NJF_FUSE_THREADS)
 #define NJF_FUSE_CAM_FLOATS 21  // rows 0..2 of ctxt_w2c + the 9 intrinsics: a CamCtx
-static_assert(NJF_FUSE_ITEMS * NJF_FUSE_THREADS == NJF_FIELD_SELECT_BLOCK, "fusion block");
 static_assert(sizeof(CamCtx) == NJF_FUSE_CAM_FLOATS * sizeof(float), "CamCtx layout");
 struct FuseArgs {
   NjfFieldGrid grid;
@@ -2683,25 +2707,25 @@ struct FuseArgs {
 // thread takes a camera out of LDS once per view and keeps the running state of its four nodes in registers.  fp32 adds in
 // view order, one IEEE division, no atomics: the result is a function of the inputs alone.
 template <int MODE>
-__global__ void __launch_bounds__(NJF_FUSE_THREADS) field_fuse_kernel(FuseArgs a) {
+__global__ void __launch_bounds__(NJF_BLOCK_THREADS) field_fuse_kernel(FuseArgs a) {
   __shared__ float cams[NJF_FIELD_MAX_VIEWS * NJF_FUSE_CAM_FLOATS];
   const int g = blockIdx.x / a.blocks_per_scene;
   const int first = (blockIdx.x - g * a.blocks_per_scene) * NJF_FIELD_SELECT_BLOCK;
   if (a.w2c) {
-    for (int t = threadIdx.x; t < a.views * NJF_FUSE_CAM_FLOATS; t += NJF_FUSE_THREADS) {
+    for (int t = threadIdx.x; t < a.views * NJF_FUSE_CAM_FLOATS; t += NJF_BLOCK_THREADS) {
       const int v = t / NJF_FUSE_CAM_FLOATS, e = t - v * NJF_FUSE_CAM_FLOATS;
       const size_t b = (size_t)g * a.views + v;
       cams[t] = e < 12 ? a.w2c[b * 16 + e] : a.k[b * 9 + (e - 12)];
     }
     __syncthreads();
   }
-  float px[NJF_FUSE_ITEMS], py[NJF_FUSE_ITEMS], pz[NJF_FUSE_ITEMS], acc[NJF_FUSE_ITEMS];
-  int count[NJF_FUSE_ITEMS];
-  unsigned mask[NJF_FUSE_ITEMS];
+  float px[NJF_BLOCK_ITEMS], py[NJF_BLOCK_ITEMS], pz[NJF_BLOCK_ITEMS], acc[NJF_BLOCK_ITEMS];
+  int count[NJF_BLOCK_ITEMS];
+  unsigned mask[NJF_BLOCK_ITEMS];
   const int yz = a.grid.dims[1] * a.grid.dims[2];
 #pragma unroll
-  for (int it = 0; it < NJF_FUSE_ITEMS; ++it) {
-    const int n = min(first + it * NJF_FUSE_THREADS + (int)threadIdx.x, a.nodes - 1);  // (the node of field_node)
+  for (int it = 0; it < NJF_BLOCK_ITEMS; ++it) {
+    const int n = min(first + it * NJF_BLOCK_THREADS + (int)threadIdx.x, a.nodes - 1);  // (the node of field_node)
     const int ix = n / yz, r = n - ix * yz;
     const int iy = r / a.grid.dims[2], iz = r - iy * a.grid.dims[2];
     px[it] = fmaf((float)ix, a.grid.step[0], a.grid.origin[0]);
@@ -2721,8 +2745,8 @@ __global__ void __launch_bounds__(NJF_FUSE_THREADS) field_fuse_kernel(FuseArgs a
     }
     const float* __restrict__ row = a.values + ((size_t)g * a.views + v) * (size_t)a.nodes;
 #pragma unroll
-    for (int it = 0; it < NJF_FUSE_ITEMS; ++it) {
-      const int n = first + it * NJF_FUSE_THREADS + (int)threadIdx.x;
+    for (int it = 0; it < NJF_BLOCK_ITEMS; ++it) {
+      const int n = first + it * NJF_BLOCK_THREADS + (int)threadIdx.x;
       if (n >= a.nodes) continue;
       if (a.w2c && !point_in_view(cam, px[it], py[it], pz[it])) continue;
       const float d = row[n];
@@ -2735,8 +2759,8 @@ __global__ void __launch_bounds__(NJF_FUSE_THREADS) field_fuse_kernel(FuseArgs a
     }
   }
 #pragma unroll
-  for (int it = 0; it < NJF_FUSE_ITEMS; ++it) {
-    const int n = first + it * NJF_FUSE_THREADS + (int)threadIdx.x;
+  for (int it = 0; it < NJF_BLOCK_ITEMS; ++it) {
+    const int n = first + it * NJF_BLOCK_THREADS + (int)threadIdx.x;
     if (n >= a.nodes) continue;
     const bool ok = count[it] >= a.min_views;
     float f = acc[it];
@@ -3076,7 +3100,7 @@ __global__ void __launch_bounds__(NJF_CC_THREADS) components_merge_kernel(Compon
 
 // launch 3 (parent is final: plain loads of what launches 1 and 2 wrote)
 __global__ void __launch_bounds__(NJF_CC_THREADS) components_label_kernel(ComponentArgs a) {
-  __shared__ int wave_part[NJF_MESH_WAVES];
+  __shared__ int wave_part[NJF_CC_WAVES];
   const FieldList& fl = a.sel.list;
   const long long base = (long long)blockIdx.x * NJF_FIELD_COMPONENTS_BLOCK;
   const int nloc = (int)min((long long)NJF_FIELD_COMPONENTS_BLOCK, (long long)fl.total - base);
@@ -3103,7 +3127,7 @@ __global__ void __launch_bounds__(NJF_CC_THREADS) components_label_kernel(Compon
     const int c = a.sizes[gi];              // > 0 at the local roots of launch 1 only
     if (c > 0) atomicAdd(a.root_size + x, c);
   }
-  const int s = mesh_block_sum(roots, wave_part);
+  const int s = block_sum(roots, wave_part);
   if (threadIdx.x == 0 && s > 0) atomicAdd(a.count, s);
 }
 
@@ -3128,13 +3152,8 @@ __global__ void __launch_bounds__(NJF_CC_THREADS) components_size_kernel(Compone
 // exact), M = prod(m_c + 1) per element.  hit(b, q) = (coarse_valid == null || coarse_valid[b, q]) && coarse_values[b, q] >=
 // threshold (NaN: no hit); block j is ACTIVE iff a coarse node q with max(0, j_c - d) <= q_c <= min(m_c, j_c + 1 + d) on every
 // axis is a hit; fine node i is in the BAND iff an active block j has j_c*k <= i_c <= (j_c + 1)*k on every axis -- the
-// candidates per axis are {ceil(i_c / k) - 1, floor(i_c / k)} clipped to [0, m_c - 1].  Workgroups of 1024 consecutive nodes,
-// item-major, like the selection; integer arithmetic, no atomics apart from the one integer add per workgroup of the leak
-// count: the output bytes do not depend on scheduling.
-#define NJF_BAND_THREADS 256
-#define NJF_BAND_ITEMS (NJF_FIELD_BAND_BLOCK / NJF_BAND_THREADS)
-static_assert(NJF_BAND_ITEMS * NJF_BAND_THREADS == NJF_FIELD_BAND_BLOCK && NJF_FIELD_BAND_BLOCK == NJF_FIELD_SELECT_BLOCK,
-              "band block");
+// candidates per axis are {ceil(i_c / k) - 1, floor(i_c / k)} clipped to [0, m_c - 1].  Workgroups of 1024 consecutive nodes
+// on the workgroup primitives, like the selection; the one atomic is an integer add per workgroup of the leak count.
 struct BandArgs {
   int dims[3];                   // fine grid
   int nodes, total;              // N, B*N
@@ -3155,8 +3174,8 @@ struct BandArgs {
 };
 
 // one thread per block: any hit among its (2d + 2)^3 clipped coarse nodes
-__global__ void __launch_bounds__(NJF_BAND_THREADS) band_blocks_kernel(BandArgs a) {
-  const int g = blockIdx.x * NJF_BAND_THREADS + threadIdx.x;
+__global__ void __launch_bounds__(NJF_BLOCK_THREADS) band_blocks_kernel(BandArgs a) {
+  const int g = blockIdx.x * NJF_BLOCK_THREADS + threadIdx.x;
   if (g >= a.batch * a.nb) return;
   const int b = g / a.nb, j = g - b * a.nb;
   const int myz = a.m[1] * a.m[2];
@@ -3197,12 +3216,12 @@ __device__ __forceinline__ bool band_node(const BandArgs& a, int gi) {
 }
 
 // band bytes + per-workgroup counts
-__global__ void __launch_bounds__(NJF_BAND_THREADS) band_count_kernel(BandArgs a) {
-  __shared__ int wave_count[NJF_BAND_THREADS / 64];
+__global__ void __launch_bounds__(NJF_BLOCK_THREADS) band_count_kernel(BandArgs a) {
+  __shared__ int wave_count[NJF_BLOCK_WAVES];
   int n = 0;
 #pragma unroll
-  for (int it = 0; it < NJF_BAND_ITEMS; ++it) {
-    const long long i = (long long)blockIdx.x * NJF_FIELD_BAND_BLOCK + it * NJF_BAND_THREADS + threadIdx.x;
+  for (int it = 0; it < NJF_BLOCK_ITEMS; ++it) {
+    const long long i = (long long)blockIdx.x * NJF_FIELD_BAND_BLOCK + it * NJF_BLOCK_THREADS + threadIdx.x;
     bool in = false;
     if (i < a.total) {
       in = band_node(a, (int)i);
@@ -3210,43 +3229,22 @@ __global__ void __launch_bounds__(NJF_BAND_THREADS) band_count_kernel(BandArgs a
     }
     n += __popcll(__ballot(in));  // wave-uniform
   }
-  if ((threadIdx.x & 63) == 0) wave_count[threadIdx.x >> 6] = n;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int s = 0;
-    for (int w = 0; w < NJF_BAND_THREADS / 64; ++w) s += wave_count[w];
-    a.block_counts[blockIdx.x] = s;
-  }
+  const int s = block_sum_waves(n, wave_count);
+  if (threadIdx.x == 0) a.block_counts[blockIdx.x] = s;
 }
 
 // the ascending global indices of the band nodes (the band bytes and the scanned offsets come from earlier launches)
-__global__ void __launch_bounds__(NJF_BAND_THREADS) band_scatter_kernel(BandArgs a) {
-  constexpr int WAVES = NJF_BAND_THREADS / 64;
-  __shared__ int wave_count[NJF_BAND_ITEMS][WAVES];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+__global__ void __launch_bounds__(NJF_BLOCK_THREADS) band_scatter_kernel(BandArgs a) {
+  __shared__ int wave_count[NJF_BLOCK_ITEMS][NJF_BLOCK_WAVES];
   unsigned flags = 0;
-  int before[NJF_BAND_ITEMS];
 #pragma unroll
-  for (int it = 0; it < NJF_BAND_ITEMS; ++it) {
-    const long long i = (long long)blockIdx.x * NJF_FIELD_BAND_BLOCK + it * NJF_BAND_THREADS + threadIdx.x;
-    const bool in = i < a.total && a.band[i] != 0;
-    flags |= in ? 1u << it : 0u;
-    const unsigned long long m = __ballot(in);
-    before[it] = __popcll(m & ((1ull << lane) - 1ull));
-    if (lane == 0) wave_count[it][wave] = __popcll(m);
+  for (int it = 0; it < NJF_BLOCK_ITEMS; ++it) {
+    const long long i = (long long)blockIdx.x * NJF_FIELD_BAND_BLOCK + it * NJF_BLOCK_THREADS + threadIdx.x;
+    flags |= i < a.total && a.band[i] != 0 ? 1u << it : 0u;
   }
-  __syncthreads();
-  int base = a.block_counts[blockIdx.x];
-#pragma unroll
-  for (int it = 0; it < NJF_BAND_ITEMS; ++it) {
-    int rank = base;
-    for (int w = 0; w < wave; ++w) rank += wave_count[it][w];
-    if ((flags >> it) & 1u) {
-      rank += before[it];
-      if (rank < a.out_capacity) a.out_indices[rank] = blockIdx.x * NJF_FIELD_BAND_BLOCK + it * NJF_BAND_THREADS + threadIdx.x;
-    }
-    for (int w = 0; w < WAVES; ++w) base += wave_count[it][w];
-  }
+  block_flag_ranks(flags, a.block_counts[blockIdx.x], wave_count, [&](int it, int rank) {
+    if (rank < a.out_capacity) a.out_indices[rank] = blockIdx.x * NJF_FIELD_BAND_BLOCK + it * NJF_BLOCK_THREADS + threadIdx.x;
+  });
 }
 
 // out[indices[i]] = values[i] for i < min(*count, capacity); an index outside [0, out_size) is skipped
@@ -3271,15 +3269,15 @@ struct BandLeakArgs {
 };
 
 // entries with a neighbour g +- dir_k (the seven mesh directions, inside the grid: no wrap at the faces) outside the band
-__global__ void __launch_bounds__(NJF_BAND_THREADS) band_leaks_kernel(BandLeakArgs a) {
-  __shared__ int wave_count[NJF_BAND_THREADS / 64];
+__global__ void __launch_bounds__(NJF_BLOCK_THREADS) band_leaks_kernel(BandLeakArgs a) {
+  __shared__ int wave_count[NJF_BLOCK_WAVES];
   const int entries = counted_length(a.count, a.capacity);
   const long long base = (long long)blockIdx.x * NJF_FIELD_BAND_BLOCK;
   if (base >= entries) return;  // (uniform over the workgroup)
   int n = 0;
 #pragma unroll
-  for (int it = 0; it < NJF_BAND_ITEMS; ++it) {
-    const long long i = base + it * NJF_BAND_THREADS + threadIdx.x;
+  for (int it = 0; it < NJF_BLOCK_ITEMS; ++it) {
+    const long long i = base + it * NJF_BLOCK_THREADS + threadIdx.x;
     bool leak = false;
     if (i < entries) {
       const int g = a.indices[i];
@@ -3302,21 +3300,16 @@ __global__ void __launch_bounds__(NJF_BAND_THREADS) band_leaks_kernel(BandLeakAr
     }
     n += __popcll(__ballot(leak));
   }
-  if ((threadIdx.x & 63) == 0) wave_count[threadIdx.x >> 6] = n;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int s = 0;
-    for (int w = 0; w < NJF_BAND_THREADS / 64; ++w) s += wave_count[w];
-    if (s) atomicAdd(a.leaks, s);  // one integer add per workgroup: the sum does not depend on the order
-  }
+  const int s = block_sum_waves(n, wave_count);
+  if (threadIdx.x == 0 && s) atomicAdd(a.leaks, s);  // one integer add per workgroup: the sum does not depend on the order
 }
 
 // =============================================================================================
 // rigid twists per part and command channel (njf_field_twists)
 // =============================================================================================
 // J_a(x) = v_a + omega_a x (x - c) fitted per part (the rows of one label) and channel, in double, without floating-point atomics:
-// workgroup (chunk, part) compacts the chunk's matching rows IN ORDER into LDS, thread t accumulates list entries t, t + 256, ...
-// sequentially, a fixed butterfly and the four wave partials in wave order give partial[part][chunk][.], and a finishing
+// workgroup (chunk, part) compacts the chunk's matching rows IN ORDER into LDS (block_flag_ranks), thread t accumulates list
+// entries t, t + 256, ... sequentially, the butterfly (wave_sum) and the four wave partials in wave order give partial[part][chunk][.], and a finishing
 // kernel adds the chunks in ascending order.  Every sum therefore has an order that depends on (n, K, A) alone.
 #define NJF_TWIST_THREADS 256
 #define NJF_TWIST_ITEMS (NJF_FIELD_TWISTS_CHUNK / NJF_TWIST_THREADS)
@@ -3346,46 +3339,20 @@ __device__ __forceinline__ double twist_weight(const TwistArgs& a, long long i) 
 }
 
 // the chunk's rows of label `part`, as offsets into the chunk, ascending, into list[]; returns their number
-__device__ __forceinline__ int twist_compact(const int* labels, int part, int rows, int* list, int (*wave_count)[NJF_TWIST_THREADS / 64]) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+// (block_flag_ranks from 0: the ranks are the places in the list; the workgroup size comes with wave_count)
+template <int ITEMS, int WAVES>
+__device__ __forceinline__ int twist_compact(const int* labels, int part, int rows, int* list, int (&wave_count)[ITEMS][WAVES]) {
+  static_assert(ITEMS * WAVES * 64 == NJF_FIELD_TWISTS_CHUNK && ITEMS <= 32, "a chunk per workgroup");
   const long long base = (long long)blockIdx.x * NJF_FIELD_TWISTS_CHUNK;
   unsigned flags = 0;
 #pragma unroll
-  for (int it = 0; it < NJF_TWIST_ITEMS; ++it) {
-    const long long i = base + it * NJF_TWIST_THREADS + tid;
+  for (int it = 0; it < ITEMS; ++it) {
+    const long long i = base + it * (WAVES * 64) + threadIdx.x;
     if (i < rows && labels[i] == part) flags |= 1u << it;
   }
-#pragma unroll
-  for (int it = 0; it < NJF_TWIST_ITEMS; ++it) {
-    const unsigned long long m = __ballot((flags >> it) & 1u);
-    if (lane == 0) wave_count[it][wave] = __popcll(m);
-  }
+  const int m = block_flag_ranks(flags, 0, wave_count, [&](int it, int rank) { list[rank] = it * (WAVES * 64) + threadIdx.x; });
   __syncthreads();
-  int run = 0;
-#pragma unroll
-  for (int it = 0; it < NJF_TWIST_ITEMS; ++it) {
-    int off = run;
-#pragma unroll
-    for (int w = 0; w < NJF_TWIST_THREADS / 64; ++w) {
-      const int c = wave_count[it][w];
-      if (w < wave) off += c;
-      run += c;
-    }
-    const unsigned long long m = __ballot((flags >> it) & 1u);
-    if ((flags >> it) & 1u) list[off + __popcll(m & ((1ull << lane) - 1ull))] = it * NJF_TWIST_THREADS + tid;
-  }
-  __syncthreads();
-  return run;
-}
-
-__device__ __forceinline__ int twist_compact(const TwistArgs& a, int part, int rows, int* list, int (*wave_count)[NJF_TWIST_THREADS / 64]) {
-  return twist_compact(a.labels, part, rows, list, wave_count);
-}
-
-__device__ __forceinline__ double twist_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);  // (a + b == b + a bit for bit: every lane ends with the same sum)
-  return v;
+  return m;
 }
 
 // pass A: nodes, W = sum w, S = sum w x
@@ -3395,7 +3362,7 @@ __global__ void __launch_bounds__(NJF_TWIST_THREADS) twist_sums_kernel(TwistArgs
   __shared__ double red[NJF_TWIST_THREADS / 64][4];
   const int p = blockIdx.y, tid = threadIdx.x;
   if (p >= twist_active(a)) return;  // (uniform over the workgroup)
-  const int m = twist_compact(a, a.parts[p], twist_rows(a), list, wave_count);
+  const int m = twist_compact(a.labels, a.parts[p], twist_rows(a), list, wave_count);
   const long long base = (long long)blockIdx.x * NJF_FIELD_TWISTS_CHUNK;
   double acc[4] = {0.0, 0.0, 0.0, 0.0};
   for (int e = tid; e < m; e += NJF_TWIST_THREADS) {
@@ -3409,7 +3376,7 @@ __global__ void __launch_bounds__(NJF_TWIST_THREADS) twist_sums_kernel(TwistArgs
   }
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
-    const double s = twist_wave_sum(acc[k]);
+    const double s = wave_sum(acc[k]);
     if ((tid & 63) == 0) red[tid >> 6][k] = s;
   }
   __syncthreads();
@@ -3457,7 +3424,7 @@ __global__ void __launch_bounds__(NJF_TWIST_THREADS) twist_moments_kernel(TwistA
   __shared__ double red[NJF_TWIST_THREADS / 64][NJF_TWIST_MAX_VALUES];
   const int p = blockIdx.y, tid = threadIdx.x;
   if (p >= twist_active(a)) return;
-  const int m = twist_compact(a, a.parts[p], twist_rows(a), list, wave_count);
+  const int m = twist_compact(a.labels, a.parts[p], twist_rows(a), list, wave_count);
   const long long base = (long long)blockIdx.x * NJF_FIELD_TWISTS_CHUNK;
   const double cx = a.centroid[p * 3], cy = a.centroid[p * 3 + 1], cz = a.centroid[p * 3 + 2];
   {
@@ -3477,7 +3444,7 @@ __global__ void __launch_bounds__(NJF_TWIST_THREADS) twist_moments_kernel(TwistA
     }
 #pragma unroll
     for (int k = 0; k < 6; ++k) {
-      const double s = twist_wave_sum(acc[k]);
+      const double s = wave_sum(acc[k]);
       if ((tid & 63) == 0) red[tid >> 6][k] = s;
     }
   }
@@ -3501,7 +3468,7 @@ __global__ void __launch_bounds__(NJF_TWIST_THREADS) twist_moments_kernel(TwistA
     }
 #pragma unroll
     for (int k = 0; k < 7; ++k) {
-      const double s = twist_wave_sum(acc[k]);
+      const double s = wave_sum(acc[k]);
       if ((tid & 63) == 0) red[tid >> 6][6 + 7 * ch + k] = s;
     }
   }
@@ -3581,7 +3548,7 @@ __global__ void __launch_bounds__(NJF_TWIST_THREADS) twist_residual_kernel(Twist
     tw[tid / 3][tid % 3] = a.omega[p * A * 3 + tid];
     tw[tid / 3][3 + tid % 3] = a.velocity[p * A * 3 + tid];
   }
-  const int m = twist_compact(a, a.parts[p], twist_rows(a), list, wave_count);  // (its barriers publish tw)
+  const int m = twist_compact(a.labels, a.parts[p], twist_rows(a), list, wave_count);  // (its barriers publish tw)
   const long long base = (long long)blockIdx.x * NJF_FIELD_TWISTS_CHUNK;
   const double cx = a.centroid[p * 3], cy = a.centroid[p * 3 + 1], cz = a.centroid[p * 3 + 2];
   double acc[NJF_MAX_ACTION_DIM];
@@ -3609,7 +3576,7 @@ __global__ void __launch_bounds__(NJF_TWIST_THREADS) twist_residual_kernel(Twist
 #pragma unroll
   for (int ch = 0; ch < NJF_MAX_ACTION_DIM; ++ch) {
     if (ch < A) {  // (uniform)
-      const double s = twist_wave_sum(acc[ch]);
+      const double s = wave_sum(acc[ch]);
       if ((tid & 63) == 0) red[tid >> 6][ch] = s;
     }
   }
@@ -3669,12 +3636,6 @@ __global__ void __launch_bounds__(NJF_JOINT_THREADS) joint_slots_kernel(JointArg
   if (p < active && a.parts[p] == label) a.volume[g] = p;  // g < B*N
 }
 
-__device__ __forceinline__ long long joint_wave_sum(long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
 // One thread per row: the slots of its positive neighbours, 64-bit integer adds into the pair table.  COMBINE: the lanes of a
 // wave that hold the same pair in one direction (a flat face: all of them) are added up first -- a leader loop over the wave's
 // distinct keys -- and the leader alone touches memory; otherwise every lane adds for itself.  Same table either way.
@@ -3724,9 +3685,9 @@ __global__ void __launch_bounds__(NJF_JOINT_THREADS) joint_contacts_kernel(Joint
         const unsigned long long same = __ballot(mine);
         long long tx = mine ? sx : 0, ty = mine ? sy : 0, tz = mine ? sz : 0;
         if (same & (same - 1)) {  // more than one lane holds the key
-          tx = joint_wave_sum(tx);
-          ty = joint_wave_sum(ty);
-          tz = joint_wave_sum(tz);
+          tx = wave_sum(tx);
+          ty = wave_sum(ty);
+          tz = wave_sum(tz);
         }
         if (lane == leader) {
           unsigned long long* e = a.table + (size_t)k0 * 4;
@@ -3744,8 +3705,8 @@ __global__ void __launch_bounds__(NJF_JOINT_THREADS) joint_contacts_kernel(Joint
 // One workgroup: the ordered compaction of the K*K table entries with at least min_contacts contacts (entry lo*K + hi ascending
 // is (lo, hi) ascending), the true count, and the padding of the rows past it.
 __global__ void __launch_bounds__(NJF_JOINT_LIST_THREADS) joint_list_kernel(JointArgs a) {
-  __shared__ int wave_count[NJF_JOINT_LIST_THREADS / 64];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  __shared__ int wave_count[1][NJF_JOINT_LIST_THREADS / 64];
+  const int tid = threadIdx.x;
   const int entries = a.K * a.K;
   int run = 0;
   for (int base = 0; base < entries; base += NJF_JOINT_LIST_THREADS) {
@@ -3753,18 +3714,7 @@ __global__ void __launch_bounds__(NJF_JOINT_LIST_THREADS) joint_list_kernel(Join
     long long c = 0;
     if (e < entries) c = (long long)a.table[(size_t)e * 4];
     const bool keep = c >= (long long)a.min_contacts;  // (min_contacts >= 1: an empty entry never passes)
-    const unsigned long long m = __ballot(keep);
-    if (lane == 0) wave_count[wave] = __popcll(m);
-    __syncthreads();
-    int off = run;
-#pragma unroll
-    for (int w = 0; w < NJF_JOINT_LIST_THREADS / 64; ++w) {
-      const int n = wave_count[w];
-      if (w < wave) off += n;
-      run += n;
-    }
-    if (keep) {
-      const int j = off + __popcll(m & ((1ull << lane) - 1ull));
+    run += block_flag_ranks(keep ? 1u : 0u, run, wave_count, [&](int, int j) {
       if (j < a.J) {
         const int lo = e / a.K, hi = e - lo * a.K;
         a.part_a[j] = lo;
@@ -3772,7 +3722,7 @@ __global__ void __launch_bounds__(NJF_JOINT_LIST_THREADS) joint_list_kernel(Join
         a.contacts[j] = c;
         a.status[j] = a.part_status[lo] | a.part_status[hi];
       }
-    }
+    });
     __syncthreads();
   }
   if (tid == 0) *a.out_count = run;  // (at most K*(K-1)/2 < 2^15)
@@ -4154,8 +4104,7 @@ __device__ __forceinline__ int ik_walk_status(const int* parent, const int* bits
 
 __global__ void __launch_bounds__(NJF_IK_THREADS) ik_moments_kernel(IkArgs a) {
   __shared__ int list[NJF_FIELD_TWISTS_CHUNK];
-  __shared__ int wave_count[NJF_TWIST_ITEMS][NJF_TWIST_THREADS / 64];
-  static_assert(NJF_IK_THREADS == NJF_TWIST_THREADS, "twist_compact is written for this workgroup size");
+  __shared__ int wave_count[NJF_FIELD_TWISTS_CHUNK / NJF_IK_THREADS][NJF_IK_THREADS / 64];
   const PoseArgs& s = a.pose;
   const int p = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   if (p >= counted_length(s.parts_count, s.K) || s.parts[p] < 0) return;  // (uniform; the finishing launch does not read it)
@@ -4204,7 +4153,7 @@ __global__ void __launch_bounds__(NJF_IK_THREADS) ik_moments_kernel(IkArgs a) {
     double mine = 0.0;
 #pragma unroll
     for (int k = 0; k < NJF_IK_MOMENTS; ++k) {
-      const double v = twist_wave_sum(acc[k]);
+      const double v = wave_sum(acc[k]);
       if (lane == k) mine = v;
     }
     if (lane < NJF_IK_MOMENTS) out[lane] = mine;
@@ -4250,8 +4199,7 @@ __device__ __forceinline__ int ikm_scatter_index(int lane, int j) {
 template <bool BUTTERFLY>
 __global__ void __launch_bounds__(NJF_IK_THREADS) ikm_moments_kernel(IkArgs a) {
   __shared__ int list[NJF_FIELD_TWISTS_CHUNK];
-  __shared__ int wave_count[NJF_TWIST_ITEMS][NJF_TWIST_THREADS / 64];
-  static_assert(NJF_IK_THREADS == NJF_TWIST_THREADS, "twist_compact is written for this workgroup size");
+  __shared__ int wave_count[NJF_FIELD_TWISTS_CHUNK / NJF_IK_THREADS][NJF_IK_THREADS / 64];
   static_assert(NJF_IKM_MOMENTS == 74, "the reduce-scatter's halves are written out for 74 sums");
   const PoseArgs& s = a.pose;
   const int p = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -4319,7 +4267,7 @@ __global__ void __launch_bounds__(NJF_IK_THREADS) ikm_moments_kernel(IkArgs a) {
       double mine[2] = {0.0, 0.0};
 #pragma unroll
       for (int k = 0; k < NJF_IKM_MOMENTS; ++k) {
-        const double v = twist_wave_sum(acc[k]);
+        const double v = wave_sum(acc[k]);
         if (lane == (k & 63)) mine[k >> 6] = v;
       }
       out[lane] = mine[0];
@@ -4584,7 +4532,7 @@ __global__ void __launch_bounds__(NJF_IK_THREADS) ik_solve_kernel(IkArgs a) {
     {
       const int lane = tid & 63, wave = tid >> 6;
       auto add = [&](int e, double share) {  // (called under conditions that are the same in every thread)
-        const double v = twist_wave_sum(counted ? share : 0.0);
+        const double v = wave_sum(counted ? share : 0.0);
         if (lane == 0) red[wave][e] = v;
       };
       if constexpr (METRIC) {
@@ -4903,72 +4851,30 @@ __global__ void __launch_bounds__(NJF_NN_THREADS) nn_points_kernel(CellList l, c
 
 // workgroup b: the sum of the counts [b * 1024, (b + 1) * 1024) to start[b * 1024]
 __global__ void __launch_bounds__(NJF_NN_THREADS) nn_scan_sums_kernel(const int* counts, int* start, long long L) {
-  __shared__ int wave_sum[NJF_NN_THREADS / 64];
+  __shared__ int wave_part[NJF_NN_THREADS / 64];
   const long long base = (long long)blockIdx.x * NJF_NN_SCAN_BLOCK + threadIdx.x * NJF_NN_SCAN_ITEMS;
   int v = 0;
 #pragma unroll
   for (int e = 0; e < NJF_NN_SCAN_ITEMS; ++e)
     if (base + e < L) v += counts[base + e];
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int s = 0;
-    for (int w = 0; w < NJF_NN_THREADS / 64; ++w) s += wave_sum[w];
-    start[(long long)blockIdx.x * NJF_NN_SCAN_BLOCK] = s;
-  }
+  const int s = block_sum(v, wave_part);
+  if (threadIdx.x == 0) start[(long long)blockIdx.x * NJF_NN_SCAN_BLOCK] = s;
 }
 
-// one workgroup: the block sums at start[b * 1024] -> their exclusive prefix sums in place, the total to start[L]
-// (select_scan_kernel's scheme on a strided array)
-__global__ void __launch_bounds__(NJF_NN_THREADS) nn_scan_blocks_kernel(int* start, long long L, int blocks) {
-  __shared__ int part[NJF_NN_THREADS];
-  const int t = threadIdx.x;
-  const int per = (blocks + NJF_NN_THREADS - 1) / NJF_NN_THREADS;  // a contiguous run per thread
-  const int lo = min(t * per, blocks), hi = min(lo + per, blocks);
-  int s = 0;
-  for (int i = lo; i < hi; ++i) s += start[(long long)i * NJF_NN_SCAN_BLOCK];
-  part[t] = s;
-  __syncthreads();
-  if (t == 0) {
-    int run = 0;
-    for (int i = 0; i < NJF_NN_THREADS; ++i) {
-      const int c = part[i];
-      part[i] = run;
-      run += c;
-    }
-    start[L] = run;
-  }
-  __syncthreads();
-  int run = part[t];
-  for (int i = lo; i < hi; ++i) {
-    const int c = start[(long long)i * NJF_NN_SCAN_BLOCK];
-    start[(long long)i * NJF_NN_SCAN_BLOCK] = run;
-    run += c;
-  }
-}
-
-// workgroup b: start[c] for its 1024 cells from the block's offset and the counts, which are cleared for the fill
+// workgroup b: start[c] for its 1024 cells from the block's offset and the counts, which are cleared for the fill.  A thread
+// holds NJF_NN_SCAN_ITEMS consecutive cells: one item, their sum, to block_count_ranks.
 __global__ void __launch_bounds__(NJF_NN_THREADS) nn_scan_cells_kernel(int* counts, int* start, long long L) {
-  __shared__ int wave_sum[NJF_NN_THREADS / 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  __shared__ int wave_part[1][NJF_NN_THREADS / 64];
   const long long base = (long long)blockIdx.x * NJF_NN_SCAN_BLOCK + threadIdx.x * NJF_NN_SCAN_ITEMS;
-  int c[NJF_NN_SCAN_ITEMS], mine = 0;
+  int c[NJF_NN_SCAN_ITEMS], mine[1] = {0}, first[1];
 #pragma unroll
   for (int e = 0; e < NJF_NN_SCAN_ITEMS; ++e) {
     c[e] = base + e < L ? counts[base + e] : 0;
-    mine += c[e];
+    mine[0] += c[e];
   }
-  int incl = mine;
-  for (int o = 1; o < 64; o <<= 1) {
-    const int t = __shfl_up(incl, o, 64);
-    if (lane >= o) incl += t;
-  }
-  if (lane == 63) wave_sum[wave] = incl;
-  const int offset = start[(long long)blockIdx.x * NJF_NN_SCAN_BLOCK];  // (read by all before thread 0 overwrites it)
-  __syncthreads();
-  int run = offset + incl - mine;
-  for (int w = 0; w < wave; ++w) run += wave_sum[w];
+  // (the block's offset is read by all in front of the barrier inside, thread 0 overwrites it behind it)
+  block_count_ranks(mine, start[(long long)blockIdx.x * NJF_NN_SCAN_BLOCK], first, wave_part);
+  int run = first[0];
 #pragma unroll
   for (int e = 0; e < NJF_NN_SCAN_ITEMS; ++e)
     if (base + e < L) {
@@ -6505,11 +6411,6 @@ __device__ __forceinline__ double wave_incl_suffix_scan(double v, int lane) {
   }
   return v;
 }
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 // the scan of the lanes in front of this one: the inclusive scan shifted by a lane (NOT `incl - v`, see above)
 __device__ __forceinline__ double shifted_scan(double incl, int lane) {
   const double t = __shfl_up(incl, 1, 64);
@@ -7018,13 +6919,13 @@ extern "C" int njf_field_select(const NjfFieldGrid* grid, const NjfCameras* cams
   a.blocks = (int)(((long long)capacity + NJF_FIELD_SELECT_BLOCK - 1) / NJF_FIELD_SELECT_BLOCK);
   hipStream_t s = (hipStream_t)stream;
   if (a.blocks > 0) {
-    select_count_kernel<<<a.blocks, NJF_SELECT_THREADS, 0, s>>>(a);
+    select_count_kernel<<<a.blocks, NJF_BLOCK_THREADS, 0, s>>>(a);
     if ((rc = launch_status())) return rc;
   }
-  select_scan_kernel<<<1, NJF_SELECT_THREADS, 0, s>>>(workspace, a.blocks, out_count);
+  block_offsets_kernel<1><<<1, NJF_BLOCK_THREADS, 0, s>>>(workspace, a.blocks, out_count);
   if ((rc = launch_status())) return rc;
   if (a.blocks > 0 && out_capacity > 0) {
-    select_scatter_kernel<<<a.blocks, NJF_SELECT_THREADS, 0, s>>>(a);
+    select_scatter_kernel<<<a.blocks, NJF_BLOCK_THREADS, 0, s>>>(a);
     if ((rc = launch_status())) return rc;
   }
   return NJF_OK;
@@ -7107,13 +7008,13 @@ extern "C" int njf_field_mesh_vertices(const NjfFieldGrid* grid, const NjfCamera
   const int blocks = (int)(((long long)a.sel.list.total + NJF_FIELD_MESH_BLOCK - 1) / NJF_FIELD_MESH_BLOCK);
   hipStream_t s = (hipStream_t)stream;
   if (phase & NJF_FIELD_MESH_COUNT) {
-    mesh_mask_kernel<<<blocks, NJF_MESH_THREADS, 0, s>>>(a);
+    mesh_mask_kernel<<<blocks, NJF_BLOCK_THREADS, 0, s>>>(a);
     if ((rc = launch_status())) return rc;
-    select_scan_kernel<<<1, NJF_SELECT_THREADS, 0, s>>>(workspace, blocks, vertex_count);
+    block_offsets_kernel<1><<<1, NJF_BLOCK_THREADS, 0, s>>>(workspace, blocks, vertex_count);
     if ((rc = launch_status())) return rc;
   }
   if (phase & NJF_FIELD_MESH_EMIT) {
-    mesh_vertex_kernel<<<blocks, NJF_MESH_THREADS, 0, s>>>(a);
+    mesh_vertex_kernel<<<blocks, NJF_BLOCK_THREADS, 0, s>>>(a);
     if ((rc = launch_status())) return rc;
   }
   return NJF_OK;
@@ -7136,13 +7037,13 @@ extern "C" int njf_field_mesh_triangles(const NjfFieldGrid* grid, int batch, con
   const int blocks = (a.total_cells + NJF_FIELD_MESH_BLOCK - 1) / NJF_FIELD_MESH_BLOCK;
   hipStream_t s = (hipStream_t)stream;
   if (phase & NJF_FIELD_MESH_COUNT) {
-    mesh_triangle_count_kernel<<<blocks, NJF_MESH_THREADS, 0, s>>>(a);
+    mesh_triangle_count_kernel<<<blocks, NJF_BLOCK_THREADS, 0, s>>>(a);
     if ((rc = launch_status())) return rc;
-    select_scan_kernel<<<1, NJF_SELECT_THREADS, 0, s>>>(workspace, blocks, triangle_count);
+    block_offsets_kernel<1><<<1, NJF_BLOCK_THREADS, 0, s>>>(workspace, blocks, triangle_count);
     if ((rc = launch_status())) return rc;
   }
   if ((phase & NJF_FIELD_MESH_EMIT) && max_triangles > 0) {
-    mesh_triangle_kernel<<<blocks, NJF_MESH_THREADS, 0, s>>>(a);
+    mesh_triangle_kernel<<<blocks, NJF_BLOCK_THREADS, 0, s>>>(a);
     if ((rc = launch_status())) return rc;
   }
   return NJF_OK;
@@ -7195,9 +7096,9 @@ extern "C" int njf_field_fuse(const NjfFieldGrid* grid, const NjfCameras* cams, 
   a.valid = valid;
   const int blocks = scenes * a.blocks_per_scene;  // <= G*N
   hipStream_t s = (hipStream_t)stream;
-  if (mode == NJF_FIELD_FUSE_MEAN) field_fuse_kernel<NJF_FIELD_FUSE_MEAN><<<blocks, NJF_FUSE_THREADS, 0, s>>>(a);
-  else if (mode == NJF_FIELD_FUSE_MIN) field_fuse_kernel<NJF_FIELD_FUSE_MIN><<<blocks, NJF_FUSE_THREADS, 0, s>>>(a);
-  else field_fuse_kernel<NJF_FIELD_FUSE_MAX><<<blocks, NJF_FUSE_THREADS, 0, s>>>(a);
+  if (mode == NJF_FIELD_FUSE_MEAN) field_fuse_kernel<NJF_FIELD_FUSE_MEAN><<<blocks, NJF_BLOCK_THREADS, 0, s>>>(a);
+  else if (mode == NJF_FIELD_FUSE_MIN) field_fuse_kernel<NJF_FIELD_FUSE_MIN><<<blocks, NJF_BLOCK_THREADS, 0, s>>>(a);
+  else field_fuse_kernel<NJF_FIELD_FUSE_MAX><<<blocks, NJF_BLOCK_THREADS, 0, s>>>(a);
   return launch_status();
 }
 
@@ -7339,14 +7240,14 @@ extern "C" int njf_field_band(const NjfFieldGrid* grid, int factor, int dilate, 
   a.block_counts = workspace;
   hipStream_t s = (hipStream_t)stream;
   const int blocks = (int)(((long long)a.total + NJF_FIELD_BAND_BLOCK - 1) / NJF_FIELD_BAND_BLOCK);
-  band_blocks_kernel<<<(batch * a.nb + NJF_BAND_THREADS - 1) / NJF_BAND_THREADS, NJF_BAND_THREADS, 0, s>>>(a);
+  band_blocks_kernel<<<(batch * a.nb + NJF_BLOCK_THREADS - 1) / NJF_BLOCK_THREADS, NJF_BLOCK_THREADS, 0, s>>>(a);
   if ((rc = launch_status())) return rc;
-  band_count_kernel<<<blocks, NJF_BAND_THREADS, 0, s>>>(a);
+  band_count_kernel<<<blocks, NJF_BLOCK_THREADS, 0, s>>>(a);
   if ((rc = launch_status())) return rc;
-  select_scan_kernel<<<1, NJF_SELECT_THREADS, 0, s>>>(workspace, blocks, out_count);
+  block_offsets_kernel<1><<<1, NJF_BLOCK_THREADS, 0, s>>>(workspace, blocks, out_count);
   if ((rc = launch_status())) return rc;
   if (out_capacity > 0) {
-    band_scatter_kernel<<<blocks, NJF_BAND_THREADS, 0, s>>>(a);
+    band_scatter_kernel<<<blocks, NJF_BLOCK_THREADS, 0, s>>>(a);
     if ((rc = launch_status())) return rc;
   }
   return NJF_OK;
@@ -7382,7 +7283,7 @@ extern "C" int njf_field_band_leaks(const NjfFieldGrid* grid, int batch, const u
   a.capacity = capacity;
   a.leaks = leaks;
   const int blocks = (int)(((long long)capacity + NJF_FIELD_BAND_BLOCK - 1) / NJF_FIELD_BAND_BLOCK);
-  band_leaks_kernel<<<blocks, NJF_BAND_THREADS, 0, s>>>(a);
+  band_leaks_kernel<<<blocks, NJF_BLOCK_THREADS, 0, s>>>(a);
   return launch_status();
 }
 
@@ -7795,7 +7696,7 @@ static int exclusive_scan_1024(int* counts, int* start, long long L, hipStream_t
   int rc;
   nn_scan_sums_kernel<<<blocks, NJF_NN_THREADS, 0, s>>>(counts, start, L);
   if ((rc = launch_status())) return rc;
-  nn_scan_blocks_kernel<<<1, NJF_NN_THREADS, 0, s>>>(start, L, blocks);
+  block_offsets_kernel<NJF_NN_SCAN_BLOCK><<<1, NJF_BLOCK_THREADS, 0, s>>>(start, blocks, start + L);
   if ((rc = launch_status())) return rc;
   nn_scan_cells_kernel<<<blocks, NJF_NN_THREADS, 0, s>>>(counts, start, L);
   return launch_status();
