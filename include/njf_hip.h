@@ -1066,6 +1066,52 @@ int njf_field_visible(const float* points, const int* count, const int* labels, 
                       float tolerance, float* depth, int* index, int* covered, int* seen, float* culled, int* visible, int* pixel,
                       float* z, int* workspace, long long workspace_words, int phases, void* stream);
 
+/* ---- posed rows against a depth frame by projection: occlusion, free space, window match (ABI v20, additive) ----
+ * For each of M problems: every row of a posed point set is projected into V depth cameras, classified against the ORGANISED cloud
+ * those cameras observed -- njf_field_depth_points' output, pixel by pixel --, and matched to the closest observed point in a window
+ * of pixels around its own.  The frame tells what njf_field_visible cannot know: what the SCENE hides (a row behind something else
+ * is not matched to that thing) and where the camera saw through (a row in free space).  No cell list, no build, no workspace.
+ * Inputs, all on the device: points [Mq,n,3] float, Mq = 1 or M; count int32 [1] or NULL (= n); labels int32 [n] or NULL; frame
+ * [Mo,V*H*W,3] float, Mo = 1 or M: row v*H*W + row*W + col is the point of pixel (row, col) of view v, three NaNs (anything not
+ * three finite numbers) where the pixel gave no point; k [V,3,3] and w2c [V,4,4] float, njf_field_visible's, shared by the problems.
+ * READ ROW, PROJECTION, INSIDE and the own pixel: njf_field_visible's, word for word -- the kernels call the same device function,
+ *        so the bits are the same.  pixel [M,V,n] int32 and z [M,V,n] float: njf_field_visible's, with its fills (-1; NaN when the row
+ *        is not read).
+ * STATE  of row i in view v, state [M,V,n] int32: NJF_FIELD_FRAME_OUTSIDE (0) when the row is not read or not inside; else, with
+ *        (fx, fy, fz) the frame's point at the own pixel, NJF_FIELD_FRAME_NO_RETURN (1) when these are not three finite numbers;
+ *        else with zo = fmaf(w[10], fz, fmaf(w[9], fy, fmaf(w[8], fx, w[11]))), the chain that gave zc from the row: IN_FRONT (2)
+ *        when zo - zc > tolerance * zo; else BEHIND (4) when zc - zo > tolerance * zo; else ON (3).  A float subtraction, a float
+ *        product and a comparison each, nothing contracted; a comparison with a NaN is false.
+ * SEARCHED in view v: the state is not OUTSIDE and not BEHIND; with NJF_FIELD_FRAME_KEEP_HIDDEN: not OUTSIDE.
+ * WINDOW the pixels (row + dr, col + dc), |dr|, |dc| <= reach, that lie in the image: clipped to [0, H) x [0, W) before any address
+ *        is formed, so j = v*H*W + r*W + c lies in [0, V*H*W).
+ * RESULT over the windows of all views in which the row is searched: the frame point of three finite coordinates with the smallest
+ *        d2 = (dx*dx + dy*dy) + dz*dz in float, dx = q.x - p.x and so on (njf_field_nearest's DISTANCE, in its order, no contraction),
+ *        ties to the LOWEST frame row j; accepted iff d2 <= (float)max_distance * (float)max_distance, a float product.
+ * Outputs: index [M,n] int32, distance2 [M,n] float, matched [M,n,3] float, found [M] int32: njf_field_nearest's, with its fills
+ *        (-1 / +inf / three NaNs) -- index is a row of the frame; states [M,5] int32: the (v, i) pairs of every state code, i < n
+ *        (they add up to V n).  Every element of every output is written.
+ * One lane per (m, i), which loops over the views and the window.  Integer atomics only: one per workgroup and counter (found and
+ * the five states), after a workgroup sum.  Two memsets (found, states) and one launch; one stream, no host read (capture-safe).
+ * `phases`: NJF_FIELD_FRAME_MATCH [| NJF_FIELD_FRAME_KEEP_HIDDEN].
+ * Returns, before the launch: NJF_E_NULL for a missing pointer (count and labels may be NULL); NJF_E_VALUE for unknown phases (a
+ * modifier without MATCH included), M outside [1, NJF_FIELD_POSE_MAX_COMMANDS], Mq or Mo not 1 or M, V outside [1,
+ * NJF_FIELD_VISIBLE_MAX_VIEWS], reach outside [0, NJF_FIELD_FRAME_MAX_REACH], near, tolerance or (float)max_distance negative or
+ * not finite; NJF_E_SHAPE for n < 0, H or W < 1, Mo * V * H * W >= 2^31 or M * V * n >= 2^31. */
+#define NJF_FIELD_FRAME_MAX_REACH 8
+#define NJF_FIELD_FRAME_OUTSIDE 0    /* state */
+#define NJF_FIELD_FRAME_NO_RETURN 1
+#define NJF_FIELD_FRAME_IN_FRONT 2
+#define NJF_FIELD_FRAME_ON 3
+#define NJF_FIELD_FRAME_BEHIND 4
+#define NJF_FIELD_FRAME_STATES 5
+#define NJF_FIELD_FRAME_MATCH 1      /* phases */
+#define NJF_FIELD_FRAME_KEEP_HIDDEN 2  /* with MATCH: BEHIND rows are searched too */
+int njf_field_frame(const float* points, const int* count, const int* labels, int num_queries, int n, int num_problems,
+                    const float* frame, int num_frames, const float* k, const float* w2c, int views, int height, int width,
+                    int reach, float near, float tolerance, double max_distance, int* pixel, float* z, int* state, int* index,
+                    float* distance2, float* matched, int* found, int* states, int phases, void* stream);
+
 /* ---- stand-alone sampler / compositing ops (API parity with the un-fused reference calls) -- */
 /* RaySamples.get_weights (ray_samplers.py:77-101): deltas, densities [N,S] -> weights [N,S]. */
 int njf_alpha_weights(const float* deltas, const float* densities, int rays, int samples, float* weights, void* stream);

@@ -8116,6 +8116,167 @@ extern "C" int njf_field_visible(const float* points, const int* count, const in
   return NJF_OK;
 }
 
+// ---- posed rows against a depth frame by projection (njf_field_frame) --------------------------------------------
+// A row is read and projected by vis_read and vis_project -- njf_field_visible's own, so pixel and z are its bits --, classified
+// against the frame's point at its own pixel, and matched to the closest frame point in the pixel window around it.  The frame is
+// njf_field_depth_points' organised cloud: the point of pixel (row, col) of view v is row v*H*W + row*W + col, NaN = none.
+struct FrmArgs {
+  VisArgs vis;         // points, count, labels, k, w2c, Mq, M, V, n, H, W, pixels, near, tolerance, pixel, z; the rest is not read
+  const float* frame;  // [Mo, V*H*W, 3]
+  int Mo, reach;
+  bool keep_hidden;
+  float max_d2;
+  int* state;          // [M,V,n]
+  int* index;          // [M,n]
+  float* distance2;    // [M,n]
+  int* matched;        // [M,n,3] (the bits of the floats)
+  int* found;          // [M]
+  int* states;         // [M,5]
+};
+
+#define NJF_FRM_THREADS 256
+#define NJF_FRM_WAVES (NJF_FRM_THREADS / 64)
+static_assert(NJF_FIELD_VISIBLE_MAX_VIEWS < 64, "a row's states are tallied in fields of 6 bits");
+
+// one lane per (m, i): it loops over the views and walks its window.  A workgroup lies in one problem: one atomic per counter
+// for its four waves.  (A wave per row, the lanes sharing the window, was built and measured: DESIGN.md section 26.)
+__global__ void __launch_bounds__(NJF_FRM_THREADS) frm_match_kernel(FrmArgs a) {
+  __shared__ int part[NJF_FIELD_FRAME_STATES + 1][NJF_FRM_WAVES];
+  const VisArgs& s = a.vis;
+  const long long i = (long long)blockIdx.x * NJF_FRM_THREADS + threadIdx.x;
+  const int m = blockIdx.y;
+  const bool live = i < s.n;
+  NnBest b{INFINITY, 0x7fffffff, 0, 0, 0};                 // (j < V H W < 2^31 - 1 beats it at d2 = +inf)
+  unsigned tally = 0;                                      // 6 bits per state: the views in which the row has it (<= 32)
+  const float* frame = a.frame + (long long)(a.Mo == 1 ? 0 : m) * s.V * s.pixels * 3;
+  if (live) {
+    float x = 0.f, y = 0.f, z = 0.f;
+    const bool read = vis_read(s, m, i, x, y, z);
+    for (int v = 0; v < s.V; ++v) {
+      int own = -1, st = NJF_FIELD_FRAME_OUTSIDE;
+      float zc = __int_as_float(0x7fc00000);
+      if (read) {
+        const VisPixel p = vis_project(s, v, x, y, z);
+        zc = p.z;
+        if (p.inside) {  // judged in float: 0 <= row < H, 0 <= col < W
+          const int row = (int)p.row, col = (int)p.col;
+          const int base = (int)(v * s.pixels);  // V H W < 2^31
+          own = row * s.W + col;
+          const float* f = frame + (long long)(base + own) * 3;
+          const float fx = f[0], fy = f[1], fz = f[2];
+          if (!nn_finite(fx, fy, fz)) {
+            st = NJF_FIELD_FRAME_NO_RETURN;
+          } else {
+            const float* w = s.w2c + v * 16;
+            const float zo = fmaf(w[10], fz, fmaf(w[9], fy, fmaf(w[8], fx, w[11])));
+            const float slack = __fmul_rn(s.tolerance, zo);
+            st = __fsub_rn(zo, zc) > slack ? NJF_FIELD_FRAME_IN_FRONT
+                                           : __fsub_rn(zc, zo) > slack ? NJF_FIELD_FRAME_BEHIND : NJF_FIELD_FRAME_ON;
+          }
+          if (st != NJF_FIELD_FRAME_BEHIND || a.keep_hidden) {
+            // the window, clipped to the image before any address is formed: base + r W + c lies in [0, V H W)
+            const int r0 = max(row - a.reach, 0), r1 = min(row + a.reach, s.H - 1);
+            const int c0 = max(col - a.reach, 0), c1 = min(col + a.reach, s.W - 1);
+            for (int r = r0; r <= r1; ++r)
+              for (int c = c0; c <= c1; ++c) {
+                const int j = base + r * s.W + c;
+                const float* q = frame + (long long)j * 3;
+                const float px = q[0], py = q[1], pz = q[2];
+                if (!nn_finite(px, py, pz)) continue;
+                const float dx = x - px, dy = y - py, dz = z - pz;
+                nn_take(b, (dx * dx + dy * dy) + dz * dz, j, __float_as_int(px), __float_as_int(py), __float_as_int(pz));
+              }
+          }
+        }
+      }
+      const long long o = ((long long)m * s.V + v) * s.n + i;
+      s.pixel[o] = own;
+      s.z[o] = zc;
+      a.state[o] = st;
+      tally += 1u << (6 * st);
+    }
+  }
+  const bool ok = live && b.j != 0x7fffffff && b.d2 <= a.max_d2;
+  if (live) {
+    const long long row = (long long)m * s.n + i;
+    const int nan = 0x7fc00000;
+    a.index[row] = ok ? b.j : -1;
+    a.distance2[row] = ok ? b.d2 : INFINITY;
+    a.matched[row * 3] = ok ? b.x : nan;
+    a.matched[row * 3 + 1] = ok ? b.y : nan;
+    a.matched[row * 3 + 2] = ok ? b.z : nan;
+  }
+#pragma unroll
+  for (int c = 0; c < NJF_FIELD_FRAME_STATES; ++c) {
+    const int t = block_sum((int)((tally >> (6 * c)) & 63u), part[c]);
+    if (threadIdx.x == 0 && t) atomicAdd(&a.states[m * NJF_FIELD_FRAME_STATES + c], t);
+  }
+  const int accepted = block_sum_waves(__popcll(__ballot(ok)), part[NJF_FIELD_FRAME_STATES]);
+  if (threadIdx.x == 0 && accepted) atomicAdd(&a.found[m], accepted);
+}
+
+extern "C" int njf_field_frame(const float* points, const int* count, const int* labels, int num_queries, int n, int num_problems,
+                               const float* frame, int num_frames, const float* k, const float* w2c, int views, int height,
+                               int width, int reach, float near, float tolerance, double max_distance, int* pixel, float* z,
+                               int* state, int* index, float* distance2, float* matched, int* found, int* states, int phases,
+                               void* stream) {
+  const bool known = phases == NJF_FIELD_FRAME_MATCH || phases == (NJF_FIELD_FRAME_MATCH | NJF_FIELD_FRAME_KEEP_HIDDEN);
+  if (!points || !frame || !k || !w2c || !pixel || !z || !state || !index || !distance2 || !matched || !found || !states)
+    return NJF_E_NULL;
+  if (!known) return NJF_E_VALUE;
+  if (num_problems < 1 || num_problems > NJF_FIELD_POSE_MAX_COMMANDS) return NJF_E_VALUE;
+  if (num_queries != 1 && num_queries != num_problems) return NJF_E_VALUE;
+  if (num_frames != 1 && num_frames != num_problems) return NJF_E_VALUE;
+  if (views < 1 || views > NJF_FIELD_VISIBLE_MAX_VIEWS) return NJF_E_VALUE;
+  if (reach < 0 || reach > NJF_FIELD_FRAME_MAX_REACH) return NJF_E_VALUE;
+  if (!(near >= 0.0f) || !(near < INFINITY) || !(tolerance >= 0.0f) || !(tolerance < INFINITY)) return NJF_E_VALUE;
+  const float limit = (float)max_distance;
+  if (!(limit >= 0.0f) || !(limit < INFINITY)) return NJF_E_VALUE;
+  if (n < 0 || height < 1 || width < 1) return NJF_E_SHAPE;
+  if ((long long)height * width >= (1LL << 31) || (long long)num_frames * views * height * width >= (1LL << 31) ||
+      (long long)num_problems * views * n >= (1LL << 31))
+    return NJF_E_SHAPE;
+  FrmArgs a{};
+  a.vis.points = points;
+  a.vis.count = count;
+  a.vis.labels = labels;
+  a.vis.k = k;
+  a.vis.w2c = w2c;
+  a.vis.Mq = num_queries;
+  a.vis.M = num_problems;
+  a.vis.V = views;
+  a.vis.n = n;
+  a.vis.H = height;
+  a.vis.W = width;
+  a.vis.pixels = (long long)height * width;
+  a.vis.near = near;
+  a.vis.tolerance = tolerance;
+  a.vis.pixel = pixel;
+  a.vis.z = z;
+  a.frame = frame;
+  a.Mo = num_frames;
+  a.reach = reach;
+  a.keep_hidden = (phases & NJF_FIELD_FRAME_KEEP_HIDDEN) != 0;
+  a.max_d2 = limit * limit;
+  a.state = state;
+  a.index = index;
+  a.distance2 = distance2;
+  a.matched = (int*)matched;
+  a.found = found;
+  a.states = states;
+  hipStream_t s = (hipStream_t)stream;
+  hipError_t e;
+  if ((e = hipMemsetAsync(found, 0, (size_t)num_problems * sizeof(int), s)) != hipSuccess) return (int)e;
+  if ((e = hipMemsetAsync(states, 0, (size_t)num_problems * NJF_FIELD_FRAME_STATES * sizeof(int), s)) != hipSuccess) return (int)e;
+  if (n > 0) {
+    frm_match_kernel<<<dim3((unsigned)(((long long)n + NJF_FRM_THREADS - 1) / NJF_FRM_THREADS), (unsigned)num_problems), NJF_FRM_THREADS, 0,
+                       s>>>(a);
+    int rc;
+    if ((rc = launch_status())) return rc;
+  }
+  return NJF_OK;
+}
+
 extern "C" int njf_resnetfc_backward(const float* d_out, int d_out_dim, const float* activations, const float* w_backward,
                                      int points, float* deltas, float* colsum_partial, const unsigned* masks, int precision,
                                      const float* d_out_absmax, void* deltas16, void* stream) {

@@ -1406,9 +1406,10 @@ class FieldVisibility:
     z: torch.Tensor           # [M, V, n] fp32: the row's camera-space z, NaN for a row that is not read
 
 
-def _check_view(name: str, view, like: torch.Tensor, of: str, m: int, n: int):
+def _check_view(name: str, view, like: torch.Tensor, of: str, m: int, n: int, splat: bool = True):
     """The checks of a ``FieldView`` against ``m`` problems of ``n`` rows on the device of ``like`` (called ``of``);
-    ``(V, near, tolerance)`` with the two numbers as the kernel's floats."""
+    ``(V, near, tolerance)`` with the two numbers as the kernel's floats.  Without ``splat`` the two fields of the z-buffer,
+    ``footprint`` and ``tolerance``, are not read: ``(V, near)``."""
     if not isinstance(view, FieldView):
         raise ValueError(f"{name}: the view must be a FieldView")
     k, c2w = view.intrinsics, view.cam2world
@@ -1422,10 +1423,10 @@ def _check_view(name: str, view, like: torch.Tensor, of: str, m: int, n: int):
         if isinstance(value, bool) or not isinstance(value, int) or value < 1:
             raise ValueError(f"{name}: {what} must be an integer >= 1 (got {value})")
     f = view.footprint
-    if isinstance(f, bool) or not isinstance(f, int) or not 0 <= f <= hip.FIELD_VISIBLE_MAX_FOOTPRINT:
+    if splat and (isinstance(f, bool) or not isinstance(f, int) or not 0 <= f <= hip.FIELD_VISIBLE_MAX_FOOTPRINT):
         raise ValueError(f"{name}: footprint must be an integer in [0, {hip.FIELD_VISIBLE_MAX_FOOTPRINT}] (got {f})")
     floats = []
-    for what, value in (("near", view.near), ("tolerance", view.tolerance)):
+    for what, value in (("near", view.near), ("tolerance", view.tolerance))[:2 if splat else 1]:
         if isinstance(value, bool) or not isinstance(value, (int, float)) or math.isnan(value):
             raise ValueError(f"{name}: {what} must be a finite number >= 0 (got {value})")
         with np.errstate(over="ignore"):
@@ -1440,7 +1441,7 @@ def _check_view(name: str, view, like: torch.Tensor, of: str, m: int, n: int):
     for what, t in (("intrinsics", k), ("cam2world", c2w)):
         if t.device != like.device:
             raise ValueError(f"{name}: {what} must live on the device of {of}")
-    return v, floats[0], floats[1]
+    return (v, *floats)
 
 
 class _Visibility:
@@ -1889,6 +1890,216 @@ def _cloud_cells(cloud: FieldPointCloud, name: str) -> FieldGrid:
     upper_corner = tuple(o + s * (d - 1) for o, s, d in zip(grid.origin, grid.step, grid.dims))
     return cell_grid(tuple(min(o, u) for o, u in zip(grid.origin, upper_corner)),
                      tuple(max(o, u) for o, u in zip(grid.origin, upper_corner)), max(abs(s) for s in grid.step))
+
+
+# ---- posed rows against a depth frame by projection: occlusion, free space, window match --------------------
+@dataclass
+class FieldFrameMatches(FieldNearest):
+    """``FieldNearest`` of a match by projection into an organised depth frame (``frame_matches``; include/njf_hip.h:
+    njf_field_frame): ``index`` is a row ``v * H * W + row * W + col`` of the frame.  ``state[m, v, i]`` says how row i agrees with
+    the frame at its own pixel in view v -- 0 outside the image (or not read), 1 no return there, 2 in front of what the camera
+    saw (free space), 3 on it, 4 behind it (hidden by the scene) --, ``states[m, c]`` counts the (v, i) pairs of code c."""
+
+    state: torch.Tensor       # [M, V, n] int32: hip.FIELD_FRAME_OUTSIDE .. FIELD_FRAME_BEHIND
+    states: torch.Tensor      # [M, 5] int32: the (v, i) pairs per code
+    pixel: torch.Tensor       # [M, V, n] int32: FieldVisibility.pixel
+    z: torch.Tensor           # [M, V, n] fp32: FieldVisibility.z
+
+    def explained(self) -> torch.Tensor:
+        """``[M]`` float64: ON / (ON + IN_FRONT + NO_RETURN) of ``states`` -- the share of the rows the cameras should see that
+        sit where they saw a surface; NaN when no row is in an image and not hidden."""
+        s = self.states.to(torch.float64)
+        on = s[:, hip.FIELD_FRAME_ON]
+        return on / (on + s[:, hip.FIELD_FRAME_IN_FRONT] + s[:, hip.FIELD_FRAME_NO_RETURN])
+
+
+@dataclass
+class FieldFrameRegistration(FieldVisibleRegistration):
+    """``FieldVisibleRegistration`` of a registration to an organised depth frame (``register_commands_frame``): ``matches`` is a
+    ``FieldFrameMatches``, ``states_history`` holds its ``states`` of every round."""
+
+    states_history: torch.Tensor     # [R, M, 5] int32
+
+
+def _check_frame(name: str, frame, view, max_distance, reach, tolerance, keep_hidden, count, labels, n: int, mq: int, like: torch.Tensor,
+                 of: str, m_other: int = 1):
+    """The checks of the frame, the cameras and the window search that ``frame_matches`` and the registrations to a frame share;
+    ``like`` (called ``of``) rules the device.  ``(frame [Mo, V H W, 3], M, V, near, tolerance, count)``, the numbers as the
+    kernel's floats."""
+    if not torch.is_tensor(frame) or frame.dtype != torch.float32 or frame.dim() not in (2, 3) or frame.shape[-1] != 3 \
+            or frame.shape[-2] < 1:
+        raise ValueError(f"{name}: frame must be fp32 [T, 3] or [Mo, T, 3] with T >= 1")
+    frame = frame if frame.dim() == 3 else frame[None]
+    mo, t = frame.shape[:2]
+    m = max(mo, mq, m_other)
+    if not 1 <= m <= hip.FIELD_POSE_MAX_COMMANDS or mo < 1 or mq < 1:
+        raise ValueError(f"{name}: 1 to {hip.FIELD_POSE_MAX_COMMANDS} problems (got {min(mo, mq, m)} and {m})")
+    if mo not in (1, m) or mq not in (1, m):
+        raise ValueError(f"{name}: frame and points hold one set or one per problem (got {mo} and {mq} for {m} problems)")
+    v, near = _check_view(name, view, like, of, m, n, splat=False)
+    if v * view.height * view.width != t:
+        raise ValueError(f"{name}: frame must hold V * height * width = {v * view.height * view.width} rows (got {t})")
+    if isinstance(max_distance, bool) or not isinstance(max_distance, (int, float)) or math.isnan(max_distance):
+        raise ValueError(f"{name}: max_distance must be a finite number >= 0 (got {max_distance})")
+    with np.errstate(over="ignore"):
+        if not 0.0 <= float(np.float32(max_distance)) < math.inf:              # the kernel's float
+            raise ValueError(f"{name}: max_distance must be a finite number >= 0 (got {max_distance})")
+    if isinstance(reach, bool) or not isinstance(reach, int) or not 0 <= reach <= hip.FIELD_FRAME_MAX_REACH:
+        raise ValueError(f"{name}: reach must be an integer in [0, {hip.FIELD_FRAME_MAX_REACH}] (got {reach})")
+    if isinstance(tolerance, bool) or not isinstance(tolerance, (int, float)) or math.isnan(tolerance):
+        raise ValueError(f"{name}: tolerance must be a finite number >= 0 (got {tolerance})")
+    with np.errstate(over="ignore"):
+        tolerance32 = float(np.float32(tolerance))
+    if not 0.0 <= tolerance32 < math.inf:
+        raise ValueError(f"{name}: tolerance must be a finite number >= 0 (got {tolerance})")
+    if not isinstance(keep_hidden, bool):
+        raise ValueError(f"{name}: keep_hidden must be a bool (got {keep_hidden})")
+    count = _one_int32(name, "count", count, like)
+    if labels is not None and (not torch.is_tensor(labels) or labels.dtype != torch.int32 or tuple(labels.shape) != (n,)):
+        raise ValueError(f"{name}: labels must be int32 [{n}]")
+    for what, value in (("frame", frame), ("labels", labels)):
+        if value is not None and value.device != like.device:
+            raise ValueError(f"{name}: {what} must live on the device of {of}")
+    return frame, m, v, near, tolerance32, count
+
+
+class _FrameMatch:
+    """The launch of ``frame_matches`` for ``m`` problems of ``n`` rows: the world-to-camera matrices (``hip.inverse``) are made
+    once, ``__call__`` takes the points ``[Mq, n, 3]`` of one round."""
+
+    def __init__(self, frame: torch.Tensor, view: FieldView, v: int, near: float, tolerance: float, max_distance: float, reach: int,
+                 keep_hidden: bool, m: int, n: int, dev):
+        self.frame, self.k, self.w2c = frame.contiguous(), view.intrinsics.contiguous(), hip.inverse(view.cam2world).contiguous()
+        self.shape, self.m, self.n, self.dev = (v, view.height, view.width), m, n, dev
+        self.kw = dict(reach=reach, near=near, tolerance=tolerance,
+                       phase=hip.FIELD_FRAME_MATCH | (hip.FIELD_FRAME_KEEP_HIDDEN if keep_hidden else 0))
+        self.max_distance = max_distance
+
+    def __call__(self, points: torch.Tensor, count, labels) -> FieldFrameMatches:
+        (v, h, w), m, n = self.shape, self.m, self.n
+        i32, f32 = dict(dtype=torch.int32, device=self.dev), dict(dtype=torch.float32, device=self.dev)
+        out = FieldFrameMatches(index=torch.empty(m, n, **i32), distance2=torch.empty(m, n, **f32), matched=torch.empty(m, n, 3, **f32),
+                                found=torch.empty(m, **i32), state=torch.empty(m, v, n, **i32),
+                                states=torch.empty(m, hip.FIELD_FRAME_STATES, **i32), pixel=torch.empty(m, v, n, **i32),
+                                z=torch.empty(m, v, n, **f32))
+        hip.field_frame(points, self.frame, self.k, self.w2c, h, w, self.max_distance, {f: getattr(out, f) for f in out.__dataclass_fields__},
+                        m, count=count, labels=labels, **self.kw)
+        return out
+
+
+def frame_matches(points: torch.Tensor, frame: torch.Tensor, view: FieldView, max_distance: float, *, reach: int = 4,
+                  tolerance: float = 0.02, keep_hidden: bool = False, labels: Optional[torch.Tensor] = None,
+                  count: Optional[torch.Tensor] = None) -> FieldFrameMatches:
+    """The rows of ``points`` ``[n, 3]`` or ``[Mq, n, 3]`` (fp32) against the depth frame the cameras of ``view`` made (DESIGN.md
+    section 26): ``frame`` ``[V H W, 3]`` or ``[Mo, V H W, 3]`` (fp32) is the ORGANISED cloud of ``depth_points`` for the V views of
+    a scene -- row ``v H W + row W + col`` is the point of that pixel, NaN where it gave none.  M = max(Mq, Mo) problems, each of
+    Mq and Mo 1 or M.  A row (read as ``visible_rows`` reads it, and projected by the same code: ``pixel`` and ``z`` are its bits)
+    is classified in every view against the frame's point at its own pixel, whose camera-space z is ``zo``: no return there, in
+    front of it (``zo - z > tolerance * zo``: the row floats where the camera saw through), behind it (``z - zo > tolerance *
+    zo``: the scene hides it) or on it.  A row is then matched to the closest frame point -- ``nearest_points``' distance and tie
+    rule -- among the pixels within ``reach`` (0 to 8) of its own, over all views in which it is inside the image and, unless
+    ``keep_hidden``, not behind the frame; accepted within ``max_distance``.  The window must cover the displacement between the
+    posed row and its counterpart, in pixels: a row that moved further finds a worse point or none.  ``view.footprint`` and
+    ``view.tolerance`` are not read.  No cell list, no workspace, integer atomics only, no host read: equal bytes from call to
+    call, capturable."""
+    name = "frame_matches"
+    if not torch.is_tensor(points) or points.dtype != torch.float32 or points.dim() not in (2, 3) or points.shape[-1] != 3:
+        raise ValueError(f"{name}: points must be fp32 [n, 3] or [Mq, n, 3]")
+    points = points if points.dim() == 3 else points[None]
+    mq, n = points.shape[:2]
+    frame, m, v, near, tolerance, count = _check_frame(name, frame, view, max_distance, reach, tolerance, keep_hidden, count, labels, n,
+                                                       mq, points, "points")
+    if points.device.type != "cuda":
+        raise ValueError(f"{name}: the tensors must live on the GPU; there is no CPU path")
+    run = _FrameMatch(frame, view, v, near, tolerance, max_distance, reach, keep_hidden, m, n, points.device)
+    return run(points.contiguous(), count, None if labels is None else labels.contiguous())
+
+
+def register_commands_frame(twists: FieldTwists, xyz: torch.Tensor, labels: torch.Tensor, frame: torch.Tensor, max_distance: float,
+                            view: FieldView, *, observed_information: Optional[torch.Tensor] = None, reach: int = 4,
+                            tolerance: float = 0.02, keep_hidden: bool = False, joints: Optional[FieldJoints] = None, tree=None,
+                            count: Optional[torch.Tensor] = None, weights: Optional[torch.Tensor] = None,
+                            init: Optional[torch.Tensor] = None, lower=None, upper=None, reg: float = 0.0, rounds: int = 8,
+                            iterations: int = 3, damping: float = 1e-3) -> FieldFrameRegistration:
+    """``register_commands_visible`` to the depth frame itself instead of to its points as an unordered set (DESIGN.md section
+    26): ``frame`` is ``frame_matches``' organised cloud of the cameras of ``view``.  Every round goes pose, ``visible_rows`` of the
+    posed rows (what the BODY hides; ``view.footprint`` and ``view.tolerance``), ``frame_matches`` on its ``culled`` rows (what the
+    SCENE hides, with ``reach``, ``tolerance`` and ``keep_hidden``) instead of the cell-list query, solve.  A row behind a foreign
+    object is free instead of being pulled onto that object.  With ``observed_information`` (fp32 ``[V H W, 6]`` or ``[Mo, V H W,
+    6]``, indexed by frame row) the loop is ``register_commands_metric``'s.  There is no lattice, no build and no workspace
+    beyond the z-buffer's.  The result adds ``states_history``; ``matches.explained()`` of the last round says how much of what
+    the cameras should see of the fit they did see.  No host read: capturable after one eager call."""
+    name = "register_commands_frame"
+    k, a_dim = _check_twists(name, twists)
+    n = _check_points(name, xyz, labels, None, a_dim)
+    if isinstance(rounds, bool) or not isinstance(rounds, int) or not 1 <= rounds <= 1000:
+        raise ValueError(f"{name}: rounds must be an integer in [1, 1000] (got {rounds})")
+    starts = init.shape[0] if torch.is_tensor(init) and init.dim() == 2 else 1
+    frame, m, v, near, tolerance32, count = _check_frame(name, frame, view, max_distance, reach, tolerance, keep_hidden, count, None, n, 1,
+                                                         xyz, "xyz", m_other=max(starts, 1))
+    cull = _check_view(name, view, xyz, "xyz", m, n)
+    mo, t = frame.shape[:2]
+    metric = observed_information is not None
+    if metric:
+        if not torch.is_tensor(observed_information) or observed_information.dtype != torch.float32 \
+                or tuple(observed_information.shape) not in ((t, 6), (mo, t, 6)):
+            raise ValueError(f"{name}: observed_information must be fp32 [{t}, 6] or [{mo}, {t}, 6]")
+        if observed_information.device != xyz.device:
+            raise ValueError(f"{name}: observed_information must live on the device of xyz")
+    parts_count, links, count, lower_box, upper_box = _check_solver(name, twists, xyz, labels, m, n, k, a_dim, xyz, "xyz", joints, tree,
+                                                                    weights, count, init, lower, upper, reg, iterations, damping)
+    if xyz.device.type != "cuda":
+        raise ValueError(f"{name}: the tensors must live on the GPU; there is no CPU path")
+    dev = xyz.device
+    u = torch.zeros(m, a_dim, dtype=torch.float32, device=dev) if init is None else init
+    if lower_box is not None:
+        u = torch.maximum(u, lower_box)
+    if upper_box is not None:
+        u = torch.minimum(u, upper_box)
+    base = _registration_outputs(cull, rounds, m, a_dim, dev)
+    out = FieldFrameRegistration(**{f: getattr(base, f) for f in base.__dataclass_fields__},
+                                 states_history=torch.empty(rounds, m, hip.FIELD_FRAME_STATES, dtype=torch.int32, device=dev))
+    labels_c = labels.contiguous()
+    cull = _Visibility(view, *cull, m, n, dev)
+    match = _FrameMatch(frame, view, v, near, tolerance32, max_distance, reach, keep_hidden, m, n, dev)
+    source = observed_information.reshape(-1, t, 6).expand(m, t, 6) if metric else None
+    solver = dict(joints=joints, tree=tree, weights=weights, count=count, lower=lower, upper=upper, reg=reg, iterations=iterations,
+                  damping=damping)
+    for r in range(rounds):
+        _, posed = _pose(name, twists, u, joints, tree, points=(xyz, labels, count, None))
+        seen = cull(posed, count, labels_c)
+        near_r = match(seen.culled, count, labels_c)
+        if metric:
+            information = torch.gather(source, 1, near_r.index.clamp_min(0).long()[:, :, None].expand(m, n, 6))
+            fit = solve_commands_metric(twists, xyz, labels, near_r.matched, information, init=u, **solver)
+        else:
+            fit = solve_commands(twists, xyz, labels, near_r.matched, init=u, **solver)
+        out.commands_history[r].copy_(fit.commands)
+        out.cost_history[r].copy_(fit.cost)
+        out.found_history[r].copy_(near_r.found)
+        out.visible_history[r].copy_(seen.visible)
+        out.states_history[r].copy_(near_r.states)
+        out.fit, out.matches, u = fit, near_r, fit.commands
+    return out
+
+
+def cloud_registration_frame(cloud: FieldPointCloud, labels: torch.Tensor, twists: FieldTwists, frame: torch.Tensor, max_distance: float,
+                             view: FieldView, *, observed_information: Optional[torch.Tensor] = None, reach: int = 4,
+                             tolerance: float = 0.02, keep_hidden: bool = False, joints: Optional[FieldJoints] = None, tree=None,
+                             weights: Optional[torch.Tensor] = None, init: Optional[torch.Tensor] = None, lower=None, upper=None,
+                             reg: float = 0.0, rounds: int = 8, iterations: int = 3, damping: float = 1e-3) -> FieldFrameRegistration:
+    """``register_commands_frame`` on the rows of an extracted cloud, as ``cloud_registration`` is ``register_commands`` on them:
+    ``cloud.xyz`` and ``cloud.count`` with ``labels`` ``[n]`` int32, the per-row result of ``cloud_components``."""
+    name = "cloud_registration_frame"
+    if not isinstance(cloud, FieldPointCloud):
+        raise ValueError(f"{name}: cloud must be a FieldPointCloud")
+    try:
+        return register_commands_frame(twists, cloud.xyz, labels, frame, max_distance, view, observed_information=observed_information,
+                                       reach=reach, tolerance=tolerance, keep_hidden=keep_hidden, joints=joints, tree=tree,
+                                       count=cloud.count, weights=weights, init=init, lower=lower, upper=upper, reg=reg, rounds=rounds,
+                                       iterations=iterations, damping=damping)
+    except ValueError as err:
+        raise ValueError(str(err).replace("register_commands_frame:", f"{name}:", 1)) from None
 
 
 # ---- coarse-to-fine band (DESIGN.md section 14) ----------------------------------------------------------------------------------

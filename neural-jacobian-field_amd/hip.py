@@ -189,6 +189,8 @@ _SIGNATURES = {
                           C.c_longlong, C.c_int, _vp], C.c_int),
     "njf_field_visible": ([_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
                            C.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_longlong, C.c_int, _vp], C.c_int),
+    "njf_field_frame": ([_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
+                         C.c_float, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp], C.c_int),
     "njf_pack_resnetfc_backward": ([C.POINTER(ResnetFcWeights), _vp, C.c_int, _vp], C.c_int),
     "njf_resnetfc_backward": ([_vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp], C.c_int),
     "njf_pack_transformer_backward": ([_vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, _vp], C.c_int),
@@ -1497,6 +1499,46 @@ def field_visible(points: torch.Tensor, k: torch.Tensor, w2c: torch.Tensor, heig
             float(tolerance), o("depth", _ptr), o("index", _int32_ptr), o("covered", _int32_ptr), o("seen", _int32_ptr),
             o("culled", _ptr), o("visible", _int32_ptr), o("pixel", _int32_ptr), o("z", _ptr),
             _int32_ptr(workspace, "workspace"), 0 if workspace is None else int(workspace.numel()), int(phase))
+
+
+# ---- posed rows against a depth frame by projection (include/njf_hip.h: njf_field_frame) ----------------------------------------------
+FIELD_FRAME_MATCH = 1                                  # NJF_FIELD_FRAME_MATCH: two memsets and one launch
+FIELD_FRAME_KEEP_HIDDEN = 2                            # NJF_FIELD_FRAME_KEEP_HIDDEN: BEHIND rows are searched too
+FIELD_FRAME_MAX_REACH = 8                              # NJF_FIELD_FRAME_MAX_REACH
+FIELD_FRAME_STATE_NAMES = ("outside", "no_return", "in_front", "on", "behind")   # NJF_FIELD_FRAME_OUTSIDE .. _BEHIND = 0 .. 4
+FIELD_FRAME_OUTSIDE, FIELD_FRAME_NO_RETURN, FIELD_FRAME_IN_FRONT, FIELD_FRAME_ON, FIELD_FRAME_BEHIND = range(5)
+FIELD_FRAME_STATES = 5                                 # NJF_FIELD_FRAME_STATES
+FIELD_FRAME_OUTPUTS = (("pixel", torch.int32), ("z", torch.float32), ("state", torch.int32), ("index", torch.int32),
+                       ("distance2", torch.float32), ("matched", torch.float32), ("found", torch.int32), ("states", torch.int32))
+
+
+def field_frame(points: torch.Tensor, frame: torch.Tensor, k: torch.Tensor, w2c: torch.Tensor, height: int, width: int,
+                max_distance: float, out: dict, problems: int, count=None, labels=None, reach: int = 4, near: float = 0.0,
+                tolerance: float = 0.02, phase: int = FIELD_FRAME_MATCH) -> None:
+    """njf_field_frame on ``points`` [Mq, n, 3] and the organised cloud ``frame`` [Mo, V * H * W, 3] (fp32) for ``problems`` = M
+    problems, Mq and Mo each 1 or M, through the cameras ``k`` [V, 3, 3] and ``w2c`` [V, 4, 4] (fp32) of images of ``height`` x
+    ``width``.  ``count`` [1], ``labels`` [n]: int32 or None.  ``out`` maps pixel, z, state [M, V, n], index, distance2 [M, n],
+    matched [M, n, 3], found [M] and states [M, 5] (FIELD_FRAME_OUTPUTS holds the element types) to tensors of their shapes.
+    ``phase``: FIELD_FRAME_MATCH [+ FIELD_FRAME_KEEP_HIDDEN]."""
+    mq, n = _cloud_shape("field_frame", "points", "Mq, n", points)
+    mo, t = _cloud_shape("field_frame", "frame", "Mo, V * H * W", frame)
+    m, h, w = int(problems), int(height), int(width)
+    if k.dim() != 3 or tuple(k.shape[1:]) != (3, 3) or w2c.dim() != 3 or tuple(w2c.shape) != (k.shape[0], 4, 4):
+        raise ValueError("njf_hip: field_frame needs k [V, 3, 3] and w2c [V, 4, 4]")
+    v = int(k.shape[0])
+    if t != v * h * w:
+        raise ValueError(f"njf_hip: field_frame needs frame [Mo, {v * h * w}, 3] for {v} views of {h} x {w} (got {t} rows)")
+    if count is not None and count.numel() != 1:
+        raise ValueError("njf_hip: field_frame count must hold one int32")
+    if labels is not None and labels.numel() != n:
+        raise ValueError("njf_hip: field_frame needs labels [n]")
+    _check_output_sizes("field_frame", out, dict(pixel=m * v * n, z=m * v * n, state=m * v * n, index=m * n, distance2=m * n,
+                                                 matched=3 * m * n, found=m, states=m * FIELD_FRAME_STATES))
+    _launch("njf_field_frame", load_library().njf_field_frame, _ptr(points, "points"), _int32_ptr(count, "count"),
+            _int32_ptr(labels, "labels"), mq, n, m, _ptr(frame, "frame"), mo, _ptr(k, "k"), _ptr(w2c, "w2c"), v, h, w, int(reach),
+            float(near), float(tolerance), float(max_distance), _int32_ptr(out["pixel"], "pixel"), _ptr(out["z"], "z"),
+            _int32_ptr(out["state"], "state"), _int32_ptr(out["index"], "index"), _ptr(out["distance2"], "distance2"),
+            _ptr(out["matched"], "matched"), _int32_ptr(out["found"], "found"), _int32_ptr(out["states"], "states"), int(phase))
 
 
 def solve_action(mean_position, jacobian, projection, target_flow, visible_mask, init_action, iterations: int,
