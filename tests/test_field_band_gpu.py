@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+import block_offsets_cases as K
 import field_band_restatement as R
 import field_components_restatement as RC
 
@@ -76,6 +77,22 @@ def test_band_from_values_equals_the_restatement(dev, dims, k, d):
     _assert_equals_restatement(dev, dims, k, values, 0.9, None, d)
     _assert_equals_restatement(dev, dims, k, values, 0.85, valid, d)
     _assert_equals_restatement(dev, dims, k, values, 0.85, valid.astype(np.uint8), d)
+
+
+@pytest.mark.parametrize("dims,batch,kind,d", K.BAND_CASES)
+def test_band_past_256_workgroups_equals_the_restatement(dev, dims, batch, kind, d):
+    """The band's list with two sums per thread of the one-workgroup scan of its offsets: 302 workgroups at 65 x 65 x 73, 305 at
+    two elements of 49 x 49 x 65 (k = 8).  "late": hits only on the last coarse x layer of the last element -- every offset in
+    front of workgroup 256 is zero, the first that is not belongs to a run past it (tests/test_block_primitives_cpu.py)."""
+    values = K.band_values(dims, batch, kind)
+    band, _, in_band = _assert_equals_restatement(dev, dims, K.BAND_FACTOR, values, K.BAND_THRESHOLD, None, d)
+    nodes = batch * dims[0] * dims[1] * dims[2]
+    blocks = K.workgroups(nodes, K.BAND_BLOCK)
+    filled = np.flatnonzero(K.block_sums(in_band.reshape(-1), K.BAND_BLOCK))
+    print(f"workgroups {blocks}, per {K.per_thread(blocks)}, survivors {int(band.count.item())} of {nodes}, in {filled.size} workgroups "
+          f"({filled[0]} .. {filled[-1]})")
+    assert blocks > K.THREADS and 0 < int(band.count.item()) < nodes
+    assert kind != "late" or filled[0] >= K.THREADS
 
 
 @pytest.mark.parametrize("share", [0.05, 0.5])

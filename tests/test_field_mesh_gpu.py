@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+import block_offsets_cases as K
 import field_mesh_restatement as R
 
 pytestmark = pytest.mark.gpu
@@ -93,6 +94,25 @@ def test_mesh_from_values_equals_the_restatement(dev, kind, dims, batch):
     if kind != "random":        # closed surfaces strictly inside the grid: the checks run on the GPU output itself
         per_body = 2 if kind == "sphere" else 0
         R.assert_closed_oriented(got["vertices"], got["triangles"], per_body * batch)
+
+
+@pytest.mark.parametrize("dims,batch,kind", K.MESH_CASES)
+def test_mesh_past_256_counting_blocks_equals_the_restatement(dev, dims, batch, kind):
+    """Both scans of the mesh (nodes -> vertex offsets, cells -> triangle offsets) with two sums per thread of the one-workgroup
+    scan: 281 and 269 workgroups at 67 x 66 x 65, 286 and 270 at two elements of 53 x 52 x 53.  The random field has vertices
+    in all workgroups but one, the sphere leaves more than fifty empty at either end (tests/test_block_primitives_cpu.py)."""
+    from neural_jacobian_field_amd.field_volume import mesh_from_values
+    grid = _grid(dims)
+    values = _analytic(grid, kind, batch)
+    got = _numpy(mesh_from_values(grid, torch.from_numpy(values).to(dev), 0.0))
+    ref = _assert_equals_restatement(got, grid, values, 0.0)
+    for what, block_of, total in (("vertices", ref["vertex_node"], batch * grid.num_nodes),
+                                  ("triangles", ref["triangle_cell"], batch * (dims[0] - 1) * (dims[1] - 1) * (dims[2] - 1))):
+        blocks = K.workgroups(total, K.MESH_BLOCK)
+        filled = np.unique(block_of // K.MESH_BLOCK)
+        print(f"{what}: workgroups {blocks}, per {K.per_thread(blocks)}, survivors {block_of.shape[0]}, in {filled.size} workgroups "
+              f"({filled[0]} .. {filled[-1]})")
+        assert blocks > K.THREADS and block_of.shape[0] > 0
 
 
 def test_masked_form_and_special_values(dev):

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+import block_offsets_cases as K
 import field_commands_restatement as F
 import field_joints_restatement as J
 import field_nearest_restatement as N
@@ -126,6 +127,23 @@ def test_random_clouds_inside_and_outside_the_box(dev, n, t, dims):
     queries[rng.random((2, n)) < 0.03, 2] = np.nan
     for reach in (0.9 * cell, 3.5 * cell):
         _check(dev, observed, queries, _cells(origin, cell, dims), reach, what=f"n {n} T {t} dims {dims} reach {reach:.3f}")
+
+
+@pytest.mark.parametrize("dims,clouds", K.CELL_CASES)
+def test_a_cell_list_past_256_scan_blocks(dev, dims, clouds):
+    """The list's build with two sums per thread of the one-workgroup scan of its block sums (281 scan blocks of one cloud, 286 of
+    three); the first queries sit at the centres of the cells at the seams of that scan, each with two points of its own
+    (tests/block_offsets_cases.py, checked by tests/test_block_primitives_cpu.py)."""
+    case = K.cell_case(dims, clouds)
+    got, want = _check(dev, case["points"], case["queries"], _cells(K.CELL_ORIGIN, K.CELL_SIZE, dims), K.CELL_REACH,
+                       what=f"cell list {dims} x {clouds}")
+    blocks = K.workgroups(case["positions"], K.SCAN_BLOCK)
+    print(f"scan blocks {blocks}, per {K.per_thread(blocks)}, found {want['found'].tolist()} of {K.CELL_QUERIES}")
+    assert blocks > K.THREADS and want["found"].min() > K.CELL_QUERIES // 2
+    crafted = {(cloud, row) for cloud, row, _ in case["crafted"]}
+    for cloud in range(clouds):
+        seams = sum(p // case["cells"] == cloud for p in K.crafted_positions(dims, clouds))
+        assert all((cloud, int(j)) in crafted for j in want["index"][cloud, :seams])
 
 
 def test_one_crowded_cell_and_ties(dev):

@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 import torch
 
+import block_offsets_cases as K
 import field_joints_restatement as J
 import field_normals_restatement as NS
 import field_voxels_restatement as S
@@ -123,6 +124,24 @@ def test_every_output_equals_the_restatement(dev, dims):
     print(f"{dims}: kept cells per case {kept}")
     assert kept[-1] == 1 if dims == (1, 1, 1) else kept[-1] >= 64
     _check(dev, _cloud(rng, 3, 257, cells), cells, min_points=2, what=f"{dims} min_points 2")
+
+
+@pytest.mark.parametrize("dims,clouds", K.CELL_CASES)
+def test_a_cell_list_past_256_scan_blocks(dev, dims, clouds):
+    """The stride-1,024 instance of the one-workgroup scan with two sums per thread, in the list's build and again over the kept
+    flags: 287,430 positions (281 scan blocks) of one cloud, 291,870 (286) of three, whose boundaries fall inside a thread's
+    run.  Two points each around the centres of the cells at the ends of the first scan blocks, on both sides of block 256, on
+    both sides of the seam between two clouds and in the last position (tests/test_block_primitives_cpu.py)."""
+    case = K.cell_case(dims, clouds)
+    cells = _cells(K.CELL_ORIGIN, K.CELL_SIZE, dims)
+    _, want = _check(dev, case["points"], cells, what=f"{dims} x {clouds}")
+    blocks = K.workgroups(case["positions"], K.SCAN_BLOCK)
+    print(f"scan blocks {blocks}, per {K.per_thread(blocks)}, kept cells {want['count'].tolist()}, outside {want['outside'].tolist()}")
+    assert blocks > K.THREADS and want["count"].min() > 2500
+    for cloud, _, cell in case["crafted"]:
+        row = np.flatnonzero(want["cell"][cloud] == cell)
+        assert row.size == 1 and want["weight"][cloud, row[0]] >= K.CRAFTED_PER_CELL
+    _check(dev, case["points"], cells, min_points=2, what=f"{dims} x {clouds} min_points 2")
 
 
 def test_one_crowded_cell_and_a_cloud_that_misses_the_lattice(dev):
