@@ -1112,6 +1112,62 @@ int njf_field_frame(const float* points, const int* count, const int* labels, in
                     int reach, float near, float tolerance, double max_distance, int* pixel, float* z, int* state, int* index,
                     float* distance2, float* matched, int* found, int* states, int phases, void* stream);
 
+/* ---- depth frames fused into a truncated signed distance on a grid; the distance and its gradient at rows (ABI v20, additive;
+ * DESIGN.md section 27) ---------------------------------------------------------------------------------------------------------------
+ * njf_field_tsdf: for each of M problems, V depth images are fused into one value and one weight per node of `grid`.  Inputs, all on
+ * the device: depth [M,V,H,W] float, the camera-space z of every pixel (njf_field_depth_points' NJF_FIELD_DEPTH_Z); k [V,3,3] and w2c
+ * [V,4,4] float, njf_field_visible's, shared by the problems; values_in and weight_in [M,N] float, the running state, both or
+ * neither (NULL) -- they may BE values and weight: a lane reads and writes its own node only.
+ * NODE g of problem m, g = (ix*ny + iy)*nz + iz, at p = fmaf((float)i_c, step[c], origin[c]) per component (njf_field_points' floats):
+ *        sum = 0, c = 0; for v = 0 .. V-1 in this order: the node is projected by njf_field_visible's PROJECTION, word for word -- the
+ *        kernels call the same device function, so zc, row and col are the bits njf_field_visible reports for the node as a row, with
+ *        this `near`.  The view CONTRIBUTES iff the node is INSIDE, d = depth[m, v, row*W + col] is finite, near < d <= far
+ *        (njf_field_depth_points' validity) and s = d - zc (one float subtraction) satisfies s >= -truncation (inclusive; a
+ *        comparison with a NaN is false); then sum = sum + fminf(s, truncation) and c = c + 1.0f, float additions, nothing contracted.
+ * UPDATE with W0 = weight_in[m,g] and D0 = values_in[m,g], W0 = 0 without a state:
+ *        c == 0:          values = D0, weight = W0 (the state copied through); without a state values = NaN, weight = 0;
+ *        c > 0, W0 > 0:   values = fmaf(W0, D0, sum) / (W0 + c), an IEEE division; weight = fminf(W0 + c, max_weight);
+ *        c > 0 otherwise: values = sum / c, an IEEE division -- D0 is not read and may be NaN --; weight = fminf(c, max_weight).
+ *        The value is positive in observed free space (in front of the surface) and negative behind it.
+ * known [M] int32: the nodes of the problem with weight > 0 after the update.
+ * Every element of every output is written.  One lane per (m, g), workgroups of 256 consecutive nodes of one problem; one integer
+ * atomic per workgroup for `known`, after a workgroup sum.  One memset (known) and one launch; one stream, no host read (capture-safe).
+ * Returns, before the launch: NJF_E_NULL for a missing pointer, or one of values_in / weight_in without the other; NJF_E_VALUE for M
+ * outside [1, NJF_FIELD_POSE_MAX_COMMANDS], V outside [1, NJF_FIELD_VISIBLE_MAX_VIEWS], near negative or not finite, far not > near
+ * (NaN included; +inf is allowed), truncation not in (0, inf), max_weight not > 0 (NaN included; +inf is allowed); NJF_E_SHAPE for H or
+ * W < 1, a dims[c] < 1, nx*ny*nz, M * N or M * V * H * W >= 2^31.
+ *
+ * njf_field_tsdf_sample: the trilinear interpolant of such a field, and its exact derivative, at the rows of a point set.  Inputs, all
+ * on the device: points [Mq,n,3] float, Mq = 1 or M; count int32 [1] or NULL (= n); labels int32 [n] or NULL; values and weight [Mf,N]
+ * float, Mf = 1 or M.  A row is READ by njf_field_visible's READ ROW rule (the same device function).
+ * CELL   per axis c: g_c = (x_c - origin[c]) / step[c], one float subtraction and one IEEE division.  The row is IN THE GRID iff g_c >=
+ *        0 and g_c <= (float)(dims[c] - 1) on all three axes (a comparison with a NaN is false); then i_c = min((int)floorf(g_c),
+ *        dims[c] - 2) and f_c = g_c - (float)i_c, a float subtraction: a row on the last node plane has f_c = 1 in the last cell.
+ * STATE  state [M,n] int32: NJF_FIELD_TSDF_OUTSIDE (0) when the row is not read or not in the grid; else NJF_FIELD_TSDF_UNKNOWN (1)
+ *        when weight == 0 at any of the eight corners (i_x + a, i_y + b, i_z + c), a, b, c in {0, 1}; else NJF_FIELD_TSDF_KNOWN (2).
+ * KNOWN  rows, with C[a][b][c] the values at the corners and lerp(u, w, f) = fmaf(f, w - u, u), w - u a float subtraction:
+ *        e[a][b] = lerp(C[a][b][0], C[a][b][1], f_z); h[a] = lerp(e[a][0], e[a][1], f_y); distance = lerp(h[0], h[1], f_x);
+ *        gradient.x = (h[1] - h[0]) / step[0];
+ *        gradient.y = lerp(q[0], q[1], f_x) / step[1], q[a] = e[a][1] - e[a][0];
+ *        gradient.z = lerp(t[0], t[1], f_x) / step[2], t[a] = lerp(r[a][0], r[a][1], f_y), r[a][b] = C[a][b][1] - C[a][b][0];
+ *        float subtractions and IEEE divisions, nothing contracted beyond the fmaf written here.
+ * Outputs: state; distance [M,n] float and gradient [M,n,3] float, NaN unless the row is KNOWN; states [M,3] int32: the rows i < n of
+ * every state code (they add up to n).  Every element of every output is written.  One lane per (m, i); one integer atomic per
+ * workgroup and counter, after a workgroup sum.  One memset (states) and one launch; one stream, no host read (capture-safe).
+ * Returns, before the launch: NJF_E_NULL for a missing pointer (count and labels may be NULL); NJF_E_VALUE for M outside [1,
+ * NJF_FIELD_POSE_MAX_COMMANDS], Mq or Mf not 1 or M, a step[c] not in (0, inf), an origin[c] that is not finite, a dims[c] of 1;
+ * NJF_E_SHAPE for a dims[c] < 1, n < 0, nx*ny*nz, M * n or Mf * N >= 2^31. */
+#define NJF_FIELD_TSDF_OUTSIDE 0     /* state */
+#define NJF_FIELD_TSDF_UNKNOWN 1
+#define NJF_FIELD_TSDF_KNOWN 2
+#define NJF_FIELD_TSDF_STATES 3
+int njf_field_tsdf(const NjfFieldGrid* grid, const float* depth, int num_problems, int views, int height, int width, const float* k,
+                   const float* w2c, float near, float far, float truncation, float max_weight, const float* values_in,
+                   const float* weight_in, float* values, float* weight, int* known, void* stream);
+int njf_field_tsdf_sample(const float* points, const int* count, const int* labels, int num_queries, int n, int num_problems,
+                          const NjfFieldGrid* grid, const float* values, const float* weight, int num_fields, int* state,
+                          float* distance, float* gradient, int* states, void* stream);
+
 /* ---- stand-alone sampler / compositing ops (API parity with the un-fused reference calls) -- */
 /* RaySamples.get_weights (ray_samplers.py:77-101): deltas, densities [N,S] -> weights [N,S]. */
 int njf_alpha_weights(const float* deltas, const float* densities, int rays, int samples, float* weights, void* stream);

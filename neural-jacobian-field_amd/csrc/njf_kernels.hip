@@ -2063,15 +2063,19 @@ __device__ __forceinline__ int field_global_index(const FieldList& l, int i) {
   return min(max(gi, 0), l.total - 1);
 }
 
+// the coordinate of the node of linear index n
+__device__ __forceinline__ void grid_node(const NjfFieldGrid& grid, int n, float& px, float& py, float& pz) {
+  const int yz = grid.dims[1] * grid.dims[2];
+  const int ix = n / yz, r = n - ix * yz;
+  const int iy = r / grid.dims[2], iz = r - iy * grid.dims[2];
+  px = fmaf((float)ix, grid.step[0], grid.origin[0]);
+  py = fmaf((float)iy, grid.step[1], grid.origin[1]);
+  pz = fmaf((float)iz, grid.step[2], grid.origin[2]);
+}
+
 __device__ __forceinline__ void field_node(const FieldList& l, int gi, int& b, float& px, float& py, float& pz) {
   b = gi / l.nodes;
-  const int n = gi - b * l.nodes;
-  const int yz = l.grid.dims[1] * l.grid.dims[2];
-  const int ix = n / yz, r = n - ix * yz;
-  const int iy = r / l.grid.dims[2], iz = r - iy * l.grid.dims[2];
-  px = fmaf((float)ix, l.grid.step[0], l.grid.origin[0]);
-  py = fmaf((float)iy, l.grid.step[1], l.grid.origin[1]);
-  pz = fmaf((float)iz, l.grid.step[2], l.grid.origin[2]);
+  grid_node(l.grid, gi - b * l.nodes, px, py, pz);
 }
 
 // ---- the decoder at points: one evaluator, three sources of points ------------------------------------------------------
@@ -8273,6 +8277,246 @@ extern "C" int njf_field_frame(const float* points, const int* count, const int*
                        s>>>(a);
     int rc;
     if ((rc = launch_status())) return rc;
+  }
+  return NJF_OK;
+}
+
+// ---- depth frames fused into a truncated signed distance on a grid, and sampled at rows (njf_field_tsdf) --------
+// A node is projected by vis_project -- njf_field_visible's own, so its pixel and z are the bits njf_field_visible reports for the
+// node as a row --, and a row of the sampler is read by vis_read.
+struct TsdfArgs {
+  VisArgs vis;             // k, w2c, V, H, W, pixels, near (fuse); points, count, labels, Mq, n (sample); the rest is not read
+  NjfFieldGrid grid;
+  int nodes;               // N
+  const float* depth;      // [M,V,H,W]
+  const float* values_in;  // [M,N] or NULL (both or neither)
+  const float* weight_in;
+  float far, truncation, max_weight;
+  float* values;           // [M,N]
+  float* weight;           // [M,N]
+  int* known;              // [M]
+};
+
+#define NJF_TSDF_THREADS 256
+#define NJF_TSDF_WAVES (NJF_TSDF_THREADS / 64)
+
+// one lane per (m, g): consecutive lanes are consecutive nodes.  A lane reads and writes its own node only, so the state may be
+// the outputs.  A workgroup lies in one problem: one atomic for its four waves.
+__global__ void __launch_bounds__(NJF_TSDF_THREADS) tsdf_fuse_kernel(TsdfArgs a) {
+  __shared__ int part[NJF_TSDF_WAVES];
+  const VisArgs& s = a.vis;
+  const long long g = (long long)blockIdx.x * NJF_TSDF_THREADS + threadIdx.x;
+  const int m = blockIdx.y;
+  int has = 0;
+  if (g < a.nodes) {
+    float x, y, z;
+    grid_node(a.grid, (int)g, x, y, z);
+    float sum = 0.0f, c = 0.0f;
+    for (int v = 0; v < s.V; ++v) {
+      const VisPixel p = vis_project(s, v, x, y, z);
+      if (!p.inside) continue;  // judged in float: 0 <= row < H, 0 <= col < W
+      const float d = a.depth[((long long)m * s.V + v) * s.pixels + ((int)p.row * s.W + (int)p.col)];
+      const float sd = __fsub_rn(d, p.z);
+      if (fabsf(d) < INFINITY && d > s.near && d <= a.far && sd >= -a.truncation) {  // (NaN: false)
+        sum = __fadd_rn(sum, fminf(sd, a.truncation));
+        c = __fadd_rn(c, 1.0f);
+      }
+    }
+    const long long o = (long long)m * a.nodes + g;
+    const float w0 = a.weight_in ? a.weight_in[o] : 0.0f;
+    float value, weight;
+    if (c == 0.0f) {
+      value = a.values_in ? a.values_in[o] : __int_as_float(0x7fc00000);
+      weight = w0;
+    } else if (w0 > 0.0f) {
+      value = __fdiv_rn(fmaf(w0, a.values_in[o], sum), __fadd_rn(w0, c));
+      weight = fminf(__fadd_rn(w0, c), a.max_weight);
+    } else {  // nothing fused into the node so far: the old value is not read
+      value = __fdiv_rn(sum, c);
+      weight = fminf(c, a.max_weight);
+    }
+    a.values[o] = value;
+    a.weight[o] = weight;
+    has = weight > 0.0f;
+  }
+  const int t = block_sum(has, part);
+  if (threadIdx.x == 0 && t) atomicAdd(&a.known[m], t);
+}
+
+static int check_tsdf_grid(const NjfFieldGrid* grid, int min_dim, long long& nodes) {
+  for (int c = 0; c < 3; ++c)
+    if (grid->dims[c] < 1) return NJF_E_SHAPE;
+  for (int c = 0; c < 3; ++c)
+    if (grid->dims[c] < min_dim) return NJF_E_VALUE;
+  nodes = (long long)grid->dims[0] * grid->dims[1] * grid->dims[2];
+  return nodes >= (1LL << 31) ? NJF_E_SHAPE : NJF_OK;
+}
+
+extern "C" int njf_field_tsdf(const NjfFieldGrid* grid, const float* depth, int num_problems, int views, int height, int width,
+                              const float* k, const float* w2c, float near, float far, float truncation, float max_weight,
+                              const float* values_in, const float* weight_in, float* values, float* weight, int* known,
+                              void* stream) {
+  if (!grid || !depth || !k || !w2c || !values || !weight || !known || (!values_in != !weight_in)) return NJF_E_NULL;
+  if (num_problems < 1 || num_problems > NJF_FIELD_POSE_MAX_COMMANDS) return NJF_E_VALUE;
+  if (views < 1 || views > NJF_FIELD_VISIBLE_MAX_VIEWS) return NJF_E_VALUE;
+  if (!(near >= 0.0f) || !(near < INFINITY) || !(far > near)) return NJF_E_VALUE;
+  if (!(truncation > 0.0f) || !(truncation < INFINITY) || !(max_weight > 0.0f)) return NJF_E_VALUE;
+  if (height < 1 || width < 1) return NJF_E_SHAPE;
+  long long nodes;
+  int rc;
+  if ((rc = check_tsdf_grid(grid, 1, nodes))) return rc;
+  if ((long long)height * width >= (1LL << 31) || (long long)num_problems * views * height * width >= (1LL << 31) ||
+      num_problems * nodes >= (1LL << 31))
+    return NJF_E_SHAPE;
+  TsdfArgs a{};
+  a.vis.k = k;
+  a.vis.w2c = w2c;
+  a.vis.M = num_problems;
+  a.vis.V = views;
+  a.vis.H = height;
+  a.vis.W = width;
+  a.vis.pixels = (long long)height * width;
+  a.vis.near = near;
+  a.grid = *grid;
+  a.nodes = (int)nodes;
+  a.depth = depth;
+  a.values_in = values_in;
+  a.weight_in = weight_in;
+  a.far = far;
+  a.truncation = truncation;
+  a.max_weight = max_weight;
+  a.values = values;
+  a.weight = weight;
+  a.known = known;
+  hipStream_t s = (hipStream_t)stream;
+  hipError_t e;
+  if ((e = hipMemsetAsync(known, 0, (size_t)num_problems * sizeof(int), s)) != hipSuccess) return (int)e;
+  tsdf_fuse_kernel<<<dim3((unsigned)((nodes + NJF_TSDF_THREADS - 1) / NJF_TSDF_THREADS), (unsigned)num_problems), NJF_TSDF_THREADS, 0,
+                     s>>>(a);
+  return launch_status();
+}
+
+struct TsdfSampleArgs {
+  VisArgs vis;          // points, count, labels, Mq, n: what vis_read reads
+  NjfFieldGrid grid;
+  int Mf, nodes;
+  const float* values;  // [Mf,N]
+  const float* weight;  // [Mf,N]
+  int* state;           // [M,n]
+  float* distance;      // [M,n]
+  float* gradient;      // [M,n,3]
+  int* states;          // [M,3]
+};
+
+__device__ __forceinline__ float tsdf_lerp(float u, float w, float f) { return fmaf(f, __fsub_rn(w, u), u); }
+
+// one lane per (m, i).  A workgroup lies in one problem: one atomic per counter for its four waves.
+__global__ void __launch_bounds__(NJF_TSDF_THREADS) tsdf_sample_kernel(TsdfSampleArgs a) {
+  __shared__ int part[NJF_FIELD_TSDF_STATES][NJF_TSDF_WAVES];
+  const VisArgs& s = a.vis;
+  const long long i = (long long)blockIdx.x * NJF_TSDF_THREADS + threadIdx.x;
+  const int m = blockIdx.y;
+  const bool live = i < s.n;
+  int st = NJF_FIELD_TSDF_OUTSIDE;
+  if (live) {
+    const float nan = __int_as_float(0x7fc00000);
+    float distance = nan, gx = nan, gy = nan, gz = nan;
+    float x[3] = {0.f, 0.f, 0.f};
+    bool in = vis_read(s, m, i, x[0], x[1], x[2]);
+    int cell[3];
+    float f[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const float gc = __fdiv_rn(__fsub_rn(x[c], a.grid.origin[c]), a.grid.step[c]);
+      in = in && gc >= 0.0f && gc <= (float)(a.grid.dims[c] - 1);  // (NaN: false)
+      cell[c] = in ? min((int)floorf(gc), a.grid.dims[c] - 2) : 0;   // 0 <= gc <= dims - 1 < 2^31: the conversion is exact
+      f[c] = __fsub_rn(gc, (float)cell[c]);
+    }
+    if (in) {
+      // the cell's eight corners: node (cell + (a, b, c)), every index in [0, N)
+      const int nz = a.grid.dims[2], yz = a.grid.dims[1] * nz;
+      const long long base = (long long)(a.Mf == 1 ? 0 : m) * a.nodes + ((cell[0] * a.grid.dims[1] + cell[1]) * nz + cell[2]);
+      const float* val = a.values + base;
+      const float* wgt = a.weight + base;
+      float C[2][2][2];
+      bool known = true;
+#pragma unroll
+      for (int ia = 0; ia < 2; ++ia)
+#pragma unroll
+        for (int ib = 0; ib < 2; ++ib)
+#pragma unroll
+          for (int ic = 0; ic < 2; ++ic) {
+            const int o = ia * yz + ib * nz + ic;
+            known = known && !(wgt[o] == 0.0f);
+            C[ia][ib][ic] = val[o];
+          }
+      st = known ? NJF_FIELD_TSDF_KNOWN : NJF_FIELD_TSDF_UNKNOWN;
+      if (known) {
+        float e[2][2], h[2], q[2], t[2];
+#pragma unroll
+        for (int ia = 0; ia < 2; ++ia) {
+          e[ia][0] = tsdf_lerp(C[ia][0][0], C[ia][0][1], f[2]);
+          e[ia][1] = tsdf_lerp(C[ia][1][0], C[ia][1][1], f[2]);
+          h[ia] = tsdf_lerp(e[ia][0], e[ia][1], f[1]);
+          q[ia] = __fsub_rn(e[ia][1], e[ia][0]);
+          t[ia] = tsdf_lerp(__fsub_rn(C[ia][0][1], C[ia][0][0]), __fsub_rn(C[ia][1][1], C[ia][1][0]), f[1]);
+        }
+        distance = tsdf_lerp(h[0], h[1], f[0]);
+        gx = __fdiv_rn(__fsub_rn(h[1], h[0]), a.grid.step[0]);
+        gy = __fdiv_rn(tsdf_lerp(q[0], q[1], f[0]), a.grid.step[1]);
+        gz = __fdiv_rn(tsdf_lerp(t[0], t[1], f[0]), a.grid.step[2]);
+      }
+    }
+    const long long row = (long long)m * s.n + i;
+    a.state[row] = st;
+    a.distance[row] = distance;
+    a.gradient[row * 3] = gx;
+    a.gradient[row * 3 + 1] = gy;
+    a.gradient[row * 3 + 2] = gz;
+  }
+#pragma unroll
+  for (int c = 0; c < NJF_FIELD_TSDF_STATES; ++c) {
+    const int t = block_sum((int)(live && st == c), part[c]);
+    if (threadIdx.x == 0 && t) atomicAdd(&a.states[m * NJF_FIELD_TSDF_STATES + c], t);
+  }
+}
+
+extern "C" int njf_field_tsdf_sample(const float* points, const int* count, const int* labels, int num_queries, int n,
+                                     int num_problems, const NjfFieldGrid* grid, const float* values, const float* weight,
+                                     int num_fields, int* state, float* distance, float* gradient, int* states, void* stream) {
+  if (!points || !grid || !values || !weight || !state || !distance || !gradient || !states) return NJF_E_NULL;
+  if (num_problems < 1 || num_problems > NJF_FIELD_POSE_MAX_COMMANDS) return NJF_E_VALUE;
+  if (num_queries != 1 && num_queries != num_problems) return NJF_E_VALUE;
+  if (num_fields != 1 && num_fields != num_problems) return NJF_E_VALUE;
+  for (int c = 0; c < 3; ++c)
+    if (!(grid->step[c] > 0.0f) || !(grid->step[c] < INFINITY) || !(fabsf(grid->origin[c]) < INFINITY)) return NJF_E_VALUE;
+  long long nodes;
+  int rc;
+  if ((rc = check_tsdf_grid(grid, 2, nodes))) return rc;
+  if (n < 0 || (long long)num_problems * n >= (1LL << 31) || num_fields * nodes >= (1LL << 31)) return NJF_E_SHAPE;
+  TsdfSampleArgs a{};
+  a.vis.points = points;
+  a.vis.count = count;
+  a.vis.labels = labels;
+  a.vis.Mq = num_queries;
+  a.vis.M = num_problems;
+  a.vis.n = n;
+  a.grid = *grid;
+  a.Mf = num_fields;
+  a.nodes = (int)nodes;
+  a.values = values;
+  a.weight = weight;
+  a.state = state;
+  a.distance = distance;
+  a.gradient = gradient;
+  a.states = states;
+  hipStream_t s = (hipStream_t)stream;
+  hipError_t e;
+  if ((e = hipMemsetAsync(states, 0, (size_t)num_problems * NJF_FIELD_TSDF_STATES * sizeof(int), s)) != hipSuccess) return (int)e;
+  if (n > 0) {
+    tsdf_sample_kernel<<<dim3((unsigned)(((long long)n + NJF_TSDF_THREADS - 1) / NJF_TSDF_THREADS), (unsigned)num_problems),
+                         NJF_TSDF_THREADS, 0, s>>>(a);
+    return launch_status();
   }
   return NJF_OK;
 }

@@ -2102,6 +2102,182 @@ def cloud_registration_frame(cloud: FieldPointCloud, labels: torch.Tensor, twist
         raise ValueError(str(err).replace("register_commands_frame:", f"{name}:", 1)) from None
 
 
+# ---- depth frames fused into a truncated signed distance -----------------------------------------------------
+@dataclass
+class FieldDistance:
+    """A truncated signed distance on the nodes of ``grid``, fused from depth frames (``fuse_depth``; include/njf_hip.h:
+    njf_field_tsdf), per problem: ``values`` is positive in the free space the cameras saw through, negative behind the surface,
+    clipped to ``truncation`` in front of it and not observed further than ``truncation`` behind it; ``weight`` is the number of
+    views that contributed to the node (at most ``max_weight``), 0 where none did -- ``values`` is NaN there."""
+
+    grid: FieldGrid
+    truncation: float         # the kernel's float
+    values: torch.Tensor      # [M, N] fp32
+    weight: torch.Tensor      # [M, N] fp32
+    known: torch.Tensor       # [M] int32: the nodes with weight > 0
+
+    def mesh(self, **capacities) -> "FieldMesh":
+        """The fused surface: ``mesh_from_values`` of ``-values`` at 0 over the nodes with a weight (inside = behind the surface);
+        ``max_vertices`` and ``max_triangles`` as there."""
+        return mesh_from_values(self.grid, -self.values, 0.0, valid=self.weight > 0, **capacities)
+
+
+@dataclass
+class FieldClearance:
+    """A ``FieldDistance`` at the rows of a point set (``sample_distance``; include/njf_hip.h: njf_field_tsdf_sample): ``state[m, i]``
+    is 0 for a row outside the grid (or not read), 1 where a corner of its cell was never observed, 2 where ``distance`` and
+    ``gradient`` -- the trilinear interpolant and its exact derivative -- are known; they are NaN otherwise."""
+
+    state: torch.Tensor       # [M, n] int32: hip.FIELD_TSDF_OUTSIDE, _UNKNOWN, _KNOWN
+    distance: torch.Tensor    # [M, n] fp32
+    gradient: torch.Tensor    # [M, n, 3] fp32
+    states: torch.Tensor      # [M, 3] int32: the rows per code
+
+    def cost(self) -> torch.Tensor:
+        """``[M]`` float64: the mean of ``|distance|`` over the KNOWN rows -- how far the rows lie from the fused surface, rows in
+        observed free space included; NaN with no KNOWN row."""
+        known = self.state == hip.FIELD_TSDF_KNOWN
+        total = torch.where(known, self.distance.to(torch.float64).abs(), 0.0).sum(dim=1)
+        return total / known.sum(dim=1).to(torch.float64)
+
+    def surface_targets(self, points: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``(targets [M, n, 3], information [M, n, 6])`` for ``solve_commands_metric``: the foot of every KNOWN row of ``points``
+        (``[n, 3]`` or ``[Mq, n, 3]``, the sampled points) on the surface along the gradient, ``x - distance g / (g . g)``, and
+        ``plane_information(g / |g|)``; NaN -- the solver's "row left out" -- for rows that are not KNOWN or have ``g . g == 0``."""
+        name = "FieldClearance.surface_targets"
+        m, n = self.state.shape
+        if not torch.is_tensor(points) or points.dtype != torch.float32 or points.dim() not in (2, 3) or points.shape[-1] != 3 \
+                or points.shape[-2] != n or (points.dim() == 3 and points.shape[0] not in (1, m)):
+            raise ValueError(f"{name}: points must be fp32 [{n}, 3] or [Mq, {n}, 3] with Mq 1 or {m}")
+        if points.device != self.state.device:
+            raise ValueError(f"{name}: points must live on the device of the sample")
+        g = self.gradient
+        gg = (g * g).sum(dim=-1, keepdim=True)
+        ok = (self.state == hip.FIELD_TSDF_KNOWN)[..., None] & (gg > 0)
+        nan = torch.full((), math.nan, dtype=torch.float32, device=g.device)
+        targets = torch.where(ok, points - self.distance[..., None] * g / gg, nan)
+        return targets, torch.where(ok, plane_information(torch.where(ok, g, nan)), nan)
+
+
+def _check_positive(name: str, what: str, value, finite: bool) -> float:
+    """``value`` as the kernel's float: a number > 0, finite when ``finite``."""
+    rule = f"{name}: {what} must be a {'finite ' if finite else ''}number > 0"
+    if isinstance(value, bool) or not isinstance(value, (int, float)) or math.isnan(value):
+        raise ValueError(f"{rule} (got {value})")
+    with np.errstate(over="ignore"):
+        value32 = float(np.float32(value))
+    if not value32 > 0.0 or (finite and value32 == math.inf):
+        raise ValueError(f"{rule} (got {value})")
+    return value32
+
+
+def fuse_depth(grid: FieldGrid, depth: torch.Tensor, view: FieldView, truncation: float, *, far: float = math.inf,
+               max_weight: float = math.inf, into: Optional[FieldDistance] = None) -> FieldDistance:
+    """The depth images ``depth`` ``[V, H, W]`` or ``[M, V, H, W]`` (fp32, camera-space z: ``depth_points``' ``kind="z"``,
+    ``FieldVisibility.depth``) of the cameras of ``view`` fused into a truncated signed distance on ``grid``.
+    Every node is projected into every view by the code ``visible_rows`` projects rows with; where it falls on a pixel with
+    ``view.near < d <= far`` it sees ``s = d - z``: free space in front of the surface when positive, and nothing when it lies
+    further than ``truncation`` behind it.  The views that see it add ``min(s, truncation)`` to a running mean whose weight is the
+    number of views, held at ``max_weight`` so that an old frame fades.  ``into`` -- an earlier result on the same grid, with the
+    same truncation and M -- is updated in place and returned; a node no view sees keeps its state, NaN with weight 0 at first.
+    ``view.footprint`` and ``view.tolerance`` are not read.  One launch, one integer atomic per workgroup, no host read: equal bytes
+    from call to call, capturable."""
+    name = "fuse_depth"
+    if not isinstance(grid, FieldGrid):
+        raise ValueError(f"{name}: grid must be a FieldGrid")
+    if not torch.is_tensor(depth) or depth.dtype != torch.float32 or depth.dim() not in (3, 4):
+        raise ValueError(f"{name}: depth must be fp32 [V, H, W] or [M, V, H, W]")
+    depth = depth if depth.dim() == 4 else depth[None]
+    m = depth.shape[0]
+    if not 1 <= m <= hip.FIELD_POSE_MAX_COMMANDS:
+        raise ValueError(f"{name}: 1 to {hip.FIELD_POSE_MAX_COMMANDS} problems (got {m})")
+    v, near = _check_view(name, view, depth, "depth", m, 0, splat=False)
+    if tuple(depth.shape[1:]) != (v, view.height, view.width):
+        raise ValueError(f"{name}: depth must hold [{v}, {view.height}, {view.width}] images (got {tuple(depth.shape[1:])})")
+    truncation = _check_positive(name, "truncation", truncation, True)
+    max_weight = _check_positive(name, "max_weight", max_weight, False)
+    if isinstance(far, bool) or not isinstance(far, (int, float)) or math.isnan(far):
+        raise ValueError(f"{name}: far must be a number > near (got {far})")
+    with np.errstate(over="ignore"):
+        far = float(np.float32(far))
+    if not far > near:
+        raise ValueError(f"{name}: far must be a number > near (got {far} and {near})")
+    nodes = grid.num_nodes
+    if m * nodes >= 2 ** 31:
+        raise ValueError(f"{name}: M * nodes must stay below 2**31")
+    if into is not None:
+        if not isinstance(into, FieldDistance):
+            raise ValueError(f"{name}: into must be a FieldDistance")
+        if into.grid != grid or into.truncation != truncation:
+            raise ValueError(f"{name}: into must be of the same grid and truncation")
+        for what, t, shape in (("values", into.values, (m, nodes)), ("weight", into.weight, (m, nodes)), ("known", into.known, (m,))):
+            if not torch.is_tensor(t) or t.dtype != (torch.int32 if what == "known" else torch.float32) or tuple(t.shape) != shape \
+                    or not t.is_contiguous():
+                raise ValueError(f"{name}: into.{what} must be a contiguous {'int32' if what == 'known' else 'fp32'} {list(shape)}")
+            if t.device != depth.device:
+                raise ValueError(f"{name}: into.{what} must live on the device of depth")
+    if depth.device.type != "cuda":
+        raise ValueError(f"{name}: the tensors must live on the GPU; there is no CPU path")
+    dev = depth.device
+    out = into if into is not None else FieldDistance(
+        grid=grid, truncation=truncation, values=torch.empty(m, nodes, dtype=torch.float32, device=dev),
+        weight=torch.empty(m, nodes, dtype=torch.float32, device=dev), known=torch.empty(m, dtype=torch.int32, device=dev))
+    hip.field_tsdf(grid.c_grid(), depth.contiguous(), view.intrinsics.contiguous(), hip.inverse(view.cam2world).contiguous(), truncation,
+                   dict(values=out.values, weight=out.weight, known=out.known), near=near, far=far, max_weight=max_weight,
+                   values_in=None if into is None else into.values, weight_in=None if into is None else into.weight)
+    return out
+
+
+def sample_distance(points: torch.Tensor, field: FieldDistance, *, labels: Optional[torch.Tensor] = None,
+                    count: Optional[torch.Tensor] = None) -> FieldClearance:
+    """The fused distance ``field`` (``fuse_depth``) and its gradient at the rows of ``points`` ``[n, 3]`` or ``[Mq, n, 3]`` (fp32):
+    M = max(Mq, Mf) problems, Mq and the field's Mf each 1 or M.  A row is read as ``visible_rows`` reads it (below ``count``, finite,
+    of a label >= 0); a read row inside the grid's box lies in one cell, and where all eight corners of that cell have a weight the
+    trilinear interpolant of their values is its ``distance`` and the exact derivative of that interpolant its ``gradient`` --
+    which points away from the surface, into free space.  ``FieldClearance.cost()`` ranks poses: a row in observed free space pays
+    its distance to the surface.  One launch, integer atomics only, no host read: equal bytes from call to call, capturable."""
+    name = "sample_distance"
+    if not torch.is_tensor(points) or points.dtype != torch.float32 or points.dim() not in (2, 3) or points.shape[-1] != 3:
+        raise ValueError(f"{name}: points must be fp32 [n, 3] or [Mq, n, 3]")
+    points = points if points.dim() == 3 else points[None]
+    mq, n = points.shape[:2]
+    if not isinstance(field, FieldDistance) or not isinstance(field.grid, FieldGrid):
+        raise ValueError(f"{name}: field must be a FieldDistance")
+    grid = field.grid
+    if any(d < 2 for d in grid.dims) or not all(0.0 < s < math.inf for s in grid.step):
+        raise ValueError(f"{name}: the field's grid needs two nodes or more and a finite step > 0 on every axis "
+                         f"(got dims {grid.dims}, step {grid.step})")
+    for what, t in (("values", field.values), ("weight", field.weight)):
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != grid.num_nodes:
+            raise ValueError(f"{name}: field.{what} must be fp32 [Mf, {grid.num_nodes}]")
+    mf = field.values.shape[0]
+    if field.weight.shape[0] != mf:
+        raise ValueError(f"{name}: field.values and field.weight must hold the same problems")
+    m = max(mq, mf)
+    if not 1 <= m <= hip.FIELD_POSE_MAX_COMMANDS or mq < 1 or mf < 1:
+        raise ValueError(f"{name}: 1 to {hip.FIELD_POSE_MAX_COMMANDS} problems (got {min(mq, mf, m)} and {m})")
+    if mq not in (1, m) or mf not in (1, m):
+        raise ValueError(f"{name}: field and points hold one set or one per problem (got {mf} and {mq} for {m} problems)")
+    if m * n >= 2 ** 31:
+        raise ValueError(f"{name}: M * n must stay below 2**31")
+    count = _one_int32(name, "count", count, points)
+    if labels is not None and (not torch.is_tensor(labels) or labels.dtype != torch.int32 or tuple(labels.shape) != (n,)):
+        raise ValueError(f"{name}: labels must be int32 [{n}]")
+    for what, t in (("field.values", field.values), ("field.weight", field.weight), ("labels", labels)):
+        if t is not None and t.device != points.device:
+            raise ValueError(f"{name}: {what} must live on the device of points")
+    if points.device.type != "cuda":
+        raise ValueError(f"{name}: the tensors must live on the GPU; there is no CPU path")
+    dev = points.device
+    out = FieldClearance(state=torch.empty(m, n, dtype=torch.int32, device=dev), distance=torch.empty(m, n, dtype=torch.float32, device=dev),
+                         gradient=torch.empty(m, n, 3, dtype=torch.float32, device=dev),
+                         states=torch.empty(m, hip.FIELD_TSDF_STATES, dtype=torch.int32, device=dev))
+    hip.field_tsdf_sample(points.contiguous(), grid.c_grid(), field.values.contiguous(), field.weight.contiguous(),
+                          {f: getattr(out, f) for f in out.__dataclass_fields__}, m, count=count,
+                          labels=None if labels is None else labels.contiguous())
+    return out
+
+
 # ---- coarse-to-fine band (DESIGN.md section 14) ----------------------------------------------------------------------------------
 @dataclass
 class FieldBand:

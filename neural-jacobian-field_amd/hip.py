@@ -191,6 +191,10 @@ _SIGNATURES = {
                            C.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_longlong, C.c_int, _vp], C.c_int),
     "njf_field_frame": ([_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
                          C.c_float, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp], C.c_int),
+    "njf_field_tsdf": ([C.POINTER(FieldGrid), _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_float, C.c_float, C.c_float,
+                        C.c_float, _vp, _vp, _vp, _vp, _vp, _vp], C.c_int),
+    "njf_field_tsdf_sample": ([_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.POINTER(FieldGrid), _vp, _vp, C.c_int, _vp, _vp, _vp, _vp,
+                               _vp], C.c_int),
     "njf_pack_resnetfc_backward": ([C.POINTER(ResnetFcWeights), _vp, C.c_int, _vp], C.c_int),
     "njf_resnetfc_backward": ([_vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp], C.c_int),
     "njf_pack_transformer_backward": ([_vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, _vp], C.c_int),
@@ -1539,6 +1543,56 @@ def field_frame(points: torch.Tensor, frame: torch.Tensor, k: torch.Tensor, w2c:
             float(near), float(tolerance), float(max_distance), _int32_ptr(out["pixel"], "pixel"), _ptr(out["z"], "z"),
             _int32_ptr(out["state"], "state"), _int32_ptr(out["index"], "index"), _ptr(out["distance2"], "distance2"),
             _ptr(out["matched"], "matched"), _int32_ptr(out["found"], "found"), _int32_ptr(out["states"], "states"), int(phase))
+
+
+# ---- depth frames fused into a truncated signed distance, and sampled at rows (include/njf_hip.h: njf_field_tsdf) ---------------------
+FIELD_TSDF_STATE_NAMES = ("outside", "unknown", "known")   # NJF_FIELD_TSDF_OUTSIDE, _UNKNOWN, _KNOWN = 0, 1, 2
+FIELD_TSDF_OUTSIDE, FIELD_TSDF_UNKNOWN, FIELD_TSDF_KNOWN = range(3)
+FIELD_TSDF_STATES = 3                                  # NJF_FIELD_TSDF_STATES
+FIELD_TSDF_OUTPUTS = (("values", torch.float32), ("weight", torch.float32), ("known", torch.int32))
+FIELD_TSDF_SAMPLE_OUTPUTS = (("state", torch.int32), ("distance", torch.float32), ("gradient", torch.float32), ("states", torch.int32))
+
+
+def field_tsdf(grid: FieldGrid, depth: torch.Tensor, k: torch.Tensor, w2c: torch.Tensor, truncation: float, out: dict,
+               near: float = 0.0, far: float = float("inf"), max_weight: float = float("inf"), values_in=None, weight_in=None) -> None:
+    """njf_field_tsdf on ``depth`` [M, V, H, W] (fp32, camera-space z) through the cameras ``k`` [V, 3, 3] and ``w2c`` [V, 4, 4] onto
+    the nodes of ``grid``.  ``out`` maps values, weight [M, N] (fp32) and known [M] (int32) to tensors of their shapes;
+    ``values_in`` and ``weight_in`` [M, N]: the running state, both or neither -- they may be the outputs themselves."""
+    if depth.dim() != 4:
+        raise ValueError("njf_hip: field_tsdf needs depth [M, V, H, W]")
+    m, v, h, w = (int(s) for s in depth.shape)
+    if k.dim() != 3 or tuple(k.shape) != (v, 3, 3) or tuple(w2c.shape) != (v, 4, 4):
+        raise ValueError(f"njf_hip: field_tsdf needs k [{v}, 3, 3] and w2c [{v}, 4, 4]")
+    nodes = int(grid.dims[0]) * int(grid.dims[1]) * int(grid.dims[2])
+    _check_output_sizes("field_tsdf", out, dict(values=m * nodes, weight=m * nodes, known=m))
+    for name, t in (("values_in", values_in), ("weight_in", weight_in)):
+        if t is not None and t.numel() != m * nodes:
+            raise ValueError(f"njf_hip: field_tsdf {name} must hold {m * nodes} elements (got {t.numel()})")
+    _launch("njf_field_tsdf", load_library().njf_field_tsdf, C.byref(grid), _ptr(depth, "depth"), m, v, h, w, _ptr(k, "k"),
+            _ptr(w2c, "w2c"), float(near), float(far), float(truncation), float(max_weight), _ptr(values_in, "values_in"),
+            _ptr(weight_in, "weight_in"), _ptr(out["values"], "values"), _ptr(out["weight"], "weight"),
+            _int32_ptr(out["known"], "known"))
+
+
+def field_tsdf_sample(points: torch.Tensor, grid: FieldGrid, values: torch.Tensor, weight: torch.Tensor, out: dict, problems: int,
+                      count=None, labels=None) -> None:
+    """njf_field_tsdf_sample on ``points`` [Mq, n, 3] (fp32) in the field ``values``, ``weight`` [Mf, N] (fp32) on ``grid`` for
+    ``problems`` = M problems, Mq and Mf each 1 or M.  ``count`` [1], ``labels`` [n]: int32 or None.  ``out`` maps state, distance
+    [M, n], gradient [M, n, 3] and states [M, 3] (FIELD_TSDF_SAMPLE_OUTPUTS holds the element types) to tensors of their shapes."""
+    mq, n = _cloud_shape("field_tsdf_sample", "points", "Mq, n", points)
+    m = int(problems)
+    nodes = int(grid.dims[0]) * int(grid.dims[1]) * int(grid.dims[2])
+    if values.dim() != 2 or values.shape[1] != nodes or tuple(weight.shape) != tuple(values.shape):
+        raise ValueError(f"njf_hip: field_tsdf_sample needs values and weight [Mf, {nodes}]")
+    if count is not None and count.numel() != 1:
+        raise ValueError("njf_hip: field_tsdf_sample count must hold one int32")
+    if labels is not None and labels.numel() != n:
+        raise ValueError("njf_hip: field_tsdf_sample needs labels [n]")
+    _check_output_sizes("field_tsdf_sample", out, dict(state=m * n, distance=m * n, gradient=3 * m * n, states=m * FIELD_TSDF_STATES))
+    _launch("njf_field_tsdf_sample", load_library().njf_field_tsdf_sample, _ptr(points, "points"), _int32_ptr(count, "count"),
+            _int32_ptr(labels, "labels"), mq, n, m, C.byref(grid), _ptr(values, "values"), _ptr(weight, "weight"),
+            int(values.shape[0]), _int32_ptr(out["state"], "state"), _ptr(out["distance"], "distance"),
+            _ptr(out["gradient"], "gradient"), _int32_ptr(out["states"], "states"))
 
 
 def solve_action(mean_position, jacobian, projection, target_flow, visible_mask, init_action, iterations: int,

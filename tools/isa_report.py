@@ -24,7 +24,7 @@ FLAGS = [f for f in entry.HIPCC_FLAGS if f not in ("-shared", "-fPIC")] + sys.ar
 KERNELS = ["render_kernel", "proposal_kernel", "points_kernel", "project_kernel", "solve_action_kernel",
            "scatter_footprint_kernel", "relu_backward_kernel", "upsample_concat_kernel", "resnetfc_backward_kernel", "mesh_",
            "field_fuse_kernel", "field_combine_kernel", "components_", "band_", "field_scatter_kernel", "twist_", "joint_", "pose_", "ik_", "ikm_",
-           "nn_", "nrm_", "depth_points_kernel", "vox_", "vis_", "frm_", "block_offsets_kernel"]
+           "nn_", "nrm_", "depth_points_kernel", "vox_", "vis_", "frm_", "tsdf_", "block_offsets_kernel"]
 
 
 def demangle(names):
