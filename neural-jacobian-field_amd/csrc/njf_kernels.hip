@@ -4802,22 +4802,37 @@ struct CellList {
   int4* records;    // [slots]: (x, y, z as their bits, j)
 };
 
+__device__ __forceinline__ bool nn_finite(float x, float y, float z) {
+  return fabsf(x) < INFINITY && fabsf(y) < INFINITY && fabsf(z) < INFINITY;  // (NaN compares false)
+}
+
+// A posed point set and the one rule by which every entry that takes one reads a row of it (the READ ROW of include/njf_hip.h):
+// below the count, finite and, with labels, of a label >= 0.
+struct RowSet {
+  const float* points;  // [Mq,n,3]
+  const int* count;     // [1] or null
+  const int* labels;    // [n] or null
+  int Mq, n;
+};
+
+// row i < n of problem m: false = not read (x, y, z then hold no meaning)
+__device__ __forceinline__ bool row_read(const RowSet& r, int m, long long i, float& x, float& y, float& z) {
+  if (i >= counted_length(r.count, r.n)) return false;
+  const float* p = r.points + ((long long)(r.Mq == 1 ? 0 : m) * r.n + i) * 3;
+  x = p[0], y = p[1], z = p[2];
+  if (!nn_finite(x, y, z)) return false;
+  return !r.labels || r.labels[i] >= 0;
+}
+
 struct NnArgs {
   CellList list;
-  const float* queries;       // [Mq,n,3]
-  const int* count;           // [1] or null
-  const int* labels;          // [n] or null
-  int Mq, M, n;
+  RowSet rows;                // the queries
   float max_distance, max_d2;
   int* index;                 // [M,n]
   float* distance2;           // [M,n]
   int* matched;               // [M,n,3] (the bits of the floats)
   int* found;                 // [M]
 };
-
-__device__ __forceinline__ bool nn_finite(float x, float y, float z) {
-  return fabsf(x) < INFINITY && fabsf(y) < INFINITY && fabsf(z) < INFINITY;  // (NaN compares false)
-}
 
 __device__ __forceinline__ int nn_cell_axis(float p, float origin, float inv_cell, int dim) {
   const float f = floorf((p - origin) * inv_cell);
@@ -4924,22 +4939,17 @@ __device__ __forceinline__ bool cell_ring(const CellList& l, long long cells, in
 struct CellQuery {
   long long i;
   bool live;      // i < n
-  bool searched;  // below the count and finite (rows from the count on are not read)
+  bool searched;  // read by row_read
   float x, y, z;
 };
 
 template <bool WAVE>
-__device__ __forceinline__ CellQuery cell_query(const float* queries, const int* count, int Mq, int n, int m) {
+__device__ __forceinline__ CellQuery cell_query(const RowSet& rows, int m) {
   CellQuery q{WAVE ? (long long)blockIdx.x * (NJF_NN_THREADS / 64) + (threadIdx.x >> 6)
                    : (long long)blockIdx.x * NJF_NN_THREADS + threadIdx.x,
               false, false, 0.f, 0.f, 0.f};
-  q.live = q.i < n;
-  q.searched = q.live && q.i < counted_length(count, n);
-  if (q.searched) {
-    const float* p = queries + ((long long)(Mq == 1 ? 0 : m) * n + q.i) * 3;
-    q.x = p[0], q.y = p[1], q.z = p[2];
-    q.searched = nn_finite(q.x, q.y, q.z);
-  }
+  q.live = q.i < rows.n;
+  q.searched = q.live && row_read(rows, m, q.i, q.x, q.y, q.z);
   return q;
 }
 
@@ -4954,8 +4964,21 @@ struct NnBest {
   int j, x, y, z;  // the record's index and the bits of its coordinates
 };
 
+#define NJF_NN_NO_INDEX 0x7fffffff  // every index j of a record or a frame point lies below it
+__device__ __forceinline__ NnBest nn_none() { return NnBest{INFINITY, NJF_NN_NO_INDEX, 0, 0, 0}; }
+
 __device__ __forceinline__ void nn_take(NnBest& b, float d2, int j, int x, int y, int z) {
   if (d2 < b.d2 || (d2 == b.d2 && j < b.j)) b = NnBest{d2, j, x, y, z};
+}
+
+// the match of one row: the best, or where it is not accepted -1, +inf and NaN
+__device__ __forceinline__ void match_store(int* index, float* distance2, int* matched, long long row, bool ok, const NnBest& b) {
+  const int nan = 0x7fc00000;
+  index[row] = ok ? b.j : -1;
+  distance2[row] = ok ? b.d2 : INFINITY;
+  matched[row * 3] = ok ? b.x : nan;
+  matched[row * 3 + 1] = ok ? b.y : nan;
+  matched[row * 3 + 2] = ok ? b.z : nan;
 }
 
 // the lanes of the wave form agree on the best after every ring
@@ -4963,11 +4986,10 @@ template <bool WAVE>
 __global__ void __launch_bounds__(NJF_NN_THREADS) nn_query_kernel(NnArgs a) {
   const int lane = threadIdx.x & 63;
   const int m = blockIdx.y;
-  CellQuery q = cell_query<WAVE>(a.queries, a.count, a.Mq, a.n, m);
-  if (q.searched && a.labels) q.searched = a.labels[q.i] >= 0;
+  const CellQuery q = cell_query<WAVE>(a.rows, m);
   const long long i = q.i;
   const bool live = q.live, searched = q.searched;
-  NnBest b{INFINITY, 0x7fffffff, 0, 0, 0};
+  NnBest b = nn_none();
   if (searched) {
     int cx, cy, cz;
     nn_cell(a.list, q.x, q.y, q.z, cx, cy, cz);
@@ -4990,16 +5012,8 @@ __global__ void __launch_bounds__(NJF_NN_THREADS) nn_query_kernel(NnArgs a) {
     }
   }
   const bool writer = live && (!WAVE || lane == 0);
-  const bool ok = writer && searched && b.j != 0x7fffffff && b.d2 <= a.max_d2;
-  if (writer) {
-    const long long row = (long long)m * a.n + i;
-    const int nan = 0x7fc00000;
-    a.index[row] = ok ? b.j : -1;
-    a.distance2[row] = ok ? b.d2 : INFINITY;
-    a.matched[row * 3] = ok ? b.x : nan;
-    a.matched[row * 3 + 1] = ok ? b.y : nan;
-    a.matched[row * 3 + 2] = ok ? b.z : nan;
-  }
+  const bool ok = writer && searched && b.j != NJF_NN_NO_INDEX && b.d2 <= a.max_d2;
+  if (writer) match_store(a.index, a.distance2, a.matched, (long long)m * a.rows.n + i, ok, b);
   const int accepted = __popcll(__ballot(ok));
   if (lane == 0 && accepted) atomicAdd(&a.found[m], accepted);
 }
@@ -5011,10 +5025,9 @@ __global__ void __launch_bounds__(NJF_NN_THREADS) nn_query_kernel(NnArgs a) {
 // scheduling; integer sums do not.  A second launch turns the sums into a covariance and takes its eigenvectors in double.
 struct NrmArgs {
   CellList list;           // (the finish reads none of it)
-  const float* queries;    // [Mq,n,3]
-  const int* count;        // [1] or null
+  RowSet rows;             // the queries; labels null
   const float* viewpoint;  // [Mv,3] or null
-  int Mq, Mv, M, n;
+  int Mv;
   float r2;                // (float)radius * (float)radius
   int rings;               // R
   double scale;            // 2^18 / (double)(float)radius
@@ -5032,7 +5045,7 @@ template <bool WAVE>
 __global__ void __launch_bounds__(NJF_NN_THREADS) __attribute__((amdgpu_waves_per_eu(1, 7))) nrm_moments_kernel(NrmArgs a) {
   const int lane = threadIdx.x & 63;
   const int m = blockIdx.y;
-  const CellQuery q = cell_query<WAVE>(a.queries, a.count, a.Mq, a.n, m);
+  const CellQuery q = cell_query<WAVE>(a.rows, m);
   const long long i = q.i;
   const bool live = q.live;
   long long sum[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -5064,7 +5077,7 @@ __global__ void __launch_bounds__(NJF_NN_THREADS) __attribute__((amdgpu_waves_pe
 #pragma unroll
       for (int e = 0; e < 10; ++e) sum[e] += shfl_xor_i64(sum[e], o);
   if (live && (!WAVE || lane == 0)) {
-    long long* out = a.moments + ((long long)m * a.n + i) * 10;
+    long long* out = a.moments + ((long long)m * a.rows.n + i) * 10;
 #pragma unroll
     for (int e = 0; e < 10; ++e) out[e] = sum[e];
   }
@@ -5096,13 +5109,13 @@ __device__ __forceinline__ void nrm_rotate(double& app, double& aqq, double& apq
 __global__ void __launch_bounds__(NJF_NN_THREADS) nrm_finish_kernel(NrmArgs a) {
   const int m = blockIdx.y;
   const long long i = (long long)blockIdx.x * NJF_NN_THREADS + threadIdx.x;
-  if (i >= a.n) return;
-  const long long row = (long long)m * a.n + i;
+  if (i >= a.rows.n) return;
+  const long long row = (long long)m * a.rows.n + i;
   const double nan = __longlong_as_double(0x7ff8000000000000LL);
   long long N = 0;
   double lam[3] = {nan, nan, nan}, nrm[3] = {nan, nan, nan};
   bool have = false;
-  if (i < counted_length(a.count, a.n)) {  // (rows from the count on are not read)
+  if (i < counted_length(a.rows.count, a.rows.n)) {  // (rows from the count on are not read)
     const long long* s = a.moments + row * 10;
     N = s[0];
     if (N >= a.min_neighbours) {
@@ -5148,7 +5161,7 @@ __global__ void __launch_bounds__(NJF_NN_THREADS) nrm_finish_kernel(NrmArgs a) {
           const float* v = a.viewpoint + (long long)(a.Mv == 1 ? 0 : m) * 3;
           const float vx = v[0], vy = v[1], vz = v[2];
           if (nn_finite(vx, vy, vz)) {
-            const float* q = a.queries + ((long long)(a.Mq == 1 ? 0 : m) * a.n + i) * 3;
+            const float* q = a.rows.points + ((long long)(a.rows.Mq == 1 ? 0 : m) * a.rows.n + i) * 3;
             seen = true;
             toward = (v0 * ((double)vx - (double)q[0]) + v1 * ((double)vy - (double)q[1])) + v2 * ((double)vz - (double)q[2]);
           }
@@ -7739,12 +7752,7 @@ extern "C" int njf_field_nearest(const float* observed, const int* observed_coun
   const bool build = phases & NJF_FIELD_NEAREST_BUILD, query = phases & NJF_FIELD_NEAREST_QUERY;
   if (!workspace || (build && !observed) || (query && (!found || (n > 0 && (!queries || !index || !distance2 || !matched)))))
     return NJF_E_NULL;
-  a.queries = queries;
-  a.count = count;
-  a.labels = labels;
-  a.Mq = num_queries;
-  a.M = num_problems;
-  a.n = n;
+  a.rows = RowSet{queries, count, labels, num_queries, n};
   a.max_d2 = a.max_distance * a.max_distance;
   a.index = index;
   a.distance2 = distance2;
@@ -7797,13 +7805,9 @@ extern "C" int njf_field_normals(const float* observed, const int* observed_coun
   hipStream_t s = (hipStream_t)stream;
   if (build && (rc = cell_list_build(a.list, observed, observed_count, s))) return rc;
   if (n == 0 || !(sums || finish)) return NJF_OK;
-  a.queries = queries;
-  a.count = count;
+  a.rows = RowSet{queries, count, nullptr, num_queries, n};
   a.viewpoint = viewpoint;
-  a.Mq = num_queries;
   a.Mv = num_viewpoints;
-  a.M = num_problems;
-  a.n = n;
   a.r2 = reach * reach;
   a.rings = 1;  // the smallest r >= 1 whose rings beyond it hold nothing within the radius: nn_query_kernel's second stop test
   while (a.rings < NJF_FIELD_NEAREST_MAX_RINGS && !(((float)a.rings - 0.0078125f) * a.list.cell > reach)) ++a.rings;
@@ -7890,17 +7894,21 @@ extern "C" int njf_field_voxels(const float* points, const int* points_count, in
 // The key image holds (bits(z) << 32) | row per pixel, cleared to all ones; z > near >= 0 is finite, so the bits order as the
 // floats do and a 64-bit unsigned minimum picks the smallest z, ties to the lowest row, in any order of arrival.  The splat and the
 // test project through the one function below, so a row's own pixel is the same in both.
+// The pinhole cameras of njf_field_visible, njf_field_frame and njf_field_tsdf, and the one projection through them.
+struct ViewSet {
+  const float* k;    // [V,3,3]
+  const float* w2c;  // [V,4,4]
+  int V, H, W;
+  long long pixels;  // H * W
+  float near;
+};
+
 struct VisArgs {
-  const float* points;  // [Mq,n,3]
-  const int* count;     // [1] or NULL
-  const int* labels;    // [n] or NULL
-  const float* k;       // [V,3,3]
-  const float* w2c;     // [V,4,4]
-  int Mq, M, V, n, H, W, f;
-  long long pixels;     // H * W
-  long long total;      // M * V * H * W < 2^31
+  RowSet rows;
+  ViewSet views;
+  int f;
   unsigned chunks;      // workgroups of the resolve per image
-  float near, tolerance;
+  float tolerance;
   unsigned long long* keys;  // [M,V,H,W]
   float* depth;         // [M,V,H,W]
   int* index;           // [M,V,H,W]
@@ -7918,21 +7926,17 @@ struct VisPixel {
   bool inside;        // projectable and 0 <= col < W, 0 <= row < H
 };
 
-// the READ ROW of njf_field_nearest: below the count, finite, and of a label >= 0
-__device__ __forceinline__ bool vis_read(const VisArgs& a, int m, long long i, float& x, float& y, float& z) {
-  if (i >= counted_length(a.count, a.n)) return false;
-  const float* p = a.points + ((long long)(a.Mq == 1 ? 0 : m) * a.n + i) * 3;
-  x = p[0], y = p[1], z = p[2];
-  if (!nn_finite(x, y, z)) return false;
-  return !a.labels || a.labels[i] >= 0;
+// the camera-space z of a world point in the view whose w2c begins at w
+__device__ __forceinline__ float camera_z(const float* w, float x, float y, float z) {
+  return fmaf(w[10], z, fmaf(w[9], y, fmaf(w[8], x, w[11])));
 }
 
-__device__ __forceinline__ VisPixel vis_project(const VisArgs& a, int v, float x, float y, float z) {
+__device__ __forceinline__ VisPixel vis_project(const ViewSet& a, int v, float x, float y, float z) {
   const float* w = a.w2c + v * 16;
   const float* k = a.k + v * 9;
   const float xc = fmaf(w[2], z, fmaf(w[1], y, fmaf(w[0], x, w[3])));
   const float yc = fmaf(w[6], z, fmaf(w[5], y, fmaf(w[4], x, w[7])));
-  const float zc = fmaf(w[10], z, fmaf(w[9], y, fmaf(w[8], x, w[11])));
+  const float zc = camera_z(w, x, y, z);
   VisPixel p;
   p.z = zc;
   p.projectable = fabsf(zc) < INFINITY && zc > a.near;
@@ -7951,20 +7955,21 @@ template <bool PRE>
 __global__ void __launch_bounds__(256) vis_splat_kernel(VisArgs a) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   const int v = blockIdx.y, m = blockIdx.z;
-  if (i >= a.n) return;
+  const ViewSet& s = a.views;
+  if (i >= a.rows.n) return;
   float x, y, z;
-  if (!vis_read(a, m, i, x, y, z)) return;
-  const VisPixel p = vis_project(a, v, x, y, z);
+  if (!row_read(a.rows, m, i, x, y, z)) return;
+  const VisPixel p = vis_project(s, v, x, y, z);
   const float f = (float)a.f;
   // a footprint pixel inside the image: judged in float, before any conversion (NaN and infinities compare false)
-  if (!p.projectable || !(p.col >= -f && p.col < (float)a.W + f && p.row >= -f && p.row < (float)a.H + f)) return;
+  if (!p.projectable || !(p.col >= -f && p.col < (float)s.W + f && p.row >= -f && p.row < (float)s.H + f)) return;
   const int col = (int)p.col, row = (int)p.row;  // |col| <= W + 4, |row| <= H + 4: exact
   const unsigned long long key = ((unsigned long long)__float_as_uint(p.z) << 32) | (unsigned)i;
-  unsigned long long* image = a.keys + ((long long)m * a.V + v) * a.pixels;
-  const int r0 = max(row - a.f, 0), r1 = min(row + a.f, a.H - 1), c0 = max(col - a.f, 0), c1 = min(col + a.f, a.W - 1);
+  unsigned long long* image = a.keys + ((long long)m * s.V + v) * s.pixels;
+  const int r0 = max(row - a.f, 0), r1 = min(row + a.f, s.H - 1), c0 = max(col - a.f, 0), c1 = min(col + a.f, s.W - 1);
   for (int r = r0; r <= r1; ++r)
     for (int c = c0; c <= c1; ++c) {
-      unsigned long long* slot = image + (long long)r * a.W + c;
+      unsigned long long* slot = image + (long long)r * s.W + c;
       if (PRE && *slot <= key) continue;
       atomicMin(slot, key);
     }
@@ -7984,8 +7989,8 @@ __global__ void __launch_bounds__(256) vis_resolve_kernel(VisArgs a) {
   for (int j = 0; j < NJF_VIS_RESOLVE_PIXELS / 256; ++j) {
     const long long r = first + j * 256 + threadIdx.x;
     bool won = false;
-    if (r < a.pixels) {
-      const long long p = (long long)image * a.pixels + r;  // < M * V * H * W
+    if (r < a.views.pixels) {
+      const long long p = (long long)image * a.views.pixels + r;  // < M * V * H * W
       const unsigned long long key = a.keys[p];
       won = key != ~0ull;
       a.depth[p] = won ? __uint_as_float((unsigned)(key >> 32)) : 0.0f;
@@ -8005,38 +8010,70 @@ __global__ void __launch_bounds__(256) vis_test_kernel(VisArgs a) {
   __syncthreads();
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   const int m = blockIdx.y;
-  const bool live = i < a.n;
+  const ViewSet& s = a.views;
+  const bool live = i < a.rows.n;
   unsigned seen = 0;
   if (live) {
     float x = 0.f, y = 0.f, z = 0.f;
-    const bool read = vis_read(a, m, i, x, y, z);
-    for (int v = 0; v < a.V; ++v) {
+    const bool read = row_read(a.rows, m, i, x, y, z);
+    for (int v = 0; v < s.V; ++v) {
       int own = -1;
       float zc = __int_as_float(0x7fc00000);
       if (read) {
-        const VisPixel p = vis_project(a, v, x, y, z);
+        const VisPixel p = vis_project(s, v, x, y, z);
         zc = p.z;
         if (p.inside) {
-          own = (int)p.row * a.W + (int)p.col;
-          const float zmin = a.depth[((long long)m * a.V + v) * a.pixels + own];
+          own = (int)p.row * s.W + (int)p.col;
+          const float zmin = a.depth[((long long)m * s.V + v) * s.pixels + own];
           if (__fsub_rn(p.z, zmin) <= __fmul_rn(a.tolerance, zmin)) seen |= 1u << v;
         }
       }
-      const long long o = ((long long)m * a.V + v) * a.n + i;
+      const long long o = ((long long)m * s.V + v) * a.rows.n + i;
       a.pixel[o] = own;
       a.z[o] = zc;
     }
     const float nan = __int_as_float(0x7fc00000);
-    float* c = a.culled + ((long long)m * a.n + i) * 3;
+    float* c = a.culled + ((long long)m * a.rows.n + i) * 3;
     c[0] = seen ? x : nan;
     c[1] = seen ? y : nan;
     c[2] = seen ? z : nan;
-    a.seen[(long long)m * a.n + i] = (int)seen;
+    a.seen[(long long)m * a.rows.n + i] = (int)seen;
   }
   const int n = __popcll(__ballot(seen != 0));  // a workgroup lies in one problem: one atomic for its four waves
   if ((threadIdx.x & 63) == 0 && n) atomicAdd(&block_seen, n);
   __syncthreads();
   if (threadIdx.x == 0 && block_seen) atomicAdd(&a.visible[m], block_seen);
+}
+
+// The checks that njf_field_visible, njf_field_frame, njf_field_tsdf and njf_field_tsdf_sample share.  These entries judge in
+// classes -- every NJF_E_NULL, then every NJF_E_VALUE, then every NJF_E_SHAPE --, so the problems with their rows and the views
+// have one helper per class each; inside a class the order cannot show.
+static bool one_or_each(int sets, int num_problems) { return sets == 1 || sets == num_problems; }
+static bool nonnegative_finite(float v) { return v >= 0.0f && v < INFINITY; }  // (NaN: false)
+
+// NJF_E_VALUE: M in its range; Mq, Mo, Mf one set for all problems or one each
+static int problems_value(int num_problems, int sets_a = 1, int sets_b = 1) {
+  if (num_problems < 1 || num_problems > NJF_FIELD_POSE_MAX_COMMANDS) return NJF_E_VALUE;
+  return one_or_each(sets_a, num_problems) && one_or_each(sets_b, num_problems) ? NJF_OK : NJF_E_VALUE;
+}
+
+// NJF_E_VALUE: V in its range; near and the tolerance finite and not negative
+static int views_value(int views, float near, float tolerance = 0.0f) {
+  if (views < 1 || views > NJF_FIELD_VISIBLE_MAX_VIEWS) return NJF_E_VALUE;
+  return nonnegative_finite(near) && nonnegative_finite(tolerance) ? NJF_OK : NJF_E_VALUE;
+}
+
+// NJF_E_SHAPE: n rows with `per_row` outputs each (M, or M V) stay below 2^31
+static int rows_shape(int n, long long per_row) { return n < 0 || per_row * n >= (1LL << 31) ? NJF_E_SHAPE : NJF_OK; }
+
+// NJF_E_SHAPE: an image, and the V images of `sets` problems, stay below 2^31 pixels
+static int views_shape(long long sets, int views, int height, int width) {
+  if (height < 1 || width < 1 || (long long)height * width >= (1LL << 31)) return NJF_E_SHAPE;
+  return sets * views * height * width >= (1LL << 31) ? NJF_E_SHAPE : NJF_OK;
+}
+
+static ViewSet view_set(const float* k, const float* w2c, int views, int height, int width, float near) {
+  return ViewSet{k, w2c, views, height, width, (long long)height * width, near};
 }
 
 extern "C" int njf_field_visible(const float* points, const int* count, const int* labels, int num_queries, int n,
@@ -8052,34 +8089,17 @@ extern "C" int njf_field_visible(const float* points, const int* count, const in
       ((resolve || test) && !depth) || (resolve && (!index || !covered)) ||
       (test && (!seen || !culled || !visible || !pixel || !z)))
     return NJF_E_NULL;
-  if (!known) return NJF_E_VALUE;
-  if (num_problems < 1 || num_problems > NJF_FIELD_POSE_MAX_COMMANDS) return NJF_E_VALUE;
-  if (num_queries != 1 && num_queries != num_problems) return NJF_E_VALUE;
-  if (views < 1 || views > NJF_FIELD_VISIBLE_MAX_VIEWS) return NJF_E_VALUE;
+  if (!known || problems_value(num_problems, num_queries) || views_value(views, near, tolerance)) return NJF_E_VALUE;
   if (footprint < 0 || footprint > NJF_FIELD_VISIBLE_MAX_FOOTPRINT) return NJF_E_VALUE;
-  if (!(near >= 0.0f) || !(near < INFINITY) || !(tolerance >= 0.0f) || !(tolerance < INFINITY)) return NJF_E_VALUE;
-  if (n < 0 || height < 1 || width < 1) return NJF_E_SHAPE;
   const long long images = (long long)num_problems * views;
-  if ((long long)height * width >= (1LL << 31) || images * height * width >= (1LL << 31) || images * n >= (1LL << 31))
-    return NJF_E_SHAPE;
+  if (views_shape(num_problems, views, height, width) || rows_shape(n, images)) return NJF_E_SHAPE;
   if ((splat || resolve) && workspace_words < NJF_FIELD_VISIBLE_WORKSPACE(num_problems, views, height, width)) return NJF_E_SHAPE;
   VisArgs a;
-  a.points = points;
-  a.count = count;
-  a.labels = labels;
-  a.k = k;
-  a.w2c = w2c;
-  a.Mq = num_queries;
-  a.M = num_problems;
-  a.V = views;
-  a.n = n;
-  a.H = height;
-  a.W = width;
+  a.rows = RowSet{points, count, labels, num_queries, n};
+  a.views = view_set(k, w2c, views, height, width, near);
   a.f = footprint;
-  a.pixels = (long long)height * width;
-  a.total = images * a.pixels;
-  a.chunks = (unsigned)((a.pixels + NJF_VIS_RESOLVE_PIXELS - 1) / NJF_VIS_RESOLVE_PIXELS);
-  a.near = near;
+  const long long pixels = a.views.pixels;
+  a.chunks = (unsigned)((pixels + NJF_VIS_RESOLVE_PIXELS - 1) / NJF_VIS_RESOLVE_PIXELS);
   a.tolerance = tolerance;
   a.keys = (unsigned long long*)(((uintptr_t)workspace + 7) & ~(uintptr_t)7);  // the spare word of the workspace pays for this
   a.depth = depth;
@@ -8095,7 +8115,7 @@ extern "C" int njf_field_visible(const float* points, const int* count, const in
   int rc;
   const unsigned row_blocks = (unsigned)(((long long)n + 255) / 256);
   if (splat) {
-    if ((e = hipMemsetAsync(a.keys, 0xff, (size_t)a.total * sizeof(unsigned long long), s)) != hipSuccess) return (int)e;
+    if ((e = hipMemsetAsync(a.keys, 0xff, (size_t)(images * pixels) * sizeof(unsigned long long), s)) != hipSuccess) return (int)e;
     if (n > 0) {
       const dim3 grid(row_blocks, (unsigned)views, (unsigned)num_problems);
       if (phases & NJF_FIELD_VISIBLE_DIRECT)
@@ -8121,15 +8141,18 @@ extern "C" int njf_field_visible(const float* points, const int* count, const in
 }
 
 // ---- posed rows against a depth frame by projection (njf_field_frame) --------------------------------------------
-// A row is read and projected by vis_read and vis_project -- njf_field_visible's own, so pixel and z are its bits --, classified
+// A row is read and projected by row_read and vis_project -- njf_field_visible's own, so pixel and z are its bits --, classified
 // against the frame's point at its own pixel, and matched to the closest frame point in the pixel window around it.  The frame is
 // njf_field_depth_points' organised cloud: the point of pixel (row, col) of view v is row v*H*W + row*W + col, NaN = none.
 struct FrmArgs {
-  VisArgs vis;         // points, count, labels, k, w2c, Mq, M, V, n, H, W, pixels, near, tolerance, pixel, z; the rest is not read
+  RowSet rows;
+  ViewSet views;
   const float* frame;  // [Mo, V*H*W, 3]
   int Mo, reach;
   bool keep_hidden;
-  float max_d2;
+  float tolerance, max_d2;
+  int* pixel;          // [M,V,n]
+  float* z;            // [M,V,n]
   int* state;          // [M,V,n]
   int* index;          // [M,n]
   float* distance2;    // [M,n]
@@ -8146,16 +8169,16 @@ static_assert(NJF_FIELD_VISIBLE_MAX_VIEWS < 64, "a row's states are tallied in f
 // for its four waves.  (A wave per row, the lanes sharing the window, was built and measured: DESIGN.md section 26.)
 __global__ void __launch_bounds__(NJF_FRM_THREADS) frm_match_kernel(FrmArgs a) {
   __shared__ int part[NJF_FIELD_FRAME_STATES + 1][NJF_FRM_WAVES];
-  const VisArgs& s = a.vis;
+  const ViewSet& s = a.views;
   const long long i = (long long)blockIdx.x * NJF_FRM_THREADS + threadIdx.x;
   const int m = blockIdx.y;
-  const bool live = i < s.n;
-  NnBest b{INFINITY, 0x7fffffff, 0, 0, 0};                 // (j < V H W < 2^31 - 1 beats it at d2 = +inf)
+  const bool live = i < a.rows.n;
+  NnBest b = nn_none();                                    // (j < V H W < 2^31 - 1 beats it at d2 = +inf)
   unsigned tally = 0;                                      // 6 bits per state: the views in which the row has it (<= 32)
   const float* frame = a.frame + (long long)(a.Mo == 1 ? 0 : m) * s.V * s.pixels * 3;
   if (live) {
     float x = 0.f, y = 0.f, z = 0.f;
-    const bool read = vis_read(s, m, i, x, y, z);
+    const bool read = row_read(a.rows, m, i, x, y, z);
     for (int v = 0; v < s.V; ++v) {
       int own = -1, st = NJF_FIELD_FRAME_OUTSIDE;
       float zc = __int_as_float(0x7fc00000);
@@ -8171,9 +8194,8 @@ __global__ void __launch_bounds__(NJF_FRM_THREADS) frm_match_kernel(FrmArgs a) {
           if (!nn_finite(fx, fy, fz)) {
             st = NJF_FIELD_FRAME_NO_RETURN;
           } else {
-            const float* w = s.w2c + v * 16;
-            const float zo = fmaf(w[10], fz, fmaf(w[9], fy, fmaf(w[8], fx, w[11])));
-            const float slack = __fmul_rn(s.tolerance, zo);
+            const float zo = camera_z(s.w2c + v * 16, fx, fy, fz);
+            const float slack = __fmul_rn(a.tolerance, zo);
             st = __fsub_rn(zo, zc) > slack ? NJF_FIELD_FRAME_IN_FRONT
                                            : __fsub_rn(zc, zo) > slack ? NJF_FIELD_FRAME_BEHIND : NJF_FIELD_FRAME_ON;
           }
@@ -8193,23 +8215,15 @@ __global__ void __launch_bounds__(NJF_FRM_THREADS) frm_match_kernel(FrmArgs a) {
           }
         }
       }
-      const long long o = ((long long)m * s.V + v) * s.n + i;
-      s.pixel[o] = own;
-      s.z[o] = zc;
+      const long long o = ((long long)m * s.V + v) * a.rows.n + i;
+      a.pixel[o] = own;
+      a.z[o] = zc;
       a.state[o] = st;
       tally += 1u << (6 * st);
     }
   }
-  const bool ok = live && b.j != 0x7fffffff && b.d2 <= a.max_d2;
-  if (live) {
-    const long long row = (long long)m * s.n + i;
-    const int nan = 0x7fc00000;
-    a.index[row] = ok ? b.j : -1;
-    a.distance2[row] = ok ? b.d2 : INFINITY;
-    a.matched[row * 3] = ok ? b.x : nan;
-    a.matched[row * 3 + 1] = ok ? b.y : nan;
-    a.matched[row * 3 + 2] = ok ? b.z : nan;
-  }
+  const bool ok = live && b.j != NJF_NN_NO_INDEX && b.d2 <= a.max_d2;
+  if (live) match_store(a.index, a.distance2, a.matched, (long long)m * a.rows.n + i, ok, b);
 #pragma unroll
   for (int c = 0; c < NJF_FIELD_FRAME_STATES; ++c) {
     const int t = block_sum((int)((tally >> (6 * c)) & 63u), part[c]);
@@ -8227,41 +8241,22 @@ extern "C" int njf_field_frame(const float* points, const int* count, const int*
   const bool known = phases == NJF_FIELD_FRAME_MATCH || phases == (NJF_FIELD_FRAME_MATCH | NJF_FIELD_FRAME_KEEP_HIDDEN);
   if (!points || !frame || !k || !w2c || !pixel || !z || !state || !index || !distance2 || !matched || !found || !states)
     return NJF_E_NULL;
-  if (!known) return NJF_E_VALUE;
-  if (num_problems < 1 || num_problems > NJF_FIELD_POSE_MAX_COMMANDS) return NJF_E_VALUE;
-  if (num_queries != 1 && num_queries != num_problems) return NJF_E_VALUE;
-  if (num_frames != 1 && num_frames != num_problems) return NJF_E_VALUE;
-  if (views < 1 || views > NJF_FIELD_VISIBLE_MAX_VIEWS) return NJF_E_VALUE;
+  if (!known || problems_value(num_problems, num_queries, num_frames) || views_value(views, near, tolerance)) return NJF_E_VALUE;
   if (reach < 0 || reach > NJF_FIELD_FRAME_MAX_REACH) return NJF_E_VALUE;
-  if (!(near >= 0.0f) || !(near < INFINITY) || !(tolerance >= 0.0f) || !(tolerance < INFINITY)) return NJF_E_VALUE;
   const float limit = (float)max_distance;
-  if (!(limit >= 0.0f) || !(limit < INFINITY)) return NJF_E_VALUE;
-  if (n < 0 || height < 1 || width < 1) return NJF_E_SHAPE;
-  if ((long long)height * width >= (1LL << 31) || (long long)num_frames * views * height * width >= (1LL << 31) ||
-      (long long)num_problems * views * n >= (1LL << 31))
-    return NJF_E_SHAPE;
-  FrmArgs a{};
-  a.vis.points = points;
-  a.vis.count = count;
-  a.vis.labels = labels;
-  a.vis.k = k;
-  a.vis.w2c = w2c;
-  a.vis.Mq = num_queries;
-  a.vis.M = num_problems;
-  a.vis.V = views;
-  a.vis.n = n;
-  a.vis.H = height;
-  a.vis.W = width;
-  a.vis.pixels = (long long)height * width;
-  a.vis.near = near;
-  a.vis.tolerance = tolerance;
-  a.vis.pixel = pixel;
-  a.vis.z = z;
+  if (!nonnegative_finite(limit)) return NJF_E_VALUE;
+  if (views_shape(num_frames, views, height, width) || rows_shape(n, (long long)num_problems * views)) return NJF_E_SHAPE;
+  FrmArgs a;
+  a.rows = RowSet{points, count, labels, num_queries, n};
+  a.views = view_set(k, w2c, views, height, width, near);
   a.frame = frame;
   a.Mo = num_frames;
   a.reach = reach;
   a.keep_hidden = (phases & NJF_FIELD_FRAME_KEEP_HIDDEN) != 0;
+  a.tolerance = tolerance;
   a.max_d2 = limit * limit;
+  a.pixel = pixel;
+  a.z = z;
   a.state = state;
   a.index = index;
   a.distance2 = distance2;
@@ -8283,9 +8278,9 @@ extern "C" int njf_field_frame(const float* points, const int* count, const int*
 
 // ---- depth frames fused into a truncated signed distance on a grid, and sampled at rows (njf_field_tsdf) --------
 // A node is projected by vis_project -- njf_field_visible's own, so its pixel and z are the bits njf_field_visible reports for the
-// node as a row --, and a row of the sampler is read by vis_read.
+// node as a row --, and a row of the sampler is read by row_read.
 struct TsdfArgs {
-  VisArgs vis;             // k, w2c, V, H, W, pixels, near (fuse); points, count, labels, Mq, n (sample); the rest is not read
+  ViewSet views;
   NjfFieldGrid grid;
   int nodes;               // N
   const float* depth;      // [M,V,H,W]
@@ -8304,7 +8299,7 @@ struct TsdfArgs {
 // the outputs.  A workgroup lies in one problem: one atomic for its four waves.
 __global__ void __launch_bounds__(NJF_TSDF_THREADS) tsdf_fuse_kernel(TsdfArgs a) {
   __shared__ int part[NJF_TSDF_WAVES];
-  const VisArgs& s = a.vis;
+  const ViewSet& s = a.views;
   const long long g = (long long)blockIdx.x * NJF_TSDF_THREADS + threadIdx.x;
   const int m = blockIdx.y;
   int has = 0;
@@ -8357,26 +8352,13 @@ extern "C" int njf_field_tsdf(const NjfFieldGrid* grid, const float* depth, int 
                               const float* values_in, const float* weight_in, float* values, float* weight, int* known,
                               void* stream) {
   if (!grid || !depth || !k || !w2c || !values || !weight || !known || (!values_in != !weight_in)) return NJF_E_NULL;
-  if (num_problems < 1 || num_problems > NJF_FIELD_POSE_MAX_COMMANDS) return NJF_E_VALUE;
-  if (views < 1 || views > NJF_FIELD_VISIBLE_MAX_VIEWS) return NJF_E_VALUE;
-  if (!(near >= 0.0f) || !(near < INFINITY) || !(far > near)) return NJF_E_VALUE;
+  if (problems_value(num_problems) || views_value(views, near) || !(far > near)) return NJF_E_VALUE;
   if (!(truncation > 0.0f) || !(truncation < INFINITY) || !(max_weight > 0.0f)) return NJF_E_VALUE;
-  if (height < 1 || width < 1) return NJF_E_SHAPE;
   long long nodes;
-  int rc;
-  if ((rc = check_tsdf_grid(grid, 1, nodes))) return rc;
-  if ((long long)height * width >= (1LL << 31) || (long long)num_problems * views * height * width >= (1LL << 31) ||
-      num_problems * nodes >= (1LL << 31))
-    return NJF_E_SHAPE;
-  TsdfArgs a{};
-  a.vis.k = k;
-  a.vis.w2c = w2c;
-  a.vis.M = num_problems;
-  a.vis.V = views;
-  a.vis.H = height;
-  a.vis.W = width;
-  a.vis.pixels = (long long)height * width;
-  a.vis.near = near;
+  if (views_shape(num_problems, views, height, width) || check_tsdf_grid(grid, 1, nodes) || num_problems * nodes >= (1LL << 31))
+    return NJF_E_SHAPE;  // (with one node per axis allowed, the grid's faults are all of this class)
+  TsdfArgs a;
+  a.views = view_set(k, w2c, views, height, width, near);
   a.grid = *grid;
   a.nodes = (int)nodes;
   a.depth = depth;
@@ -8397,7 +8379,7 @@ extern "C" int njf_field_tsdf(const NjfFieldGrid* grid, const float* depth, int 
 }
 
 struct TsdfSampleArgs {
-  VisArgs vis;          // points, count, labels, Mq, n: what vis_read reads
+  RowSet rows;
   NjfFieldGrid grid;
   int Mf, nodes;
   const float* values;  // [Mf,N]
@@ -8413,7 +8395,7 @@ __device__ __forceinline__ float tsdf_lerp(float u, float w, float f) { return f
 // one lane per (m, i).  A workgroup lies in one problem: one atomic per counter for its four waves.
 __global__ void __launch_bounds__(NJF_TSDF_THREADS) tsdf_sample_kernel(TsdfSampleArgs a) {
   __shared__ int part[NJF_FIELD_TSDF_STATES][NJF_TSDF_WAVES];
-  const VisArgs& s = a.vis;
+  const RowSet& s = a.rows;
   const long long i = (long long)blockIdx.x * NJF_TSDF_THREADS + threadIdx.x;
   const int m = blockIdx.y;
   const bool live = i < s.n;
@@ -8422,7 +8404,7 @@ __global__ void __launch_bounds__(NJF_TSDF_THREADS) tsdf_sample_kernel(TsdfSampl
     const float nan = __int_as_float(0x7fc00000);
     float distance = nan, gx = nan, gy = nan, gz = nan;
     float x[3] = {0.f, 0.f, 0.f};
-    bool in = vis_read(s, m, i, x[0], x[1], x[2]);
+    bool in = row_read(s, m, i, x[0], x[1], x[2]);
     int cell[3];
     float f[3];
 #pragma unroll
@@ -8485,22 +8467,15 @@ extern "C" int njf_field_tsdf_sample(const float* points, const int* count, cons
                                      int num_problems, const NjfFieldGrid* grid, const float* values, const float* weight,
                                      int num_fields, int* state, float* distance, float* gradient, int* states, void* stream) {
   if (!points || !grid || !values || !weight || !state || !distance || !gradient || !states) return NJF_E_NULL;
-  if (num_problems < 1 || num_problems > NJF_FIELD_POSE_MAX_COMMANDS) return NJF_E_VALUE;
-  if (num_queries != 1 && num_queries != num_problems) return NJF_E_VALUE;
-  if (num_fields != 1 && num_fields != num_problems) return NJF_E_VALUE;
+  if (problems_value(num_problems, num_queries, num_fields)) return NJF_E_VALUE;
   for (int c = 0; c < 3; ++c)
     if (!(grid->step[c] > 0.0f) || !(grid->step[c] < INFINITY) || !(fabsf(grid->origin[c]) < INFINITY)) return NJF_E_VALUE;
   long long nodes;
   int rc;
   if ((rc = check_tsdf_grid(grid, 2, nodes))) return rc;
-  if (n < 0 || (long long)num_problems * n >= (1LL << 31) || num_fields * nodes >= (1LL << 31)) return NJF_E_SHAPE;
-  TsdfSampleArgs a{};
-  a.vis.points = points;
-  a.vis.count = count;
-  a.vis.labels = labels;
-  a.vis.Mq = num_queries;
-  a.vis.M = num_problems;
-  a.vis.n = n;
+  if (rows_shape(n, num_problems) || num_fields * nodes >= (1LL << 31)) return NJF_E_SHAPE;
+  TsdfSampleArgs a;
+  a.rows = RowSet{points, count, labels, num_queries, n};
   a.grid = *grid;
   a.Mf = num_fields;
   a.nodes = (int)nodes;

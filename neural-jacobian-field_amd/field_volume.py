@@ -387,6 +387,21 @@ class FieldTwists:
                                                                r[:, None, :].expand(-1, self.omega.shape[1], 3), dim=-1)
 
 
+def _check_labels(name: str, labels, n: int, optional: bool = False) -> None:
+    if optional and labels is None:
+        return
+    if not torch.is_tensor(labels) or labels.dtype != torch.int32 or tuple(labels.shape) != (n,):
+        raise ValueError(f"{name}: labels must be int32 [{n}]")
+
+
+def _posed_points(name: str, points, layout: str):
+    """``points`` fp32 ``[n, 3]`` or ``[<layout>, n, 3]`` as the 3-D tensor, and its ``(Mq, n)``."""
+    if not torch.is_tensor(points) or points.dtype != torch.float32 or points.dim() not in (2, 3) or points.shape[-1] != 3:
+        raise ValueError(f"{name}: points must be fp32 [n, 3] or [{layout}, n, 3]")
+    points = points if points.dim() == 3 else points[None]
+    return points, tuple(points.shape[:2])
+
+
 def _one_int32(name: str, what: str, t, like: torch.Tensor):
     if t is None:
         return None
@@ -416,8 +431,7 @@ def fit_twists(xyz: torch.Tensor, jacobian: torch.Tensor, labels: torch.Tensor, 
     a_dim = jacobian.shape[1]
     if a_dim > hip.MAX_ACTION_DIM:
         raise ValueError(f"{name}: at most {hip.MAX_ACTION_DIM} command channels (got {a_dim})")
-    if not torch.is_tensor(labels) or labels.dtype != torch.int32 or tuple(labels.shape) != (n,):
-        raise ValueError(f"{name}: labels must be int32 [{n}]")
+    _check_labels(name, labels, n)
     if not torch.is_tensor(parts) or parts.dtype != torch.int32 or parts.dim() != 1:
         raise ValueError(f"{name}: parts must be int32 [K]")
     k = parts.shape[0]
@@ -642,8 +656,7 @@ def _joints(name: str, grid: FieldGrid, index, labels, twists, batch, count, con
     if not torch.is_tensor(index) or index.dtype != torch.int32 or index.dim() != 1:
         raise ValueError(f"{name}: index must be int32 [n]")
     n = index.shape[0]
-    if not torch.is_tensor(labels) or labels.dtype != torch.int32 or tuple(labels.shape) != (n,):
-        raise ValueError(f"{name}: labels must be int32 [{n}]")
+    _check_labels(name, labels, n)
     if not isinstance(twists, FieldTwists):
         raise ValueError(f"{name}: twists must be a FieldTwists")
     parts = twists.labels
@@ -757,8 +770,7 @@ def _check_points(name: str, xyz, labels, jacobian, a_dim: int) -> int:
     if not torch.is_tensor(xyz) or xyz.dtype != torch.float32 or xyz.dim() != 2 or xyz.shape[1] != 3:
         raise ValueError(f"{name}: xyz must be fp32 [n, 3]")
     n = xyz.shape[0]
-    if not torch.is_tensor(labels) or labels.dtype != torch.int32 or tuple(labels.shape) != (n,):
-        raise ValueError(f"{name}: labels must be int32 [{n}]")
+    _check_labels(name, labels, n)
     if jacobian is not None and (not torch.is_tensor(jacobian) or jacobian.dtype != torch.float32
                                  or tuple(jacobian.shape) != (n, a_dim, 3)):
         raise ValueError(f"{name}: jacobian must be fp32 [{n}, {a_dim}, 3] or None")
@@ -1115,8 +1127,7 @@ def _check_nearest(name: str, observed, cells, max_distance, observed_count, cou
                          f"of {cell}); take a larger cell")
     _check_cloud_count(name, "observed_count", observed_count, mo)
     count = _one_int32(name, "count", count, like)
-    if labels is not None and (not torch.is_tensor(labels) or labels.dtype != torch.int32 or tuple(labels.shape) != (n,)):
-        raise ValueError(f"{name}: labels must be int32 [{n}]")
+    _check_labels(name, labels, n, optional=True)
     for what, v in (("observed", observed), ("observed_count", observed_count), ("labels", labels)):
         if v is not None and v.device != like.device:
             raise ValueError(f"{name}: {what} must live on the device of {of}")
@@ -1476,16 +1487,12 @@ def visible_rows(points: torch.Tensor, view: FieldView, *, labels: Optional[torc
     ``depth_points(kind="z")`` with the same cameras; ``culled`` goes into ``nearest_points`` as its queries.  The z-buffer is a
     64-bit integer minimum, so the order of the atomics cannot matter: equal bytes from call to call, no host read, capturable."""
     name = "visible_rows"
-    if not torch.is_tensor(points) or points.dtype != torch.float32 or points.dim() not in (2, 3) or points.shape[-1] != 3:
-        raise ValueError(f"{name}: points must be fp32 [n, 3] or [M, n, 3]")
-    points = points if points.dim() == 3 else points[None]
-    m, n = points.shape[:2]
+    points, (m, n) = _posed_points(name, points, "M")
     if not 1 <= m <= hip.FIELD_POSE_MAX_COMMANDS:
         raise ValueError(f"{name}: 1 to {hip.FIELD_POSE_MAX_COMMANDS} problems (got {m})")
     v, near, tolerance = _check_view(name, view, points, "points", m, n)
     count = _one_int32(name, "count", count, points)
-    if labels is not None and (not torch.is_tensor(labels) or labels.dtype != torch.int32 or tuple(labels.shape) != (n,)):
-        raise ValueError(f"{name}: labels must be int32 [{n}]")
+    _check_labels(name, labels, n, optional=True)
     if labels is not None and labels.device != points.device:
         raise ValueError(f"{name}: labels must live on the device of points")
     if points.device.type != "cuda":
@@ -1955,8 +1962,7 @@ def _check_frame(name: str, frame, view, max_distance, reach, tolerance, keep_hi
     if not isinstance(keep_hidden, bool):
         raise ValueError(f"{name}: keep_hidden must be a bool (got {keep_hidden})")
     count = _one_int32(name, "count", count, like)
-    if labels is not None and (not torch.is_tensor(labels) or labels.dtype != torch.int32 or tuple(labels.shape) != (n,)):
-        raise ValueError(f"{name}: labels must be int32 [{n}]")
+    _check_labels(name, labels, n, optional=True)
     for what, value in (("frame", frame), ("labels", labels)):
         if value is not None and value.device != like.device:
             raise ValueError(f"{name}: {what} must live on the device of {of}")
@@ -2003,10 +2009,7 @@ def frame_matches(points: torch.Tensor, frame: torch.Tensor, view: FieldView, ma
     ``view.tolerance`` are not read.  No cell list, no workspace, integer atomics only, no host read: equal bytes from call to
     call, capturable."""
     name = "frame_matches"
-    if not torch.is_tensor(points) or points.dtype != torch.float32 or points.dim() not in (2, 3) or points.shape[-1] != 3:
-        raise ValueError(f"{name}: points must be fp32 [n, 3] or [Mq, n, 3]")
-    points = points if points.dim() == 3 else points[None]
-    mq, n = points.shape[:2]
+    points, (mq, n) = _posed_points(name, points, "Mq")
     frame, m, v, near, tolerance, count = _check_frame(name, frame, view, max_distance, reach, tolerance, keep_hidden, count, labels, n,
                                                        mq, points, "points")
     if points.device.type != "cuda":
@@ -2237,10 +2240,7 @@ def sample_distance(points: torch.Tensor, field: FieldDistance, *, labels: Optio
     which points away from the surface, into free space.  ``FieldClearance.cost()`` ranks poses: a row in observed free space pays
     its distance to the surface.  One launch, integer atomics only, no host read: equal bytes from call to call, capturable."""
     name = "sample_distance"
-    if not torch.is_tensor(points) or points.dtype != torch.float32 or points.dim() not in (2, 3) or points.shape[-1] != 3:
-        raise ValueError(f"{name}: points must be fp32 [n, 3] or [Mq, n, 3]")
-    points = points if points.dim() == 3 else points[None]
-    mq, n = points.shape[:2]
+    points, (mq, n) = _posed_points(name, points, "Mq")
     if not isinstance(field, FieldDistance) or not isinstance(field.grid, FieldGrid):
         raise ValueError(f"{name}: field must be a FieldDistance")
     grid = field.grid
@@ -2261,8 +2261,7 @@ def sample_distance(points: torch.Tensor, field: FieldDistance, *, labels: Optio
     if m * n >= 2 ** 31:
         raise ValueError(f"{name}: M * n must stay below 2**31")
     count = _one_int32(name, "count", count, points)
-    if labels is not None and (not torch.is_tensor(labels) or labels.dtype != torch.int32 or tuple(labels.shape) != (n,)):
-        raise ValueError(f"{name}: labels must be int32 [{n}]")
+    _check_labels(name, labels, n, optional=True)
     for what, t in (("field.values", field.values), ("field.weight", field.weight), ("labels", labels)):
         if t is not None and t.device != points.device:
             raise ValueError(f"{name}: {what} must live on the device of points")

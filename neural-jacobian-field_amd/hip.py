@@ -1282,6 +1282,25 @@ def _cloud_shape(op: str, name: str, layout: str, cloud) -> tuple:
     return int(cloud.shape[0]), int(cloud.shape[1])
 
 
+def _posed_rows(op: str, points, count, labels, name: str = "points") -> tuple:
+    """(Mq, n) of the posed rows ``points`` [Mq, n, 3] (or the shape tuple that stands for them) with ``count`` [1] and ``labels``
+    [n], each int32 or None."""
+    mq, n = _cloud_shape(op, name, "Mq, n", points)
+    if count is not None and count.numel() != 1:
+        raise ValueError(f"njf_hip: {op} count must hold one int32")
+    if labels is not None and labels.numel() != n:
+        raise ValueError(f"njf_hip: {op} needs labels [n]")
+    return mq, n
+
+
+def _view_count(op: str, k, w2c, views: Optional[int] = None) -> int:
+    """V of the cameras ``k`` [V, 3, 3] and ``w2c`` [V, 4, 4]; ``views``: the V they must have, where the caller knows one."""
+    v, shown = (int(k.shape[0]) if k.dim() else -1, "V") if views is None else (views, views)
+    if tuple(k.shape) != (v, 3, 3) or tuple(w2c.shape) != (v, 4, 4):
+        raise ValueError(f"njf_hip: {op} needs k [{shown}, 3, 3] and w2c [{shown}, 4, 4]")
+    return v
+
+
 def _check_output_sizes(op: str, out: dict, sizes: dict) -> None:
     for name, size in sizes.items():
         if out[name].numel() != size:
@@ -1304,16 +1323,12 @@ def field_nearest(observed: Optional[torch.Tensor], queries: Optional[torch.Tens
     and writes ``out``; a phase without the build takes the SHAPE ``(Mo, T)`` for ``observed``, one without the query the shape
     ``(Mq, n)`` for ``queries`` and None for ``out``.  ``workspace``: int32, ``field_nearest_workspace`` elements."""
     mo, t = _cloud_shape("field_nearest", "observed", "Mo, T", observed)
-    (mq, n), m = _cloud_shape("field_nearest", "queries", "Mq, n", queries), int(problems)
+    (mq, n), m = _posed_rows("field_nearest", queries, count, labels, "queries"), int(problems)
     build, query = bool(phase & FIELD_NEAREST_BUILD), bool(phase & FIELD_NEAREST_QUERY)
     if (build and not torch.is_tensor(observed)) or (query and not torch.is_tensor(queries)):
         raise ValueError("njf_hip: field_nearest needs the observed points to build and the queries to query")
     if observed_count is not None and observed_count.numel() != mo:
         raise ValueError("njf_hip: field_nearest needs observed_count [Mo]")
-    if count is not None and count.numel() != 1:
-        raise ValueError("njf_hip: field_nearest count must hold one int32")
-    if labels is not None and labels.numel() != n:
-        raise ValueError("njf_hip: field_nearest needs labels [n]")
     if query:
         _check_output_sizes("field_nearest", out, dict(index=m * n, distance2=m * n, matched=3 * m * n, found=m))
     if workspace is None:
@@ -1350,14 +1365,12 @@ def field_normals(observed: Optional[torch.Tensor], queries: Optional[torch.Tens
     writes the other outputs; a phase without the build takes the SHAPE ``(Mo, T)`` for ``observed``.  ``workspace``: int32,
     ``field_normals_workspace`` elements, not needed by the finish alone."""
     mo, t = _cloud_shape("field_normals", "observed", "Mo, T", observed)
-    (mq, n), m = _cloud_shape("field_normals", "queries", "Mq, n", queries), int(problems)
+    (mq, n), m = _posed_rows("field_normals", queries, count, None, "queries"), int(problems)
     build, sums, finish = (bool(phase & p) for p in FIELD_NORMALS_PHASES)
     if (build and not torch.is_tensor(observed)) or ((sums or finish) and not torch.is_tensor(queries)):
         raise ValueError("njf_hip: field_normals needs the observed points to build and the queries for the moments and the finish")
     if observed_count is not None and observed_count.numel() != mo:
         raise ValueError("njf_hip: field_normals needs observed_count [Mo]")
-    if count is not None and count.numel() != 1:
-        raise ValueError("njf_hip: field_normals count must hold one int32")
     if viewpoint is not None and (viewpoint.dim() != 2 or viewpoint.shape[1] != 3):
         raise ValueError("njf_hip: field_normals needs viewpoint [Mv, 3]")
     sizes = dict(moments=10 * m * n) if sums or finish else {}
@@ -1477,15 +1490,8 @@ def field_visible(points: torch.Tensor, k: torch.Tensor, w2c: torch.Tensor, heig
     FIELD_VISIBLE_DIRECT] reads the points and writes the workspace, FIELD_VISIBLE_RESOLVE writes depth, index and covered from
     it, FIELD_VISIBLE_TEST reads the points and ``out["depth"]`` and writes the other five.  ``workspace``: int32,
     ``field_visible_workspace`` elements."""
-    mq, n = _cloud_shape("field_visible", "points", "Mq, n", points)
-    m, h, w = int(problems), int(height), int(width)
-    if k.dim() != 3 or tuple(k.shape[1:]) != (3, 3) or w2c.dim() != 3 or tuple(w2c.shape) != (k.shape[0], 4, 4):
-        raise ValueError("njf_hip: field_visible needs k [V, 3, 3] and w2c [V, 4, 4]")
-    v = int(k.shape[0])
-    if count is not None and count.numel() != 1:
-        raise ValueError("njf_hip: field_visible count must hold one int32")
-    if labels is not None and labels.numel() != n:
-        raise ValueError("njf_hip: field_visible needs labels [n]")
+    mq, n = _posed_rows("field_visible", points, count, labels)
+    m, v, h, w = int(problems), _view_count("field_visible", k, w2c), int(height), int(width)
     splat, resolve, test = (bool(phase & p) for p in FIELD_VISIBLE_PHASES)
     sizes = {}
     if resolve or test:
@@ -1524,18 +1530,11 @@ def field_frame(points: torch.Tensor, frame: torch.Tensor, k: torch.Tensor, w2c:
     ``width``.  ``count`` [1], ``labels`` [n]: int32 or None.  ``out`` maps pixel, z, state [M, V, n], index, distance2 [M, n],
     matched [M, n, 3], found [M] and states [M, 5] (FIELD_FRAME_OUTPUTS holds the element types) to tensors of their shapes.
     ``phase``: FIELD_FRAME_MATCH [+ FIELD_FRAME_KEEP_HIDDEN]."""
-    mq, n = _cloud_shape("field_frame", "points", "Mq, n", points)
+    mq, n = _posed_rows("field_frame", points, count, labels)
     mo, t = _cloud_shape("field_frame", "frame", "Mo, V * H * W", frame)
-    m, h, w = int(problems), int(height), int(width)
-    if k.dim() != 3 or tuple(k.shape[1:]) != (3, 3) or w2c.dim() != 3 or tuple(w2c.shape) != (k.shape[0], 4, 4):
-        raise ValueError("njf_hip: field_frame needs k [V, 3, 3] and w2c [V, 4, 4]")
-    v = int(k.shape[0])
+    m, v, h, w = int(problems), _view_count("field_frame", k, w2c), int(height), int(width)
     if t != v * h * w:
         raise ValueError(f"njf_hip: field_frame needs frame [Mo, {v * h * w}, 3] for {v} views of {h} x {w} (got {t} rows)")
-    if count is not None and count.numel() != 1:
-        raise ValueError("njf_hip: field_frame count must hold one int32")
-    if labels is not None and labels.numel() != n:
-        raise ValueError("njf_hip: field_frame needs labels [n]")
     _check_output_sizes("field_frame", out, dict(pixel=m * v * n, z=m * v * n, state=m * v * n, index=m * n, distance2=m * n,
                                                  matched=3 * m * n, found=m, states=m * FIELD_FRAME_STATES))
     _launch("njf_field_frame", load_library().njf_field_frame, _ptr(points, "points"), _int32_ptr(count, "count"),
@@ -1561,8 +1560,7 @@ def field_tsdf(grid: FieldGrid, depth: torch.Tensor, k: torch.Tensor, w2c: torch
     if depth.dim() != 4:
         raise ValueError("njf_hip: field_tsdf needs depth [M, V, H, W]")
     m, v, h, w = (int(s) for s in depth.shape)
-    if k.dim() != 3 or tuple(k.shape) != (v, 3, 3) or tuple(w2c.shape) != (v, 4, 4):
-        raise ValueError(f"njf_hip: field_tsdf needs k [{v}, 3, 3] and w2c [{v}, 4, 4]")
+    _view_count("field_tsdf", k, w2c, v)
     nodes = int(grid.dims[0]) * int(grid.dims[1]) * int(grid.dims[2])
     _check_output_sizes("field_tsdf", out, dict(values=m * nodes, weight=m * nodes, known=m))
     for name, t in (("values_in", values_in), ("weight_in", weight_in)):
@@ -1579,15 +1577,11 @@ def field_tsdf_sample(points: torch.Tensor, grid: FieldGrid, values: torch.Tenso
     """njf_field_tsdf_sample on ``points`` [Mq, n, 3] (fp32) in the field ``values``, ``weight`` [Mf, N] (fp32) on ``grid`` for
     ``problems`` = M problems, Mq and Mf each 1 or M.  ``count`` [1], ``labels`` [n]: int32 or None.  ``out`` maps state, distance
     [M, n], gradient [M, n, 3] and states [M, 3] (FIELD_TSDF_SAMPLE_OUTPUTS holds the element types) to tensors of their shapes."""
-    mq, n = _cloud_shape("field_tsdf_sample", "points", "Mq, n", points)
+    mq, n = _posed_rows("field_tsdf_sample", points, count, labels)
     m = int(problems)
     nodes = int(grid.dims[0]) * int(grid.dims[1]) * int(grid.dims[2])
     if values.dim() != 2 or values.shape[1] != nodes or tuple(weight.shape) != tuple(values.shape):
         raise ValueError(f"njf_hip: field_tsdf_sample needs values and weight [Mf, {nodes}]")
-    if count is not None and count.numel() != 1:
-        raise ValueError("njf_hip: field_tsdf_sample count must hold one int32")
-    if labels is not None and labels.numel() != n:
-        raise ValueError("njf_hip: field_tsdf_sample needs labels [n]")
     _check_output_sizes("field_tsdf_sample", out, dict(state=m * n, distance=m * n, gradient=3 * m * n, states=m * FIELD_TSDF_STATES))
     _launch("njf_field_tsdf_sample", load_library().njf_field_tsdf_sample, _ptr(points, "points"), _int32_ptr(count, "count"),
             _int32_ptr(labels, "labels"), mq, n, m, C.byref(grid), _ptr(values, "values"), _ptr(weight, "weight"),
