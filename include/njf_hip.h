@@ -82,7 +82,8 @@ extern "C" {
                                   dumps) return the "unknown mode" error; (d) never part of a MIXED code */
 
 /* njf_render_forward / njf_points_forward: density + colour networks in precision `d`, Jacobian head in `j` (both one of
- * F32 / F16X2 / F16F6; mixed forms exist for the two split precisions).  A plain NJF_PRECISION_* value means d = j. */
+ * F32 / F16X2 / F16F6; mixed forms exist for the two split precisions).  A plain NJF_PRECISION_* value means d = j, and is the only code of
+ * d = j: NJF_PRECISION_MIXED(d, d) returns the "unknown mode" error like every other code outside the six accepted ones. */
 #define NJF_PRECISION_MIXED(d, j) ((d) | (((j) + 1) << 4))
 
 #define NJF_JACOBIAN_NONE 0

@@ -56,8 +56,10 @@ static inline int jacobian_precision(int p) { return (p >> 4) ? (p >> 4) - 1 : (
 static inline bool valid_precision(int p) {
   if (p < 0 || p > 0xff || !valid_base_precision(density_precision(p)) || !valid_base_precision(jacobian_precision(p))) return false;
   const int d = density_precision(p), j = jacobian_precision(p);
-  // mixed forms: the two split-precision modes in either order (the plain-fp16 mode reads an fp16 map: never mixed)
-  return d == j || (d != NJF_PRECISION_F32 && j != NJF_PRECISION_F32 && d != NJF_PRECISION_F16 && j != NJF_PRECISION_F16);
+  // d = j has ONE code, the plain value: NJF_PRECISION_MIXED(d, d) is refused, so that every accepted code is one a caller can
+  // have meant.  Mixed forms: the two split-precision modes in either order (the plain-fp16 mode reads an fp16 map: never mixed)
+  if (d == j) return (p >> 4) == 0;
+  return d != NJF_PRECISION_F32 && j != NJF_PRECISION_F32 && d != NJF_PRECISION_F16 && j != NJF_PRECISION_F16;
 }
 
 static inline int launch_status() {

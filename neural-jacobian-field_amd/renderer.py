@@ -60,7 +60,8 @@ class FusedRenderer:
     """Feature map in, rendered rays out (``jacobian_mlp`` decoder by default): see the module docstring."""
 
     def __init__(self, device: torch.device, num_proposal_networks: int = 1, action_dim: int = 8,
-                 precision: Optional[str] = None, proposal_precision: Optional[str] = None, decoder: str = "jacobian_mlp"):
+                 precision: Optional[str] = None, proposal_precision: Optional[str] = None, decoder: str = "jacobian_mlp",
+                 jacobian_precision: Optional[str] = None):
         if torch.device(device).type != "cuda":
             raise ValueError("FusedRenderer needs a GPU device; the rendering hot path has no CPU fallback")
         hip.load_library()
@@ -73,7 +74,7 @@ class FusedRenderer:
                                    "rendering": {"num_proposal_samples": [64] * num_proposal_networks, "num_nerf_samples": 64},
                                    "action_decoder": {"name": decoder}})
         self.model = Model(cfg).to(self.device).eval().requires_grad_(False)
-        self.model.set_precision(hip.DEFAULT_PRECISION if precision is None else precision, proposal_precision)
+        self.model.set_precision(hip.DEFAULT_PRECISION if precision is None else precision, proposal_precision, jacobian_precision)
         self.precision = self.model.decoder.precision
 
     # ------------------------------------------------------------------ weights

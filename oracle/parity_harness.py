@@ -197,9 +197,10 @@ def general_pose(seed: int, batch: int, scale: float = 0.15) -> torch.Tensor:
 
 
 def make_case(batch: int, height: int, width: int, rays: Optional[int], action_dim: int, seed: int = 0,
-              identity_context: bool = True):
-    """Seeded synthetic batch: weights, feature map, cameras, rays -- all CPU tensors."""
-    params = synthetic.seeded_state_dict(synthetic.model_shapes("jacobian_mlp", action_dim, with_encoder=False), seed)
+              identity_context: bool = True, decoder: str = "jacobian_mlp"):
+    """Seeded synthetic batch: weights, feature map, cameras, rays -- all CPU tensors.  ``decoder``: the action
+    decoder whose weights are seeded and which both sides evaluate (``case["decoder_kind"]``)."""
+    params = synthetic.seeded_state_dict(synthetic.model_shapes(decoder, action_dim, with_encoder=False), seed)
     cams = synthetic.synthetic_cameras(batch)
     if not identity_context:
         cams["ctxt_c2w"] = general_pose(seed + 5, batch)
@@ -213,8 +214,11 @@ def make_case(batch: int, height: int, width: int, rays: Optional[int], action_d
     origins, directions, _ = orc.world_rays_with_z(xy, cams["trgt_k_norm"], cams["trgt_c2w"])
     k_pix = orc.denormalize_intrinsics(cams["trgt_k_norm"], width, height)
     action = synthetic.synthetic_action(batch, action_dim, seed + 2)
-    return dict(params=params, feats=feats, cams=cams, origins=origins.contiguous(), directions=directions.contiguous(),
+    case = dict(params=params, feats=feats, cams=cams, origins=origins.contiguous(), directions=directions.contiguous(),
                 k_pix=k_pix, action=action)
+    if decoder != "jacobian_mlp":
+        case["decoder_kind"] = decoder
+    return case
 
 
 def oracle_forward(case, s_prop, s_final, anneal: float = 1.0):
@@ -295,11 +299,13 @@ def final_stage_fp64(case, bins32: torch.Tensor):
 
 def hip_forward(case, s_prop, s_final, device, anneal: float = 1.0, request: Optional[RenderRequest] = None,
                 final_bins: Optional[torch.Tensor] = None, precision: Optional[str] = None,
-                proposal_precision: Optional[str] = None):
+                proposal_precision: Optional[str] = None, jacobian_precision: Optional[str] = None):
+    """``jacobian_precision``: the split precision of the Jacobian head where it differs from ``precision`` (Model.set_precision)."""
     c = case["cams"]
     dev = lambda t: t.to(device)
     action_dim = case["action"].shape[-1]
-    fr = FusedRenderer(device, 1, action_dim, precision=precision, proposal_precision=proposal_precision)
+    fr = FusedRenderer(device, 1, action_dim, precision=precision, proposal_precision=proposal_precision,
+                       decoder=case.get("decoder_kind", "jacobian_mlp"), jacobian_precision=jacobian_precision)
     fr.load_weights({k: dev(v) for k, v in case["params"].items()})
     gmap = dev(case["feats"]).contiguous()   # the hoisted maps are produced inside the render call
     # inverses are taken on the CPU here so both sides see bit-identical world->camera matrices
@@ -315,12 +321,14 @@ def hip_forward(case, s_prop, s_final, device, anneal: float = 1.0, request: Opt
 def run_parity_case(batch=1, height=16, width=16, rays=96, s_prop=32, s_final=32, action_dim=8, device=None,
                     tol: float = 1e-4, seed: int = 0, identity_context: bool = True, anneal: float = 1.0,
                     precision: Optional[str] = None, param_hook=None, case_id: Optional[int] = None,
-                    proposal_precision: Optional[str] = None) -> Dict:
+                    proposal_precision: Optional[str] = None, jacobian_precision: Optional[str] = None) -> Dict:
     """``param_hook(params)``: optional in-place edit of the seeded state dict (e.g. the reference's own initialisation
     of the Jacobian head) before both sides see it.  ``case_id``: index into PARITY_CASES -- the bound of every key is
     then ``max(tol, 2 x floor)`` with the floor taken from the REFERENCE's own fp32-vs-fp64 difference
     (tests/golden/harness_reference.npz), and the end-to-end outputs are additionally compared with the reference's
-    fp32 outputs themselves (keys ``ref_*``).  Without a case id (or without the fixture) the floor is the oracle's."""
+    fp32 outputs themselves (keys ``ref_*``).  Without a case id (or without the fixture) the floor is the oracle's.
+    ``jacobian_precision``: the Jacobian head in the other split precision; the report's ``precision`` then names both
+    ("f16f6/j:f16x2") and the asserted truth rule is the accelerated modes' (``truth_asserted`` with the density precision)."""
     device = device or torch.device("cuda:0")
     case = make_case(batch, height, width, rays, action_dim, seed, identity_context)
     if param_hook is not None:
@@ -338,13 +346,14 @@ def run_parity_case(batch=1, height=16, width=16, rays=96, s_prop=32, s_final=32
         if key is not None:
             _oracle_cache[key] = ref
     req = RenderRequest(vis=True, sample_weights=True, per_sample=True)
-    res, _, _ = hip_forward(case, s_prop, s_final, device, anneal, req, precision=precision, proposal_precision=proposal_precision)
+    res, _, _ = hip_forward(case, s_prop, s_final, device, anneal, req, precision=precision, proposal_precision=proposal_precision,
+                            jacobian_precision=jacobian_precision)
     ref_bins = torch.cat([ref.samples_list[1].spacing_starts[..., 0], ref.samples_list[1].spacing_ends[..., -1:, 0]], -1)
     # Per-sample quantities are compared at IDENTICAL sample locations (the oracle's final bins): the
     # inverse-CDF output differs by ~1e-6 between any two fp32 implementations and the positional
     # encoding turns that into O(1e-3) differences of individual samples, which is conditioning, not error.
     res2, _, _ = hip_forward(case, s_prop, s_final, device, anneal, req, final_bins=ref_bins, precision=precision,
-                             proposal_precision=proposal_precision)
+                             proposal_precision=proposal_precision, jacobian_precision=jacobian_precision)
     torch.cuda.synchronize(device)
     errs = {
         # end to end (Model.forward standard_output, model.py:363-369)
@@ -532,6 +541,8 @@ def run_parity_case(batch=1, height=16, width=16, rays=96, s_prop=32, s_final=32
         placement_row = mixed and r["key"].replace("truth:", "") in PLACEMENT_KEYS
         r["asserted_ok"] = truth_asserted(r, proposal_precision if placement_row else mode, placement_reduced=not mixed)
     asserted_failed = [r["key"] for r in truth_rows if r["asserted_ok"] is False]
+    if jacobian_precision is not None and jacobian_precision != mode:
+        mode = f"{mode}/j:{jacobian_precision}"
     return {"truth_asserted_ok": not asserted_failed, "truth_asserted_failed": asserted_failed,
             "truth_asserted_rows": sum(r["asserted_ok"] is not None for r in truth_rows), "precision": mode if not mixed else f"{mode}+{proposal_precision}",
             "ok": bool(ok), "tol": REDUCED_TOL if reduced else tol, "worst": worst, "model_floor": {k: float(f"{v:.3e}") for k, v in model.items()}, "errors": {k: float(f"{v:.3e}") for k, v in errs.items()},

@@ -21,8 +21,7 @@ def dev():
     return torch.device("cuda:0")
 
 
-@pytest.fixture(scope="module")
-def model_and_golden(dev, golden):
+def make_model_and_golden(dev, golden):
     from neural_jacobian_field_amd import synthetic
     from neural_jacobian_field_amd.config import model_cfg_from_dict
     from neural_jacobian_field_amd.model import Model
@@ -34,6 +33,11 @@ def model_and_golden(dev, golden):
     model.to(dev).eval().requires_grad_(False)  # inference: the in-kernel compositing path
     g64 = {k + "_f64": v for k, v in golden("model_mlp_f64").items()}  # the reference evaluated in float64 (floors)
     return model, {k: v.to(dev) for k, v in {**g, **g64}.items()}
+
+
+@pytest.fixture(scope="module")
+def model_and_golden(dev, golden):
+    return make_model_and_golden(dev, golden)
 
 
 def _inputs(g):
@@ -196,17 +200,14 @@ def test_model_forward_from_reference_features(model_and_golden, margins, precis
     _check_forward(margins, f"model_mlp.forward[{precision}]", out, g, encoder=False, truth_assert=precision == "f32")
 
 
-def test_decoder_forward_at_reference_sample_locations(model_and_golden, margins):
-    """ActionDecoder.forward / DensityDecoderMlp.get_density / encode_image on the reference's own sample positions.
-    Floors: the reference's float64 decoder evaluated at the SAME (fp32) positions -- what is left is one-ulp
-    camera-space differences times the positional encoding's gain (general context pose on batch element 1)."""
+def check_mlp_decoder_at_reference_positions(model, g, margins, c):
+    """The body of test_decoder_forward_at_reference_sample_locations; ``c`` names the rows in the margins table (shared with
+    tests/test_head_precisions_gpu.py, which runs it with the Jacobian head in the other split precision)."""
     from neural_jacobian_field_amd.decoder import PixelEncoding
-    model, g = model_and_golden
     enc = PixelEncoding(g["features"], g["ctxt_c2w"], g["ctxt_k_norm"], g["action"])
     pos = g["final_positions"]
     dirs = g["directions"][..., None, :].expand(pos.shape).contiguous()
     dec = model.decoder.forward(pos, dirs, enc)
-    c = "model_mlp.decoder@ref-positions"
     margins(c, "density", dec.density, g["dec_density"], g["dec_density_f64"])
     margins(c, "color", dec.color, g["dec_color"], g["dec_color_f64"])
     margins(c, "flow", dec.flow, g["dec_flow"], g["dec_flow_f64"])
@@ -220,6 +221,14 @@ def test_decoder_forward_at_reference_sample_locations(model_and_golden, margins
     margins(c, "compute_density.density", head.density.reshape(g["dec_density"].shape), g["dec_density"], g["dec_density_f64"])
     margins(c, "compute_density.jacobian", extras["jacobian_head_output"].reshape(g["dec_action_features"].shape),
             g["dec_action_features"], g["dec_action_features_f64"])
+
+
+def test_decoder_forward_at_reference_sample_locations(model_and_golden, margins):
+    """ActionDecoder.forward / DensityDecoderMlp.get_density / encode_image on the reference's own sample positions.
+    Floors: the reference's float64 decoder evaluated at the SAME (fp32) positions -- what is left is one-ulp
+    camera-space differences times the positional encoding's gain (general context pose on batch element 1)."""
+    model, g = model_and_golden
+    check_mlp_decoder_at_reference_positions(model, g, margins, "model_mlp.decoder@ref-positions")
 
 
 def test_identity_context_element_is_tight(model_and_golden):
@@ -355,8 +364,7 @@ def test_generic_sampler_route_equals_fused_route(model_and_golden, margins):
 
 
 # ---- jacobian_transformer decoder (default Allegro head; fixture uses A=6 -> exercises key masking) ----
-@pytest.fixture(scope="module")
-def transformer_model_and_golden(dev, golden):
+def make_transformer_model_and_golden(dev, golden):
     from neural_jacobian_field_amd import synthetic
     from neural_jacobian_field_amd.config import model_cfg_from_dict
     from neural_jacobian_field_amd.model import Model
@@ -370,9 +378,14 @@ def transformer_model_and_golden(dev, golden):
     return model, {k: v.to(dev) for k, v in {**g, **g64}.items()}
 
 
-def test_transformer_decoder_at_reference_sample_locations(transformer_model_and_golden, margins):
+@pytest.fixture(scope="module")
+def transformer_model_and_golden(dev, golden):
+    return make_transformer_model_and_golden(dev, golden)
+
+
+def check_transformer_decoder_at_reference_positions(model, g, margins, c):
+    """The body of test_transformer_decoder_at_reference_sample_locations (``c``: the rows' name in the margins table)."""
     from neural_jacobian_field_amd.decoder import PixelEncoding
-    model, g = transformer_model_and_golden
     enc = PixelEncoding(g["features"], g["ctxt_c2w"], g["ctxt_k_norm"], g["action"])
     pos = g["final_positions"]
     dirs = g["directions"][..., None, :].expand(pos.shape).contiguous()
@@ -382,7 +395,6 @@ def test_transformer_decoder_at_reference_sample_locations(transformer_model_and
     assert rel(dec.flow[0], g["dec_flow"][0]) < 1e-4
     assert rel(dec.density[0], g["dec_density"][0]) < 1e-4
     # general pose element: the reference's own float64 evaluation at the same positions is the yardstick
-    c = "model_transformer.decoder@ref-positions"
     margins(c, "action_features", dec.action_features, g["dec_action_features"], g["dec_action_features_f64"])
     margins(c, "flow", dec.flow, g["dec_flow"], g["dec_flow_f64"])
     margins(c, "density", dec.density, g["dec_density"], g["dec_density_f64"])
@@ -391,13 +403,23 @@ def test_transformer_decoder_at_reference_sample_locations(transformer_model_and
     margins(c, "encode_image.action_features", fo.action_features, g["enc_action_features"], g["encpos_action_features_f64"])
 
 
-def test_transformer_model_forward_vs_reference_golden(transformer_model_and_golden, margins):
+def test_transformer_decoder_at_reference_sample_locations(transformer_model_and_golden, margins):
     model, g = transformer_model_and_golden
+    check_transformer_decoder_at_reference_positions(model, g, margins, "model_transformer.decoder@ref-positions")
+
+
+def check_transformer_model_forward(model, g, margins, c):
+    """The body of test_transformer_model_forward_vs_reference_golden (``c``: the rows' name in the margins table)."""
     out = model.forward(*_inputs(g), compute_vis_features=True)
-    _check_forward(margins, "model_transformer.forward[through encoder]", out, g)
+    _check_forward(margins, c + "[through encoder]", out, g)
     with _from_reference_features(model, g):
         out = model.forward(*_inputs(g), compute_vis_features=True)
-    _check_forward(margins, "model_transformer.forward", out, g, encoder=False)
+    _check_forward(margins, c, out, g, encoder=False)
+
+
+def test_transformer_model_forward_vs_reference_golden(transformer_model_and_golden, margins):
+    model, g = transformer_model_and_golden
+    check_transformer_model_forward(model, g, margins, "model_transformer.forward")
 
 
 @pytest.mark.parametrize("kind,tag,A", [("jacobian_mlp", "mlp", 8), ("jacobian_transformer", "transformer", 6)])
@@ -456,8 +478,9 @@ def test_arm_head_vs_reference_golden(dev, golden, margins, kind, tag, A):
         model.zero_grad(set_to_none=True)
 
 
-def test_transformer_head_with_eight_keys(dev, golden, margins):
-    """A = 8: every key slot of the folded attention is live (the A = 6 fixture above exercises the masking)."""
+def check_transformer_head_with_eight_keys(dev, golden, margins, tag, precisions=None):
+    """The body of test_transformer_head_with_eight_keys; ``tag`` names the rows in the margins table, ``precisions`` =
+    (density, head) runs it with the head in the other split precision (tests/test_head_precisions_gpu.py)."""
     from neural_jacobian_field_amd import synthetic
     from neural_jacobian_field_amd.config import model_cfg_from_dict
     from neural_jacobian_field_amd.decoder import PixelEncoding
@@ -468,20 +491,27 @@ def test_transformer_head_with_eight_keys(dev, golden, margins):
     model = Model(cfg)
     model.load_state_dict(synthetic.seeded_state_dict(synthetic.model_shapes("jacobian_transformer", 8), seed=0), strict=True)
     model.to(dev).eval().requires_grad_(False)
+    if precisions is not None:
+        model.set_precision(precisions[0], jacobian_precision=precisions[1])
     enc = PixelEncoding(g["features"], g["ctxt_c2w"], g["ctxt_k_norm"], g["action"])
     pos = g["final_positions"]
     dirs = g["directions"][..., None, :].expand(pos.shape).contiguous()
     dec = model.decoder.forward(pos, dirs, enc)
-    c = "model_transformer8.decoder@ref-positions"
+    c = tag + ".decoder@ref-positions"
     margins(c, "action_features", dec.action_features, g["dec_action_features"], g["dec_action_features_f64"])
     margins(c, "flow", dec.flow, g["dec_flow"], g["dec_flow_f64"])
     margins(c, "density", dec.density, g["dec_density"], g["dec_density_f64"])
     with _from_reference_features(model, g):
         out = model.forward(*_inputs(g), compute_vis_features=True)
-    c = "model_transformer8.forward"
+    c = tag + ".forward"
     for key, got in (("rgb", out.standard_output.rgb), ("depth", out.standard_output.depth),
                      ("optical_flow", out.standard_output.optical_flow), ("vis_action_features", out.vis_output.action_features)):
         margins(c, key, got, g[key], g[key + "_f64"], self_noise=_noise(g, key, False))
+
+
+def test_transformer_head_with_eight_keys(dev, golden, margins):
+    """A = 8: every key slot of the folded attention is live (the A = 6 fixture above exercises the masking)."""
+    check_transformer_head_with_eight_keys(dev, golden, margins, "model_transformer8")
 
 
 def test_two_proposal_levels_vs_reference_golden(dev, golden, margins):
@@ -529,8 +559,7 @@ def test_two_proposal_levels_vs_reference_golden(dev, golden, margins):
 
 
 # ---- flow_mlp decoder (the reference's direct-flow ablation, models/decoder/action_decoder_flow.py) ----
-@pytest.fixture(scope="module")
-def flow_model_and_golden(dev, golden):
+def make_flow_model_and_golden(dev, golden):
     from neural_jacobian_field_amd import synthetic
     from neural_jacobian_field_amd.config import model_cfg_from_dict
     from neural_jacobian_field_amd.model import Model
@@ -544,17 +573,21 @@ def flow_model_and_golden(dev, golden):
     return model, {k: v.to(dev) for k, v in {**g, **g64}.items()}
 
 
-def test_flow_mlp_decoder_at_reference_sample_locations(flow_model_and_golden, margins):
-    """The action enters the flow head as a latent input; on the fused path it is a per-image bias of the hoisted map."""
+@pytest.fixture(scope="module")
+def flow_model_and_golden(dev, golden):
+    return make_flow_model_and_golden(dev, golden)
+
+
+def check_flow_mlp_decoder_at_reference_positions(model, g, margins, c):
+    """The body of test_flow_mlp_decoder_at_reference_sample_locations (``c``: the rows' name in the margins table)."""
     from neural_jacobian_field_amd.decoder import PixelEncoding
-    model, g = flow_model_and_golden
     enc = PixelEncoding(g["features"], g["ctxt_c2w"], g["ctxt_k_norm"], g["action"])
     pos = g["final_positions"]
     dirs = g["directions"][..., None, :].expand(pos.shape).contiguous()
     dec = model.decoder.forward(pos, dirs, enc)
     assert rel(dec.flow[0], g["dec_flow"][0]) < 1e-4        # identity-context batch element: tight
     assert rel(dec.density[0], g["dec_density"][0]) < 1e-4
-    c = "model_flow.decoder@ref-positions"                  # general pose element: the reference's float64 run is the yardstick
+    # general pose element: the reference's float64 run is the yardstick
     margins(c, "flow", dec.flow, g["dec_flow"], g["dec_flow_f64"])
     margins(c, "color", dec.color, g["dec_color"], g["dec_color_f64"])
     margins(c, "density", dec.density, g["dec_density"], g["dec_density_f64"])
@@ -564,6 +597,13 @@ def test_flow_mlp_decoder_at_reference_sample_locations(flow_model_and_golden, m
     # the reference's flow_mlp.encode_image as it is (action_decoder_flow.py:246-279): a map object yielding the density alone
     only = list(model.decoder.encode_image(pos, enc))
     assert len(only) == 1 and only[0].shape == dec.density.shape and rel(only[0], dec.density) < 1e-6
+    return dec
+
+
+def test_flow_mlp_decoder_at_reference_sample_locations(flow_model_and_golden, margins):
+    """The action enters the flow head as a latent input; on the fused path it is a per-image bias of the hoisted map."""
+    model, g = flow_model_and_golden
+    check_flow_mlp_decoder_at_reference_positions(model, g, margins, "model_flow.decoder@ref-positions")
 
 
 def test_flow_mlp_model_forward_vs_reference_golden(flow_model_and_golden, margins):

@@ -76,8 +76,14 @@ def as_dtype(mode):
     return lambda t: t
 
 
-@pytest.fixture(scope="module")
-def setup():
+# the two mixed forms of Model.set_precision(d, jacobian_precision=j): the Jacobian head in the OTHER split precision
+HEAD_MIXES = (("f16f6", "f16x2"), ("f16x2", "f16f6"))
+# Oracle gradients and their floors, per test body and action dimension: they depend on the case alone, not on the MFMA precision
+# under test, so the runs of one body under several precisions share them (each is nine CPU evaluations of the oracle)
+_ORACLE_RUNS = {}
+
+
+def build_setup(action_dim=8):
     if not torch.cuda.is_available():
         pytest.skip("needs an MI355X")
     import __graft_entry__ as g
@@ -88,10 +94,10 @@ def setup():
     from neural_jacobian_field_amd.model import CameraInput, Model, RenderingInput, RobotInput
     dev = torch.device("cuda:0")
     B, H, W, R, S = 2, 16, 16, 40, 32
-    case = ph.make_case(B, H, W, R, 8, seed=4)
-    full = synthetic.seeded_state_dict(synthetic.model_shapes("jacobian_mlp", 8), seed=4)
+    case = ph.make_case(B, H, W, R, action_dim, seed=4)
+    full = synthetic.seeded_state_dict(synthetic.model_shapes("jacobian_mlp", action_dim), seed=4)
     full.update(case["params"])  # decoder / proposal weights of the case + a seeded encoder
-    model = Model(model_cfg_from_dict({"action_dim": 8, "rendering": {"num_proposal_samples": [S], "num_nerf_samples": S},
+    model = Model(model_cfg_from_dict({"action_dim": action_dim, "rendering": {"num_proposal_samples": [S], "num_nerf_samples": S},
                                        "action_decoder": {"name": "jacobian_mlp"}}))
     model.load_state_dict(full, strict=True)
     model.to(dev).eval()
@@ -111,52 +117,120 @@ def setup():
     return dict(model=model, case=case, full=full, image=image, target=target, cam=cam, rin=rin, rob=rob, dev=dev, S=S)
 
 
-def test_action_mode_gradients_match_oracle_autograd(setup, margins):
+@pytest.fixture(scope="module")
+def setup():
+    return build_setup()
+
+
+def fused_render_outputs(model):
+    """Context manager: the output dictionaries of every Model._fused_render call made inside it (the activation dumps of a
+    training forward among them), in call order."""
+    import contextlib
+
+    @contextlib.contextmanager
+    def scope():
+        seen, real = [], model._fused_render
+
+        def spy(*args, **kwargs):
+            res = real(*args, **kwargs)
+            seen.append(res[0])
+            return res
+
+        model._fused_render = spy
+        try:
+            yield seen
+        finally:
+            del model._fused_render
+    return scope()
+
+
+def head_precisions(model, precisions):
+    """Context manager: ``Model.set_precision(d, jacobian_precision=j)`` for ``precisions = (d, j)`` (None: nothing changes), the
+    package's default precision afterwards."""
+    import contextlib
+    from neural_jacobian_field_amd import hip
+
+    @contextlib.contextmanager
+    def scope():
+        if precisions is not None:
+            model.set_precision(precisions[0], jacobian_precision=precisions[1])
+            assert model.decoder.precision == precisions[0] and model.decoder.j_precision == precisions[1]
+        try:
+            yield
+        finally:
+            if precisions is not None:
+                model.set_precision(hip.DEFAULT_PRECISION)
+    return scope()
+
+
+def check_action_mode_gradients(s, margins, tag="train.action[jacobian_mlp]", precisions=None):
+    """The body of test_action_mode_gradients_match_oracle_autograd on a ``build_setup`` dictionary (any action dimension);
+    ``precisions = (d, j)``: with the density / colour networks on ``d`` and the Jacobian head on ``j``."""
     import njf_oracle as orc
-    import parity_harness as ph
+    from neural_jacobian_field_amd import training
     from neural_jacobian_field_amd.training import JACOBIAN_PARAM_ORDER
-    s = setup
     model, case, dev = s["model"], s["case"], s["dev"]
-    out = model.forward(s["cam"], s["rin"], s["rob"])
-    assert out.standard_output.optical_flow.requires_grad and not out.standard_output.rgb.requires_grad
-    loss = 0.01 * torch.nn.functional.mse_loss(out.standard_output.optical_flow, s["target"].to(dev))
-    loss.backward()
+    model.zero_grad(set_to_none=True)
+    with head_precisions(model, precisions), fused_render_outputs(model) as rendered:
+        out = model.forward(s["cam"], s["rin"], s["rob"])
+        assert out.standard_output.optical_flow.requires_grad and not out.standard_output.rgb.requires_grad
+        loss = 0.01 * torch.nn.functional.mse_loss(out.standard_output.optical_flow, s["target"].to(dev))
+        loss.backward()
+        # the head's activation dump is stored as the training storage setting says for the HEAD's forward precision
+        # (the last one: the range check of a model's first forward pass renders with dumps of its own before it)
+        dumps = [o["jac_act"] for o in rendered if "jac_act" in o]
+        assert dumps and dumps[-1].dtype == training.activation_dump_dtype(model.decoder.j_precision)
+        assert dumps[-1].shape == (11, case["origins"].shape[0] * case["origins"].shape[1] * s["S"], 128)
     # oracle: same weights, encoder features from the oracle's own encoder, autograd through everything
     c = case["cams"]
-    losses = {}
+    key = ("action[jacobian_mlp]", case["action"].shape[-1])
+    if key not in _ORACLE_RUNS:
+        losses = {}
 
-    with torch.no_grad():
-        feats = orc.encoder_features({k[len("encoder."):]: v for k, v in s["full"].items() if k.startswith("encoder.")}, s["image"])
+        with torch.no_grad():
+            feats = orc.encoder_features({k[len("encoder."):]: v for k, v in s["full"].items() if k.startswith("encoder.")}, s["image"])
 
-    def oracle_backward(mode):
-        cv = as_dtype(mode)
-        params = {k: cv(v.clone()) for k, v in s["full"].items()}
-        for k in params:
-            if k.startswith("decoder.jacobian_head."):
-                params[k].requires_grad_(True)
-        origins, directions = moved_rays(case["origins"], case["directions"], mode)
-        ref = orc.model_forward(params, features=cv(feats if feature_seed(mode) is None else noisy(feats, seed=feature_seed(mode))),
-                                ctxt_c2w=cv(c["ctxt_c2w"]), ctxt_k_norm=cv(c["ctxt_k_norm"]),
-                                trgt_c2w=cv(c["trgt_c2w"]), trgt_k_pix=cv(case["k_pix"]), origins=cv(origins),
-                                directions=cv(directions), z_near=cv(c["z_near"]), z_far=cv(c["z_far"]),
-                                action=cv(case["action"]),
-                                num_proposal_samples=[s["S"]], num_nerf_samples=s["S"], decoder_kind="jacobian_mlp")
-        ref_loss = orc.flow_loss(ref.optical_flow, cv(s["target"]))
-        ref_loss.backward()
-        losses[mode] = ref_loss.detach().reshape(1)
-        return {n: params["decoder.jacobian_head." + n].grad for n in JACOBIAN_PARAM_ORDER}
+        def oracle_backward(mode):
+            cv = as_dtype(mode)
+            params = {k: cv(v.clone()) for k, v in s["full"].items()}
+            for k in params:
+                if k.startswith("decoder.jacobian_head."):
+                    params[k].requires_grad_(True)
+            origins, directions = moved_rays(case["origins"], case["directions"], mode)
+            ref = orc.model_forward(params, features=cv(feats if feature_seed(mode) is None else noisy(feats, seed=feature_seed(mode))),
+                                    ctxt_c2w=cv(c["ctxt_c2w"]), ctxt_k_norm=cv(c["ctxt_k_norm"]),
+                                    trgt_c2w=cv(c["trgt_c2w"]), trgt_k_pix=cv(case["k_pix"]), origins=cv(origins),
+                                    directions=cv(directions), z_near=cv(c["z_near"]), z_far=cv(c["z_far"]),
+                                    action=cv(case["action"]),
+                                    num_proposal_samples=[s["S"]], num_nerf_samples=s["S"], decoder_kind="jacobian_mlp")
+            ref_loss = orc.flow_loss(ref.optical_flow, cv(s["target"]))
+            ref_loss.backward()
+            losses[mode] = ref_loss.detach().reshape(1)
+            return {n: params["decoder.jacobian_head." + n].grad for n in JACOBIAN_PARAM_ORDER}
 
-    floor64, floor, g_ref = gradient_floor(oracle_backward, JACOBIAN_PARAM_ORDER)
-    margins("train.action[jacobian_mlp]", "loss", loss.reshape(1), losses[None],
+        _ORACLE_RUNS[key] = gradient_floor(oracle_backward, JACOBIAN_PARAM_ORDER) + (losses,)
+    floor64, floor, g_ref, losses = _ORACLE_RUNS[key]
+    margins(tag, "loss", loss.reshape(1), losses[None],
             floor=max(rel(losses[m], losses[None]) for m in FLOOR_MODES), floor_fp64=rel(losses["fp64"], losses[None]))
     head = dict(model.decoder.jacobian_head.named_parameters())
     for name in JACOBIAN_PARAM_ORDER:
         assert head[name].grad is not None and torch.isfinite(head[name].grad).all(), name
         # bound: twice the oracle's own movement under one-ulp rays (sample locations feed a 2*pi*512-gain encoding)
-        margins("train.action[jacobian_mlp]", "grad " + name, head[name].grad, g_ref[name], floor=floor[name],
+        margins(tag, "grad " + name, head[name].grad, g_ref[name], floor=floor[name],
                 floor_fp64=floor64[name])
     # frozen parameters received no gradient
     assert all(p.grad is None for n, p in model.named_parameters() if "jacobian_head" not in n)
+
+
+def test_action_mode_gradients_match_oracle_autograd(setup, margins):
+    check_action_mode_gradients(setup, margins)
+
+
+@pytest.mark.parametrize("precisions", HEAD_MIXES, ids="/j:".join)
+def test_action_mode_gradients_with_the_head_in_the_other_split_precision(setup, margins, precisions):
+    """render_kernel<1, P, 1, AF, PJ> with PJ != P: the action-mode training forward under Model.set_precision(d,
+    jacobian_precision=j), same rule as above (gradient_floor); the activation dump follows the HEAD's precision."""
+    check_action_mode_gradients(setup, margins, tag=f"train.action[jacobian_mlp:{'/j:'.join(precisions)}]", precisions=precisions)
 
 
 def test_one_adam_step_reduces_the_flow_loss_and_repacks_weights(setup):
@@ -189,17 +263,23 @@ def test_flow_backward_outside_action_mode_is_refused_loudly(setup):
         model.zero_grad(set_to_none=True)
 
 
-@pytest.mark.parametrize("precision", ["f32", "default"])
+@pytest.mark.parametrize("precision", ["f32", "default"] + ["/j:".join(mix) for mix in HEAD_MIXES])
 def test_perception_mode_gradients_match_oracle_autograd(setup, margins, precision):
     """Reference perception mode (model_wrapper.py:117-146): every parameter trains; the losses read rgb, depth and
     the per-level weights.  HIP forward with activation dumps + GEMM backward, against autograd through the CPU oracle
     (encoder included).  Deterministic (un-jittered) samples so both sides place the same points.  Run with exact fp32
-    products and in the package's default precision (f16f6 final pass, f16x2 proposal pass)."""
+    products, in the package's default precision (f16f6 final pass, f16x2 proposal pass), and with the Jacobian head in the other
+    split precision than the density and colour networks ("d/j:j": render_kernel<1, P, 2, AF, PJ> with PJ != P -- the flow it
+    computes is a value only here, the dumped networks are the density net and the colour head in ``d``)."""
     import njf_oracle as orc
     from neural_jacobian_field_amd import hip
     s = setup
     model, case, dev = s["model"], s["case"], s["dev"]
-    model.set_precision("f32" if precision == "f32" else hip.DEFAULT_PRECISION)
+    if "/j:" in precision:
+        model.set_precision(precision.split("/j:")[0], jacobian_precision=precision.split("/j:")[1])
+        assert model.decoder.j_precision == precision.split("/j:")[1] != model.decoder.precision
+    else:
+        model.set_precision("f32" if precision == "f32" else hip.DEFAULT_PRECISION)
     tag = f"train.perception[{precision}]"
     req = {n: p.requires_grad for n, p in model.named_parameters()}
     for p in model.parameters():
@@ -264,8 +344,9 @@ def test_perception_mode_gradients_match_oracle_autograd(setup, margins, precisi
             losses[mode] = ref_loss.detach().reshape(1)
             return {n: params[n].grad for n in names}
 
-        base = oracle_backward(None)
-        moved = {mode: oracle_backward(mode) for mode in FLOOR_MODES}
+        if "perception" not in _ORACLE_RUNS:   # (the oracle's runs do not depend on the precision under test)
+            _ORACLE_RUNS["perception"] = (oracle_backward(None), {mode: oracle_backward(mode) for mode in FLOOR_MODES}, losses)
+        base, moved, losses = _ORACLE_RUNS["perception"]
         margins(tag, "loss", loss.reshape(1), losses[None],
                 floor=max(rel(losses[m], losses[None]) for m in FLOOR_MODES), floor_fp64=rel(losses["fp64"], losses[None]))
         # EVERY parameter is held to ITS OWN floors (a group's largest floor used to excuse the group's worst
@@ -375,16 +456,14 @@ def test_wrapper_training_step_perception_and_action(setup):
         model.eval()
 
 
-def test_transformer_action_mode_gradients_match_oracle_autograd(setup, margins):
-    """jacobian_transformer (the shipped Allegro decoder, model_allegro.yaml:26) in action mode: the kernel evaluates
-    the folded head, the backward pass recomputes the un-folded head on the dumped encoding + footprint; gradients of
-    every "jacobian*" parameter against autograd through the CPU oracle."""
+def check_transformer_action_mode_gradients(s, margins, A=6, tag="train.action[jacobian_transformer]", precisions=None):
+    """The body of test_transformer_action_mode_gradients_match_oracle_autograd for a head of ``A`` keys; ``precisions = (d, j)``:
+    with the density / colour networks on ``d`` and the transformer head on ``j``."""
     import njf_oracle as orc
     from neural_jacobian_field_amd import synthetic
     from neural_jacobian_field_amd.config import model_cfg_from_dict
     from neural_jacobian_field_amd.model import Model, RobotInput
-    s = setup
-    case, dev, A = s["case"], s["dev"], 6
+    case, dev = s["case"], s["dev"]
     full = synthetic.seeded_state_dict(synthetic.model_shapes("jacobian_transformer", A), seed=6)
     model = Model(model_cfg_from_dict({"action_dim": A, "rendering": {"num_proposal_samples": [s["S"]], "num_nerf_samples": s["S"]},
                                        "action_decoder": {"name": "jacobian_transformer"}}))
@@ -398,39 +477,57 @@ def test_transformer_action_mode_gradients_match_oracle_autograd(setup, margins)
     trainable = [n for n, p in model.named_parameters() if p.requires_grad]
     assert trainable and all(n.startswith("decoder.jacobian") for n in trainable)
     action = torch.randn(case["action"].shape[0], A, generator=torch.Generator().manual_seed(8)) * 0.3
-    out = model.forward(s["cam"], s["rin"], RobotInput(action.to(dev)))
-    loss = 0.01 * torch.nn.functional.mse_loss(out.standard_output.optical_flow, s["target"].to(dev))
-    loss.backward()
+    with head_precisions(model, precisions):
+        out = model.forward(s["cam"], s["rin"], RobotInput(action.to(dev)))
+        loss = 0.01 * torch.nn.functional.mse_loss(out.standard_output.optical_flow, s["target"].to(dev))
+        loss.backward()
 
     c = case["cams"]
-    losses = {}
+    key = ("action[jacobian_transformer]", A)
+    if key not in _ORACLE_RUNS:
+        losses = {}
 
-    with torch.no_grad():
-        feats = orc.encoder_features({k[len("encoder."):]: v for k, v in full.items() if k.startswith("encoder.")}, s["image"])
+        with torch.no_grad():
+            feats = orc.encoder_features({k[len("encoder."):]: v for k, v in full.items() if k.startswith("encoder.")}, s["image"])
 
-    def oracle_backward(mode):
-        cv = as_dtype(mode)
-        params = {k: cv(v.clone()) for k, v in full.items()}
-        for k in trainable:
-            params[k].requires_grad_(True)
-        origins, directions = moved_rays(case["origins"], case["directions"], mode)
-        ref = orc.model_forward(params, features=cv(feats if feature_seed(mode) is None else noisy(feats, seed=feature_seed(mode))),
-                                ctxt_c2w=cv(c["ctxt_c2w"]), ctxt_k_norm=cv(c["ctxt_k_norm"]),
-                                trgt_c2w=cv(c["trgt_c2w"]), trgt_k_pix=cv(case["k_pix"]), origins=cv(origins),
-                                directions=cv(directions), z_near=cv(c["z_near"]), z_far=cv(c["z_far"]), action=cv(action),
-                                num_proposal_samples=[s["S"]], num_nerf_samples=s["S"], decoder_kind="jacobian_transformer")
-        ref_loss = orc.flow_loss(ref.optical_flow, cv(s["target"]))
-        ref_loss.backward()
-        losses[mode] = ref_loss.detach().reshape(1)
-        return {k: params[k].grad for k in trainable}
+        def oracle_backward(mode):
+            cv = as_dtype(mode)
+            params = {k: cv(v.clone()) for k, v in full.items()}
+            for k in trainable:
+                params[k].requires_grad_(True)
+            origins, directions = moved_rays(case["origins"], case["directions"], mode)
+            ref = orc.model_forward(params, features=cv(feats if feature_seed(mode) is None else noisy(feats, seed=feature_seed(mode))),
+                                    ctxt_c2w=cv(c["ctxt_c2w"]), ctxt_k_norm=cv(c["ctxt_k_norm"]),
+                                    trgt_c2w=cv(c["trgt_c2w"]), trgt_k_pix=cv(case["k_pix"]), origins=cv(origins),
+                                    directions=cv(directions), z_near=cv(c["z_near"]), z_far=cv(c["z_far"]), action=cv(action),
+                                    num_proposal_samples=[s["S"]], num_nerf_samples=s["S"], decoder_kind="jacobian_transformer")
+            ref_loss = orc.flow_loss(ref.optical_flow, cv(s["target"]))
+            ref_loss.backward()
+            losses[mode] = ref_loss.detach().reshape(1)
+            return {k: params[k].grad for k in trainable}
 
-    floor64, floor, g_ref = gradient_floor(oracle_backward, trainable)
-    margins("train.action[jacobian_transformer]", "loss", loss.reshape(1), losses[None],
+        _ORACLE_RUNS[key] = gradient_floor(oracle_backward, trainable) + (losses,)
+    floor64, floor, g_ref, losses = _ORACLE_RUNS[key]
+    margins(tag, "loss", loss.reshape(1), losses[None],
             floor=max(rel(losses[m], losses[None]) for m in FLOOR_MODES), floor_fp64=rel(losses["fp64"], losses[None]))
     named = dict(model.named_parameters())
     for k in trainable:
-        margins("train.action[jacobian_transformer]", "grad " + k, named[k].grad, g_ref[k], floor=floor[k], floor_fp64=floor64[k])
+        margins(tag, "grad " + k, named[k].grad, g_ref[k], floor=floor[k], floor_fp64=floor64[k])
     assert all(p.grad is None for n, p in named.items() if n not in trainable)
+
+
+def test_transformer_action_mode_gradients_match_oracle_autograd(setup, margins):
+    """jacobian_transformer (the shipped Allegro decoder, model_allegro.yaml:26) in action mode: the kernel evaluates
+    the folded head, the backward pass recomputes the un-folded head on the dumped encoding + footprint; gradients of
+    every "jacobian*" parameter against autograd through the CPU oracle."""
+    check_transformer_action_mode_gradients(setup, margins)
+
+
+@pytest.mark.parametrize("precisions", HEAD_MIXES, ids="/j:".join)
+def test_transformer_action_mode_gradients_with_the_head_in_the_other_split_precision(setup, margins, precisions):
+    """render_kernel<2, P, 1, AF, PJ> with PJ != P, same rule as above."""
+    check_transformer_action_mode_gradients(setup, margins, tag=f"train.action[jacobian_transformer:{'/j:'.join(precisions)}]",
+                                            precisions=precisions)
 
 
 @pytest.mark.parametrize("rays,samples", [(37, 64), (5, 20), (9, 200), (1, 1)])
